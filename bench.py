@@ -2,6 +2,10 @@
 """Benchmark of the hot path: ground filter + tower clustering on a synthetic corridor.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--mode stream|tiled] [--points P] [--kind corridor|uniform]
+                  [--dump-outputs DIR]
+
+--dump-outputs DIR (e.g. bench_outputs/, which git ignores) writes the outputs of the last timed step as .npy files:
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 One "step" = one pass of stages B + C + D0 (float32 centroid/centring, percentile height
 filter, chunked exact DBSCAN, label grouping) over one resident float32 [P,3] tile per GPU.
@@ -34,6 +38,38 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 EPS, MIN_POINTS, CHUNK = 8.0, 80, 50000
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: all files together
+DUMP_SAMPLE_ROWS = 1 << 20     # per-point outputs with more rows than this are written as a fixed sample of rows
+DUMP_SEED = 20261015
+
+
+def dump_outputs(dirname, whole, per_row, n_rows):
+    """--dump-outputs: writes what the timed path handed its caller in the last timed step as DIR/<name>.npy, float32
+    arrays as they are and everything else as float64 (exact for the integers here), so that two builds can be
+    compared output for output.  `whole` maps names to small arrays (numpy or device tensors) written in full;
+    `per_row` maps names to tensors of n_rows rows, written in full up to DUMP_SAMPLE_ROWS rows and otherwise as the
+    same DUMP_SAMPLE_ROWS rows of each, drawn with a fixed seed; sample_rows.npy holds the row indices either way.
+    Returns a summary for the result line."""
+    import torch
+    if n_rows <= DUMP_SAMPLE_ROWS:
+        rows = np.arange(n_rows, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, DUMP_SAMPLE_ROWS, replace=False))
+    arrays = {"sample_rows": rows}
+    for name, v in whole.items():
+        arrays[name] = v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    for name, t in per_row.items():
+        assert t.shape[0] == n_rows, (name, tuple(t.shape), n_rows)
+        arrays[name] = t.index_select(0, torch.from_numpy(rows).to(t.device)).cpu().numpy()
+    arrays = {name: a if a.dtype in (np.float32, np.float64) else a.astype(np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_BUDGET_BYTES})")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+    return {"dir": dirname, "files": sorted(f"{name}.npy" for name in arrays), "bytes": int(total),
+            "rows": int(n_rows), "rows_written": int(len(rows)), "sample_seed": DUMP_SEED}
 
 
 def _tile_sum(points, side, chunk, query_mask_fn=None):
@@ -181,10 +217,12 @@ def prepare_tiled(points_total, kind, frame, rank, world, dev, seed):
                                      device=dev, dtype=torch.float32)
 
 
-def run_tiled(points_total, kind, frame, rank, world, dev, steps, warmup, seed, verify=False, prepared=None):
+def run_tiled(points_total, kind, frame, rank, world, dev, steps, warmup, seed, verify=False, prepared=None,
+              dump_dir=None):
     """BASELINE configs[3] on `world` ranks: every rank generates its own x-tile + halo of ONE strip corridor of
     points_total points and runs tiles.tiled_step on it.  Timed like the main loop (barrier + synchronize on both
-    sides, max over ranks).  Returns the result dict on rank 0, None elsewhere."""
+    sides, max over ranks).  With dump_dir, rank 0 writes its tile's result of the last timed step there
+    (dump_outputs).  Returns the result dict on rank 0, None elsewhere."""
     import torch
     import torch.distributed as dist
     from pointcloudhookup_amd import synth, tiles
@@ -213,6 +251,16 @@ def run_tiled(points_total, kind, frame, rank, world, dev, steps, warmup, seed, 
         res = step(trace)
     barrier()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if dump_dir and rank == 0:                             # labels are defined on the owned rows only
+        dumped = dump_outputs(dump_dir,
+                              dict(centroid=np.asarray(res["centroid"], np.float32),
+                                   threshold=np.array([res["threshold"]], np.float32),
+                                   counts=np.array([res["nclusters"], res["used_fallback"], res["survivors"]],
+                                                   np.float64)),
+                              dict(points=res["points"], rows=res["rows"], own=res["own"],
+                                   labels=torch.where(res["own"], res["labels"], -2)),
+                              int(res["points"].shape[0]))
     calls = {k: (v - calls_before.get(k, 0)) / steps for k, v in tiles.COLLECTIVES.items() if v - calls_before.get(k, 0)}
     if trace:                                              # host timestamps of every phase of every timed step, per rank
         prev = t0
@@ -295,7 +343,7 @@ def run_tiled(points_total, kind, frame, rank, world, dev, steps, warmup, seed, 
             "collectives_per_step_rank0": calls, "collectives_per_step_rank0_total": round(sum(calls.values()), 2),
             "forced_collectives": bool(os.environ.get("PCH_TILES_FORCE_COLLECTIVES") == "1"),
             "devices": "one GPU shared by all ranks (rehearsal)" if os.environ.get("PCH_BENCH_SINGLE_DEVICE") else "one GPU per rank",
-            "steps": steps, "ms_per_step": round(1e3 * ph[0] / steps, 3),
+            "steps": steps, "ms_per_step": round(1e3 * ph[0] / steps, 3), "dump_outputs": dumped,
             "Mpts_per_s": round(points_total * steps / ph[0] / 1e6, 1),
             "phase_ms_max_over_ranks": {"centroid_chain+threshold+filter": round(ph[1], 3),
                                         "local_fit": round(ph[2], 3), "reconciliation": round(ph[3], 3)},
@@ -332,7 +380,13 @@ def main():
                     help="BASELINE config 5: a real .las file run end to end through the drop-in modules "
                          "(voxel downsample -> extract_towers); reported as a side value, 'skipped' without a file")
     ap.add_argument("--cpu-budget-s", type=float, default=20.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, "
+                         f"at most {DUMP_BUDGET_BYTES >> 20} MB; per-point outputs above {DUMP_SAMPLE_ROWS} rows as a "
+                         "fixed, seeded sample of rows")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.points is None:
         args.points = 100_000_000 if args.mode == "stream" else 400_000_000
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -369,7 +423,7 @@ def main():
         seed = synth.SEED0 + 3
         ops.set_profiling(False)
         res = run_tiled(int(args.points), args.kind, args.frame, rank, world, dev, args.steps, args.warmup, seed,
-                        verify=args.verify)
+                        verify=args.verify, dump_dir=args.dump_outputs)
         if rank == 0 and res.get("verified_against_single_gpu_run") is False:
             print(json.dumps({"error": "tiled labels differ from the single-GPU run", "tiled": res}), file=sys.stderr)
             if world > 1:
@@ -385,6 +439,7 @@ def main():
                               "frame": "global-offset (+437000,+3139000,+80)" if args.frame == "offset" else "local",
                               "seed": seed, "parallelism": f"x-tiles x{world}"},
                    "tiled": res, "roofline": res.get("roofline"), "cpu_baseline": None,
+                   "dump_outputs": res.get("dump_outputs"),
                    "note": "cpu_baseline is carried by the default (--mode stream) line"}
             print(json.dumps(out))
         if world > 1:
@@ -436,6 +491,17 @@ def main():
         elapsed = float(t.item())
     NF = int(cl["ground"]["count"])
     K = int(cl["nclusters"])
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        g = cl["ground"]
+        counts = [NF, K, g["count_at_offset"], g["used_fallback"]]
+        if world > 1:
+            counts += [cl["label_offset"], cl["global_clusters"]]
+        dumped = dump_outputs(args.dump_outputs,
+                              dict(centroid=g["centroid"], base_threshold=np.array([g["base"], g["threshold"]], np.float32),
+                                   aabb=g["aabb"], counts=np.array(counts, np.float64), offsets=cl["offsets"],
+                                   stats=cl["stats"]),
+                              dict(points=g["points"], labels=cl["labels"], perm=cl["perm"]), NF)
 
     # ---- config-4 side run (every rank takes part): ONE cloud of world x tiled-points-per-gpu points
     tiled_res = None
@@ -614,6 +680,7 @@ def main():
         "step_traffic": step_traffic,
         "counter_figures_dropped": traffic_dropped,
         "tiled": tiled_res,
+        "dump_outputs": dumped,
     }
 
     # ---- side measurements (none of them in `value`)

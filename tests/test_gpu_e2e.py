@@ -309,6 +309,60 @@ def test_tiled_step_over_rccl_with_forced_collectives(cuda):
         "backend", "collectives_per_step_rank0", "ms_per_step", "phase_ms_max_over_ranks", "clusters", "kept_points")}))
 
 
+def _bench_dump(root, out_dir, *argv):
+    import json
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "PCH_DIST_BACKEND",
+              "PCH_BENCH_SINGLE_DEVICE", "PCH_TILES_FORCE_COLLECTIVES"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", *argv,
+                        "--dump-outputs", str(out_dir)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    files = {f[:-4]: np.load(out_dir / f) for f in sorted(os.listdir(out_dir))}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(os.path.getsize(out_dir / f) for f in os.listdir(out_dir)) <= 64 << 20
+    return out, files
+
+
+def test_bench_dump_outputs_are_the_timed_steps_result(cuda, tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step returned.  Two runs with the same arguments write
+    the same bytes, the result line carries the requested number of steps and ms_per_step, and the files equal
+    pipeline.cluster_points on the same seeded input (stream mode), resp. hold the tiled run's centroid (tiled)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = 3_000_000
+    args = ("--points", str(n), "--steps", "3", "--warmup", "1", "--no-side", "--no-cpu-baseline")
+    out, a = _bench_dump(root, tmp_path / "a", *args)
+    _, b = _bench_dump(root, tmp_path / "b", *args)
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    assert out["dump_outputs"]["rows"] == out["config"]["filtered_points"]
+    assert a.keys() == b.keys() and {"points", "labels", "perm", "centroid", "offsets"} <= set(a)
+    for k in a:
+        assert a[k].dtype == b[k].dtype and np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), k
+
+    raw = synth.corridor_torch(n, seed=synth.SEED0 + 2, kind="corridor", offset=True, device=cuda, dtype=torch.float32)
+    cl = pipeline.cluster_points(raw, 8.0, 80, 50000)
+    idx = torch.from_numpy(a["sample_rows"].astype(np.int64)).to(cuda)
+    assert np.array_equal(a["centroid"].view(np.uint32), cl["ground"]["centroid"].view(np.uint32))
+    assert np.array_equal(a["points"].view(np.uint32), cl["ground"]["points"][idx].cpu().numpy().view(np.uint32))
+    assert np.array_equal(a["labels"], cl["labels"][idx].cpu().numpy().astype(np.float64))
+    assert np.array_equal(a["perm"], cl["perm"][idx].cpu().numpy().astype(np.float64))
+    assert np.array_equal(a["offsets"], cl["offsets"].cpu().numpy().astype(np.float64))
+    assert np.array_equal(a["counts"][:2], [cl["ground"]["count"], cl["nclusters"]])
+    del raw, cl
+
+    targs = ("--mode", "tiled", "--points", "12000000", "--steps", "2", "--warmup", "1")
+    out, t1 = _bench_dump(root, tmp_path / "t1", *targs)
+    _, t2 = _bench_dump(root, tmp_path / "t2", *targs)
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["dump_outputs"]["rows"] > 0
+    assert {"points", "rows", "own", "labels", "centroid", "threshold"} <= set(t1) and t1.keys() == t2.keys()
+    for k in t1:
+        assert np.array_equal(t1[k].view(np.uint8), t2[k].view(np.uint8)), k
+    assert np.array_equal(t1["centroid"], np.asarray(out["tiled"]["centroid"], np.float32))
+
+
 def test_rccl_probe_failure_degrades_to_gloo(cuda):
     """tiles.init_from_env with automatic backend choice: the default group is gloo and an RCCL group is PROBED.  Two
     ranks on this one GPU make RCCL refuse (duplicate device) - the run must go on with gloo exchanges and still

@@ -300,6 +300,43 @@ def test_bench_launches_its_own_ranks():
     # more than 3 ranks on one shared device are refused before any GPU work
     r = _bench("--gpus", "4", PCH_BENCH_SINGLE_DEVICE="1", RANK="0", WORLD_SIZE="4", LOCAL_RANK="0")
     assert r.returncode != 0 and "at most 3 ranks" in r.stderr
+    # --steps is the number of timed steps: zero of them is an error, not a division by zero after the warm-up
+    r = _bench("--gpus", "1", "--steps", "0", PCH_BENCH_DRYRUN="1")
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 stays float32, integers and flags become exact float64, per-row
+    outputs are written whole up to DUMP_SAMPLE_ROWS rows and above that as one fixed sample of rows shared by all
+    of them, and the files together stay within the budget."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = bench.DUMP_SAMPLE_ROWS + 12345
+    pts = torch.arange(3 * n, dtype=torch.float32).reshape(n, 3)
+    rows = torch.arange(n, dtype=torch.int64) + (1 << 40)
+    labels = (torch.arange(n, dtype=torch.int32) % 7) - 1
+    info = bench.dump_outputs(str(tmp_path / "a"), dict(centroid=np.array([1.5, 2.5, 3.5], np.float32),
+                                                        offsets=torch.tensor([0, 5, 9], dtype=torch.int64)),
+                              dict(points=pts, rows=rows, labels=labels, own=labels >= 0), n)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"sample_rows", "centroid", "offsets", "points", "rows", "labels", "own"}
+    assert sorted(info["files"]) == sorted(f"{k}.npy" for k in got) and info["rows"] == n
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["points"].dtype == np.float32 and got["centroid"].dtype == np.float32
+    assert sum(a.nbytes for a in got.values()) == info["bytes"] <= bench.DUMP_BUDGET_BYTES
+    idx = got["sample_rows"].astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE_ROWS and np.all(np.diff(idx) > 0) and idx[-1] < n
+    assert np.array_equal(got["points"], pts.numpy()[idx])
+    assert np.array_equal(got["rows"].astype(np.int64), rows.numpy()[idx])
+    assert np.array_equal(got["labels"], labels.numpy()[idx].astype(np.float64))
+    assert np.array_equal(got["own"], (labels.numpy()[idx] >= 0).astype(np.float64))
+    assert np.array_equal(got["offsets"], [0.0, 5.0, 9.0])
+    # the same call writes the same rows; a short output is written whole
+    bench.dump_outputs(str(tmp_path / "b"), {}, dict(points=pts), n)
+    assert np.array_equal(np.load(tmp_path / "b" / "sample_rows.npy"), got["sample_rows"])
+    bench.dump_outputs(str(tmp_path / "c"), {}, dict(points=pts[:10]), 10)
+    assert np.array_equal(np.load(tmp_path / "c" / "points.npy"), pts.numpy()[:10])
 
 
 def test_dedup_centres_first_wins():
