@@ -166,9 +166,10 @@ int pch_percentile_f32(const float* base, int64_t n, int64_t stride, const float
                        double q_percent, float* out,
                        void* ws, size_t ws_bytes, void* stream);
 
-/* The three histogram passes of the radix select and the "smallest key above" pass one by one, for a
+/* The three histogram passes of the radix select and the "smallest key above" pass one at a time, for a
  * percentile over values that are spread over several GPUs (pointcloudhookup_amd/tiles.py::shared_percentile:
- * every rank histograms its part, the histograms are all-reduced, the host picks the bin).  Keys are the
+ * every rank histograms its part, the histograms are all-reduced, the host picks the bin).  They run the same
+ * kernels as pch_percentile_f32, so the tiled threshold is the one pch_percentile_f32 gives.  Keys are the
  * order-preserving uint32 images of the floats (sign bit flipped / complemented; NaN = 0xFFFFFFFF).
  * pass 0: bins = key >> 20 (4096), pass 1: (key >> 8) & 0xFFF among keys with key >> 20 == prefix,
  * pass 2: key & 0xFF among keys with key >> 8 == prefix.  out_hist [4096] uint32 (device), out_nan [1] uint64

@@ -23,9 +23,7 @@ struct SelState {
     unsigned long long less;       // elements strictly below the current prefix
     uint32_t prefix;               // resolved high bits
     uint32_t need_next;            // 1: k1 is not inside the final bin of k0
-    uint32_t v0key, v1key;
-    unsigned long long nan_count;
-    uint32_t next_min;             // min key > v0key (pass 4)
+    uint32_t v0key;                // the selected key (after the last pick)
     uint32_t pad;
 };
 
@@ -60,110 +58,15 @@ __device__ __forceinline__ void sel_gate(const SelGate& g, const float*& base, i
     if (g.ok && *g.ok) { base = g.alt_base; n = (int64_t)*g.alt_n; stride = 1; }
 }
 
-template <int PASS>
-__global__ __launch_bounds__(256) void sel_hist_k(const float* __restrict__ base_in, int64_t n,
-                                                  int64_t stride, SelState* __restrict__ st,
-                                                  uint32_t* __restrict__ hist, SelGate gate = SelGate{nullptr, nullptr, nullptr}) {
-    const float* base = base_in;
-    sel_gate(gate, base, n, stride);
-    // pass 0 sees a handful of hot bins (z of a flat corridor): SEL_REP0 copies of the histogram, picked
-    // by lane, divide the same-address serialisation of the LDS atomics
-    constexpr int REP = PASS == 0 ? SEL_REP0 : 1;
-    __shared__ uint32_t hh[REP][SEL_BINS];
-    for (int j = threadIdx.x; j < REP * SEL_BINS; j += 256) (&hh[0][0])[j] = 0;
-    __syncthreads();
-    uint32_t* h = hh[lane_id() & (REP - 1)];
-    const uint32_t prefix = st->prefix;
-    unsigned long long nans = 0;
-    auto take = [&](bool in, float v) {
-        const uint32_t k = sel_key(v);
-        if (PASS == 0) {
-            if (in) atomicAdd(&h[k >> 20], 1u);
-            nans += (in && v != v);
-        } else if (PASS == 1) {
-            sel_hist_add<1>(h, in && (k >> 20) == prefix, (k >> 8) & 0xFFFu);
-        } else {
-            sel_hist_add<1>(h, in && (k >> 8) == prefix, k & 0xFFu);
-        }
-    };
-    // a workgroup takes tiles of 4096 values; on a contiguous, 16-byte aligned column every thread
-    // keeps four float4 loads in flight (the histogram update behind a load is a dependent chain)
-    const int64_t span = (int64_t)gridDim.x * SEL_TILE;
-    const bool vec = stride == 1 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0;
-    for (int64_t t0 = (int64_t)blockIdx.x * SEL_TILE; t0 < n; t0 += span) {    // wave-uniform trip count
-        if (vec && t0 + SEL_TILE <= n) {
-            const float4* b4 = reinterpret_cast<const float4*>(base + t0);
-            float4 q[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) q[r] = b4[r * 256 + threadIdx.x];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { take(true, q[r].x); take(true, q[r].y); take(true, q[r].z); take(true, q[r].w); }
-        } else {
-#pragma unroll 4
-            for (int r = 0; r < SEL_TILE / 256; ++r) {
-                const int64_t i = t0 + r * 256 + threadIdx.x;
-                const bool in = i < n;
-                take(in, in ? base[i * stride] : 0.0f);
-            }
-        }
-    }
-    __syncthreads();
-    const int nb = (PASS == 2) ? 256 : SEL_BINS;
-    for (int j = threadIdx.x; j < nb; j += 256) {
-        uint32_t t = 0;
-#pragma unroll
-        for (int r = 0; r < REP; ++r) t += hh[r][j];
-        if (t) atomicAdd(&hist[j], t);
-    }
-    if (PASS == 0) {
-        nans = wave_reduce_add(nans);
-        if (lane_id() == 0 && nans) atomicAdd(&st->nan_count, nans);
-    }
-}
-
-// pass 4 (only when needed): smallest key strictly above v0key
-__global__ __launch_bounds__(256) void sel_next_k(const float* __restrict__ base_in, int64_t n,
-                                                  int64_t stride, SelState* __restrict__ st,
-                                                  SelGate gate = SelGate{nullptr, nullptr, nullptr}) {
-    const float* base = base_in;
-    sel_gate(gate, base, n, stride);
-    if (st->need_next == 0) return;
-    const uint32_t v0 = st->v0key;
-    uint32_t best = 0xFFFFFFFFu;
-    auto take = [&](float v) {
-        const uint32_t k = sel_key(v);
-        if (k > v0 && k < best) best = k;
-    };
-    const int64_t span = (int64_t)gridDim.x * SEL_TILE;
-    const bool vec = stride == 1 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0;
-    for (int64_t t0 = (int64_t)blockIdx.x * SEL_TILE; t0 < n; t0 += span) {
-        if (vec && t0 + SEL_TILE <= n) {
-            const float4* b4 = reinterpret_cast<const float4*>(base + t0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float4 q = b4[r * 256 + threadIdx.x];
-                take(q.x); take(q.y); take(q.z); take(q.w);
-            }
-        } else {
-            for (int r = 0; r < SEL_TILE / 256; ++r) {
-                const int64_t i = t0 + r * 256 + threadIdx.x;
-                if (i < n) take(base[i * stride]);
-            }
-        }
-    }
-    best = wave_reduce_min(best);
-    if (lane_id() == 0 && best != 0xFFFFFFFFu) atomicMin(&st->next_min, best);
-}
-
 __device__ __forceinline__ float sel_key_to_float(uint32_t k) {
     return (k == 0xFFFFFFFFu) ? __uint_as_float(0x7FC00000u) : f32_unordered(k);
 }
 
 // (the interpolation itself is numpy's _lerp in float32: a + (b-a)*t, and b - (b-a)*(1-t) where t >= 0.5,
 // numpy/lib/_function_base_impl.py:4639-4660; NaN anywhere -> NaN.  scal: [0] = percentile,
-// [1] = percentile + add1, [2] = percentile + add2 - see selx_lerp_k)
+// [1] = percentile + add1, [2] = percentile + add2 - see sel_lerp_k)
 
-// ---- the same select with every pick folded into its consumer --------------------------------------
+// ---- the select, with every pick folded into its consumer ----------------------------------------
 // A kernel of a few microseconds still costs a launch slot (~5 us each on this stream), and a percentile used
 // to be 9 of them (27 with the sample bracket below).  Here the single-workgroup pick of pass p runs as the
 // prologue of whatever needs its result - histogram pass p+1, the "next key" pass, the bracket sweep, the final
@@ -175,7 +78,7 @@ struct SelRun {
     unsigned long long nan_count;
     uint32_t next_min, pad;
 };
-__device__ __forceinline__ uint32_t* selx_hist_of(uint32_t* hist, int run, int pass) {
+__host__ __device__ __forceinline__ uint32_t* sel_hist_of(uint32_t* hist, int run, int pass) {
     return hist + ((pass == 0 ? 0 : run) * 3 + pass) * SEL_BINS;        // pass 0 has no prefix: one histogram for all runs
 }
 
@@ -222,8 +125,10 @@ __device__ __forceinline__ SelState sel_pick_block(const SelState& in, const uin
     return out;
 }
 
-template <int PASS, int NR>
-__global__ __launch_bounds__(256) void selx_hist_k(const float* __restrict__ base_in, int64_t n, int64_t stride,
+// PICK = false: no pick prologue, the prefix is taken as the caller left it in run[r].st[PASS] (the passes one at a
+// time, pch_select_hist_f32)
+template <int PASS, int NR, bool PICK = true>
+__global__ __launch_bounds__(256) void sel_hist_k(const float* __restrict__ base_in, int64_t n, int64_t stride,
                                                    SelRun* __restrict__ run, uint32_t* __restrict__ hist,
                                                    SelGate gate) {
     const float* base = base_in;
@@ -232,6 +137,8 @@ __global__ __launch_bounds__(256) void selx_hist_k(const float* __restrict__ bas
     // workgroups have no tile - they leave before the pick and the 16 KB of LDS zeroing (workgroup 0 stays: it records
     // the pick)
     if (blockIdx.x != 0 && (int64_t)blockIdx.x * SEL_TILE >= n) return;
+    // pass 0 sees a handful of hot bins (z of a flat corridor): SEL_REP0 copies of the histogram, picked by lane,
+    // divide the same-address serialisation of the LDS atomics
     constexpr int REP = PASS == 0 ? SEL_REP0 : 1;
     constexpr int NH = PASS == 0 ? 1 : NR;
     __shared__ uint32_t hh[NH][REP][SEL_BINS];
@@ -239,11 +146,13 @@ __global__ __launch_bounds__(256) void selx_hist_k(const float* __restrict__ bas
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
         prefix[r] = 0;
-        if (PASS >= 1) {
+        if (PASS >= 1 && PICK) {
             const SelState st = sel_pick_block<(PASS >= 1 ? PASS - 1 : 0)>(run[r].st[PASS >= 1 ? PASS - 1 : 0],
-                                                                             selx_hist_of(hist, r, PASS >= 1 ? PASS - 1 : 0));
+                                                                             sel_hist_of(hist, r, PASS >= 1 ? PASS - 1 : 0));
             if (blockIdx.x == 0 && threadIdx.x == 0) run[r].st[PASS] = st;
             prefix[r] = st.prefix;
+        } else if (PASS >= 1) {
+            prefix[r] = run[r].st[PASS].prefix;
         }
     }
     for (int j = threadIdx.x; j < NH * REP * SEL_BINS; j += 256) (&hh[0][0][0])[j] = 0;
@@ -263,6 +172,8 @@ __global__ __launch_bounds__(256) void selx_hist_k(const float* __restrict__ bas
             }
         }
     };
+    // a workgroup takes tiles of 4096 values; on a contiguous, 16-byte aligned column every thread keeps four float4
+    // loads in flight (the histogram update behind a load is a dependent chain)
     const int64_t span = (int64_t)gridDim.x * SEL_TILE;
     const bool vec = stride == 1 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0;
     for (int64_t t0 = (int64_t)blockIdx.x * SEL_TILE; t0 < n; t0 += span) {    // wave-uniform trip count
@@ -286,7 +197,7 @@ __global__ __launch_bounds__(256) void selx_hist_k(const float* __restrict__ bas
     constexpr int nb = (PASS == 2) ? 256 : SEL_BINS;
 #pragma unroll
     for (int r = 0; r < NH; ++r) {
-        uint32_t* out = selx_hist_of(hist, r, PASS);
+        uint32_t* out = sel_hist_of(hist, r, PASS);
         for (int j = threadIdx.x; j < nb; j += 256) {
             uint32_t t = 0;
 #pragma unroll
@@ -301,13 +212,18 @@ __global__ __launch_bounds__(256) void selx_hist_k(const float* __restrict__ bas
 }
 
 // smallest key strictly above the selected one (only when rank+1 lies beyond its final bin); the last pick first
-__global__ __launch_bounds__(256) void selx_next_k(const float* __restrict__ base_in, int64_t n, int64_t stride,
+// (PICK = false: the key and need_next as the caller left them in run->st[3], pch_select_min_above_f32)
+template <bool PICK = true>
+__global__ __launch_bounds__(256) void sel_next_k(const float* __restrict__ base_in, int64_t n, int64_t stride,
                                                    SelRun* __restrict__ run, uint32_t* __restrict__ hist, SelGate gate) {
     const float* base = base_in;
     sel_gate(gate, base, n, stride);
-    if (blockIdx.x != 0 && (int64_t)blockIdx.x * SEL_TILE >= n) return;      // no tile (see selx_hist_k)
-    const SelState st = sel_pick_block<2>(run->st[2], selx_hist_of(hist, 0, 2));
-    if (blockIdx.x == 0 && threadIdx.x == 0) run->st[3] = st;
+    if (blockIdx.x != 0 && (int64_t)blockIdx.x * SEL_TILE >= n) return;      // no tile (see sel_hist_k)
+    SelState st = run->st[3];
+    if (PICK) {
+        st = sel_pick_block<2>(run->st[2], sel_hist_of(hist, 0, 2));
+        if (blockIdx.x == 0 && threadIdx.x == 0) run->st[3] = st;
+    }
     if (st.need_next == 0) return;
     const uint32_t v0 = st.v0key;
     uint32_t best = 0xFFFFFFFFu;
@@ -337,7 +253,7 @@ __global__ __launch_bounds__(256) void selx_next_k(const float* __restrict__ bas
 }
 
 // the final interpolation; picked = 0: the last pick has not run yet (there was no "next" pass)
-__global__ __launch_bounds__(256) void selx_lerp_k(const SelRun* __restrict__ run, const uint32_t* __restrict__ hist2,
+__global__ __launch_bounds__(256) void sel_lerp_k(const SelRun* __restrict__ run, const uint32_t* __restrict__ hist2,
                                                    int picked, int same_index, float gamma,
                                                    const float* __restrict__ sub, float add1, float add2,
                                                    float* __restrict__ scal) {
@@ -405,8 +321,8 @@ __global__ __launch_bounds__(256) void sel_bracket_k(const float* __restrict__ b
     __shared__ float stage[SEL_STAGE];
     __shared__ uint32_t nstage, gbase;
     // the last picks of the two sample selects; a bracket that reaches the bottom / top of the sample is open there
-    const uint32_t Lk = sel_pick_block<2>(lohi[0].st[2], selx_hist_of(hist, 0, 2)).v0key;
-    const uint32_t Hk = sel_pick_block<2>(lohi[1].st[2], selx_hist_of(hist, 1, 2)).v0key;
+    const uint32_t Lk = sel_pick_block<2>(lohi[0].st[2], sel_hist_of(hist, 0, 2)).v0key;
+    const uint32_t Hk = sel_pick_block<2>(lohi[1].st[2], sel_hist_of(hist, 1, 2)).v0key;
     const uint32_t L = lo_is_min ? 0u : Lk, H = hi_is_max ? 0xFFFFFFFFu : Hk;
     unsigned long long less = 0, nans = 0;
     const uint64_t lt = lanemask_lt();
@@ -476,14 +392,13 @@ __global__ void sel_bracket_fix_k(BrState* __restrict__ br, SelRun* __restrict__
     br->ok = ok ? 1u : 0u;
     SelState z;
     z.rank = ok ? k0 - less : k0;
-    z.less = 0; z.prefix = 0; z.need_next = 0; z.v0key = 0; z.v1key = 0;
-    z.nan_count = 0; z.next_min = 0; z.pad = 0;
+    z.less = 0; z.prefix = 0; z.need_next = 0; z.v0key = 0; z.pad = 0;
     run->st[0] = z;
     run->nan_count = ok ? br->nan : 0ull;                  // (the full passes count NaN themselves)
 }
 
 // one launch in front of a select: clears the histograms (and the bracket state), sets the ranks of up to 3 runs
-__global__ __launch_bounds__(256) void selx_init_k(uint32_t* __restrict__ hist, int nwords, SelRun* __restrict__ runs,
+__global__ __launch_bounds__(256) void sel_init_k(uint32_t* __restrict__ hist, int nwords, SelRun* __restrict__ runs,
                                                    int nruns, unsigned long long r0, unsigned long long r1,
                                                    unsigned long long r2, BrState* __restrict__ br,
                                                    uint32_t* __restrict__ also_zero, int64_t also_words) {
@@ -503,25 +418,21 @@ __global__ __launch_bounds__(256) void selx_init_k(uint32_t* __restrict__ hist, 
 }
 
 struct SelWs {
-    SelState* st;
-    uint32_t* hist;
     float*    scal;     // 4 floats
-    // bracketed select (n >= SEL_BRACKET_MIN)
     SelRun*   run;      // [0], [1]: the two ends of the sample bracket, [2]: the select proper
-    uint32_t* xhist;    // [3 runs][3 passes][SEL_BINS]
+    uint32_t* hist;     // [3 runs][3 passes][SEL_BINS]
+    // bracketed select (n >= SEL_BRACKET_MIN)
     BrState*  br;
     float    *sample, *cand;
     int64_t   ns;       // sample size
     uint32_t  cap;      // candidate capacity
-    uint32_t* also_zero;   // optional: words sel_init clears for the caller (see selx_init_k)
+    uint32_t* also_zero;   // optional: words sel_init clears for the caller (see sel_init_k)
     int64_t   also_words;
 };
 static void sel_plan(Arena& a, SelWs& w, int64_t n = 0) {
-    w.st = a.take<SelState>(1);
-    w.hist = a.take<uint32_t>(SEL_BINS);
     w.scal = a.take<float>(4);
     w.run = a.take<SelRun>(3);
-    w.xhist = a.take<uint32_t>(9 * SEL_BINS);
+    w.hist = a.take<uint32_t>(9 * SEL_BINS);
     w.br = nullptr; w.sample = w.cand = nullptr; w.ns = 0; w.cap = 0;
     w.also_zero = nullptr; w.also_words = 0;
     if (n >= SEL_BRACKET_MIN) {
@@ -559,10 +470,10 @@ static int select_rounds(const float* base, int64_t n, int64_t stride, bool with
     if (gb > 2048) gb = 2048;
     if (gb < 1) gb = 1;
     const dim3 grid((unsigned)gb), blk(256);
-    PCH_LAUNCH("sel_hist0", (selx_hist_k<0, 1>), grid, blk, 0, s, base, n, stride, run, hist, gate);
-    PCH_LAUNCH("sel_hist1", (selx_hist_k<1, 1>), grid, blk, 0, s, base, n, stride, run, hist, gate);
-    PCH_LAUNCH("sel_hist2", (selx_hist_k<2, 1>), grid, blk, 0, s, base, n, stride, run, hist, gate);
-    if (with_next) PCH_LAUNCH("sel_next", selx_next_k, grid, blk, 0, s, base, n, stride, run, hist, gate);
+    PCH_LAUNCH("sel_hist0", (sel_hist_k<0, 1>), grid, blk, 0, s, base, n, stride, run, hist, gate);
+    PCH_LAUNCH("sel_hist1", (sel_hist_k<1, 1>), grid, blk, 0, s, base, n, stride, run, hist, gate);
+    PCH_LAUNCH("sel_hist2", (sel_hist_k<2, 1>), grid, blk, 0, s, base, n, stride, run, hist, gate);
+    if (with_next) PCH_LAUNCH("sel_next", sel_next_k<>, grid, blk, 0, s, base, n, stride, run, hist, gate);
     return PCH_OK;
 }
 
@@ -592,7 +503,7 @@ static int select_sample_passes(const float* src, int64_t src_stride, int64_t n,
     const SelGate always = {nullptr, nullptr, nullptr};
     const SelBracket br = select_bracket_ranks(w, n, pi);
     const int64_t ns = w.ns;
-    PCH_LAUNCH("sel_init", selx_init_k, dim3((unsigned)ceil_div(9 * SEL_BINS, 256)), dim3(256), 0, s, w.xhist,
+    PCH_LAUNCH("sel_init", sel_init_k, dim3((unsigned)ceil_div(9 * SEL_BINS, 256)), dim3(256), 0, s, w.hist,
                9 * SEL_BINS, w.run, 3, (unsigned long long)br.r_lo, (unsigned long long)br.r_hi, 0ull, w.br,
                w.also_zero, w.also_words);
     PCH_LAUNCH("sel_sample", sel_sample_k, dim3((unsigned)ceil_div(ns, 1024)), dim3(256), 0, s, src, src_stride, ns,
@@ -601,9 +512,9 @@ static int select_sample_passes(const float* src, int64_t src_stride, int64_t n,
     if (gs > 2048) gs = 2048;
     if (gs < 1) gs = 1;
     const dim3 grid((unsigned)gs), blk(256);
-    PCH_LAUNCH("sel_hist0", (selx_hist_k<0, 2>), grid, blk, 0, s, (const float*)w.sample, ns, (int64_t)1, w.run, w.xhist, always);
-    PCH_LAUNCH("sel_hist1", (selx_hist_k<1, 2>), grid, blk, 0, s, (const float*)w.sample, ns, (int64_t)1, w.run, w.xhist, always);
-    PCH_LAUNCH("sel_hist2", (selx_hist_k<2, 2>), grid, blk, 0, s, (const float*)w.sample, ns, (int64_t)1, w.run, w.xhist, always);
+    PCH_LAUNCH("sel_hist0", (sel_hist_k<0, 2>), grid, blk, 0, s, (const float*)w.sample, ns, (int64_t)1, w.run, w.hist, always);
+    PCH_LAUNCH("sel_hist1", (sel_hist_k<1, 2>), grid, blk, 0, s, (const float*)w.sample, ns, (int64_t)1, w.run, w.hist, always);
+    PCH_LAUNCH("sel_hist2", (sel_hist_k<2, 2>), grid, blk, 0, s, (const float*)w.sample, ns, (int64_t)1, w.run, w.hist, always);
     return PCH_OK;
 }
 
@@ -614,9 +525,9 @@ static int select_passes(const float* base, int64_t n, int64_t stride, double q_
     const PctIndex pi = pct_index(n, q_percent);
     const SelGate always = {nullptr, nullptr, nullptr};
     SelRun* fin = w.run + 2;
-    uint32_t* hfin = w.xhist + 6 * SEL_BINS;
+    uint32_t* hfin = w.hist + 6 * SEL_BINS;
     if (!select_is_bracketed(w, n, stride)) {
-        PCH_LAUNCH("sel_init", selx_init_k, dim3((unsigned)ceil_div(9 * SEL_BINS, 256)), dim3(256), 0, s, w.xhist,
+        PCH_LAUNCH("sel_init", sel_init_k, dim3((unsigned)ceil_div(9 * SEL_BINS, 256)), dim3(256), 0, s, w.hist,
                    9 * SEL_BINS, w.run, 3, 0ull, 0ull, (unsigned long long)pi.k0, (BrState*)nullptr, w.also_zero,
                    w.also_words);
         return select_rounds(base, n, stride, !pi.same, fin, hfin, s, always, n);
@@ -639,7 +550,7 @@ static int select_passes(const float* base, int64_t n, int64_t stride, double q_
         }
         if (gb > per_round[slot]) gb = per_round[slot];
     }
-    PCH_LAUNCH("sel_bracket", sel_bracket_k, dim3((unsigned)gb), dim3(256), 0, s, base, n, (const SelRun*)w.run, w.xhist,
+    PCH_LAUNCH("sel_bracket", sel_bracket_k, dim3((unsigned)gb), dim3(256), 0, s, base, n, (const SelRun*)w.run, w.hist,
                br.r_lo == 0 ? 1 : 0, br.r_hi == ns - 1 ? 1 : 0, w.br, w.cand, w.cap);
     PCH_LAUNCH("sel_bracket_fix", sel_bracket_fix_k, dim3(1), dim3(64), 0, s, w.br, fin, (unsigned long long)pi.k0,
                pi.same);
@@ -652,8 +563,8 @@ static int select_passes(const float* base, int64_t n, int64_t stride, double q_
 static int select_lerp(int64_t n, const float* sub, double q_percent, float add1, float add2, SelWs& w,
                        hipStream_t s) {
     const PctIndex pi = pct_index(n, q_percent);
-    PCH_LAUNCH("sel_lerp", selx_lerp_k, dim3(1), dim3(256), 0, s, (const SelRun*)(w.run + 2),
-               (const uint32_t*)(w.xhist + 8 * SEL_BINS), pi.same ? 0 : 1, pi.same, pi.gamma, sub, add1, add2, w.scal);
+    PCH_LAUNCH("sel_lerp", sel_lerp_k, dim3(1), dim3(256), 0, s, (const SelRun*)(w.run + 2),
+               (const uint32_t*)(w.hist + 8 * SEL_BINS), pi.same ? 0 : 1, pi.same, pi.gamma, sub, add1, add2, w.scal);
     return PCH_OK;
 }
 static int select_percentile(const float* base, int64_t n, int64_t stride, const float* sub,
@@ -1177,9 +1088,10 @@ extern "C" int pch_percentile_f32(const float* base, int64_t n, int64_t stride, 
     return PCH_OK;
 }
 
-// ---- the select passes one by one, for a percentile over values that are spread over several GPUs
+// ---- the select passes one at a time, for a percentile over values that are spread over several GPUs
 // (tiles.shared_percentile: every rank histograms its part, the histograms are all-reduced, the host picks
-// the bin - same arithmetic, same result as pch_percentile_f32 over the concatenation)
+// the bin).  They launch the kernels of pch_percentile_f32 without the pick prologue (PICK = false; the host
+// does the picks): same kernels, same arithmetic, same result as pch_percentile_f32 over the concatenation.
 extern "C" int pch_select_hist_f32(const float* base, int64_t n, int64_t stride, int32_t pass, uint32_t prefix,
                                    uint32_t* out_hist, unsigned long long* out_nan, void* ws, size_t ws_bytes,
                                    void* stream) {
@@ -1191,22 +1103,27 @@ extern "C" int pch_select_hist_f32(const float* base, int64_t n, int64_t stride,
     SelWs w;
     sel_plan(a, w);
     if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
-    SelState h;
+    SelRun h;
     memset(&h, 0, sizeof(h));
-    h.prefix = prefix;
-    PCH_HIP_TRY(hipMemcpyAsync(w.st, &h, sizeof(h), hipMemcpyHostToDevice, s));
-    PCH_HIP_TRY(hipMemsetAsync(w.hist, 0, sizeof(uint32_t) * SEL_BINS, s));
+    h.st[pass].prefix = prefix;                          // (pass 0 has no prefix)
+    uint32_t* hist = sel_hist_of(w.hist, 0, pass);
+    PCH_HIP_TRY(hipMemcpyAsync(w.run, &h, sizeof(h), hipMemcpyHostToDevice, s));
+    PCH_HIP_TRY(hipMemsetAsync(hist, 0, sizeof(uint32_t) * SEL_BINS, s));
     if (n > 0) {
         int64_t gb = ceil_div(n, SEL_TILE);
         if (gb > 2048) gb = 2048;
         const dim3 grid((unsigned)gb), blk(256);
-        if (pass == 0) PCH_LAUNCH("sel_hist0", sel_hist_k<0>, grid, blk, 0, s, base, n, stride, w.st, w.hist);
-        else if (pass == 1) PCH_LAUNCH("sel_hist1", sel_hist_k<1>, grid, blk, 0, s, base, n, stride, w.st, w.hist);
-        else PCH_LAUNCH("sel_hist2", sel_hist_k<2>, grid, blk, 0, s, base, n, stride, w.st, w.hist);
+        const SelGate always = {nullptr, nullptr, nullptr};
+        if (pass == 0)
+            PCH_LAUNCH("sel_hist0", (sel_hist_k<0, 1>), grid, blk, 0, s, base, n, stride, w.run, w.hist, always);
+        else if (pass == 1)
+            PCH_LAUNCH("sel_hist1", (sel_hist_k<1, 1, false>), grid, blk, 0, s, base, n, stride, w.run, w.hist, always);
+        else
+            PCH_LAUNCH("sel_hist2", (sel_hist_k<2, 1, false>), grid, blk, 0, s, base, n, stride, w.run, w.hist, always);
     }
-    PCH_HIP_TRY(hipMemcpyAsync(out_hist, w.hist, sizeof(uint32_t) * SEL_BINS, hipMemcpyDeviceToDevice, s));
+    PCH_HIP_TRY(hipMemcpyAsync(out_hist, hist, sizeof(uint32_t) * SEL_BINS, hipMemcpyDeviceToDevice, s));
     if (out_nan)
-        PCH_HIP_TRY(hipMemcpyAsync(out_nan, &w.st->nan_count, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+        PCH_HIP_TRY(hipMemcpyAsync(out_nan, &w.run->nan_count, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
     PCH_HIP_TRY(hipStreamSynchronize(s));               // `h` lives on this stack frame
     return PCH_OK;
 }
@@ -1221,18 +1138,20 @@ extern "C" int pch_select_min_above_f32(const float* base, int64_t n, int64_t st
     SelWs w;
     sel_plan(a, w);
     if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
-    SelState h;
+    SelRun h;
     memset(&h, 0, sizeof(h));
-    h.need_next = 1;
-    h.v0key = key;
+    h.st[3].need_next = 1;
+    h.st[3].v0key = key;
     h.next_min = 0xFFFFFFFFu;
-    PCH_HIP_TRY(hipMemcpyAsync(w.st, &h, sizeof(h), hipMemcpyHostToDevice, s));
+    PCH_HIP_TRY(hipMemcpyAsync(w.run, &h, sizeof(h), hipMemcpyHostToDevice, s));
     if (n > 0) {
         int64_t gb = ceil_div(n, SEL_TILE);
         if (gb > 2048) gb = 2048;
-        PCH_LAUNCH("sel_next", sel_next_k, dim3((unsigned)gb), dim3(256), 0, s, base, n, stride, w.st);
+        const SelGate always = {nullptr, nullptr, nullptr};
+        PCH_LAUNCH("sel_next", sel_next_k<false>, dim3((unsigned)gb), dim3(256), 0, s, base, n, stride, w.run, w.hist,
+                   always);
     }
-    PCH_HIP_TRY(hipMemcpyAsync(out_key, &w.st->next_min, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    PCH_HIP_TRY(hipMemcpyAsync(out_key, &w.run->next_min, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     PCH_HIP_TRY(hipStreamSynchronize(s));
     return PCH_OK;
 }
