@@ -1922,24 +1922,37 @@ static void db_plan(Arena& a, int64_t n, DbWs& w) {
     w.flag2 = a.take<uint32_t>(nn + 8);
 }
 
-// PCH_DBSCAN_SORT (chunk | global), read once per process unless pch_dbscan_set_sort_mode() overrides it:
-// 0 automatic, 1 chunk-local, 2 global
+// The cell table in the parameter order of the neighbour kernels: db_core_k takes DB_GRID_ARGS (and writes core_s /
+// cell_ncore), db_union*_k and db_border_k take DB_CELL_ARGS
+struct DbCells {
+    DbGrid g; const float4* pts; const uint32_t* cell_start; const uint64_t* cell_key; int m;
+    const int2* rowtab;          // null: more cells than the row table holds, rows are searched on the fly
+    const uint8_t* core_s; const uint32_t* cell_ncore; const float* cell_box;
+};
+#define DB_GRID_ARGS(c) (c).g, (c).pts, (c).cell_start, (c).cell_key, (c).m, (c).rowtab
+#define DB_CELL_ARGS(c) DB_GRID_ARGS(c), (c).core_s, (c).cell_ncore, (c).cell_box
+
+// Stage C's tuning switches, read here only, once per process.  PCH_DBSCAN_SORT=chunk|global: the cell sort (0
+// automatic, 1 chunk-local, 2 global), which pch_dbscan_set_sort_mode() overrides for the whole process.
+// PCH_DB_NO_BOXFOLD: no cluster boxes folded into the label kernels.  PCH_DB_NO_XCD: db_label_k's blocks in sorted
+// order, not by XCD.  Pair counting (pch_dbscan_set_pair_counting) is set per thread.
+struct DbTuning { int sort_mode; bool no_boxfold, no_xcd, count_pairs; };
 static int g_sort_mode = -1;
-static int db_sort_mode() {
+static thread_local bool g_count_pairs = false;
+static DbTuning db_tuning() {
+    static const bool no_boxfold = getenv("PCH_DB_NO_BOXFOLD") != nullptr, no_xcd = getenv("PCH_DB_NO_XCD") != nullptr;
     int m = __atomic_load_n(&g_sort_mode, __ATOMIC_RELAXED);
     if (m < 0) {
         const char* e = getenv("PCH_DBSCAN_SORT");
         m = (e && strcmp(e, "chunk") == 0) ? 1 : (e && strcmp(e, "global") == 0) ? 2 : 0;
         __atomic_store_n(&g_sort_mode, m, __ATOMIC_RELAXED);
     }
-    return m;
+    return {m, no_boxfold, no_xcd, g_count_pairs};
 }
 
-static thread_local bool g_count_pairs = false;
-
-// what pch_dbscan_relabel_i32 needs to know about the run whose workspace it continues
-struct DbLastRun { void* ws; size_t ws_bytes; int64_t n; int m; DbGrid g; bool has_rowtab; };
-static thread_local DbLastRun g_last = {nullptr, 0, 0, 0, {}, false};
+// the run whose workspace the entries below continue, and its cell table
+struct DbLastRun { void* ws; size_t ws_bytes; int64_t n; DbCells c; };
+static thread_local DbLastRun g_last = {nullptr, 0, 0, {}};
 
 void ws_touched(const void* base, size_t bytes) {
     if (!g_last.ws) return;
@@ -1948,12 +1961,317 @@ void ws_touched(const void* base, size_t bytes) {
     if (a0 < b0 + g_last.ws_bytes && b0 < a0 + bytes) g_last.ws = nullptr;
 }
 
+// The entry points that continue the grid the last pch_dbscan_f32 of this thread left in `ws` carve it up again
+// here; `entry` names the caller in the error
+static int db_continue(const char* entry, int64_t n, void* ws, size_t ws_bytes, DbWs& w) {
+    if (g_last.ws != ws || g_last.ws_bytes != ws_bytes || g_last.n != n || ws == nullptr) {
+        set_error("%s must follow pch_dbscan_f32 of this thread on the same, untouched workspace", entry);
+        return PCH_ERR_ARG;
+    }
+    Arena a(ws, ws_bytes, true);
+    db_plan(a, n, w);
+    return PCH_OK;
+}
+
 // host mirror of f32_unordered
 static float host_unordered(uint32_t k) {
     uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
     float f;
     memcpy(&f, &u, 4);
     return f;
+}
+
+// blocks of the grid-stride sweeps over the input rows (db_aabb_in_k, db_first_bad_k, db_chunkbad_k)
+static unsigned db_stride_blocks(int64_t n) { return (unsigned)std::min(ceil_div(n, DB_THREADS * 8), int64_t(2048)); }
+
+// ---- the steps of dbscan_run, in the order it runs them
+// what they share: the run's rows, outputs, stream and carved workspace
+struct DbRun {
+    const float* xyz; int64_t n, chunk_size, nchunks;
+    int32_t* labels; uint8_t* core; int32_t* out_nclusters;
+    hipStream_t s; DbWs w;
+};
+
+static int db_all_noise(const DbRun& r) {
+    PCH_HIP_TRY(hipMemsetAsync(r.labels, 0xFF, sizeof(int32_t) * (size_t)r.n, r.s));
+    if (r.core) PCH_HIP_TRY(hipMemsetAsync(r.core, 0, (size_t)r.n, r.s));
+    PCH_HIP_TRY(hipMemsetAsync(r.out_nclusters, 0, sizeof(int32_t), r.s));
+    return PCH_OK;
+}
+
+// bounding box: the caller's host copy, or measured over the finite rows.  done: not one finite row, the outputs
+// are written
+static int db_bounds(const DbRun& r, const float* aabb_host, float (&box)[6], bool& done) {
+    if (aabb_host) {
+        memcpy(box, aabb_host, sizeof(box));
+    } else {
+        uint32_t* meta = r.w.meta;
+        PCH_HIP_TRY(hipMemsetAsync(meta, 0xFF, 3 * sizeof(uint32_t), r.s));
+        PCH_HIP_TRY(hipMemsetAsync(meta + 3, 0, 3 * sizeof(uint32_t), r.s));
+        PCH_LAUNCH("db_aabb_in", db_aabb_in_k, dim3(db_stride_blocks(r.n)), dim3(DB_THREADS), 0, r.s, r.xyz, r.n, meta);
+        uint32_t mm[6];
+        PCH_HIP_TRY(hipMemcpyAsync(mm, meta, sizeof(mm), hipMemcpyDeviceToHost, r.s));
+        PCH_HIP_TRY(hipStreamSynchronize(r.s));
+        if (mm[0] == 0xFFFFFFFFu) {                        // not a single finite point: every chunk fails
+            done = true;
+            return db_all_noise(r);
+        }
+        for (int k = 0; k < 6; ++k) box[k] = host_unordered(mm[k]);
+    }
+    for (int k = 0; k < 6; ++k) {
+        if (!(box[k] == box[k]) || box[k] > 3.0e38f || box[k] < -3.0e38f) {
+            set_error("bounding box is not finite");
+            return PCH_ERR_ARG;
+        }
+    }
+    return PCH_OK;
+}
+
+// largest cell coordinate per axis -> g.mx..mz and the key bits per axis; returns the bits of a cell
+static int db_cell_bits(DbGrid& g, int mx, int my, int mz) {
+    g.mx = mx; g.my = my; g.mz = mz;
+    g.bx = bits_for((uint64_t)mx + 1); g.by = bits_for((uint64_t)my + 1); g.bz = bits_for((uint64_t)mz + 1);
+    return g.bx + g.by + g.bz;
+}
+
+// the grid of cells of side eps/sqrt(3) over the box, and the bits of its key: a cell (cellbits), then the chunk
+// (nbits in all).  Returns true when that key does not fit 64 bits.
+static bool db_grid(const DbRun& r, const float (&box)[6], double eps, int32_t min_samples, DbGrid& g, int& cellbits,
+                    int& nbits) {
+    g.ox = box[0]; g.oy = box[1]; g.oz = box[2];
+    g.cell = eps / 1.7320508075688772 * (1.0 - 1.0 / 65536.0);
+    g.inv_cell = 1.0 / g.cell;
+    g.eps2 = eps * eps;
+    g.eps2_lo = nextafterf((float)(g.eps2 * (1.0 - 1.0 / 1048576.0)), -INFINITY);
+    g.eps2_hi = nextafterf((float)(g.eps2 * (1.0 + 1.0 / 1048576.0)), INFINITY);
+    if (!(g.eps2_hi < 3.0e38f)) { g.eps2_lo = -1.0f; g.eps2_hi = NAN; }    // absurd eps: exact path only
+    g.chunk_size = r.chunk_size;
+    g.chunk_bad = r.w.chunk_bad;
+    g.chunk_cells = r.w.chunk_cells;
+    g.min_samples = min_samples;
+    int mc[3] = {0, 0, 0};
+    bool overflow = false;
+    for (int k = 0; k < 3; ++k) {
+        const double ext = ((double)box[3 + k] - (double)box[k]) * g.inv_cell;
+        if (!(ext < 2.0e9)) overflow = true;
+        else mc[k] = (int)ext + 1;            // +1: slack for the rounding of the division
+    }
+    cellbits = db_cell_bits(g, mc[0], mc[1], mc[2]);
+    nbits = cellbits + bits_for((uint64_t)r.nchunks);
+    return overflow || nbits > 64;
+}
+
+// key beyond 64 bits, several chunks: every chunk on its own, with its own bounding box (the reference fits them one
+// by one anyway)
+static int db_run_chunks(const DbRun& r, double eps, int32_t min_samples, void* ws, size_t ws_bytes, int32_t* k_host) {
+    int32_t offset = 0;
+    for (int64_t c = 0; c < r.nchunks; ++c) {
+        const int64_t lo = c * r.chunk_size, cn = (r.n - lo) < r.chunk_size ? (r.n - lo) : r.chunk_size;
+        int32_t kc = 0;
+        PCH_TRY(dbscan_run(r.xyz + 3 * lo, cn, eps, min_samples, 0, nullptr, r.labels + lo,
+                           r.core ? r.core + lo : nullptr, r.out_nclusters, ws, ws_bytes, r.s, &kc));
+        if (kc > 0 && offset > 0)
+            PCH_LAUNCH("db_add_offset", db_add_offset_k, dim3((unsigned)ceil_div(cn, DB_THREADS)), dim3(DB_THREADS), 0,
+                       r.s, r.labels + lo, cn, offset);
+        offset += kc;                    // utils/tower_extraction.py:114-116
+    }
+    PCH_HIP_TRY(hipMemcpyAsync(r.out_nclusters, &offset, sizeof(int32_t), hipMemcpyHostToDevice, r.s));
+    PCH_HIP_TRY(hipStreamSynchronize(r.s));
+    if (k_host) *k_host = offset;
+    g_last.ws = nullptr;                 // no single grid is left to relabel on
+    return PCH_OK;
+}
+
+// key beyond 64 bits, one chunk: compressed cell coordinates per axis (w.comp, see dbc_axis_keys_k) and the grid's
+// mx..bz / cellbits over them.  done: the outputs are written
+static int db_compress(const DbRun& r, DbGrid& g, int& cellbits, bool& done) {
+    const DbWs& w = r.w; const hipStream_t s = r.s; const int64_t n = r.n;
+    const unsigned gn = (unsigned)ceil_div(n, DB_THREADS);
+    int64_t* first_bad = reinterpret_cast<int64_t*>(w.meta + 12);
+    PCH_HIP_TRY(hipMemsetAsync(first_bad, 0xFF, sizeof(int64_t), s));
+    PCH_LAUNCH("db_first_bad", db_first_bad_k, dim3(db_stride_blocks(n)), dim3(DB_THREADS), 0, s, r.xyz, n,
+               reinterpret_cast<unsigned long long*>(first_bad));
+    PCH_HIP_TRY(hipMemsetAsync(w.meta + 6, 0, 6 * sizeof(uint32_t), s));
+    for (int axis = 0; axis < 3; ++axis) {
+        PCH_LAUNCH("dbc_axis_keys", dbc_axis_keys_k, dim3(gn), dim3(DB_THREADS), 0, s, r.xyz, n, axis, w.k0, w.v0);
+        PCH_TRY(radix_sort_pairs(w.k0, w.v0, w.k1, w.v1, n, 32, w.radix_ws, s));
+        const bool in1 = radix_sort_result_buffer(32) == 1;
+        const uint64_t* ksa = in1 ? w.k1 : w.k0;
+        const uint32_t* vsa = in1 ? w.v1 : w.v0;
+        PCH_LAUNCH("dbc_heads", dbc_heads_k, dim3(gn), dim3(DB_THREADS), 0, s, ksa, n, g.inv_cell, w.flag2);
+        PCH_TRY(scan_exclusive_u32(w.flag2, w.head, n, w.scan_ws, nullptr, s));
+        PCH_HIP_TRY(hipMemsetAsync(w.cell_start, 0, sizeof(uint32_t) * (size_t)(n + 8), s));
+        for (int phase = 0; phase < 2; ++phase)
+            PCH_LAUNCH("dbc_local", dbc_local_k, dim3(gn), dim3(DB_THREADS), 0, s, ksa, w.flag2, w.head, n, g.inv_cell,
+                       w.cell_box, phase, w.cid, w.cell_start, w.meta + 6);
+        PCH_TRY(scan_exclusive_u32(w.cell_start, w.cell_start, n, w.scan_ws, nullptr, s));
+        PCH_LAUNCH("dbc_comp", dbc_comp_k, dim3(gn), dim3(DB_THREADS), 0, s, vsa, w.flag2, w.head, w.cid, w.cell_start,
+                   n, axis, w.comp, w.meta + 9);
+    }
+    uint32_t back[8];                        // [0] status, [3..5] largest compressed index per axis, [6..7] first bad row
+    PCH_HIP_TRY(hipMemcpyAsync(back, w.meta + 6, sizeof(back), hipMemcpyDeviceToHost, s));
+    PCH_HIP_TRY(hipStreamSynchronize(s));
+    int64_t bad_row;
+    memcpy(&bad_row, &back[6], sizeof(bad_row));
+    if (bad_row >= 0) {                      // NaN / inf in a single fit: sklearn rejects it, everything stays noise
+        PCH_TRY(db_all_noise(r));
+        g_last.ws = nullptr;
+        done = true;
+        return PCH_OK;
+    }
+    if (back[0] != 0) { set_error("compressed cell coordinates out of range"); return PCH_ERR_RANGE; }
+    cellbits = db_cell_bits(g, (int)back[3], (int)back[4], (int)back[5]);
+    if (cellbits > 64) {
+        set_error("cell key needs %d bits even with compressed coordinates (%lld isolated points?)", cellbits, (long long)n);
+        return PCH_ERR_RANGE;
+    }
+    return PCH_OK;
+}
+
+// the cell keys in sorted order (ks) and the points in that order (w.pts)
+static int db_sorted_keys(const DbRun& r, const DbGrid& g, int cellbits, int nbits, bool compressed, int sort_mode,
+                          const uint64_t*& ks) {
+    const DbWs& w = r.w; const hipStream_t s = r.s; const int64_t n = r.n, nchunks = r.nchunks;
+    const unsigned gn = (unsigned)ceil_div(n, DB_THREADS);
+    // status / cell count / cluster count words and the per-chunk first-cell table, in one 16-byte aligned fill
+    // (meta[4..5] are bounding-box keys nobody reads any more; chunk_cells is written at the first cell of every
+    // chunk by db_cells_k, the zeros make a chunk without a cell an empty range)
+    const size_t bytes = (size_t)(reinterpret_cast<char*>(w.chunk_cells + nchunks + 1) - reinterpret_cast<char*>(w.meta + 4));
+    PCH_HIP_TRY(hipMemsetAsync(w.meta + 4, 0, (bytes + 15) & ~size_t(15), s));
+    // One workgroup per chunk only pays with enough chunks to fill the GPU (measured break-even near
+    // 100 chunks of 50 000 rows); PCH_DBSCAN_SORT=chunk / global forces a path (tests compare them)
+    if (!compressed && cellbits <= 32 && r.chunk_size <= CS_MAX_CHUNK && sort_mode != 2 &&
+        (sort_mode == 1 || nchunks >= CS_MIN_CHUNKS)) {
+        // chunk-local path: one workgroup per chunk builds keys, sorts and gathers
+        PCH_LAUNCH("db_chunksort", db_chunksort_k, dim3((unsigned)nchunks), dim3(CS_THREADS), 0, s, r.xyz, n, g,
+                   w.chunk_bad, w.xbuf, w.pts, w.k1, w.meta + 6, (unsigned long long*)w.cell_box);
+#ifdef PCH_CS_STAMPS
+        {
+            unsigned long long t[11];                    // start | sweep B | sweep H | one per pass | heads
+            PCH_HIP_TRY(hipStreamSynchronize(s));
+            PCH_HIP_TRY(hipMemcpy(t, w.cell_box, sizeof(t), hipMemcpyDeviceToHost));
+            for (int q = 1; q <= 6; ++q)
+                fprintf(stderr, "chunksort phase %d: %.2f us\n", q, (double)(long long)(t[q] - t[q - 1]) / 100.0);
+            fprintf(stderr, "chunksort tiles: rank %.2f us, offsets %.2f us, scatter %.2f us\n", (double)t[8] / 100.0,
+                    (double)t[9] / 100.0, (double)t[10] / 100.0);
+        }
+#endif
+        ks = w.k1;
+        return PCH_OK;
+    }
+    // compressed or global: keys, one radix sort of all rows, gather
+    PCH_HIP_TRY(hipMemsetAsync(w.chunk_bad, 0, sizeof(uint32_t) * (size_t)(nchunks + 1), s));
+    if (compressed) {
+        PCH_LAUNCH("db_keys_comp", db_keys_comp_k, dim3(gn), dim3(DB_THREADS), 0, s, w.comp, n, g, w.k0, w.v0);
+    } else {
+        PCH_LAUNCH("db_chunkbad", db_chunkbad_k, dim3(db_stride_blocks(n)), dim3(DB_THREADS), 0, s, r.xyz, n,
+                   r.chunk_size, w.chunk_bad);
+        PCH_LAUNCH("db_keys", db_keys_k, dim3(gn), dim3(DB_THREADS), 0, s, r.xyz, n, g, w.chunk_bad, w.k0, w.v0,
+                   w.meta + 6);
+    }
+    PCH_TRY(radix_sort_pairs(w.k0, w.v0, w.k1, w.v1, n, nbits, w.radix_ws, s));
+    const bool in1 = radix_sort_result_buffer(nbits) == 1;
+    ks = in1 ? w.k1 : w.k0;
+    PCH_LAUNCH("db_gather", db_gather_k, dim3(gn), dim3(DB_THREADS), 0, s, r.xyz, ks, in1 ? w.v1 : w.v0, n, w.pts);
+    return PCH_OK;
+}
+
+// the cells of the sorted keys, their row table, the core flags and the per-cell statistics; c: the cell table
+static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const uint64_t* ks, bool count_pairs,
+                         DbCells& c) {
+    const DbWs& w = r.w; const hipStream_t s = r.s; const int64_t n = r.n;
+    const int64_t ntile = ceil_div(n, (int64_t)SCAN_TILE);
+    PCH_LAUNCH("db_heads", db_heads_k, dim3((unsigned)ntile), dim3(DB_THREADS), 0, s, ks, n, w.scan_ws);
+    PCH_TRY(scan_tile_sums_u32(w.scan_ws, ntile, w.meta + 7, s));
+    // the cell count sizes the next grids: fetch it while db_cells_k (sized by n) runs
+    uint32_t st_m[2];
+    PCH_TRY(peek_enqueue(w.meta + 6, sizeof(st_m), s));
+    PCH_LAUNCH("db_cells", db_cells_k, dim3((unsigned)ntile), dim3(DB_THREADS), 0, s, ks, w.scan_ws, n, cellbits,
+               r.nchunks, w.cid, w.cell_start, w.cell_key, w.chunk_cells, w.cell_acc);
+    PCH_TRY(peek_wait(st_m, sizeof(st_m)));
+    if (st_m[0] != 0) {
+        set_error("finite coordinates outside the supplied bounding box");
+        return PCH_ERR_ARG;
+    }
+    const int m = (int)st_m[1];
+    const unsigned gc = (unsigned)ceil_div(m, DB_WAVES);
+    c = {g, w.pts, w.cell_start, w.cell_key, m, m <= w.rowtab_cells ? w.rowtab : nullptr, w.core_s, w.cell_ncore,
+         w.cell_box};
+    if (c.rowtab)
+        PCH_LAUNCH("db_rowtab", db_rowtab_k, dim3((unsigned)ceil_div(m, 2 * DB_WAVES)), dim3(DB_THREADS), 0, s, g,
+                   w.cell_key, m, w.rowtab);
+    if (count_pairs) {
+        PCH_HIP_TRY(hipMemsetAsync(w.core_stats, 0, 4 * sizeof(unsigned long long), s));
+        PCH_LAUNCH("db_core_counting", db_core_k<true>, dim3(gc), dim3(DB_THREADS), 0, s, DB_GRID_ARGS(c), w.core_s,
+                   w.cell_ncore, w.core_stats);
+    } else {
+        PCH_LAUNCH("db_core", db_core_k<false>, dim3(gc), dim3(DB_THREADS), 0, s, DB_GRID_ARGS(c), w.core_s,
+                   w.cell_ncore, nullptr);
+    }
+    PCH_LAUNCH("db_cellstats", db_cellstats_k, dim3((unsigned)ceil_div(n, (int64_t)DB_WAVES * 64 * DB_CS_ROUNDS)),
+               dim3(DB_THREADS), 0, s, w.pts, w.cid, w.core_s, n, w.cell_acc, w.flag, ceil_div(n, 32));
+    PCH_LAUNCH("db_cellfin", db_cellfin_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
+               w.cell_acc, m, w.cell_box, w.cell_min, w.parent, w.comp_min);
+    return PCH_OK;
+}
+
+// clusters of the core cells: union-find over their links, each component's smallest core row
+static int db_union(const DbRun& r, const DbCells& c) {
+    const DbWs& w = r.w; const hipStream_t s = r.s; const int m = c.m;
+    const unsigned gc = (unsigned)ceil_div(m, DB_WAVES);
+    // face neighbours: lane-per-pair first (needs the row table), the wave-wide search for what that left open;
+    // the flags live in w.root, which nobody needs before db_compmin_k
+    const uint8_t* face_todo = nullptr;
+    if (c.rowtab) {
+        PCH_LAUNCH("db_union_pairs", db_union_pairs_k, dim3((unsigned)ceil_div(4 * (int64_t)m, DB_THREADS)),
+                   dim3(DB_THREADS), 0, s, DB_CELL_ARGS(c), w.parent, reinterpret_cast<uint8_t*>(w.root));
+        face_todo = reinterpret_cast<const uint8_t*>(w.root);
+    }
+    PCH_LAUNCH("db_union0", db_union_face_k, dim3(gc), dim3(DB_THREADS), 0, s, DB_CELL_ARGS(c), w.parent, face_todo);
+    PCH_LAUNCH("db_flatten", db_flatten_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
+               w.parent, m);
+    PCH_LAUNCH("db_union1", db_union_k, dim3(gc), dim3(DB_THREADS), 0, s, DB_CELL_ARGS(c), w.parent);
+    PCH_LAUNCH("db_compmin", db_compmin_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
+               w.cell_min, w.cell_ncore, m, w.parent, w.root, w.comp_min);
+    return PCH_OK;
+}
+
+// the labels of core and border rows (and, with `boxes`, the cluster boxes folded in); k_host: the cluster count
+static int db_labels(const DbRun& r, const DbCells& c, const DbTuning& tune, int32_t* k_host, DbBoxOut* boxes) {
+    const DbWs& w = r.w; const hipStream_t s = r.s; const int64_t n = r.n, nchunks = r.nchunks; const int m = c.m;
+    // cluster id = rank of the cluster's smallest core row: a bitmap over the rows + a scan of its
+    // word counts (n/32 elements instead of n)
+    const int64_t nw = ceil_div(n, 32);
+    uint32_t* bits = w.flag;
+    uint32_t* wrank = w.flag + ((nw + 63) & ~int64_t(63));
+    static_assert(DB_CS_ROUNDS * 64 * DB_WAVES / DB_THREADS <= 32, "db_cellstats_k's grid has a thread per bitmap word");
+    PCH_LAUNCH("db_mark", db_mark_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
+               w.root, w.comp_min, m, bits);
+    // word ranks: popcount on load
+    if (scan1_pays(nw)) PCH_TRY(scan1_exclusive_popc_u32(bits, wrank, nw, w.scan1_b, w.meta + 8, s));
+    else PCH_TRY(scan_exclusive_popc_u32(bits, wrank, nw, w.scan_ws, w.meta + 8, s));
+    uint32_t* box_acc = (boxes && boxes->acc && boxes->cap > 0 && !tune.no_boxfold) ? boxes->acc : nullptr;
+    const int32_t box_cap = box_acc ? boxes->cap : 0;
+    PCH_LAUNCH("db_prelabel", db_prelabel_k, dim3((unsigned)(box_acc ? ceil_div(8 * (int64_t)box_cap, 256) : 1)),
+               dim3(256), 0, s, w.meta + 8, r.out_nclusters, box_acc, 8 * (int64_t)box_cap);
+    if (k_host) PCH_TRY(peek_enqueue(r.out_nclusters, sizeof(int32_t), s));    // read while the labels are written
+    // many chunks: the blocks of one chunk share an XCD (see db_label_k); otherwise blocks in sorted order
+    const int bpc = (nchunks >= 16 && !tune.no_xcd) ? (int)ceil_div(r.chunk_size, DB_LAB_TILE) : 0;
+    const unsigned gl = bpc > 0 ? (unsigned)(8 * ceil_div(nchunks, 8) * bpc) : (unsigned)ceil_div(n, DB_LAB_TILE);
+    PCH_LAUNCH("db_label", db_label_k, dim3(gl), dim3(DB_THREADS), 0, s, w.pts, w.cid, w.core_s, w.root, w.comp_min,
+               bits, wrank, n, w.cell_start, w.cell_label, r.labels, r.core, r.chunk_size, bpc, nchunks, box_acc,
+               box_cap);
+    PCH_LAUNCH("db_border", db_border_k, dim3((unsigned)ceil_div(m, DB_WAVES)), dim3(DB_THREADS), 0, s,
+               DB_CELL_ARGS(c), w.cell_label, r.labels, box_acc, box_cap);
+    if (box_acc) boxes->done = true;
+    if (k_host) {
+        PCH_TRY(peek_wait(k_host, sizeof(int32_t)));
+        if (*k_host < 0) {                              // the rank scan's bounded wait gave up: the count reads -1
+            set_error("stage C: a device-side look-back wait ran out of its budget; outputs are undefined");
+            return PCH_ERR_TIMEOUT;
+        }
+    }
+    return PCH_OK;
 }
 
 }  // namespace pch
@@ -1966,9 +2284,7 @@ extern "C" int pch_first_nonfinite_row_f32(const float* xyz, int64_t n, int64_t*
     PCH_REQUIRE(n >= 0 && out_row && (n == 0 || xyz), "bad argument");
     PCH_HIP_TRY(hipMemsetAsync(out_row, 0xFF, sizeof(int64_t), s));             // -1: every row finite
     if (n == 0) return PCH_OK;
-    int64_t gb = ceil_div(n, DB_THREADS * 8);
-    if (gb > 2048) gb = 2048;
-    PCH_LAUNCH("db_first_bad", db_first_bad_k, dim3((unsigned)gb), dim3(DB_THREADS), 0, s, xyz, n,
+    PCH_LAUNCH("db_first_bad", db_first_bad_k, dim3(db_stride_blocks(n)), dim3(DB_THREADS), 0, s, xyz, n,
                reinterpret_cast<unsigned long long*>(out_row));
     return PCH_OK;
 }
@@ -2004,277 +2320,31 @@ int pch::dbscan_run(const float* xyz, int64_t n, double eps, int32_t min_samples
     db_plan(a, n, w);
     if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
     if (chunk_size <= 0 || chunk_size > n) chunk_size = n;
-    const int64_t nchunks = ceil_div(n, chunk_size);
+    const DbRun r = {xyz, n, chunk_size, ceil_div(n, chunk_size), labels, core, out_nclusters, s, w};
+    const DbTuning tune = db_tuning();
 
-    int64_t gstride = ceil_div(n, DB_THREADS * 8);
-    if (gstride > 2048) gstride = 2048;
     float box[6];
-    if (aabb_host) {
-        memcpy(box, aabb_host, sizeof(box));
-    } else {
-        PCH_HIP_TRY(hipMemsetAsync(w.meta, 0xFF, 3 * sizeof(uint32_t), s));
-        PCH_HIP_TRY(hipMemsetAsync(w.meta + 3, 0, 3 * sizeof(uint32_t), s));
-        PCH_LAUNCH("db_aabb_in", db_aabb_in_k, dim3((unsigned)gstride), dim3(DB_THREADS), 0, s, xyz, n, w.meta);
-        uint32_t mm[6];
-        PCH_HIP_TRY(hipMemcpyAsync(mm, w.meta, sizeof(mm), hipMemcpyDeviceToHost, s));
-        PCH_HIP_TRY(hipStreamSynchronize(s));
-        if (mm[0] == 0xFFFFFFFFu) {                        // not a single finite point: every chunk fails
-            PCH_HIP_TRY(hipMemsetAsync(labels, 0xFF, sizeof(int32_t) * (size_t)n, s));
-            if (core) PCH_HIP_TRY(hipMemsetAsync(core, 0, (size_t)n, s));
-            PCH_HIP_TRY(hipMemsetAsync(out_nclusters, 0, sizeof(int32_t), s));
-            return PCH_OK;
-        }
-        for (int k = 0; k < 6; ++k) box[k] = host_unordered(mm[k]);
-    }
-    for (int k = 0; k < 6; ++k) {
-        if (!(box[k] == box[k]) || box[k] > 3.0e38f || box[k] < -3.0e38f) {
-            set_error("bounding box is not finite");
-            return PCH_ERR_ARG;
-        }
-    }
+    bool done = false;
+    PCH_TRY(db_bounds(r, aabb_host, box, done));
+    if (done) return PCH_OK;
     DbGrid g;
-    g.ox = box[0]; g.oy = box[1]; g.oz = box[2];
-    g.cell = eps / 1.7320508075688772 * (1.0 - 1.0 / 65536.0);
-    g.inv_cell = 1.0 / g.cell;
-    g.eps2 = eps * eps;
-    g.eps2_lo = nextafterf((float)(g.eps2 * (1.0 - 1.0 / 1048576.0)), -INFINITY);
-    g.eps2_hi = nextafterf((float)(g.eps2 * (1.0 + 1.0 / 1048576.0)), INFINITY);
-    if (!(g.eps2_hi < 3.0e38f)) { g.eps2_lo = -1.0f; g.eps2_hi = NAN; }    // absurd eps: exact path only
-    g.chunk_size = chunk_size;
-    g.chunk_bad = w.chunk_bad;
-    g.chunk_cells = w.chunk_cells;
-    g.min_samples = min_samples;
-    double ext[3];
-    int mc[3] = {0, 0, 0};
-    bool overflow = false;
-    for (int k = 0; k < 3; ++k) {
-        ext[k] = ((double)box[3 + k] - (double)box[k]) * g.inv_cell;
-        if (!(ext[k] < 2.0e9)) overflow = true;
-        else mc[k] = (int)ext[k] + 1;            // +1: slack for the rounding of the division
-    }
-    g.mx = mc[0]; g.my = mc[1]; g.mz = mc[2];
-    g.bx = bits_for((uint64_t)g.mx + 1);
-    g.by = bits_for((uint64_t)g.my + 1);
-    g.bz = bits_for((uint64_t)g.mz + 1);
-    int cellbits = g.bx + g.by + g.bz;
-    int nbits = cellbits + bits_for((uint64_t)nchunks);
-    if (nbits > 64) overflow = true;
-    const unsigned gn = (unsigned)ceil_div(n, DB_THREADS);
-    bool compressed = false;
+    int cellbits, nbits;
+    const bool overflow = db_grid(r, box, eps, min_samples, g, cellbits, nbits);
     if (overflow) {
-        // extent/eps beyond the 64-bit cell key (outliers, heavy tails).  Several chunks: every chunk on its own,
-        // with its own bounding box (the reference fits them one by one anyway).  One chunk: compressed coordinates.
-        if (nchunks > 1) {
-            int32_t offset = 0;
-            for (int64_t c = 0; c < nchunks; ++c) {
-                const int64_t lo = c * chunk_size, cn = (n - lo) < chunk_size ? (n - lo) : chunk_size;
-                int32_t kc = 0;
-                PCH_TRY(dbscan_run(xyz + 3 * lo, cn, eps, min_samples, 0, nullptr, labels + lo, core ? core + lo : nullptr,
-                                   out_nclusters, ws, ws_bytes, s, &kc));
-                if (kc > 0 && offset > 0)
-                    PCH_LAUNCH("db_add_offset", db_add_offset_k, dim3((unsigned)ceil_div(cn, DB_THREADS)), dim3(DB_THREADS), 0, s,
-                               labels + lo, cn, offset);
-                offset += kc;                    // utils/tower_extraction.py:114-116
-            }
-            PCH_HIP_TRY(hipMemcpyAsync(out_nclusters, &offset, sizeof(int32_t), hipMemcpyHostToDevice, s));
-            PCH_HIP_TRY(hipStreamSynchronize(s));
-            if (k_host) *k_host = offset;
-            g_last.ws = nullptr;                 // no single grid is left to relabel on
-            return PCH_OK;
-        }
-        compressed = true;
-        int64_t* first_bad = reinterpret_cast<int64_t*>(w.meta + 12);
-        PCH_HIP_TRY(hipMemsetAsync(first_bad, 0xFF, sizeof(int64_t), s));
-        PCH_LAUNCH("db_first_bad", db_first_bad_k, dim3((unsigned)gstride), dim3(DB_THREADS), 0, s, xyz, n,
-                   reinterpret_cast<unsigned long long*>(first_bad));
-        PCH_HIP_TRY(hipMemsetAsync(w.meta + 6, 0, 6 * sizeof(uint32_t), s));
-        for (int axis = 0; axis < 3; ++axis) {
-            PCH_LAUNCH("dbc_axis_keys", dbc_axis_keys_k, dim3(gn), dim3(DB_THREADS), 0, s, xyz, n, axis, w.k0, w.v0);
-            PCH_TRY(radix_sort_pairs(w.k0, w.v0, w.k1, w.v1, n, 32, w.radix_ws, s));
-            const bool in1 = radix_sort_result_buffer(32) == 1;
-            const uint64_t* ksa = in1 ? w.k1 : w.k0;
-            const uint32_t* vsa = in1 ? w.v1 : w.v0;
-            PCH_LAUNCH("dbc_heads", dbc_heads_k, dim3(gn), dim3(DB_THREADS), 0, s, ksa, n, g.inv_cell, w.flag2);
-            PCH_TRY(scan_exclusive_u32(w.flag2, w.head, n, w.scan_ws, nullptr, s));
-            PCH_HIP_TRY(hipMemsetAsync(w.cell_start, 0, sizeof(uint32_t) * (size_t)(n + 8), s));
-            for (int phase = 0; phase < 2; ++phase)
-                PCH_LAUNCH("dbc_local", dbc_local_k, dim3(gn), dim3(DB_THREADS), 0, s, ksa, (const uint32_t*)w.flag2,
-                           (const uint32_t*)w.head, n, g.inv_cell, w.cell_box, phase, w.cid, w.cell_start, w.meta + 6);
-            PCH_TRY(scan_exclusive_u32(w.cell_start, w.cell_start, n, w.scan_ws, nullptr, s));
-            PCH_LAUNCH("dbc_comp", dbc_comp_k, dim3(gn), dim3(DB_THREADS), 0, s, vsa, (const uint32_t*)w.flag2,
-                       (const uint32_t*)w.head, (const uint32_t*)w.cid, (const uint32_t*)w.cell_start, n, axis, w.comp,
-                       w.meta + 9);
-        }
-        uint32_t back[8];                        // [0] status, [3..5] largest compressed index per axis, [6..7] first bad row
-        PCH_HIP_TRY(hipMemcpyAsync(back, w.meta + 6, sizeof(back), hipMemcpyDeviceToHost, s));
-        PCH_HIP_TRY(hipStreamSynchronize(s));
-        int64_t bad_row;
-        memcpy(&bad_row, &back[6], sizeof(bad_row));
-        if (bad_row >= 0) {                      // NaN / inf in a single fit: sklearn rejects it, everything stays noise
-            PCH_HIP_TRY(hipMemsetAsync(labels, 0xFF, sizeof(int32_t) * (size_t)n, s));
-            if (core) PCH_HIP_TRY(hipMemsetAsync(core, 0, (size_t)n, s));
-            PCH_HIP_TRY(hipMemsetAsync(out_nclusters, 0, sizeof(int32_t), s));
-            g_last.ws = nullptr;
-            return PCH_OK;
-        }
-        if (back[0] != 0) { set_error("compressed cell coordinates out of range"); return PCH_ERR_RANGE; }
-        g.mx = (int)back[3]; g.my = (int)back[4]; g.mz = (int)back[5];
-        g.bx = bits_for((uint64_t)g.mx + 1);
-        g.by = bits_for((uint64_t)g.my + 1);
-        g.bz = bits_for((uint64_t)g.mz + 1);
-        cellbits = g.bx + g.by + g.bz;
+        // extent/eps beyond the 64-bit cell key (outliers, heavy tails).  Several chunks: every chunk on its own.
+        // One chunk: compressed coordinates.
+        if (r.nchunks > 1) return db_run_chunks(r, eps, min_samples, ws, ws_bytes, k_host);
+        PCH_TRY(db_compress(r, g, cellbits, done));
+        if (done) return PCH_OK;
         nbits = cellbits;
-        if (nbits > 64) {
-            set_error("cell key needs %d bits even with compressed coordinates (%lld isolated points?)", nbits, (long long)n);
-            return PCH_ERR_RANGE;
-        }
-    }
-
-    {   // status / cell count / cluster count words and the per-chunk first-cell table, in one 16-byte aligned fill
-        // (meta[4..5] are bounding-box keys nobody reads any more; chunk_cells is written at the first cell of every
-        // chunk by db_cells_k, the zeros make a chunk without a cell an empty range)
-        const size_t bytes = (size_t)(reinterpret_cast<char*>(w.chunk_cells + nchunks + 1) - reinterpret_cast<char*>(w.meta + 4));
-        PCH_HIP_TRY(hipMemsetAsync(w.meta + 4, 0, (bytes + 15) & ~size_t(15), s));
     }
     const uint64_t* ks;
-    // One workgroup per chunk only pays with enough chunks to fill the GPU (measured break-even near
-    // 100 chunks of 50 000 rows); PCH_DBSCAN_SORT=chunk / global forces a path (tests compare them)
-    const int sort_mode = db_sort_mode();
-    const bool force_global = sort_mode == 2;
-    const bool force_chunk = sort_mode == 1;
-    if (compressed) {
-        PCH_HIP_TRY(hipMemsetAsync(w.chunk_bad, 0, sizeof(uint32_t) * (size_t)(nchunks + 1), s));
-        PCH_LAUNCH("db_keys_comp", db_keys_comp_k, dim3(gn), dim3(DB_THREADS), 0, s, (const uint32_t*)w.comp, n, g, w.k0,
-                   w.v0);
-        PCH_TRY(radix_sort_pairs(w.k0, w.v0, w.k1, w.v1, n, nbits, w.radix_ws, s));
-        const bool in1 = radix_sort_result_buffer(nbits) == 1;
-        ks = in1 ? w.k1 : w.k0;
-        const uint32_t* vs = in1 ? w.v1 : w.v0;
-        PCH_LAUNCH("db_gather", db_gather_k, dim3(gn), dim3(DB_THREADS), 0, s, xyz, ks, vs, n, w.pts);
-    } else if (cellbits <= 32 && chunk_size <= CS_MAX_CHUNK && !force_global && (force_chunk || nchunks >= CS_MIN_CHUNKS)) {
-        // chunk-local path: one workgroup per chunk builds keys, sorts and gathers
-        PCH_LAUNCH("db_chunksort", db_chunksort_k, dim3((unsigned)nchunks), dim3(CS_THREADS), 0, s, xyz, n, g,
-                   w.chunk_bad, w.xbuf, w.pts, w.k1, w.meta + 6, (unsigned long long*)w.cell_box);
-#ifdef PCH_CS_STAMPS
-        {
-            unsigned long long t[11];                    // start | sweep B | sweep H | one per pass | heads
-            PCH_HIP_TRY(hipStreamSynchronize(s));
-            PCH_HIP_TRY(hipMemcpy(t, w.cell_box, sizeof(t), hipMemcpyDeviceToHost));
-            for (int q = 1; q <= 6; ++q)
-                fprintf(stderr, "chunksort phase %d: %.2f us\n", q, (double)(long long)(t[q] - t[q - 1]) / 100.0);
-            fprintf(stderr, "chunksort tiles: rank %.2f us, offsets %.2f us, scatter %.2f us\n", (double)t[8] / 100.0,
-                    (double)t[9] / 100.0, (double)t[10] / 100.0);
-        }
-#endif
-        ks = w.k1;
-    } else {
-        PCH_HIP_TRY(hipMemsetAsync(w.chunk_bad, 0, sizeof(uint32_t) * (size_t)(nchunks + 1), s));
-        PCH_LAUNCH("db_chunkbad", db_chunkbad_k, dim3((unsigned)gstride), dim3(DB_THREADS), 0, s, xyz, n,
-                   chunk_size, w.chunk_bad);
-        PCH_LAUNCH("db_keys", db_keys_k, dim3(gn), dim3(DB_THREADS), 0, s, xyz, n, g,
-                   (const uint32_t*)w.chunk_bad, w.k0, w.v0, w.meta + 6);
-        PCH_TRY(radix_sort_pairs(w.k0, w.v0, w.k1, w.v1, n, nbits, w.radix_ws, s));
-        const bool in1 = radix_sort_result_buffer(nbits) == 1;
-        ks = in1 ? w.k1 : w.k0;
-        const uint32_t* vs = in1 ? w.v1 : w.v0;
-        PCH_LAUNCH("db_gather", db_gather_k, dim3(gn), dim3(DB_THREADS), 0, s, xyz, ks, vs, n, w.pts);
-    }
-    const int64_t ntile = ceil_div(n, (int64_t)SCAN_TILE);
-    PCH_LAUNCH("db_heads", db_heads_k, dim3((unsigned)ntile), dim3(DB_THREADS), 0, s, ks, n, w.scan_ws);
-    PCH_TRY(scan_tile_sums_u32(w.scan_ws, ntile, w.meta + 7, s));
-    // the cell count sizes the next grids: fetch it while db_cells_k (sized by n) runs
-    uint32_t st_m[2];
-    PCH_TRY(peek_enqueue(w.meta + 6, sizeof(st_m), s));
-    PCH_LAUNCH("db_cells", db_cells_k, dim3((unsigned)ntile), dim3(DB_THREADS), 0, s, ks, (const uint32_t*)w.scan_ws, n,
-               cellbits, nchunks, w.cid, w.cell_start, w.cell_key, w.chunk_cells, w.cell_acc);
-    PCH_TRY(peek_wait(st_m, sizeof(st_m)));
-    if (st_m[0] != 0) {
-        set_error("finite coordinates outside the supplied bounding box");
-        return PCH_ERR_ARG;
-    }
-    const int m = (int)st_m[1];
-    const unsigned gc = (unsigned)ceil_div(m, DB_WAVES);
-    const int2* rowtab = nullptr;
-    if (m <= w.rowtab_cells) {
-        PCH_LAUNCH("db_rowtab", db_rowtab_k, dim3((unsigned)ceil_div(m, 2 * DB_WAVES)), dim3(DB_THREADS), 0, s,
-                   g, (const uint64_t*)w.cell_key, m, w.rowtab);
-        rowtab = w.rowtab;
-    }
-    if (g_count_pairs) {
-        PCH_HIP_TRY(hipMemsetAsync(w.core_stats, 0, 4 * sizeof(unsigned long long), s));
-        PCH_LAUNCH("db_core_counting", db_core_k<true>, dim3(gc), dim3(DB_THREADS), 0, s, g, (const float4*)w.pts,
-                   (const uint32_t*)w.cell_start, (const uint64_t*)w.cell_key, m, rowtab, w.core_s, w.cell_ncore,
-                   w.core_stats);
-    } else {
-        PCH_LAUNCH("db_core", db_core_k<false>, dim3(gc), dim3(DB_THREADS), 0, s, g, (const float4*)w.pts,
-                   (const uint32_t*)w.cell_start, (const uint64_t*)w.cell_key, m, rowtab, w.core_s, w.cell_ncore,
-                   (unsigned long long*)nullptr);
-    }
-    PCH_LAUNCH("db_cellstats", db_cellstats_k, dim3((unsigned)ceil_div(n, (int64_t)DB_WAVES * 64 * DB_CS_ROUNDS)),
-               dim3(DB_THREADS), 0, s, (const float4*)w.pts, (const uint32_t*)w.cid, (const uint8_t*)w.core_s, n,
-               w.cell_acc, w.flag, ceil_div(n, 32));
-    PCH_LAUNCH("db_cellfin", db_cellfin_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
-               (const uint32_t*)w.cell_acc, m, w.cell_box, w.cell_min, w.parent, w.comp_min);
-    // face neighbours: lane-per-pair first (needs the row table), the wave-wide search for what that left open;
-    // the flags live in w.root, which nobody needs before db_compmin_k
-    const uint8_t* face_todo = nullptr;
-    if (rowtab) {
-        PCH_LAUNCH("db_union_pairs", db_union_pairs_k, dim3((unsigned)ceil_div(4 * (int64_t)m, DB_THREADS)),
-                   dim3(DB_THREADS), 0, s, g, (const float4*)w.pts, (const uint32_t*)w.cell_start,
-                   (const uint64_t*)w.cell_key, m, rowtab, (const uint8_t*)w.core_s, (const uint32_t*)w.cell_ncore,
-                   (const float*)w.cell_box, w.parent, reinterpret_cast<uint8_t*>(w.root));
-        face_todo = reinterpret_cast<const uint8_t*>(w.root);
-    }
-    PCH_LAUNCH("db_union0", db_union_face_k, dim3(gc), dim3(DB_THREADS), 0, s, g, (const float4*)w.pts,
-               (const uint32_t*)w.cell_start, (const uint64_t*)w.cell_key, m, rowtab, (const uint8_t*)w.core_s,
-               (const uint32_t*)w.cell_ncore, (const float*)w.cell_box, w.parent, face_todo);
-    PCH_LAUNCH("db_flatten", db_flatten_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
-               w.parent, m);
-    PCH_LAUNCH("db_union1", db_union_k, dim3(gc), dim3(DB_THREADS), 0, s, g, (const float4*)w.pts,
-               (const uint32_t*)w.cell_start, (const uint64_t*)w.cell_key, m, rowtab, (const uint8_t*)w.core_s,
-               (const uint32_t*)w.cell_ncore, (const float*)w.cell_box, w.parent);
-    PCH_LAUNCH("db_compmin", db_compmin_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
-               (const int*)w.cell_min, (const uint32_t*)w.cell_ncore, m, w.parent, w.root, w.comp_min);
-    // cluster id = rank of the cluster's smallest core row: a bitmap over the rows + a scan of its
-    // word counts (n/32 elements instead of n)
-    const int64_t nw = ceil_div(n, 32);
-    uint32_t* bits = w.flag;
-    uint32_t* wrank = w.flag + ((nw + 63) & ~int64_t(63));
-    static_assert(DB_CS_ROUNDS * 64 * DB_WAVES / DB_THREADS <= 32, "db_cellstats_k's grid has a thread per bitmap word");
-    PCH_LAUNCH("db_mark", db_mark_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
-               (const int*)w.root, (const int*)w.comp_min, m, bits);
-    // word ranks: popcount on load
-    if (scan1_pays(nw)) PCH_TRY(scan1_exclusive_popc_u32(bits, wrank, nw, w.scan1_b, w.meta + 8, s));
-    else PCH_TRY(scan_exclusive_popc_u32(bits, wrank, nw, w.scan_ws, w.meta + 8, s));
-    static const bool no_fold = getenv("PCH_DB_NO_BOXFOLD") != nullptr;     // tuning toggle
-    uint32_t* box_acc = (boxes && boxes->acc && boxes->cap > 0 && !no_fold) ? boxes->acc : nullptr;
-    const int32_t box_cap = box_acc ? boxes->cap : 0;
-    PCH_LAUNCH("db_prelabel", db_prelabel_k, dim3((unsigned)(box_acc ? ceil_div(8 * (int64_t)box_cap, 256) : 1)),
-               dim3(256), 0, s, (const uint32_t*)(w.meta + 8), out_nclusters, box_acc, 8 * (int64_t)box_cap);
-    if (k_host) PCH_TRY(peek_enqueue(out_nclusters, sizeof(int32_t), s));    // read while the labels are written
-    {
-        // many chunks: the blocks of one chunk share an XCD (see db_label_k); otherwise blocks in sorted order
-        static const bool no_xcd = getenv("PCH_DB_NO_XCD") != nullptr;      // tuning toggle
-        const int bpc = (nchunks >= 16 && !no_xcd) ? (int)ceil_div(chunk_size, DB_LAB_TILE) : 0;
-        const unsigned gl = bpc > 0 ? (unsigned)(8 * ceil_div(nchunks, 8) * bpc) : (unsigned)ceil_div(n, DB_LAB_TILE);
-        PCH_LAUNCH("db_label", db_label_k, dim3(gl), dim3(DB_THREADS), 0, s, (const float4*)w.pts,
-                   (const uint32_t*)w.cid, (const uint8_t*)w.core_s, (const int*)w.root,
-                   (const int*)w.comp_min, (const uint32_t*)bits, (const uint32_t*)wrank, n,
-                   (const uint32_t*)w.cell_start, w.cell_label, labels, core, chunk_size, bpc, nchunks, box_acc, box_cap);
-    }
-    PCH_LAUNCH("db_border", db_border_k, dim3(gc), dim3(DB_THREADS), 0, s, g, (const float4*)w.pts,
-               (const uint32_t*)w.cell_start, (const uint64_t*)w.cell_key, m, rowtab, (const uint8_t*)w.core_s,
-               (const uint32_t*)w.cell_ncore, (const float*)w.cell_box, (const int*)w.cell_label, labels, box_acc, box_cap);
-    if (box_acc) boxes->done = true;
-    if (k_host) {
-        PCH_TRY(peek_wait(k_host, sizeof(int32_t)));
-        if (*k_host < 0) {                              // the rank scan's bounded wait gave up: the count reads -1
-            set_error("stage C: a device-side look-back wait ran out of its budget; outputs are undefined");
-            return PCH_ERR_TIMEOUT;
-        }
-    }
-    g_last.ws = ws; g_last.ws_bytes = ws_bytes; g_last.n = n; g_last.m = m; g_last.g = g;
-    g_last.has_rowtab = rowtab != nullptr;
+    DbCells c;
+    PCH_TRY(db_sorted_keys(r, g, cellbits, nbits, overflow, tune.sort_mode, ks));
+    PCH_TRY(db_cells_core(r, g, cellbits, ks, tune.count_pairs, c));
+    PCH_TRY(db_union(r, c));
+    PCH_TRY(db_labels(r, c, tune, k_host, boxes));
+    g_last = {ws, ws_bytes, n, c};
     return PCH_OK;
 }
 
@@ -2282,14 +2352,9 @@ extern "C" int pch_dbscan_first_core_rows_i32(int64_t n, int32_t* out_rows, void
     PCH_DEVICE_GUARD(out_rows ? (const void*)out_rows : (const void*)ws);
     PCH_REQUIRE(n >= 0, "bad argument");
     if (n == 0) return PCH_OK;
-    if (g_last.ws != ws || g_last.ws_bytes != ws_bytes || g_last.n != n || ws == nullptr) {
-        set_error("pch_dbscan_first_core_rows_i32 must follow pch_dbscan_f32 of this thread on the same, untouched workspace");
-        return PCH_ERR_ARG;
-    }
-    PCH_REQUIRE(out_rows != nullptr, "null output");
-    Arena a(ws, ws_bytes, true);
     DbWs w;
-    db_plan(a, n, w);
+    PCH_TRY(db_continue(__func__, n, ws, ws_bytes, w));
+    PCH_REQUIRE(out_rows != nullptr, "null output");
     const int64_t nw = ceil_div(n, 32);
     const uint32_t* bits = w.flag;
     const uint32_t* wrank = w.flag + ((nw + 63) & ~int64_t(63));
@@ -2305,13 +2370,8 @@ extern "C" int pch_dbscan_pair_stats(int64_t n, uint64_t* out4_host, void* ws, s
     PCH_REQUIRE(n >= 0 && out4_host, "bad argument");
     memset(out4_host, 0, 4 * sizeof(uint64_t));
     if (n == 0) return PCH_OK;
-    if (g_last.ws != ws || g_last.ws_bytes != ws_bytes || g_last.n != n || ws == nullptr) {
-        set_error("pch_dbscan_pair_stats must follow pch_dbscan_f32 of this thread on the same, untouched workspace");
-        return PCH_ERR_ARG;
-    }
-    Arena a(ws, ws_bytes, true);
     DbWs w;
-    db_plan(a, n, w);
+    PCH_TRY(db_continue(__func__, n, ws, ws_bytes, w));
     PCH_HIP_TRY(hipMemcpyAsync(out4_host, w.core_stats, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
     PCH_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return PCH_OK;
@@ -2324,18 +2384,12 @@ extern "C" int pch_dbscan_strip_pairs_i32(int64_t n, float x_lo, float x_hi, int
     PCH_REQUIRE(n >= 0 && cap >= 0 && out_count && (cap == 0 || out_pairs), "bad argument");
     PCH_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(int32_t), s));
     if (n == 0 || !(x_lo < x_hi)) return PCH_OK;
-    if (g_last.ws != ws || g_last.ws_bytes != ws_bytes || g_last.n != n || ws == nullptr) {
-        set_error("pch_dbscan_strip_pairs_i32 must follow pch_dbscan_f32 of this thread on the same, untouched workspace");
-        return PCH_ERR_ARG;
-    }
-    Arena a(ws, ws_bytes, true);
     DbWs w;
-    db_plan(a, n, w);
-    const int m = g_last.m;
+    PCH_TRY(db_continue(__func__, n, ws, ws_bytes, w));
+    const int m = g_last.c.m;
     PCH_LAUNCH("db_strip_pairs", db_strip_pairs_k, dim3((unsigned)ceil_div(m, DB_WAVES)), dim3(DB_THREADS), 0, s,
-               (const float4*)w.pts, (const uint32_t*)w.cell_start, (const uint8_t*)w.core_s,
-               (const uint32_t*)w.cell_ncore, (const float*)w.cell_box, (const int*)w.cell_label, m, x_lo, x_hi, cap,
-               out_pairs, out_count);
+               w.pts, w.cell_start, w.core_s, w.cell_ncore, w.cell_box, w.cell_label, m, x_lo, x_hi, cap, out_pairs,
+               out_count);
     return PCH_OK;
 }
 
@@ -2345,26 +2399,15 @@ extern "C" int pch_dbscan_relabel_i32(const int32_t* map, int32_t nmap, int64_t 
     hipStream_t s = (hipStream_t)stream;
     PCH_REQUIRE(n >= 0 && nmap >= 0 && (nmap == 0 || map) && (n == 0 || labels), "bad argument");
     if (n == 0) return PCH_OK;
-    if (g_last.ws != ws || g_last.ws_bytes != ws_bytes || g_last.n != n || ws == nullptr) {
-        set_error("pch_dbscan_relabel_i32 must follow pch_dbscan_f32 of this thread on the same, untouched workspace");
-        return PCH_ERR_ARG;
-    }
-    Arena a(ws, ws_bytes, true);
     DbWs w;
-    db_plan(a, n, w);
-    const DbGrid g = g_last.g;
-    const int m = g_last.m;
-    const unsigned gn = (unsigned)ceil_div(n, DB_THREADS);
-    const unsigned gc = (unsigned)ceil_div(m, DB_WAVES);
-    PCH_LAUNCH("db_remap_points", db_remap_points_k, dim3(gn), dim3(DB_THREADS), 0, s, (const float4*)w.pts,
-               (const uint8_t*)w.core_s, n, map, nmap, labels);
-    PCH_LAUNCH("db_remap_cells", db_remap_cells_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
-               w.cell_label, (const uint32_t*)w.cell_ncore, m, map, nmap);
-    PCH_LAUNCH("db_border", db_border_k, dim3(gc), dim3(DB_THREADS), 0, s, g, (const float4*)w.pts,
-               (const uint32_t*)w.cell_start, (const uint64_t*)w.cell_key, m,
-               g_last.has_rowtab ? (const int2*)w.rowtab : (const int2*)nullptr, (const uint8_t*)w.core_s,
-               (const uint32_t*)w.cell_ncore, (const float*)w.cell_box, (const int*)w.cell_label, labels,
-               (uint32_t*)nullptr, 0);
+    PCH_TRY(db_continue(__func__, n, ws, ws_bytes, w));
+    const DbCells& c = g_last.c;
+    PCH_LAUNCH("db_remap_points", db_remap_points_k, dim3((unsigned)ceil_div(n, DB_THREADS)), dim3(DB_THREADS), 0, s,
+               w.pts, w.core_s, n, map, nmap, labels);
+    PCH_LAUNCH("db_remap_cells", db_remap_cells_k, dim3((unsigned)ceil_div(c.m, DB_THREADS)), dim3(DB_THREADS), 0, s,
+               w.cell_label, w.cell_ncore, c.m, map, nmap);
+    PCH_LAUNCH("db_border", db_border_k, dim3((unsigned)ceil_div(c.m, DB_WAVES)), dim3(DB_THREADS), 0, s,
+               DB_CELL_ARGS(c), w.cell_label, labels, nullptr, 0);
     return PCH_OK;
 }
 
