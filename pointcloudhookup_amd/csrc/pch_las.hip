@@ -401,3 +401,91 @@ extern "C" int pch_las_write_xyz_i32(const char* path, const PchLasHeader* hdr, 
     }
     return PCH_OK;
 }
+
+// ---- LAS integer <-> scaled float64 (laspy ScaledArrayView semantics) ----------------
+namespace pch {
+struct D3 { double v[3]; };
+
+__global__ void las_scale_k(const int32_t* __restrict__ X, int64_t count, D3 sc, D3 of,
+                            double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count) return;
+    const int a = (int)(e % 3);
+    out[e] = (double)X[e] * sc.v[a] + of.v[a];          // separate mul, add (-ffp-contract=off)
+}
+// one thread per coordinate: three 4-byte loads at the head of each record (records need not be
+// 4-byte aligned: formats 2, 7, 8 ... have odd lengths), assembled from bytes when misaligned
+__global__ void las_records_k(const uint8_t* __restrict__ rec, int64_t count, int record_len,
+                              int32_t* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count) return;
+    const int64_t i = e / 3;
+    const int a = (int)(e - 3 * i);
+    const uint8_t* p = rec + i * record_len + 4 * a;
+    uint32_t v;
+    if ((reinterpret_cast<uintptr_t>(p) & 3) == 0) v = *reinterpret_cast<const uint32_t*>(p);
+    else v = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    out[e] = (int32_t)v;
+}
+__global__ void las_unscale_k(const double* __restrict__ v, int64_t count, D3 sc, D3 of,
+                              int32_t* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count) return;
+    const int a = (int)(e % 3);
+    out[e] = (int32_t)rint((v[e] - of.v[a]) / sc.v[a]); // np.round = half-to-even = rint
+}
+__global__ void cast_f64_f32_k(const double* __restrict__ in, int64_t count, float* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < count) out[e] = (float)in[e];
+}
+}  // namespace pch
+
+extern "C" int pch_las_records_xyz_i32(const uint8_t* records, int64_t n, int32_t record_len,
+                                       int32_t* out_XYZ, void* stream) {
+    PCH_DEVICE_GUARD(records);
+    PCH_REQUIRE(n >= 0 && record_len >= 12, "bad argument");
+    if (n == 0) return PCH_OK;
+    PCH_REQUIRE(records && out_XYZ, "null buffer");
+    const int64_t count = 3 * n;
+    PCH_LAUNCH("las_records", las_records_k, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0,
+               (hipStream_t)stream, records, count, (int)record_len, out_XYZ);
+    return PCH_OK;
+}
+
+extern "C" int pch_las_scale_i32_f64(const int32_t* XYZ, int64_t n, const double* scale3_host,
+                                     const double* offset3_host, double* out_xyz, void* stream) {
+    PCH_DEVICE_GUARD(XYZ);
+    PCH_REQUIRE(n >= 0 && scale3_host && offset3_host, "bad argument");
+    if (n == 0) return PCH_OK;
+    PCH_REQUIRE(XYZ && out_xyz, "null buffer");
+    D3 sc, of;
+    for (int a = 0; a < 3; ++a) { sc.v[a] = scale3_host[a]; of.v[a] = offset3_host[a]; }
+    const int64_t count = 3 * n;
+    PCH_LAUNCH("las_scale", las_scale_k, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0,
+               (hipStream_t)stream, XYZ, count, sc, of, out_xyz);
+    return PCH_OK;
+}
+
+extern "C" int pch_las_unscale_f64_i32(const double* xyz, int64_t n, const double* scale3_host,
+                                       const double* offset3_host, int32_t* out_XYZ, void* stream) {
+    PCH_DEVICE_GUARD(xyz);
+    PCH_REQUIRE(n >= 0 && scale3_host && offset3_host, "bad argument");
+    if (n == 0) return PCH_OK;
+    PCH_REQUIRE(xyz && out_XYZ, "null buffer");
+    D3 sc, of;
+    for (int a = 0; a < 3; ++a) { sc.v[a] = scale3_host[a]; of.v[a] = offset3_host[a]; }
+    const int64_t count = 3 * n;
+    PCH_LAUNCH("las_unscale", las_unscale_k, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0,
+               (hipStream_t)stream, xyz, count, sc, of, out_XYZ);
+    return PCH_OK;
+}
+
+extern "C" int pch_cast_f64_f32(const double* in, int64_t count, float* out, void* stream) {
+    PCH_DEVICE_GUARD(in);
+    PCH_REQUIRE(count >= 0, "bad count");
+    if (count == 0) return PCH_OK;
+    PCH_REQUIRE(in && out, "null buffer");
+    PCH_LAUNCH("cast_f64_f32", cast_f64_f32_k, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0,
+               (hipStream_t)stream, in, count, out);
+    return PCH_OK;
+}

@@ -137,7 +137,6 @@ constexpr int VF_WAVES   = VF_THREADS / 64;
 constexpr int VF_CAP     = VF_THREADS * VP_ROUNDS;   // 8192 rows: what one LDS sort takes
 constexpr int VF_DIGBITS = 8;                        // a batch spans at most 256 level-1 digits
 constexpr int VG_ROUNDS  = 4;                        // general (global-memory) path: rows per thread and tile
-constexpr int VG_TILE    = VF_THREADS * VG_ROUNDS;
 
 struct Row { double x, y, z; };
 
@@ -172,28 +171,54 @@ __device__ __forceinline__ uint64_t vx_key(const VoxelPlan& g, const double* __r
     return (((ix << g.by) | iy) << g.bz) | iz;
 }
 
+// Rank of this lane's digit d among the valid lanes of its wave with the same digit, after the wave_cnt[d] rows the
+// wave ranked before; the first lane of every digit then moves wave_cnt[d] past the wave's rows of that digit.
+template <int BITS>
+__device__ __forceinline__ uint32_t wave_rank(uint32_t* wave_cnt, uint32_t d, bool valid) {
+    uint32_t peers;
+    const uint32_t rk = wave_match<BITS>(d, valid, peers);
+    const uint32_t prior = wave_cnt[d];
+    __builtin_amdgcn_wave_barrier();
+    if (valid && rk == 0) wave_cnt[d] = prior + peers;
+    __builtin_amdgcn_wave_barrier();
+    return prior + rk;
+}
+
+// ---- level 1: one workgroup per tile of VP_TILE rows of a chunk -------------------------------------
+struct VxTile { int64_t c, cbeg, cend, t0; };      // chunk, its rows [cbeg, cend), the tile's first row
+__device__ __forceinline__ VxTile vx_tile(const VoxelPlan& g) {
+    const int64_t c = blockIdx.x / g.tiles_per_chunk, t = blockIdx.x % g.tiles_per_chunk, cbeg = c * g.chunk_size;
+    return {c, cbeg, (cbeg + g.chunk_size < g.n) ? cbeg + g.chunk_size : g.n, cbeg + t * VP_TILE};
+}
+// the chunk's grid origin and VP_ROUNDS rows per thread: row i0 + r * STRIDE + j in round r (rows past the chunk read
+// its first)
+template <int STRIDE>
+__device__ __forceinline__ void vx_tile_load(const double* __restrict__ xyz, const double* __restrict__ minb,
+                                             const VxTile& k, int64_t i0, int j, double (&mb)[3], Row (&q)[VP_ROUNDS]) {
+    mb[0] = minb[3 * k.c + 0]; mb[1] = minb[3 * k.c + 1]; mb[2] = minb[3 * k.c + 2];
+    const Row* __restrict__ rows = reinterpret_cast<const Row*>(xyz);
+#pragma unroll
+    for (int r = 0; r < VP_ROUNDS; ++r) {
+        const int64_t i = i0 + r * STRIDE + j;
+        q[r] = rows[i < k.cend ? i : k.cbeg];
+    }
+}
+
 // ---- level 1a: digit histogram of every tile ------------------------------------------------
 __global__ __launch_bounds__(VP_THREADS) void vx_tilehist_k(const double* __restrict__ xyz, VoxelPlan g,
                                                             const double* __restrict__ minb,
                                                             uint32_t* __restrict__ tile_hist) {
     __shared__ uint32_t hist[VP_MAXBINS];
-    const int64_t c = blockIdx.x / g.tiles_per_chunk, t = blockIdx.x % g.tiles_per_chunk;
-    const int64_t cbeg = c * g.chunk_size, cend = (cbeg + g.chunk_size < g.n) ? cbeg + g.chunk_size : g.n;
-    const int64_t t0 = cbeg + t * VP_TILE;
+    const VxTile k = vx_tile(g);
     for (int j = threadIdx.x; j < g.nb; j += VP_THREADS) hist[j] = 0;
     __syncthreads();
-    const double mb[3] = {minb[3 * c + 0], minb[3 * c + 1], minb[3 * c + 2]};
-    const Row* __restrict__ rows = reinterpret_cast<const Row*>(xyz);
+    double mb[3];
     Row q[VP_ROUNDS];
+    vx_tile_load<VP_THREADS>(xyz, minb, k, k.t0, threadIdx.x, mb, q);
 #pragma unroll
     for (int r = 0; r < VP_ROUNDS; ++r) {
-        const int64_t i = t0 + r * VP_THREADS + threadIdx.x;
-        q[r] = rows[i < cend ? i : cbeg];
-    }
-#pragma unroll
-    for (int r = 0; r < VP_ROUNDS; ++r) {
-        const int64_t i = t0 + r * VP_THREADS + threadIdx.x;
-        if (i < cend) atomicAdd(&hist[(uint32_t)(vx_key(g, mb, q[r]) >> g.rem)], 1u);
+        const int64_t i = k.t0 + r * VP_THREADS + threadIdx.x;
+        if (i < k.cend) atomicAdd(&hist[(uint32_t)(vx_key(g, mb, q[r]) >> g.rem)], 1u);
     }
     __syncthreads();
     for (int j = threadIdx.x; j < g.nb; j += VP_THREADS) tile_hist[(int64_t)blockIdx.x * g.nb + j] = hist[j];
@@ -317,6 +342,52 @@ __global__ __launch_bounds__(VP_MAXBINS) void vx_binscan_k(VoxelPlan g, uint32_t
 // <= VF_CAP rows that come out of it are contiguous there and are finished like any other batch.  (Until round 4 every
 // part swept the whole unit twice and picked its rows: 12 sweeps of a 20 000-row unit that was cut into six.)
 constexpr int VS_THREADS = 1024, VS_WAVES = VS_THREADS / 64, VS_ROUNDS = 4, VS_TILE = VS_THREADS * VS_ROUNDS;
+
+// Stable scatter of the R rows src[0, R) of a chunk (grid origin mb) to dst by the digit ((key & remmask) >> shift) & 255,
+// given base[d] = where digit d's rows start in dst: tile by tile, the rows of every wave are ranked per digit, the
+// waves are taken in order and their rows carried into base.
+template <int THREADS, int ROUNDS>
+__device__ __forceinline__ void vx_ranked_scatter(const VoxelPlan& g, const double (&mb)[3], uint64_t remmask, int shift,
+                                                  const Row* __restrict__ src, Row* __restrict__ dst, uint32_t R,
+                                                  uint32_t* base, uint32_t (*cnt)[256]) {
+    constexpr int WAVES = THREADS / 64, TILE = THREADS * ROUNDS;
+    static_assert(THREADS >= 256, "one thread per digit");
+    const int tid = threadIdx.x, w = wave_id(), l = lane_id();
+    for (uint32_t t0 = 0; t0 < R; t0 += TILE) {
+        for (int j = tid; j < WAVES * 256; j += THREADS) (&cnt[0][0])[j] = 0;
+        __syncthreads();
+        const uint32_t segb = t0 + w * (64 * ROUNDS);     // wave w owns 64 * ROUNDS consecutive rows of the tile
+        Row q[ROUNDS];
+        uint32_t dig[ROUNDS], rank[ROUNDS];
+#pragma unroll
+        for (int r = 0; r < ROUNDS; ++r) {
+            const uint32_t i = segb + r * 64 + l;
+            q[r] = src[i < R ? i : 0];
+        }
+#pragma unroll
+        for (int r = 0; r < ROUNDS; ++r) {
+            dig[r] = (uint32_t)((vx_key(g, mb, q[r]) & remmask) >> shift) & 255u;
+            rank[r] = wave_rank<8>(cnt[w], dig[r], segb + r * 64 + l < R);
+        }
+        __syncthreads();
+        if (tid < 256) {                                   // per digit: waves in order
+            uint32_t run = base[tid];
+#pragma unroll
+            for (int w2 = 0; w2 < WAVES; ++w2) {
+                const uint32_t cc = cnt[w2][tid];
+                cnt[w2][tid] = run;
+                run += cc;
+            }
+            base[tid] = run;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < ROUNDS; ++r)
+            if (segb + r * 64 + l < R) dst[cnt[w][dig[r]] + rank[r]] = q[r];
+        __syncthreads();
+    }
+}
+
 __global__ __launch_bounds__(VS_THREADS, 8) void vx_split_k(VoxelPlan g, const double* __restrict__ minb,
                                                        const Row* __restrict__ rows, Row* __restrict__ rows_b,
                                                        VoxelBatch* __restrict__ batches,
@@ -326,7 +397,7 @@ __global__ __launch_bounds__(VS_THREADS, 8) void vx_split_k(VoxelPlan g, const d
     __shared__ uint32_t cnt[VS_WAVES][256];
     __shared__ uint32_t okflag;
     const uint32_t total = *nover;
-    const int tid = threadIdx.x, w = wave_id(), l = lane_id();
+    const int tid = threadIdx.x;
     for (uint32_t o = blockIdx.x; o < total; o += gridDim.x) {
         const VoxelOversize ov = over[o];
         VoxelBatch* bt = batches + ov.slot;
@@ -376,56 +447,17 @@ __global__ __launch_bounds__(VS_THREADS, 8) void vx_split_k(VoxelPlan g, const d
         __syncthreads();
         if (okflag) {                                      // workgroup-uniform
             // exclusive scan of the digit histogram -> where every digit's rows start in the second buffer
-            uint32_t hv = tid < 256 ? hist[tid] : 0u;
+            const uint32_t hv = tid < 256 ? hist[tid] : 0u;
             const uint32_t incl = wave_scan_incl(hv);
-            if (tid < 256 && l == 63) cnt[0][w] = incl;    // (cnt[0][0..3]: the four waves' totals, consumed below)
+            if (tid < 256 && lane_id() == 63) cnt[0][wave_id()] = incl;   // (cnt[0][0..3]: the four waves' totals)
             __syncthreads();
             if (tid < 256) {
                 uint32_t b = incl - hv;
-                for (int w2 = 0; w2 < w; ++w2) b += cnt[0][w2];
+                for (int w2 = 0; w2 < wave_id(); ++w2) b += cnt[0][w2];
                 base[tid] = s + b;
             }
             __syncthreads();
-            for (uint32_t t0 = 0; t0 < R; t0 += VS_TILE) {
-                for (int j = tid; j < VS_WAVES * 256; j += VS_THREADS) (&cnt[0][0])[j] = 0;
-                __syncthreads();
-                const uint32_t segb = t0 + w * (64 * VS_ROUNDS);     // wave w owns 256 consecutive rows of the tile
-                Row q[VS_ROUNDS];
-                uint32_t dig[VS_ROUNDS], rank[VS_ROUNDS];
-#pragma unroll
-                for (int r = 0; r < VS_ROUNDS; ++r) {
-                    const uint32_t i = segb + r * 64 + l;
-                    q[r] = rows[s + (i < R ? i : 0)];
-                }
-#pragma unroll
-                for (int r = 0; r < VS_ROUNDS; ++r) {
-                    const bool valid = segb + r * 64 + l < R;
-                    dig[r] = (uint32_t)((vx_key(g, mb, q[r]) & remmask) >> sh2) & 255u;
-                    uint32_t npeer;
-                    const uint32_t rk = wave_match<8>(dig[r], valid, npeer);
-                    const uint32_t prior = cnt[w][dig[r]];
-                    __builtin_amdgcn_wave_barrier();
-                    if (valid && rk == 0) cnt[w][dig[r]] = prior + npeer;
-                    __builtin_amdgcn_wave_barrier();
-                    rank[r] = prior + rk;
-                }
-                __syncthreads();
-                if (tid < 256) {                           // per digit: waves in order
-                    uint32_t run = base[tid];
-#pragma unroll
-                    for (int w2 = 0; w2 < VS_WAVES; ++w2) {
-                        const uint32_t cc = cnt[w2][tid];
-                        cnt[w2][tid] = run;
-                        run += cc;
-                    }
-                    base[tid] = run;
-                }
-                __syncthreads();
-#pragma unroll
-                for (int r = 0; r < VS_ROUNDS; ++r)
-                    if (segb + r * 64 + l < R) rows_b[cnt[w][dig[r]] + rank[r]] = q[r];
-                __syncthreads();
-            }
+            vx_ranked_scatter<VS_THREADS, VS_ROUNDS>(g, mb, remmask, sh2, rows + s, rows_b, R, base, cnt);
         }
         __syncthreads();
     }
@@ -462,37 +494,23 @@ __global__ __launch_bounds__(VP_THREADS) void vx_scatter_k(const double* __restr
                                                            Row* __restrict__ out) {
     __shared__ uint32_t cnt[VP_WAVES][VP_MAXBINS];
     __shared__ uint32_t base[VP_MAXBINS];
-    const int64_t c = blockIdx.x / g.tiles_per_chunk, t = blockIdx.x % g.tiles_per_chunk;
-    const int64_t cbeg = c * g.chunk_size, cend = (cbeg + g.chunk_size < g.n) ? cbeg + g.chunk_size : g.n;
-    const int64_t t0 = cbeg + t * VP_TILE;
-    if (t0 >= cend) return;
+    const VxTile k = vx_tile(g);
+    if (k.t0 >= k.cend) return;
     const int w = wave_id(), l = lane_id();
     for (int j = threadIdx.x; j < VP_WAVES * g.nb; j += VP_THREADS) cnt[j / g.nb][j % g.nb] = 0;
     for (int j = threadIdx.x; j < g.nb; j += VP_THREADS)
-        base[j] = unit_start[c * g.nb + j] + tile_hist[(int64_t)blockIdx.x * g.nb + j];
+        base[j] = unit_start[k.c * g.nb + j] + tile_hist[(int64_t)blockIdx.x * g.nb + j];
     __syncthreads();
-    const double mb[3] = {minb[3 * c + 0], minb[3 * c + 1], minb[3 * c + 2]};
-    const Row* __restrict__ rows = reinterpret_cast<const Row*>(xyz);
     // wave w owns rows [w*512, w*512+512) of the tile, 64 per round: (wave, round, lane) order = file order
-    const int64_t seg = t0 + (int64_t)w * (64 * VP_ROUNDS);
+    const int64_t seg = k.t0 + (int64_t)w * (64 * VP_ROUNDS);
+    double mb[3];
     Row q[VP_ROUNDS];
     uint32_t dig[VP_ROUNDS], rank[VP_ROUNDS];
+    vx_tile_load<64>(xyz, minb, k, seg, l, mb, q);
 #pragma unroll
     for (int r = 0; r < VP_ROUNDS; ++r) {
-        const int64_t i = seg + r * 64 + l;
-        q[r] = rows[i < cend ? i : cbeg];
-    }
-#pragma unroll
-    for (int r = 0; r < VP_ROUNDS; ++r) {
-        const bool valid = seg + r * 64 + l < cend;
         dig[r] = (uint32_t)(vx_key(g, mb, q[r]) >> g.rem);
-        uint32_t np;
-        const uint32_t rk = wave_match<VP_MAXBITS>(dig[r], valid, np);
-        const uint32_t prior = cnt[w][dig[r]];
-        __builtin_amdgcn_wave_barrier();
-        if (valid && rk == 0) cnt[w][dig[r]] = prior + np;
-        __builtin_amdgcn_wave_barrier();
-        rank[r] = prior + rk;
+        rank[r] = wave_rank<VP_MAXBITS>(cnt[w], dig[r], seg + r * 64 + l < k.cend);
     }
     __syncthreads();
     for (int d = threadIdx.x; d < g.nb; d += VP_THREADS) {       // per digit: waves in order
@@ -507,7 +525,7 @@ __global__ __launch_bounds__(VP_THREADS) void vx_scatter_k(const double* __restr
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < VP_ROUNDS; ++r)
-        if (seg + r * 64 + l < cend) out[cnt[w][dig[r]] + rank[r]] = q[r];
+        if (seg + r * 64 + l < k.cend) out[cnt[w][dig[r]] + rank[r]] = q[r];
 }
 
 // The same scatter with the tile staged through LDS: the rows of a tile are first put in digit order INSIDE the tile
@@ -528,37 +546,23 @@ __global__ __launch_bounds__(VP_THREADS) void vx_scatter_lds_k(const double* __r
                                                                Row* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char vs_raw[];
     VsShared& sh = *reinterpret_cast<VsShared*>(vs_raw);
-    const int64_t c = blockIdx.x / g.tiles_per_chunk, t = blockIdx.x % g.tiles_per_chunk;
-    const int64_t cbeg = c * g.chunk_size, cend = (cbeg + g.chunk_size < g.n) ? cbeg + g.chunk_size : g.n;
-    const int64_t t0 = cbeg + t * VP_TILE;
-    if (t0 >= cend) return;
-    const uint32_t tn = (uint32_t)((cend - t0) < VP_TILE ? (cend - t0) : VP_TILE);
+    const VxTile k = vx_tile(g);
+    if (k.t0 >= k.cend) return;
+    const uint32_t tn = (uint32_t)((k.cend - k.t0) < VP_TILE ? (k.cend - k.t0) : VP_TILE);
     const int tid = threadIdx.x, w = wave_id(), l = lane_id();
     for (int j = tid; j < VP_WAVES * g.nb; j += VP_THREADS) sh.cnt[j / g.nb][j % g.nb] = 0;
     for (int j = tid; j < g.nb; j += VP_THREADS)
-        sh.gbase[j] = unit_start[c * g.nb + j] + tile_hist[(int64_t)blockIdx.x * g.nb + j];
+        sh.gbase[j] = unit_start[k.c * g.nb + j] + tile_hist[(int64_t)blockIdx.x * g.nb + j];
     __syncthreads();
-    const double mb[3] = {minb[3 * c + 0], minb[3 * c + 1], minb[3 * c + 2]};
-    const Row* __restrict__ rows = reinterpret_cast<const Row*>(xyz);
-    const int64_t seg = t0 + (int64_t)w * (64 * VP_ROUNDS);
+    const int64_t seg = k.t0 + (int64_t)w * (64 * VP_ROUNDS);
+    double mb[3];
     Row q[VP_ROUNDS];
     uint32_t dig[VP_ROUNDS], rank[VP_ROUNDS];
+    vx_tile_load<64>(xyz, minb, k, seg, l, mb, q);
 #pragma unroll
     for (int r = 0; r < VP_ROUNDS; ++r) {
-        const int64_t i = seg + r * 64 + l;
-        q[r] = rows[i < cend ? i : cbeg];
-    }
-#pragma unroll
-    for (int r = 0; r < VP_ROUNDS; ++r) {
-        const bool valid = seg + r * 64 + l < cend;
         dig[r] = (uint32_t)(vx_key(g, mb, q[r]) >> g.rem);
-        uint32_t np;
-        const uint32_t rk = wave_match<VP_MAXBITS>(dig[r], valid, np);
-        const uint32_t prior = sh.cnt[w][dig[r]];
-        __builtin_amdgcn_wave_barrier();
-        if (valid && rk == 0) sh.cnt[w][dig[r]] = prior + np;
-        __builtin_amdgcn_wave_barrier();
-        rank[r] = prior + rk;
+        rank[r] = wave_rank<VP_MAXBITS>(sh.cnt[w], dig[r], seg + r * 64 + l < k.cend);
     }
     __syncthreads();
     // per digit (one thread each, g.nb <= VP_THREADS): the waves in order -> offsets inside the digit's run; the runs
@@ -583,7 +587,7 @@ __global__ __launch_bounds__(VP_THREADS) void vx_scatter_lds_k(const double* __r
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < VP_ROUNDS; ++r)
-        if (seg + r * 64 + l < cend) {
+        if (seg + r * 64 + l < k.cend) {
             const uint32_t at = sh.lstart[dig[r]] + sh.cnt[w][dig[r]] + rank[r];
             sh.rows[at] = q[r];
             sh.dig[at] = (uint16_t)dig[r];
@@ -604,7 +608,7 @@ constexpr uint32_t VQ_MAXRUN = 32;                   // rows per voxel the group
 struct VfShared {
     union {
         struct {
-            uint32_t key[2][VF_CAP];             // 32 KB (key[0..1] together: the hash set of both LDS paths)
+            uint32_t key[2][VF_CAP];             // 32 KB
             uint16_t perm[2][VF_CAP];            // 16 KB
         };
         struct {                                 // grouping path (vf_group): hash set, per-slot row counts (one BYTE
@@ -700,30 +704,14 @@ __global__ __launch_bounds__(VF_THREADS, (2 * VF_THREADS) / 256) void vx_finish_
         const int sortbits = g.rem + dbits;
         uint32_t nvox = 0;
         const Row* fin = bufA + s;                         // where the batch's rows are when they are reduced
-        bool in_lds = false, announced = false;
+        bool in_lds = false;
         const uint32_t* srt = nullptr;                     // LDS path: sorted keys / their rows / voxel starts
         const uint16_t* sperm = nullptr;
         const uint32_t* vst = nullptr;
-        // ---------------- grouping path: rows grouped by HASH SLOT, not sorted by key ----------------
-        // The exact hash set that counts the batch's voxels already says which rows belong together; what Open3D's
-        // accumulation needs on top is the FILE ORDER inside a voxel, not an order between voxels (its own output
-        // order is unordered_map iteration order).  So: every row takes a ticket on its slot's counter (arrival
-        // order, arbitrary), the slots' counts are scanned, the rows' positions are scattered to their slot's run, and
-        // the thread of the row that arrived FIRST sorts that run (1-3 positions as a rule) and adds the rows in
-        // ascending position = file order.  Voxels leave the batch in the order of their first rows (a bit per
-        // position + prefix popcounts): deterministic, whatever the arrival order was.  One pass over the rows for
-        // the keys, no radix pass at all (the stable LDS sort below costs 3-4 passes of a ballot per key bit).
-        // A batch with a voxel of more than VQ_MAXRUN rows takes the stable sort below instead.
-        bool grouped = false, skip_early = false;
-        uint32_t gkey[VP_ROUNDS], ghs[VP_ROUNDS];           // grouping path: relative key; slot | arrival ticket << 16
-        if (R != 0 && R <= (uint32_t)VF_CAP && sortbits <= 31) {
-            for (uint32_t j = tid; j < VQ_SLOTS; j += VF_THREADS) sh.q.hset[j] = 0xFFFFFFFFu;
-            for (uint32_t j = tid; j < VQ_SLOTS / 4; j += VF_THREADS) sh.q.hcnt[j] = 0u;
-            if (tid == 0) sh.overflow = 0u;
-            __syncthreads();
-            uint32_t* const kreg = gkey;
-            uint32_t* const hs = ghs;
-            uint32_t fresh = 0;
+        // A batch that fits in LDS with keys of <= 32 bits: the relative key of row r * VF_THREADS + tid goes to kreg[r]
+        const bool in_cap = R != 0 && R <= (uint32_t)VF_CAP && sortbits <= 32;
+        uint32_t kreg[VP_ROUNDS], hs[VP_ROUNDS];            // relative key; grouping path: slot | arrival ticket << 16
+        if (in_cap) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {                   // four rows per thread in flight
                 Row q[VP_ROUNDS / 2];
@@ -738,34 +726,47 @@ __global__ __launch_bounds__(VF_THREADS, (2 * VF_THREADS) / 256) void vx_finish_
                     kreg[h * (VP_ROUNDS / 2) + r] = (uint32_t)((((k >> g.rem) - d0) << g.rem) | (k & remmask));
                 }
             }
-            {
+        }
+        // ---------------- grouping path: rows grouped by HASH SLOT, not sorted by key ----------------
+        // The exact hash set that counts the batch's voxels already says which rows belong together; what Open3D's
+        // accumulation needs on top is the FILE ORDER inside a voxel, not an order between voxels (its own output
+        // order is unordered_map iteration order).  So: every row takes a ticket on its slot's counter (arrival
+        // order, arbitrary), the slots' counts are scanned, the rows' positions are scattered to their slot's run, and
+        // the thread of the row that arrived FIRST sorts that run (1-3 positions as a rule) and adds the rows in
+        // ascending position = file order.  Voxels leave the batch in the order of their first rows (a bit per
+        // position + prefix popcounts): deterministic, whatever the arrival order was.  One pass over the rows for
+        // the keys, no radix pass at all (the stable LDS sort below costs 3-4 passes of a ballot per key bit).
+        // A batch with a voxel of more than VQ_MAXRUN rows takes the stable sort below instead; the voxel count is
+        // announced to the batches behind either way, before any sort (the batch's own prefix is only fetched at the end).
+        const bool announced = in_cap && sortbits <= 31;
+        bool grouped = false;
+        if (announced) {
+            for (uint32_t j = tid; j < VQ_SLOTS; j += VF_THREADS) sh.q.hset[j] = 0xFFFFFFFFu;
+            for (uint32_t j = tid; j < VQ_SLOTS / 4; j += VF_THREADS) sh.q.hcnt[j] = 0u;
+            if (tid == 0) sh.overflow = 0u;
+            __syncthreads();
+            uint32_t fresh = 0;
 #pragma unroll
-                for (int rr = 0; rr < VP_ROUNDS; ++rr) {
-                    const uint32_t i = rr * VF_THREADS + tid;
-                    hs[rr] = 0xFFFFFFFFu;
-                    if (i < R) {
-                        uint32_t slot = (kreg[rr] * 2654435761u) >> (32 - 13);
-                        for (;;) {
-                            const uint32_t old = atomicCAS(&sh.q.hset[slot], 0xFFFFFFFFu, kreg[rr]);
-                            if (old == 0xFFFFFFFFu) { ++fresh; break; }
-                            if (old == kreg[rr]) break;
-                            slot = (slot + 1) & (VQ_SLOTS - 1);
-                        }
-                        const uint32_t sft = (slot & 3u) * 8u;
-                        const uint32_t tk = (atomicAdd(&sh.q.hcnt[slot >> 2], 1u << sft) >> sft) & 255u;
-                        if (tk >= VQ_MAXRUN) sh.overflow = 1u;
-                        hs[rr] = slot | (tk << 16);
+            for (int rr = 0; rr < VP_ROUNDS; ++rr) {
+                const uint32_t i = rr * VF_THREADS + tid;
+                hs[rr] = 0xFFFFFFFFu;
+                if (i < R) {
+                    uint32_t slot = (kreg[rr] * 2654435761u) >> (32 - 13);
+                    for (;;) {
+                        const uint32_t old = atomicCAS(&sh.q.hset[slot], 0xFFFFFFFFu, kreg[rr]);
+                        if (old == 0xFFFFFFFFu) { ++fresh; break; }
+                        if (old == kreg[rr]) break;
+                        slot = (slot + 1) & (VQ_SLOTS - 1);
                     }
+                    const uint32_t sft = (slot & 3u) * 8u;
+                    const uint32_t tk = (atomicAdd(&sh.q.hcnt[slot >> 2], 1u << sft) >> sft) & 255u;
+                    if (tk >= VQ_MAXRUN) sh.overflow = 1u;
+                    hs[rr] = slot | (tk << 16);
                 }
             }
             VX_STAMP(8);
-            {
-                uint32_t tot;
-                vf_block_scan(fresh, sh.wsum, tot);        // (its barriers also publish the counters and the flag)
-                if (tid == 0) gf_announce(status, (int64_t)t, tot);
-                nvox = tot;
-            }
-            announced = true;
+            vf_block_scan(fresh, sh.wsum, nvox);           // (its barriers also publish the counters and the flag)
+            if (tid == 0) gf_announce(status, (int64_t)t, nvox);
             // The grouping path pays where most voxels hold one or two rows (0.1 m voxels on 100 points / m^2: 0.86 voxels
             // per row, 2.55 against 2.93 ms per 100 M rows); where rows share voxels (0.2 m: 0.45 voxels per row) the
             // stable sort below is the faster of the two (0.30 against 0.34 ms per 10 M rows) - measured, both exact.
@@ -829,82 +830,22 @@ __global__ __launch_bounds__(VF_THREADS, (2 * VF_THREADS) / 256) void vx_finish_
                     if (tid < (int)(VF_CAP / 64)) sh.q.headpre[tid] = incl - c;
                 }
                 static_assert(VF_CAP / 64 <= 64, "one wave scans the head words");
-            } else {
-                skip_early = true;                                      // the count is out already; sort stably below
             }
             __syncthreads();
             VX_STAMP(11);
         }
         if (R == 0 || grouped) {
             // a reserved slot that was not needed (publishes zero voxels below), or grouped above
-        } else if (R <= (uint32_t)VF_CAP && sortbits <= 32) {
-            // ---------------- LDS path: keys once, stable LSD passes over (key, position) ----------------
+        } else if (in_cap) {
+            // ---------------- LDS path: stable LSD passes over (key, position) ----------------
             in_lds = true;
             const int passes = (sortbits + 7) / 8;
             const uint32_t per = ((R + VF_WAVES * 64 - 1) / (VF_WAVES * 64)) * 64;   // items per wave: multiple of 64, <= 512
             const int rounds = (int)(per / 64);
-            // The number of distinct keys (= voxels) is announced to the batches behind BEFORE the sort: the keys
-            // are inserted into an exact hash set (open addressing, 2 * VF_CAP slots in the still unused key
-            // buffers) while they are computed, so nobody waits for this batch's sort (the batch's own prefix is
-            // only fetched at the end).
-            const bool early = sortbits <= 31 && !skip_early;   // 0xFFFFFFFF marks an empty slot
-            uint32_t* hset = &sh.key[0][0];
-            constexpr uint32_t HSLOTS = 2 * VF_CAP;
-            uint32_t fresh = 0;                            // keys this thread was the first to insert
-            auto insert = [&](uint32_t k) {
-                static_assert((HSLOTS & (HSLOTS - 1)) == 0, "power of two");
-                uint32_t h = ((k * 2654435761u) >> 8) & (HSLOTS - 1);
-                for (;;) {
-                    const uint32_t old = atomicCAS(&hset[h], 0xFFFFFFFFu, k);
-                    if (old == 0xFFFFFFFFu) { ++fresh; break; }
-                    if (old == k) break;
-                    h = (h + 1) & (HSLOTS - 1);
-                }
-            };
-            auto count_and_announce = [&]() {
-                uint32_t tot;
-                vf_block_scan(fresh, sh.wsum, tot);
-                if (tid == 0) gf_announce(status, (int64_t)t, tot);
-                __syncthreads();
-            };
-            if (early) {
-                for (uint32_t j = tid; j < HSLOTS; j += VF_THREADS) hset[j] = 0xFFFFFFFFu;
-                __syncthreads();
-            }
-            announced = early || skip_early;
-            if (skip_early) {
-                // the grouping path above has computed the keys and announced the count, then stood down (rows share
-                // voxels, or a voxel holds more rows than it takes): its keys are still in registers
 #pragma unroll
-                for (int r = 0; r < VP_ROUNDS; ++r) {
-                    const uint32_t i = r * VF_THREADS + tid;
-                    if (i < R) { sh.key[0][i] = gkey[r]; sh.perm[0][i] = (uint16_t)i; }
-                }
-            } else {
-                uint32_t kreg[VP_ROUNDS];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {               // four rows per thread in flight
-                    Row q[VP_ROUNDS / 2];
-#pragma unroll
-                    for (int r = 0; r < VP_ROUNDS / 2; ++r) {
-                        const uint32_t i = (h * (VP_ROUNDS / 2) + r) * VF_THREADS + tid;
-                        q[r] = src[s + (i < R ? i : 0)];
-                    }
-#pragma unroll
-                    for (int r = 0; r < VP_ROUNDS / 2; ++r) {
-                        const int rr = h * (VP_ROUNDS / 2) + r;
-                        const uint32_t i = rr * VF_THREADS + tid;
-                        const uint64_t k = vx_key(g, mb, q[r]);
-                        kreg[rr] = (uint32_t)((((k >> g.rem) - d0) << g.rem) | (k & remmask));
-                        if (early && i < R) insert(kreg[rr]);
-                    }
-                }
-                if (early) count_and_announce();
-#pragma unroll
-                for (int r = 0; r < VP_ROUNDS; ++r) {
-                    const uint32_t i = r * VF_THREADS + tid;
-                    if (i < R) { sh.key[0][i] = kreg[r]; sh.perm[0][i] = (uint16_t)i; }
-                }
+            for (int r = 0; r < VP_ROUNDS; ++r) {
+                const uint32_t i = r * VF_THREADS + tid;
+                if (i < R) { sh.key[0][i] = kreg[r]; sh.perm[0][i] = (uint16_t)i; }
             }
             __syncthreads();
             VX_STAMP(1);
@@ -922,14 +863,7 @@ __global__ __launch_bounds__(VF_THREADS, (2 * VF_THREADS) / 256) void vx_finish_
                         const bool valid = i < R;
                         kk[r] = valid ? sh.key[cur][i] : 0u;
                         pp[r] = valid ? sh.perm[cur][i] : (uint16_t)0;
-                        const uint32_t d = (kk[r] >> shift) & 255u;
-                        uint32_t np;
-                        const uint32_t rk = wave_match<8>(d, valid, np);
-                        const uint32_t prior = sh.cnt[w][d];
-                        __builtin_amdgcn_wave_barrier();
-                        if (valid && rk == 0) sh.cnt[w][d] = prior + np;
-                        __builtin_amdgcn_wave_barrier();
-                        rank[r] = prior + rk;
+                        rank[r] = wave_rank<8>(sh.cnt[w], (kk[r] >> shift) & 255u, valid);
                     }
                 }
                 __syncthreads();
@@ -1001,46 +935,7 @@ __global__ __launch_bounds__(VF_THREADS, (2 * VF_THREADS) / 256) void vx_finish_
                 const uint32_t ex = vf_block_scan(tid < 256 ? sh.hist[p][tid] : 0u, sh.wsum, all);
                 if (tid < 256) sh.base[tid] = ex;
                 __syncthreads();
-                for (uint32_t t0 = 0; t0 < R; t0 += VG_TILE) {
-                    for (int j = tid; j < VF_WAVES * 256; j += VF_THREADS) (&sh.cnt[0][0])[j] = 0;
-                    __syncthreads();
-                    const uint32_t segb = t0 + w * (64 * VG_ROUNDS);
-                    Row q[VG_ROUNDS];
-                    uint32_t dig[VG_ROUNDS], rank[VG_ROUNDS];
-#pragma unroll
-                    for (int r = 0; r < VG_ROUNDS; ++r) {
-                        const uint32_t i = segb + r * 64 + l;
-                        q[r] = a[i < R ? i : 0];
-                    }
-#pragma unroll
-                    for (int r = 0; r < VG_ROUNDS; ++r) {
-                        const bool valid = segb + r * 64 + l < R;
-                        dig[r] = (uint32_t)((vx_key(g, mb, q[r]) & remmask) >> (8 * p)) & 255u;
-                        uint32_t npeer;
-                        const uint32_t rk = wave_match<8>(dig[r], valid, npeer);
-                        const uint32_t prior = sh.cnt[w][dig[r]];
-                        __builtin_amdgcn_wave_barrier();
-                        if (valid && rk == 0) sh.cnt[w][dig[r]] = prior + npeer;
-                        __builtin_amdgcn_wave_barrier();
-                        rank[r] = prior + rk;
-                    }
-                    __syncthreads();
-                    if (tid < 256) {
-                        uint32_t run = sh.base[tid];
-#pragma unroll
-                        for (int w2 = 0; w2 < VF_WAVES; ++w2) {
-                            const uint32_t cc = sh.cnt[w2][tid];
-                            sh.cnt[w2][tid] = run;
-                            run += cc;
-                        }
-                        sh.base[tid] = run;
-                    }
-                    __syncthreads();
-#pragma unroll
-                    for (int r = 0; r < VG_ROUNDS; ++r)
-                        if (segb + r * 64 + l < R) b[sh.cnt[w][dig[r]] + rank[r]] = q[r];
-                    __syncthreads();
-                }
+                vx_ranked_scatter<VF_THREADS, VG_ROUNDS>(g, mb, remmask, 8 * p, a, b, R, sh.base, sh.cnt);
                 __threadfence_block();
                 __syncthreads();                             // this pass' rows are visible to the whole workgroup
                 Row* tswap = a; a = b; b = tswap;
@@ -1114,8 +1009,8 @@ __global__ __launch_bounds__(VF_THREADS, (2 * VF_THREADS) / 256) void vx_finish_
 #pragma unroll
                 for (int j = 0; j < HV; ++j) {
                     const int r = h * HV + j;
-                    const bool owner = ghs[r] != 0xFFFFFFFFu && (ghs[r] >> 16) == 0u;
-                    const uint32_t slot = owner ? (ghs[r] & 0xFFFFu) : 0u;
+                    const bool owner = hs[r] != 0xFFFFFFFFu && (hs[r] >> 16) == 0u;
+                    const uint32_t slot = owner ? (hs[r] & 0xFFFFu) : 0u;
                     a0[j] = sh.q.sstart[slot];
                     cn[j] = owner ? (sh.q.hcnt[slot >> 2] >> (8 * (slot & 3u))) & 255u : 0u;
                     p0[j] = owner ? sh.q.pos[a0[j]] : 0u;
@@ -1132,7 +1027,7 @@ __global__ __launch_bounds__(VF_THREADS, (2 * VF_THREADS) / 256) void vx_finish_
                         }
                         const uint32_t v = sh.q.headpre[p0[j] >> 6] +
                                            (uint32_t)__popcll(sh.q.headbits[p0[j] >> 6] & ((1ull << (p0[j] & 63u)) - 1ull));
-                        const uint64_t sk = gkey[h * HV + j];
+                        const uint64_t sk = kreg[h * HV + j];
                         const uint64_t key = ((d0 + (sk >> g.rem)) << g.rem) | (sk & remmask);
                         vf_emit(g, key, ax, ay, az, cn[j], vbase + v, out_idx, out_mean, out_count);
                     }
@@ -1178,6 +1073,19 @@ struct VoxelWs {
     uint64_t* status;
     size_t    clear_bytes;       // ticket .. end of status: zeroed before the finisher
 };
+
+// a kernel's dynamic LDS above the default limit: set once per device
+template <auto kernel>
+static int set_max_lds(size_t bytes) {
+    static bool done[PCH_MAX_DEVICES] = {};
+    const int slot = current_device_slot();
+    if (!done[slot]) {
+        PCH_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)bytes));
+        done[slot] = true;
+    }
+    return PCH_OK;
+}
 
 static int64_t voxel_nchunks(int64_t n, int64_t& chunk_size) {
     if (chunk_size <= 0 || chunk_size > n) chunk_size = n > 0 ? n : 1;
@@ -1291,13 +1199,7 @@ extern "C" int pch_voxel_downsample_f64(const double* xyz, int64_t n, double vox
     }();
     const bool scatter_lds = scatter_mode == 1 || (scatter_mode == 0 && n * (int64_t)sizeof(Row) > (int64_t(384) << 20));
     if (scatter_lds) {
-        static bool attr_s[PCH_MAX_DEVICES] = {};
-        const int slot_s = current_device_slot();
-        if (!attr_s[slot_s]) {
-            PCH_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(vx_scatter_lds_k),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(VsShared)));
-            attr_s[slot_s] = true;
-        }
+        PCH_TRY(set_max_lds<vx_scatter_lds_k>(sizeof(VsShared)));
         PCH_LAUNCH("voxel_scatter", vx_scatter_lds_k, dim3(gt), dim3(VP_THREADS), sizeof(VsShared), s, xyz, g,
                    (const double*)w.minb, (const uint32_t*)w.tile_hist, (const uint32_t*)w.unit_start, w.bufA);
     } else
@@ -1315,13 +1217,7 @@ extern "C" int pch_voxel_downsample_f64(const double* xyz, int64_t n, double vox
     int64_t fg = (int64_t)cus * 2;
     if (fg > nchunks * g.nb) fg = nchunks * g.nb;
     const size_t shm = sizeof(VfShared);
-    static bool attr_set[PCH_MAX_DEVICES] = {};
-    const int slot = current_device_slot();
-    if (!attr_set[slot]) {
-        PCH_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(vx_finish_k),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        attr_set[slot] = true;
-    }
+    PCH_TRY(set_max_lds<vx_finish_k>(shm));
     PCH_LAUNCH("voxel_finish", vx_finish_k, dim3((unsigned)fg), dim3(VF_THREADS), shm, s, g,
                (const double*)w.minb, (const VoxelBatch*)w.batches, (const uint32_t*)w.batch_prefix, w.bufA, w.bufB,
                w.vstart, w.status, w.ticket, out_idx, out_mean, out_count, out_chunk_offsets, out_m,
@@ -1347,93 +1243,5 @@ extern "C" int pch_voxel_downsample_f64(const double* xyz, int64_t n, double vox
         fprintf(stderr, "  | look-back totals so far: %llu windows, %llu failed polls\n", wins, polls);
     }
 #endif
-    return PCH_OK;
-}
-
-// ---- LAS integer <-> scaled float64 (laspy ScaledArrayView semantics) ----------------
-namespace pch {
-struct D3 { double v[3]; };
-
-__global__ void las_scale_k(const int32_t* __restrict__ X, int64_t count, D3 sc, D3 of,
-                            double* __restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= count) return;
-    const int a = (int)(e % 3);
-    out[e] = (double)X[e] * sc.v[a] + of.v[a];          // separate mul, add (-ffp-contract=off)
-}
-// one thread per coordinate: three 4-byte loads at the head of each record (records need not be
-// 4-byte aligned: formats 2, 7, 8 ... have odd lengths), assembled from bytes when misaligned
-__global__ void las_records_k(const uint8_t* __restrict__ rec, int64_t count, int record_len,
-                              int32_t* __restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= count) return;
-    const int64_t i = e / 3;
-    const int a = (int)(e - 3 * i);
-    const uint8_t* p = rec + i * record_len + 4 * a;
-    uint32_t v;
-    if ((reinterpret_cast<uintptr_t>(p) & 3) == 0) v = *reinterpret_cast<const uint32_t*>(p);
-    else v = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-    out[e] = (int32_t)v;
-}
-__global__ void las_unscale_k(const double* __restrict__ v, int64_t count, D3 sc, D3 of,
-                              int32_t* __restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= count) return;
-    const int a = (int)(e % 3);
-    out[e] = (int32_t)rint((v[e] - of.v[a]) / sc.v[a]); // np.round = half-to-even = rint
-}
-__global__ void cast_f64_f32_k(const double* __restrict__ in, int64_t count, float* __restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < count) out[e] = (float)in[e];
-}
-}  // namespace pch
-
-extern "C" int pch_las_records_xyz_i32(const uint8_t* records, int64_t n, int32_t record_len,
-                                       int32_t* out_XYZ, void* stream) {
-    PCH_DEVICE_GUARD(records);
-    PCH_REQUIRE(n >= 0 && record_len >= 12, "bad argument");
-    if (n == 0) return PCH_OK;
-    PCH_REQUIRE(records && out_XYZ, "null buffer");
-    const int64_t count = 3 * n;
-    PCH_LAUNCH("las_records", las_records_k, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0,
-               (hipStream_t)stream, records, count, (int)record_len, out_XYZ);
-    return PCH_OK;
-}
-
-extern "C" int pch_las_scale_i32_f64(const int32_t* XYZ, int64_t n, const double* scale3_host,
-                                     const double* offset3_host, double* out_xyz, void* stream) {
-    PCH_DEVICE_GUARD(XYZ);
-    PCH_REQUIRE(n >= 0 && scale3_host && offset3_host, "bad argument");
-    if (n == 0) return PCH_OK;
-    PCH_REQUIRE(XYZ && out_xyz, "null buffer");
-    D3 sc, of;
-    for (int a = 0; a < 3; ++a) { sc.v[a] = scale3_host[a]; of.v[a] = offset3_host[a]; }
-    const int64_t count = 3 * n;
-    PCH_LAUNCH("las_scale", las_scale_k, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0,
-               (hipStream_t)stream, XYZ, count, sc, of, out_xyz);
-    return PCH_OK;
-}
-
-extern "C" int pch_las_unscale_f64_i32(const double* xyz, int64_t n, const double* scale3_host,
-                                       const double* offset3_host, int32_t* out_XYZ, void* stream) {
-    PCH_DEVICE_GUARD(xyz);
-    PCH_REQUIRE(n >= 0 && scale3_host && offset3_host, "bad argument");
-    if (n == 0) return PCH_OK;
-    PCH_REQUIRE(xyz && out_XYZ, "null buffer");
-    D3 sc, of;
-    for (int a = 0; a < 3; ++a) { sc.v[a] = scale3_host[a]; of.v[a] = offset3_host[a]; }
-    const int64_t count = 3 * n;
-    PCH_LAUNCH("las_unscale", las_unscale_k, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0,
-               (hipStream_t)stream, xyz, count, sc, of, out_XYZ);
-    return PCH_OK;
-}
-
-extern "C" int pch_cast_f64_f32(const double* in, int64_t count, float* out, void* stream) {
-    PCH_DEVICE_GUARD(in);
-    PCH_REQUIRE(count >= 0, "bad count");
-    if (count == 0) return PCH_OK;
-    PCH_REQUIRE(in && out, "null buffer");
-    PCH_LAUNCH("cast_f64_f32", cast_f64_f32_k, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0,
-               (hipStream_t)stream, in, count, out);
     return PCH_OK;
 }

@@ -49,16 +49,16 @@ def _voxel_sets_equal(idx, mean, count, offs, ridx, rmean, rcount, roffs):
 @pytest.mark.parametrize("case", ["dense_core", "one_voxel_20000", "wide_keys_u64", "huge_keys_general",
                                   "ragged_tiles", "tower_like", "all_equal_points"])
 def test_voxel_paths_match_oracle(cuda, case):
-    """Every path of the voxel finisher: units sorted inside LDS with 32-bit and 64-bit items, units too
-    large for LDS (LSD passes in global memory), keys too wide for an LDS item, one voxel holding more rows
-    than an LDS tile (in-order sum across tiles), ragged partition tiles."""
+    """Every path of the voxel finisher: units sorted inside LDS on 32-bit keys, units too large for LDS
+    (LSD passes in global memory), keys too wide for an LDS key (also sorted in global memory), one voxel
+    holding more rows than an LDS tile (in-order sum across tiles), ragged partition tiles."""
     rng = np.random.default_rng(hash(case) % 2**32)
     if case == "dense_core":              # 60 000 points inside 2 m: level-1 units far above the LDS capacity
         pts, voxel, chunk = rng.normal(0, 0.6, (60000, 3)) + OFFSET, 0.05, 0
     elif case == "one_voxel_20000":       # a single voxel with 20 000 rows + scattered others
         pts = np.vstack([rng.random((20000, 3)) * 0.09 + 5.0, rng.random((3000, 3)) * 40.0]) + OFFSET
         pts, voxel, chunk = pts[rng.permutation(len(pts))], 0.1, 0
-    elif case == "wide_keys_u64":         # 2 km x 2 km x 100 m at 1 cm: 18+18+14 = 50 key bits -> 64-bit LDS items
+    elif case == "wide_keys_u64":         # 2 km x 2 km x 100 m at 1 cm: 18+18+14 = 50 key bits -> global-memory sort
         pts, voxel, chunk = rng.random((30000, 3)) * [2000.0, 2000.0, 100.0] + OFFSET, 0.01, 0
     elif case == "huge_keys_general":     # 21+21+21 = 63 key bits: too wide for an LDS item
         pts, voxel, chunk = rng.random((20000, 3)) * 2000.0 + OFFSET, 0.001, 6000
