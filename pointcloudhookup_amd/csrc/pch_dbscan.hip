@@ -150,15 +150,17 @@ __device__ __forceinline__ double db_boxbox_d2(const float* __restrict__ a, cons
 // ---- chunks that contain NaN/inf: sklearn raises for such a chunk (utils/tower_extraction.py:118-119);
 // its rows keep their own chunk key and sit in ONE cell (0,0,0) of that chunk that is never core, so
 // every chunk owns at least one cell and chunk_cells[] is complete (db_cells_k)
+__device__ __forceinline__ bool db_row_bad(const float* __restrict__ xyz, int64_t i) {   // row i holds a NaN/inf
+    const uint32_t a = __float_as_uint(xyz[3 * i + 0]) & 0x7FFFFFFFu;
+    const uint32_t b = __float_as_uint(xyz[3 * i + 1]) & 0x7FFFFFFFu;
+    const uint32_t c = __float_as_uint(xyz[3 * i + 2]) & 0x7FFFFFFFu;
+    return a >= 0x7F800000u || b >= 0x7F800000u || c >= 0x7F800000u;
+}
 __global__ __launch_bounds__(DB_THREADS) void db_chunkbad_k(const float* __restrict__ xyz, int64_t n,
                                                             int64_t chunk_size, uint32_t* __restrict__ bad) {
     for (int64_t i = (int64_t)blockIdx.x * DB_THREADS + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * DB_THREADS) {
-        const uint32_t a = __float_as_uint(xyz[3 * i + 0]) & 0x7FFFFFFFu;
-        const uint32_t b = __float_as_uint(xyz[3 * i + 1]) & 0x7FFFFFFFu;
-        const uint32_t c = __float_as_uint(xyz[3 * i + 2]) & 0x7FFFFFFFu;
-        if (a >= 0x7F800000u || b >= 0x7F800000u || c >= 0x7F800000u) atomicOr(&bad[i / chunk_size], 1u);
-    }
+         i += (int64_t)gridDim.x * DB_THREADS)
+        if (db_row_bad(xyz, i)) atomicOr(&bad[i / chunk_size], 1u);
 }
 
 // ---- first row holding NaN/inf (what sklearn's check_array rejects before DBSCAN.fit starts) ----
@@ -166,13 +168,8 @@ __global__ __launch_bounds__(DB_THREADS) void db_first_bad_k(const float* __rest
                                                              unsigned long long* __restrict__ first) {
     unsigned long long best = ~0ull;
     for (int64_t i = (int64_t)blockIdx.x * DB_THREADS + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * DB_THREADS) {
-        const uint32_t a = __float_as_uint(xyz[3 * i + 0]) & 0x7FFFFFFFu;
-        const uint32_t b = __float_as_uint(xyz[3 * i + 1]) & 0x7FFFFFFFu;
-        const uint32_t c = __float_as_uint(xyz[3 * i + 2]) & 0x7FFFFFFFu;
-        if ((a >= 0x7F800000u || b >= 0x7F800000u || c >= 0x7F800000u) && (unsigned long long)i < best)
-            best = (unsigned long long)i;
-    }
+         i += (int64_t)gridDim.x * DB_THREADS)
+        if (db_row_bad(xyz, i) && (unsigned long long)i < best) best = (unsigned long long)i;
     best = wave_reduce_min(best);
     if (lane_id() == 0 && best != ~0ull) atomicMin(first, best);
 }
@@ -683,7 +680,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_cells_k(const uint64_t* __restr
             if (base + j < n) cid[base + j] = cc[j];
     }
 }
-// ---- neighbour rows of one cell: lanes 0..24 each binary-search one (dy,dz) row ---------
+// ---- neighbour rows of one cell: lanes 0..24 each find one (dy,dz) row ------------------
 struct RowSet {
     int ca[DB_ROWS], cb[DB_ROWS];      // cell index range of every row
 };
@@ -693,17 +690,42 @@ __device__ __forceinline__ int db_lower(const uint64_t* __restrict__ a, int m, u
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < k) lo = mid + 1; else hi = mid; }
     return lo;
 }
-__device__ __forceinline__ int db_upper(const uint64_t* __restrict__ a, int m, uint64_t k) {
-    int lo = 0, hi = m;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] <= k) lo = mid + 1; else hi = mid; }
-    return lo;
+// cell-index range [x, y) of neighbour row `row` (cells x-2 .. x+2 at (dy, dz) = DB_ROW_DY/DZ[row]) of the cell `key`
+__device__ __forceinline__ int2 db_row_run(const DbGrid& g, const uint64_t* __restrict__ cell_key, uint64_t key,
+                                           int row) {
+    const uint64_t cx = key & ((1ull << g.bx) - 1);
+    const uint64_t cy = (key >> g.bx) & ((1ull << g.by) - 1);
+    const uint64_t cz = (key >> (g.bx + g.by)) & ((1ull << g.bz) - 1);
+    const int sh = g.bx + g.by + g.bz;
+    const uint64_t chunk = sh < 64 ? (key >> sh) : 0;
+    const int ny = (int)cy + DB_ROW_DY[row], nz = (int)cz + DB_ROW_DZ[row];
+    int2 v;
+    v.x = 0; v.y = 0;
+    if (ny >= 0 && ny <= g.my && nz >= 0 && nz <= g.mz) {
+        const int xlo = (int)cx - 2 < 0 ? 0 : (int)cx - 2;
+        const int xhi = (int)cx + 2 > g.mx ? g.mx : (int)cx + 2;
+        const int c0 = (int)g.chunk_cells[chunk], c1 = (int)g.chunk_cells[chunk + 1];   // neighbours share the chunk
+        v.x = c0 + db_lower(cell_key + c0, c1 - c0, db_pack(g, chunk, (uint64_t)nz, (uint64_t)ny, (uint64_t)xlo));
+        // the end of the run: cell keys are unique, so at most five cells (x - 2 .. x + 2) follow v.x, their keys
+        // ascending - five loads side by side instead of a second binary search (fourteen dependent loads in a chunk
+        // of 11 000 cells)
+        const uint64_t khi = db_pack(g, chunk, (uint64_t)nz, (uint64_t)ny, (uint64_t)xhi);
+        uint64_t kk[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) kk[i] = v.x + i < c1 ? cell_key[v.x + i] : ~0ull;
+        int cntx = 0;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) cntx += kk[i] <= khi ? 1 : 0;
+        v.y = v.x + cntx;
+    }
+    return v;
 }
 
-__device__ __forceinline__ void db_rows(const DbGrid& g, const uint64_t* __restrict__ cell_key, int m,
-                                        uint64_t key, RowSet* __restrict__ rs,
-                                        const int2* __restrict__ rowtab = nullptr, int cell = 0) {
+// the rows of `cell` (key `key`) into rs: from db_rowtab_k's table, or found here where the table is not built
+__device__ __forceinline__ void db_rows(const DbGrid& g, const uint64_t* __restrict__ cell_key, uint64_t key,
+                                        RowSet* __restrict__ rs, const int2* __restrict__ rowtab, int cell) {
     const int l = lane_id();
-    if (rowtab) {                                          // computed once by db_rowtab_k
+    if (rowtab) {
         if (l < DB_ROWS) {
             const int2 v = rowtab[(int64_t)cell * DB_ROWS + l];
             rs->ca[l] = v.x;
@@ -713,22 +735,9 @@ __device__ __forceinline__ void db_rows(const DbGrid& g, const uint64_t* __restr
         return;
     }
     if (l < DB_ROWS) {
-        const uint64_t cx = key & ((1ull << g.bx) - 1);
-        const uint64_t cy = (key >> g.bx) & ((1ull << g.by) - 1);
-        const uint64_t cz = (key >> (g.bx + g.by)) & ((1ull << g.bz) - 1);
-        const int sh = g.bx + g.by + g.bz;
-        const uint64_t chunk = sh < 64 ? (key >> sh) : 0;
-        const int ny = (int)cy + DB_ROW_DY[l], nz = (int)cz + DB_ROW_DZ[l];
-        int a = 0, b = 0;
-        if (ny >= 0 && ny <= g.my && nz >= 0 && nz <= g.mz) {
-            const int xlo = (int)cx - 2 < 0 ? 0 : (int)cx - 2;
-            const int xhi = (int)cx + 2 > g.mx ? g.mx : (int)cx + 2;
-            const int c0 = (int)g.chunk_cells[chunk], c1 = (int)g.chunk_cells[chunk + 1];   // neighbours share the chunk
-            a = c0 + db_lower(cell_key + c0, c1 - c0, db_pack(g, chunk, (uint64_t)nz, (uint64_t)ny, (uint64_t)xlo));
-            b = c0 + db_upper(cell_key + c0, c1 - c0, db_pack(g, chunk, (uint64_t)nz, (uint64_t)ny, (uint64_t)xhi));
-        }
-        rs->ca[l] = a;
-        rs->cb[l] = b;
+        const int2 v = db_row_run(g, cell_key, key, l);
+        rs->ca[l] = v.x;
+        rs->cb[l] = v.y;
     }
     __builtin_amdgcn_wave_barrier();
 }
@@ -739,32 +748,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_rowtab_k(DbGrid g, const uint64
     const int c = (blockIdx.x * DB_WAVES + wave_id()) * 2 + (lane_id() >> 5);   // two cells per wave
     const int l = lane_id() & 31;
     if (c >= m || l >= DB_ROWS) return;
-    const uint64_t key = cell_key[c];
-    const uint64_t cx = key & ((1ull << g.bx) - 1);
-    const uint64_t cy = (key >> g.bx) & ((1ull << g.by) - 1);
-    const uint64_t cz = (key >> (g.bx + g.by)) & ((1ull << g.bz) - 1);
-    const int sh = g.bx + g.by + g.bz;
-    const uint64_t chunk = sh < 64 ? (key >> sh) : 0;
-    const int ny = (int)cy + DB_ROW_DY[l], nz = (int)cz + DB_ROW_DZ[l];
-    int2 v;
-    v.x = 0; v.y = 0;
-    if (ny >= 0 && ny <= g.my && nz >= 0 && nz <= g.mz) {
-        const int xlo = (int)cx - 2 < 0 ? 0 : (int)cx - 2;
-        const int xhi = (int)cx + 2 > g.mx ? g.mx : (int)cx + 2;
-        const int c0 = (int)g.chunk_cells[chunk], c1 = (int)g.chunk_cells[chunk + 1];   // neighbours share the chunk
-        v.x = c0 + db_lower(cell_key + c0, c1 - c0, db_pack(g, chunk, (uint64_t)nz, (uint64_t)ny, (uint64_t)xlo));
-        // the end of the run: at most five cells (x - 2 .. x + 2) follow v.x, their keys ascending - five loads side by
-        // side instead of a second binary search (fourteen dependent loads in a chunk of 11 000 cells)
-        const uint64_t khi = db_pack(g, chunk, (uint64_t)nz, (uint64_t)ny, (uint64_t)xhi);
-        uint64_t kk[5];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) kk[i] = v.x + i < c1 ? cell_key[v.x + i] : ~0ull;
-        int cntx = 0;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) cntx += kk[i] <= khi ? 1 : 0;
-        v.y = v.x + cntx;
-    }
-    rowtab[(int64_t)c * DB_ROWS + l] = v;
+    rowtab[(int64_t)c * DB_ROWS + l] = db_row_run(g, cell_key, cell_key[c], l);
 }
 
 // ---- core points ---------------------------------------------------------------------
@@ -813,7 +797,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_core_k(DbGrid g, const float4* 
         return;
     }
     RowSet* rs = &rows[wave_id()];
-    db_rows(g, cell_key, m, cell_key[c], rs, rowtab, c);
+    db_rows(g, cell_key, cell_key[c], rs, rowtab, c);
     // candidate total: if even all candidates together are too few, nobody is core
     long long tot = 0;
     if (l < DB_ROWS) tot = (long long)cell_start[rs->cb[l]] - (long long)cell_start[rs->ca[l]];
@@ -1231,6 +1215,19 @@ __device__ __forceinline__ void uf_union(int* __restrict__ parent, int a, int b)
     }
 }
 
+// face neighbour dir (0: +x, 1: +y, 2: +z) of the cell `key`: the key it has if it exists and, for +y / +z, the row
+// that holds it ((dy,dz) = (1,0) / (0,1): rows 1 and 3 of DB_ROW_DY/DZ); +x is the next cell in sorted order
+struct DbFace { int row; uint64_t want; };
+__device__ __forceinline__ DbFace db_face(const DbGrid& g, uint64_t key, int dir) {
+    return {dir == 1 ? 1 : 3, key + (dir == 0 ? 1ull : (dir == 1 ? (1ull << g.bx) : (1ull << (g.bx + g.by))))};
+}
+// may core cells A and B still need a link: core boxes within eps, and plain (possibly stale) parents differ - equal
+// parents were in one set at some time, and sets only ever merge
+__device__ __forceinline__ bool db_link_open(const DbGrid& g, const float* __restrict__ cell_box,
+                                             const float* __restrict__ boxB, const int* parent, int A, int B) {
+    return !(db_boxbox_d2(cell_box + 6 * (int64_t)A, boxB) > g.eps2) && parent[A] != parent[B];
+}
+
 // one wave per core cell A.  Phase 1 (64 candidate cells at a time, one per lane): neighbour core
 // cells B > A whose core boxes are within eps and whose root differs from A's survive.
 // Phase 2 (wave-wide per survivor): look for one core pair within eps (lanes over B's points,
@@ -1254,7 +1251,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_union_k(DbGrid g, const float4*
     RowSet* rs = &rows[wave_id()];
     int* cd = cand[wave_id()];
     const uint64_t keyA = cell_key[A];
-    db_rows(g, cell_key, m, keyA, rs, rowtab, A);
+    db_rows(g, cell_key, keyA, rs, rowtab, A);
     int total;
     {
         // flatten the <= 25 runs of <= 5 cells into one candidate list (prefix over the run lengths)
@@ -1268,18 +1265,13 @@ __global__ __launch_bounds__(DB_THREADS) void db_union_k(DbGrid g, const float4*
     __builtin_amdgcn_wave_barrier();
     const uint32_t as = cell_start[A], ae = cell_start[A + 1];
     const bool a_dense = cell_ncore[A] == (ae - as);
-    const float* boxA = cell_box + 6 * (int64_t)A;
     for (int base = 0; base < total; base += 64) {
         int B = -1;
         if (base + l < total) B = cd[base + l];
         bool live = false;
         if (B > A) {                                       // every unordered pair once
-            if (cell_ncore[B] != 0 && !(db_boxbox_d2(boxA, cell_box + 6 * (int64_t)B) > g.eps2)) {
-                // plain (possibly stale) loads first: equal parents were in one set at some time,
-                // and sets only ever merge
-                live = parent[A] != parent[B];
-                if (live) live = uf_find(parent, A) != uf_find(parent, B);
-            }
+            live = cell_ncore[B] != 0 && db_link_open(g, cell_box, cell_box + 6 * (int64_t)B, parent, A, B);
+            if (live) live = uf_find(parent, A) != uf_find(parent, B);
         }
         unsigned long long todo = __ballot(live);
         while (todo) {
@@ -1324,15 +1316,14 @@ __global__ __launch_bounds__(DB_THREADS) void db_union_pairs_k(DbGrid g, const f
     if (lane_on) {
         const uint32_t ncoreA = cell_ncore[A];
         if (ncoreA != 0) {
-            const uint64_t keyA = cell_key[A];
+            const DbFace f = db_face(g, cell_key[A], dir);
             int B = -1;
             if (dir == 0) {
-                if (A + 1 < m && cell_key[A + 1] == keyA + 1ull) B = A + 1;
+                if (A + 1 < m && cell_key[A + 1] == f.want) B = A + 1;
             } else {
-                const int2 run = rowtab[(int64_t)A * DB_ROWS + (dir == 1 ? 1 : 3)];
-                const uint64_t want = keyA + (dir == 1 ? (1ull << g.bx) : (1ull << (g.bx + g.by)));
+                const int2 run = rowtab[(int64_t)A * DB_ROWS + f.row];
                 for (int k = run.x; k < run.y; ++k)
-                    if (cell_key[k] == want) { B = k; break; }
+                    if (cell_key[k] == f.want) { B = k; break; }
             }
             if (B > A) {
                 const uint32_t nB = cell_ncore[B];
@@ -1340,8 +1331,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_union_pairs_k(DbGrid g, const f
                     float boxB[6];
 #pragma unroll
                     for (int a = 0; a < 6; ++a) boxB[a] = cell_box[6 * (int64_t)B + a];
-                    bool pend = !(db_boxbox_d2(cell_box + 6 * (int64_t)A, boxB) > g.eps2);
-                    if (pend) pend = parent[A] != parent[B];
+                    bool pend = db_link_open(g, cell_box, boxB, parent, A, B);
                     int rootA = A, rootB = B;
                     if (pend) {
                         rootA = uf_find(parent, A);
@@ -1405,21 +1395,20 @@ __global__ __launch_bounds__(DB_THREADS) void db_union_face_k(DbGrid g, const fl
     const unsigned long long gmask = grp < 3 ? (0x1FFFFFull << (21 * grp)) : 0ull;
     RowSet* rs = &rows[wave_id()];
     const uint64_t keyA = cell_key[A];
-    db_rows(g, cell_key, m, keyA, rs, rowtab, A);
-    // +x is the next cell in sorted order, +y / +z sit in the runs (dy,dz) = (1,0) / (0,1)
-    // (rows 1 and 3 of DB_ROW_DY/DZ)
+    db_rows(g, cell_key, keyA, rs, rowtab, A);
     int B = -1;
     {
         bool found = false;
         int k = -1;
-        if (grp == 0) {
-            k = A + 1;
-            found = gl == 0 && k < m && cell_key[k] == keyA + 1ull;
-        } else if (grp < 3) {
-            const int r = grp == 1 ? 1 : 3;
-            const uint64_t want = keyA + (grp == 1 ? (1ull << g.bx) : (1ull << (g.bx + g.by)));
-            k = rs->ca[r] + gl;
-            found = k < rs->cb[r] && cell_key[k] == want;
+        if (grp < 3) {
+            const DbFace f = db_face(g, keyA, grp);
+            if (grp == 0) {
+                k = A + 1;
+                found = gl == 0 && k < m && cell_key[k] == f.want;
+            } else {
+                k = rs->ca[f.row] + gl;
+                found = k < rs->cb[f.row] && cell_key[k] == f.want;
+            }
         }
         const unsigned long long fm = __ballot(found) & gmask;
         if (fm) B = __shfl(k, (int)__builtin_ctzll(fm), 64);
@@ -1437,9 +1426,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_union_face_k(DbGrid g, const fl
         b_dense = nB == (be - bs);
 #pragma unroll
         for (int a = 0; a < 6; ++a) boxB[a] = cell_box[6 * (int64_t)B + a];
-        pend = nB != 0 && !(db_boxbox_d2(cell_box + 6 * (int64_t)A, boxB) > g.eps2);
-        // plain (possibly stale) loads first: equal parents were in one set at some time, and sets only merge
-        if (pend) pend = parent[A] != parent[B];
+        pend = nB != 0 && db_link_open(g, cell_box, boxB, parent, A, B);
     }
     if (gl != 0) pend = false;                             // one lane per group looks the roots up
     int rootA = A, rootB = B;
@@ -1657,7 +1644,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_border_k(DbGrid g, const float4
     if (cell_ncore[A] == (ae - as)) return;                // no border candidates here
     const int l = lane_id();
     RowSet* rs = &rows[wave_id()];
-    db_rows(g, cell_key, m, cell_key[A], rs, rowtab, A);
+    db_rows(g, cell_key, cell_key[A], rs, rowtab, A);
     // quick reject: no core cell anywhere around
     int any = 0;
     if (l < DB_ROWS)
@@ -1667,11 +1654,11 @@ __global__ __launch_bounds__(DB_THREADS) void db_border_k(DbGrid g, const float4
     // cells x-2 .. x+2 of one (y, z)): count, label and core box are read once per cell A, side by side.  One cell after
     // the other - count, label, six box words, each a dependent load, for up to 125 cells and every query again - was
     // this kernel: a lone noise point beside a tower tested ~100 boxes at ~0.4 us each, 51 us for 2.6 MB of traffic.
+    // A row never holds more than five cells: the keys of x-2 .. x+2 in one (chunk, y, z) are unique (db_row_run).
     constexpr int BR = 3, BROWS = 12;
     int Bc[BR], Bl[BR];
     bool Bd[BR];
     float Bx[BR][6];
-    bool wide = false;                                       // a row of more than five cells (never by construction)
 #pragma unroll
     for (int rd = 0; rd < BR; ++rd) {
         const int row = rd * BROWS + l / 5, k = l % 5;
@@ -1679,10 +1666,8 @@ __global__ __launch_bounds__(DB_THREADS) void db_border_k(DbGrid g, const float4
 #pragma unroll
         for (int a = 0; a < 6; ++a) Bx[rd][a] = 0.0f;
         if (l < 5 * BROWS && row < DB_ROWS) {
-            const int ca = rs->ca[row], cb = rs->cb[row];
-            wide |= cb - ca > 5;
-            const int B = ca + k;
-            if (B < cb) {
+            const int B = rs->ca[row] + k;
+            if (B < rs->cb[row]) {
                 const uint32_t nb = cell_ncore[B];
                 if (nb != 0) {
                     Bc[rd] = B;
@@ -1693,38 +1678,6 @@ __global__ __launch_bounds__(DB_THREADS) void db_border_k(DbGrid g, const float4
                 }
             }
         }
-    }
-    if (__ballot(wide)) {                                    // the plain loop, cell after cell
-        for (uint32_t q = as; q < ae; ++q) {
-            if (core_s[q]) continue;
-            const float4 qp = pts[q];
-            int best = INT_BIG;
-            for (int r = 0; r < DB_ROWS; ++r) {
-                const int cb = rs->cb[r];
-                for (int B = rs->ca[r]; B < cb; ++B) {
-                    const uint32_t nb = cell_ncore[B];
-                    if (nb == 0) continue;
-                    const int lab = cell_label[B];
-                    if (lab >= best) continue;
-                    if (db_box_d2(qp, cell_box + 6 * (int64_t)B) > g.eps2) continue;
-                    const uint32_t bs = cell_start[B], be = cell_start[B + 1];
-                    const bool b_dense = nb == (be - bs);
-                    for (uint32_t j0 = bs; j0 < be; j0 += 64) {
-                        const uint32_t j = j0 + l;
-                        bool hit = false;
-                        if (j < be && (b_dense || core_s[j])) hit = db_within2(qp, pts[j], g);
-                        if (__ballot(hit)) { best = lab; break; }
-                    }
-                }
-            }
-            if (l == 0 && best != INT_BIG) labels[__float_as_uint(qp.w)] = best;
-            if (box_acc && best != INT_BIG && best >= 0 && best < box_cap && l < 6) {
-                const float v = l % 3 == 0 ? qp.x : (l % 3 == 1 ? qp.y : qp.z);
-                const uint32_t k = f32_ordered(v);
-                atomicMax(&box_acc[8 * (int64_t)best + l], l < 3 ? ~k : k);
-            }
-        }
-        return;
     }
     for (uint32_t q = as; q < ae; ++q) {
         if (core_s[q]) continue;

@@ -472,6 +472,33 @@ def test_dbscan_nonfinite_chunk_stays_noise(cuda, oracle_clib):
     assert k == 0 and (labels.cpu().numpy() == -1).all()
 
 
+def test_dbscan_more_cells_than_the_row_table(cuda, oracle_clib):
+    """More cells than the neighbour-row table holds (max(n/4, 65 536)): the kernels find every cell's rows themselves
+    and the face links run without db_union_pairs.  Mostly isolated points, plus dense blobs in every chunk for core
+    cells, unions and border points."""
+    rng = np.random.default_rng(21)
+    eps, ms, chunk = 1.0, 10, 20000
+    parts = []
+    for c in range(4):
+        blobs = [rng.normal([rng.uniform(100, 1900), rng.uniform(20, 180), 15.0], 1.2, (1000, 3)) for _ in range(3)]
+        lone = np.column_stack([rng.uniform(0, 2000, chunk - 3000), rng.uniform(0, 200, chunk - 3000),
+                                rng.uniform(0, 30, chunk - 3000)])
+        X = np.vstack(blobs + [lone])
+        parts.append(X[rng.permutation(chunk)])
+    X = np.vstack(parts).astype(np.float32)
+    cell = eps / np.sqrt(3.0)
+    cells = sum(len(np.unique(np.floor((X[s:s + chunk] - X[s:s + chunk].min(0)) / cell), axis=0))
+                for s in range(0, len(X), chunk))
+    assert cells > 70000, cells
+    want = odb.dbscan_chunked(X, eps, ms, chunk, fit="c")
+    labels, core, k = ops.dbscan(_dev(X, cuda), eps, ms, chunk, want_core=True)
+    np.testing.assert_array_equal(labels.cpu().numpy(), want)
+    assert k == want.max() + 1
+    wcore = np.concatenate([odb.dbscan_fit_c(X[s:s + chunk], eps, ms)[1] for s in range(0, len(X), chunk)])
+    np.testing.assert_array_equal(core.cpu().numpy(), wcore)
+    assert 0 < int(wcore.sum()) < len(X) and ((want >= 0) & (wcore == 0)).any()   # core, non-core and border points
+
+
 def test_dbscan_border_tie_takes_smallest_cluster(cuda):
     # two dense lines, one border point exactly between them within eps of both
     a = np.column_stack([np.linspace(0, 1, 30), np.zeros(30), np.zeros(30)])
