@@ -2,10 +2,17 @@
 """Benchmark of the hot path: ground filter + tower clustering on a synthetic corridor.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--mode stream|tiled] [--points P] [--kind corridor|uniform]
-                  [--dump-outputs DIR]
+                  [--dump-outputs DIR] [--full]
 
 --dump-outputs DIR (e.g. bench_outputs/, which git ignores) writes the outputs of the last timed step as .npy files:
 the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints its line: the headline value, the
+config, and what the timed steps record anyway (per-kernel hipEvent times, rooflines by algorithmic bytes).  --full
+adds everything that needs work of its own: the kNN byte models and the pair-counting fit, the counter figures of
+profiles/traffic.json, the config-4 side run (`tiled`), the side measurements (other workloads, H2D, tower table,
+voxel stage, drop-ins end to end, config 5, two tiles in flight) and the CPU baseline; --no-side, --no-e2e,
+--no-tile-stream and --no-cpu-baseline leave parts of that out.  A --mode tiled line is the same with or without --full.
 
 One "step" = one pass of stages B + C + D0 (float32 centroid/centring, percentile height
 filter, chunked exact DBSCAN, label grouping) over one resident float32 [P,3] tile per GPU.
@@ -15,7 +22,7 @@ environment) this process IS a rank; started plainly with --gpus N > 1 it starts
 
 --mode stream (default; BASELINE configs[2] per GPU): every rank owns an independent 100 M-point tile, the
   reference's 50 000-row chunked DBSCAN; the only collective is the cluster-table reconciliation
-  (tiles.reconcile).  Weak scaling.  The default line also carries a `tiled` object: the config-4 path below on
+  (tiles.reconcile).  Weak scaling.  With --full the line also carries a `tiled` object: the config-4 path below on
   --tiled-points-per-gpu points per rank (50 M: at 8 GPUs exactly BASELINE configs[3]), so that the scaling runs
   show the real cross-tile path over RCCL.
 --mode tiled (BASELINE configs[3]): ONE corridor spread over the ranks as x-tiles + halo; chained float32 centroid,
@@ -205,7 +212,7 @@ def dryrun(args):
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps({"metric": "dryrun", "value": 0.0, "n_gpus": world, "ranks_seen": int(seen.item()),
-                          "mode": args.mode, "steps": args.steps, "warmup": args.warmup,
+                          "mode": args.mode, "steps": args.steps, "warmup": args.warmup, "full": args.full,
                           "parent_imported_torch": os.environ.get("PCH_BENCH_PARENT_TORCH")}))
 
 
@@ -363,21 +370,25 @@ def main():
     ap.add_argument("--verify", action="store_true",
                     help="tiled runs: rank 0 rebuilds the whole cloud, runs the single-GPU path and checks centroid, "
                          "threshold and every rank's owned labels against it (not timed)")
+    ap.add_argument("--full", action="store_true",
+                    help="stream mode: also the kNN byte models, the counter figures, the config-4 side run, the side "
+                         "measurements and the CPU baseline (a plain run times the steps and prints the line only)")
     ap.add_argument("--tiled-points-per-gpu", type=int, default=50_000_000,
-                    help="size of the config-4 side run of the default mode (x world = its cloud)")
+                    help="size of the config-4 side run of the default mode with --full (x world = its cloud)")
     ap.add_argument("--kind", default="corridor", choices=["corridor", "uniform"])
     ap.add_argument("--frame", default="offset", choices=["offset", "local"],
                     help="offset: EPSG:4547-scale coordinates like the reference's data (default); "
                          "local: corridor starts at the origin")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-tile-stream", action="store_true",
-                    help="skip the two-tiles-in-flight side measurement (profiling runs)")
+                    help="--full without the two-tiles-in-flight side measurement (profiling runs)")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip every side measurement (voxel stage, other workloads): profiling runs")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the 100 M-point LAS file run through the drop-ins")
+                    help="--full without any side measurement (voxel stage, other workloads): profiling runs")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="--full without the 100 M-point LAS file run through the drop-ins")
     ap.add_argument("--e2e-points", type=int, default=100_000_000)
     ap.add_argument("--las", default=None,
-                    help="BASELINE config 5: a real .las file run end to end through the drop-in modules "
+                    help="BASELINE config 5 (--full): a real .las file run end to end through the drop-in modules "
                          "(voxel downsample -> extract_towers); reported as a side value, 'skipped' without a file")
     ap.add_argument("--cpu-budget-s", type=float, default=20.0)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -440,7 +451,7 @@ def main():
                               "seed": seed, "parallelism": f"x-tiles x{world}"},
                    "tiled": res, "roofline": res.get("roofline"), "cpu_baseline": None,
                    "dump_outputs": res.get("dump_outputs"),
-                   "note": "cpu_baseline is carried by the default (--mode stream) line"}
+                   "note": "cpu_baseline is carried by the --full line of the default mode (--mode stream)"}
             print(json.dumps(out))
         if world > 1:
             dist.destroy_process_group()
@@ -503,9 +514,9 @@ def main():
                                    stats=cl["stats"]),
                               dict(points=g["points"], labels=cl["labels"], perm=cl["perm"]), NF)
 
-    # ---- config-4 side run (every rank takes part): ONE cloud of world x tiled-points-per-gpu points
+    # ---- config-4 side run (--full, every rank takes part): ONE cloud of world x tiled-points-per-gpu points
     tiled_res = None
-    if not args.no_side and args.tiled_points_per_gpu > 0:
+    if args.full and not args.no_side and args.tiled_points_per_gpu > 0:
         # Only what can fail BEFORE the first collective is caught per rank (building the tile: memory); whether every
         # rank got that far is agreed over the default group, so either all ranks enter tiled_step or none does.  An
         # error inside the collective phase propagates: the launcher then exits non-zero at once instead of leaving
@@ -541,7 +552,10 @@ def main():
                      key=lambda r: -r[3])
     timed = {r[0] for r in kernels}
     gpu_ms = sum(r[3] for r in kernels) + sum(v for k, v in warm_ms.items() if k not in timed)
-    knn_bytes_all, knn_bytes, occ = knn_tile_bytes(cl["ground"]["points"], EPS, CHUNK, MIN_POINTS)
+    # the kNN byte models take two cell sweeps of their own over the kept points: --full only (without them the kNN
+    # kernels have no roofline)
+    knn_bytes_all, knn_bytes, occ = (knn_tile_bytes(cl["ground"]["points"], EPS, CHUNK, MIN_POINTS) if args.full
+                                     else (None, None, None))
     dom = kernels[0]
 
     def roof(name, avg_ms, per_step=1.0):
@@ -616,7 +630,7 @@ def main():
     tr_path = os.path.join(ROOT, "profiles", "traffic.json")   # PMC passes, see profiles/README.md
     step_traffic = None
     traffic_dropped = None
-    if os.path.exists(tr_path):
+    if args.full and os.path.exists(tr_path):
         try:
             tr = json.load(open(tr_path)).get("workloads", {}).get(f"{args.kind}/{args.frame}/{N}")
             sys.path.insert(0, os.path.join(ROOT, "profiles"))
@@ -683,8 +697,8 @@ def main():
         "dump_outputs": dumped,
     }
 
-    # ---- side measurements (none of them in `value`)
-    if world == 1 and not args.no_side:
+    # ---- side measurements (--full; none of them in `value`)
+    if world == 1 and args.full and not args.no_side:
         def timed_steps(tile, k):
             pipeline.cluster_points(tile, EPS, MIN_POINTS, CHUNK)
             torch.cuda.synchronize()
@@ -876,7 +890,7 @@ def main():
     # ---- the drop-ins end to end at the HEADLINE size and the GUI's own settings (voxel 0.1 m, 500 000-row chunks:
     # pyGUI_towers_test.py:351-358): a 100 M-point format-3 LAS file (3.4 GB, warm page cache) through
     # run_voxel_downsampling, then extract_towers on its output, each with a per-stage wall-clock table
-    if world == 1 and not args.no_side and not args.no_e2e:
+    if world == 1 and args.full and not args.no_side and not args.no_e2e:
         try:
             import shutil
             import tempfile
@@ -1001,8 +1015,8 @@ def main():
         except Exception as e:
             out["dropin_end_to_end_100m"] = {"error": f"{type(e).__name__}: {e}"}
 
-    # ---- BASELINE config 5: a real .las through the drop-ins
-    if world == 1:
+    # ---- BASELINE config 5: a real .las through the drop-ins (--full)
+    if world == 1 and args.full:
         if args.las and os.path.exists(args.las):
             try:
                 import tempfile
@@ -1029,10 +1043,10 @@ def main():
             out["config5_real_las"] = {"skipped": "no file" if not args.las else f"no file at {args.las}",
                                        "note": "the reference ships no .las sample; pass --las PATH"}
 
-    # ---- tile stream side measurement (not in `value`): two host threads, each with its own HIP
+    # ---- tile stream side measurement (--full, not in `value`): two host threads, each with its own HIP
     # stream and workspace, work through tiles at the same time - one tile's latency-bound
     # clustering overlaps the other's issue/bandwidth-bound filter.  Same tile as above.
-    if world == 1 and not args.no_tile_stream:
+    if world == 1 and args.full and not args.no_tile_stream:
         try:
             import threading
             per_thread, nthreads = max(2, args.steps), 2
@@ -1076,8 +1090,8 @@ def main():
         except Exception as e:
             out["tile_stream"] = {"error": str(e)}
 
-    # ---- CPU baseline: the reference's own library calls (numpy + sklearn) on host cores
-    if world == 1 and not args.no_cpu_baseline:
+    # ---- CPU baseline (--full): the reference's own library calls (numpy + sklearn) on host cores
+    if world == 1 and args.full and not args.no_cpu_baseline:
         try:
             from oracle import ground_filter as ogf, dbscan as odb
             host = raw.cpu().numpy()

@@ -8,7 +8,7 @@ tag=$1; points=$2; kind=$3; frame=$4
 out=gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-args="bench.py --points $points --kind $kind --frame $frame --no-cpu-baseline --no-tile-stream --no-side"
+args="bench.py --points $points --kind $kind --frame $frame --full --no-cpu-baseline --no-tile-stream --no-side"
 rocprofv3 --kernel-trace --stats -d $out/stats --output-format csv -- python3 $args --steps 5 --warmup 1 > $out/stats.json 2> $out/stats.err
 echo "[collect $tag] stats done"
 rocprofv3 --pmc FETCH_SIZE -d $out/pmc_fetch --output-format csv -- python3 $args --steps 2 --warmup 1 > $out/fetch.json 2> $out/fetch.err

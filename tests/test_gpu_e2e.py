@@ -363,6 +363,30 @@ def test_bench_dump_outputs_are_the_timed_steps_result(cuda, tmp_path):
     assert np.array_equal(t1["centroid"], np.asarray(out["tiled"]["centroid"], np.float32))
 
 
+def test_bench_plain_run_leaves_the_side_measurements_to_full(cuda, tmp_path):
+    """A plain `bench.py` run prints the headline and what its timed steps recorded, nothing that needs work of its
+    own; with --full the same arguments add the kNN byte models, the config-4 side run and the CPU baseline (its labels
+    equal to the reference's on the sampled chunks), and the headline fields mean the same in both lines."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    args = ("--points", "3000000", "--steps", "2", "--warmup", "1")
+    plain, _ = _bench_dump(root, tmp_path / "plain", *args)
+    full, _ = _bench_dump(root, tmp_path / "full", *args, "--full", "--tiled-points-per-gpu", "12000000", "--no-e2e",
+                          "--cpu-budget-s", "0")
+    for out in (plain, full):
+        assert out["unit"] == "Mpts/s" and out["higher_is_better"] is True and out["steps"] == 2
+        assert out["value"] > 0 and out["ms_per_step"] > 0 and out["kernels"]
+        assert abs(out["value"] - 3e6 / out["ms_per_step"] / 1e3) <= 0.02 * out["value"]
+    assert plain["dtype"] == full["dtype"] and plain["metric"] == full["metric"]
+    assert plain["config"] == full["config"]
+    assert plain["knn_kernel"] is None and plain["knn_cell_occupancy"] is None and plain["tiled"] is None
+    side = {"other_workloads", "h2d_inclusive", "tower_table", "voxel_stage", "tile_stream", "cpu_baseline"}
+    assert not side & set(plain)
+    assert side <= set(full) and not [k for k in side - {"other_workloads"} if "error" in full[k]]
+    assert full["knn_kernel"]["kernel"] == "db_core" and full["knn_cell_occupancy"]["points"] > 0
+    assert full["tiled"]["points_total"] == 12_000_000 and full["tiled"]["clusters"] > 0
+    assert full["cpu_baseline"]["parity_on_sample"] is True
+
+
 def test_rccl_probe_failure_degrades_to_gloo(cuda):
     """tiles.init_from_env with automatic backend choice: the default group is gloo and an RCCL group is PROBED.  Two
     ranks on this one GPU make RCCL refuse (duplicate device) - the run must go on with gloo exchanges and still

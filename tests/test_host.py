@@ -305,6 +305,17 @@ def test_bench_launches_its_own_ranks():
     assert r.returncode != 0 and "--steps" in r.stderr
 
 
+def test_bench_full_is_off_by_default_and_reaches_every_rank():
+    """--full (the side measurements) is off in a plain run and, given, passed on to the ranks the launcher starts."""
+    import json
+    r = _bench("--gpus", "1", PCH_BENCH_DRYRUN="1")
+    assert r.returncode == 0 and json.loads(r.stdout)["full"] is False
+    r = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--full", PCH_BENCH_DRYRUN="1")
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads(r.stdout)
+    assert out["full"] is True and out["ranks_seen"] == 2
+
+
 def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path):
     """bench.dump_outputs (--dump-outputs): float32 stays float32, integers and flags become exact float64, per-row
     outputs are written whole up to DUMP_SAMPLE_ROWS rows and above that as one fixed sample of rows shared by all
