@@ -349,10 +349,12 @@ __device__ __forceinline__ uint32_t cs_cell_key(const DbGrid& g, float x, float 
     return (((cz << g.by) | cy) << g.bx) | cx;
 }
 
+// gate: runs only the chunks whose word is set (those db_cellscatter_k handed over); the others return at once
 __global__ __launch_bounds__(CS_THREADS) void db_chunksort_k(
-    const float* __restrict__ xyz, int64_t n, DbGrid g, uint32_t* __restrict__ bad,
+    const float* __restrict__ xyz, int64_t n, DbGrid g, const uint32_t* __restrict__ gate, uint32_t* __restrict__ bad,
     float4* __restrict__ xbuf, float4* __restrict__ pts, uint64_t* __restrict__ keys_out,
     uint32_t* __restrict__ status, unsigned long long* __restrict__ stamps) {
+    if (gate[blockIdx.x] == 0u) return;                 // workgroup-uniform
 #ifdef PCH_CS_STAMPS                                    // phase timing of one workgroup (tuning builds only)
     int stamp_i = 0;
 #define CS_STAMP() if (stamps && blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) stamps[stamp_i++] = wall_clock64();
@@ -581,6 +583,178 @@ __global__ __launch_bounds__(CS_THREADS) void db_chunksort_k(
     CS_STAMP();
     if (stamps && blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) for (int k = 0; k < 3; ++k) stamps[8 + k] = tacc[k];
 #endif
+}
+
+// ---- chunk-local counted scatter: the rows of one chunk grouped by cell, one workgroup per chunk ----------------
+// A chunk holds few distinct cells (a 50 000-row corridor chunk 105-333, a uniform one up to ~2 800), so the rows are
+// placed by a counting sort over the chunk's OWN cells instead of an LSD radix sort over 15-17-bit keys.  Sweep 1
+// reads the rows, checks them (as db_chunksort_k's sweep B) and counts every cell in an open-addressing LDS table
+// (CAS on the key word, per-lane atomics: 64 consecutive rows hold ~32 distinct cells, so wave aggregation does not
+// pay).  Then the occupied slots are compacted, sorted by key (bitonic, sized by the cell count) and an exclusive
+// scan of their counts in key order turns every count into the cell's first position.  Sweep 2 reads the rows again
+// (the chunk was just read: L2 / MALL), looks the cell up and takes its position from the cell's cursor.  12 + 12
+// bytes read, 16 + 8 written per row; the cell key is computed twice.  Rows of one cell are NOT in file order, and
+// their order can change from run to run; no reader of the sorted rows depends on it.
+// A chunk with more than CT_CELLS cells stops counting, sets ovf[c] and writes nothing else: db_chunksort_k, launched
+// right behind with ovf as its gate, sorts it.  NaN/inf and one-cell chunks keep their rows in place, as db_chunksort_k does.
+constexpr int CT_SLOTS = 4096;                  // table slots (key + count: 32 KiB)
+constexpr int CT_BITS  = 12;                    // log2(CT_SLOTS)
+constexpr int CT_CELLS = 1024;                  // cells a chunk may hold here (measured: a uniform-cloud chunk of ~1 600
+                                                // cells took longer here than in db_chunksort_k)
+constexpr uint32_t CT_EMPTY = 0xFFFFFFFFu;      // no cell key has 32 bits (this path takes cellbits <= 31)
+static_assert(CT_SLOTS == 1 << CT_BITS && CT_CELLS + CS_THREADS < CT_SLOTS, "the table never fills (see sweep 1)");
+
+__device__ __forceinline__ uint32_t ct_hash(uint32_t k) { return (k * 0x9E3779B1u) >> (32 - CT_BITS); }
+
+__global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
+    const float* __restrict__ xyz, int64_t n, DbGrid g, uint32_t* __restrict__ bad, uint32_t* __restrict__ ovf,
+    float4* __restrict__ pts, uint64_t* __restrict__ keys_out, uint32_t* __restrict__ status) {
+    __shared__ uint32_t tkey[CT_SLOTS];
+    __shared__ uint32_t tcnt[CT_SLOTS];         // sweep 1: rows per cell; sweep 2: the cell's next position
+    __shared__ uint32_t skey[CT_CELLS];         // the chunk's cell keys, sorted
+    __shared__ uint32_t wsum[CS_WAVES];
+    __shared__ uint32_t flags[5];               // [0] NaN/inf, [1] point outside the grid, [2] cells, [3] too many
+                                                // cells, [4] cells compacted so far
+    const int tid = threadIdx.x, w = wave_id(), l = lane_id();
+    const int64_t c = blockIdx.x;
+    const int64_t lo = c * g.chunk_size;
+    const int cn = (int)((n - lo) < g.chunk_size ? (n - lo) : g.chunk_size);
+    const Row3* __restrict__ rows = reinterpret_cast<const Row3*>(xyz) + lo;
+    for (int j = tid; j < CT_SLOTS; j += CS_THREADS) { tkey[j] = CT_EMPTY; tcnt[j] = 0u; }
+    if (tid < 5) flags[tid] = 0u;
+    __syncthreads();
+    constexpr int HU = 8;                               // rows per thread in flight
+    // ---- sweep 1: checks, cell counts.  A row inserts only while flags[3] is clear, and at most one new key per
+    // thread can be in flight when it is set, so the table holds at most CT_CELLS + CS_THREADS keys: a probe always
+    // ends at its key or at an empty slot (the bound on the probe loop is never reached)
+    for (int i0 = 0; i0 < cn; i0 += HU * CS_THREADS) {
+        if (__hip_atomic_load(&flags[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;   // too many cells
+        Row3 q[HU];
+#pragma unroll
+        for (int u = 0; u < HU; ++u) {
+            const int i = i0 + u * CS_THREADS + tid;
+            q[u] = rows[i < cn ? i : 0];
+        }
+#pragma unroll
+        for (int u = 0; u < HU; ++u) {
+            const bool in = i0 + u * CS_THREADS + tid < cn;
+            const bool fin = fabsf(q[u].x) < INFINITY && fabsf(q[u].y) < INFINITY && fabsf(q[u].z) < INFINITY;
+            bool ok;
+            const uint32_t k = cs_cell_key(g, q[u].x, q[u].y, q[u].z, ok);
+            if (in && !fin) flags[0] = 1u;
+            else if (in && !ok) flags[1] = 1u;
+            if (in && fin && __hip_atomic_load(&flags[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) {
+                uint32_t h = ct_hash(k);
+                for (int p = 0; p < CT_SLOTS; ++p, h = (h + 1u) & (CT_SLOTS - 1)) {
+                    const uint32_t old = atomicCAS(&tkey[h], CT_EMPTY, k);
+                    if (old == CT_EMPTY && atomicAdd(&flags[2], 1u) >= (uint32_t)CT_CELLS) flags[3] = 1u;
+                    if (old == CT_EMPTY || old == k) { atomicAdd(&tcnt[h], 1u); break; }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const bool isbad = flags[0] != 0u;                  // the whole chunk stays noise: one cell, never core
+    const uint32_t ncell = flags[2];
+    const bool over = !isbad && ncell > (uint32_t)CT_CELLS;
+    if (tid == 0) {
+        ovf[c] = over ? 1u : 0u;                        // written for every chunk: db_chunksort_k's gate
+        if (!over) {
+            bad[c] = isbad ? 1u : 0u;
+            if (!isbad && flags[1]) atomicOr(status, 1u);
+        }
+    }
+    if (over) return;                                   // db_chunksort_k takes this chunk
+    const int sh = g.bx + g.by + g.bz;
+    const uint64_t hi = sh < 64 ? ((uint64_t)c << sh) : 0ull;
+    if (isbad || ncell == 1u) {                         // rows stay where they are: one cell (cell 0 if bad)
+        for (int i = tid; i < cn; i += CS_THREADS) {
+            const Row3 q = rows[i];
+            float4 o4;
+            o4.x = q.x; o4.y = q.y; o4.z = q.z; o4.w = __uint_as_float((uint32_t)(lo + i));
+            pts[lo + i] = o4;
+            bool ok;
+            keys_out[lo + i] = isbad ? hi : (hi | cs_cell_key(g, q.x, q.y, q.z, ok));
+        }
+        return;
+    }
+    // ---- the occupied slots, compacted (in any order) and padded to a power of two ...
+    const int P = 1 << (32 - __clz((int)ncell - 1));    // 2 <= P <= CT_CELLS
+    for (int j0 = 0; j0 < CT_SLOTS; j0 += CS_THREADS) {
+        const uint32_t k = tkey[j0 + tid];
+        const uint64_t m = __ballot(k != CT_EMPTY);
+        uint32_t base = 0;
+        if (l == 0 && m) base = atomicAdd(&flags[4], (uint32_t)__popcll(m));
+        base = (uint32_t)__shfl((int)base, 0, 64);
+        if (k != CT_EMPTY) skey[base + (uint32_t)__popcll(m & lanemask_lt())] = k;
+    }
+    for (int j = (int)ncell + tid; j < P; j += CS_THREADS) skey[j] = CT_EMPTY;
+    __syncthreads();
+    // ... sorted by key (bitonic; keys are distinct) ...
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < P / 2; t += CS_THREADS) {
+                const int a = 2 * t - (t & (j - 1)), b = a + j;
+                const uint32_t ka = skey[a], kb = skey[b];
+                if ((ka > kb) == ((a & k) == 0)) { skey[a] = kb; skey[b] = ka; }
+            }
+            __syncthreads();
+        }
+    }
+    // ... and their counts scanned in that order: tcnt[slot] becomes the cell's first position.  Thread t owns the
+    // cells 4t .. 4t+3 of the sorted list (P <= 4 * CS_THREADS)
+    {
+        uint32_t slot[4], cnt[4], sum = 0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = 4 * tid + u;
+            slot[u] = 0; cnt[u] = 0;
+            if (j < (int)ncell) {
+                const uint32_t k = skey[j];
+                uint32_t h = ct_hash(k);
+                for (int p = 0; p < CT_SLOTS && tkey[h] != k; ++p) h = (h + 1u) & (CT_SLOTS - 1);
+                slot[u] = h;
+                cnt[u] = tcnt[h];
+            }
+            sum += cnt[u];
+        }
+        const uint32_t incl = wave_scan_incl(sum);
+        if (l == 63) wsum[w] = incl;
+        __syncthreads();
+        uint32_t run = incl - sum;
+        for (int w2 = 0; w2 < w; ++w2) run += wsum[w2];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (4 * tid + u < (int)ncell) tcnt[slot[u]] = run;    // only this thread touches these slots
+            run += cnt[u];
+        }
+    }
+    __syncthreads();
+    // ---- sweep 2: every row to its cell's next position
+    for (int i0 = 0; i0 < cn; i0 += HU * CS_THREADS) {
+        Row3 q[HU];
+#pragma unroll
+        for (int u = 0; u < HU; ++u) {
+            const int i = i0 + u * CS_THREADS + tid;
+            q[u] = rows[i < cn ? i : 0];
+        }
+#pragma unroll
+        for (int u = 0; u < HU; ++u) {
+            const int i = i0 + u * CS_THREADS + tid;
+            if (i < cn) {
+                bool ok;
+                const uint32_t k = cs_cell_key(g, q[u].x, q[u].y, q[u].z, ok);
+                uint32_t h = ct_hash(k);
+                for (int p = 0; p < CT_SLOTS && tkey[h] != k; ++p) h = (h + 1u) & (CT_SLOTS - 1);
+                const uint32_t pos = atomicAdd(&tcnt[h], 1u);
+                if (pos >= (uint32_t)cn) continue;      // cannot happen (every row was counted): never write outside
+                float4 o4;
+                o4.x = q[u].x; o4.y = q[u].y; o4.z = q[u].z; o4.w = __uint_as_float((uint32_t)(lo + i));
+                pts[lo + pos] = o4;
+                keys_out[lo + pos] = hi | k;
+            }
+        }
+    }
 }
 
 // ---- cells of the sorted rows.  A row is a cell head when its key differs from the key in front of it; nobody
@@ -1830,6 +2004,7 @@ struct DbWs {
     int2*     rowtab;
     int64_t   rowtab_cells;
     uint32_t* chunk_bad;
+    uint32_t* chunk_ovf;     // one word per chunk: db_cellscatter_k handed the chunk to db_chunksort_k
     uint32_t* chunk_cells;
     uint32_t* comp;          // [n][3] compressed cell coordinates (fallback for grids beyond the 64-bit key)
     uint32_t* flag2;         // [n + 8] head flags kept beside their scan
@@ -1845,6 +2020,7 @@ static void db_plan(Arena& a, int64_t n, DbWs& w) {
     w.chunk_cells = a.take<uint32_t>(nn + 8);            // ONE fill clears them all (db_plan keeps them adjacent)
     w.core_stats = a.take<unsigned long long>(4);
     w.chunk_bad = a.take<uint32_t>(nn + 8);              // one word per chunk (chunk_size >= 1)
+    w.chunk_ovf = a.take<uint32_t>(nn + 8);              // (written for every chunk by db_cellscatter_k)
     w.k0 = a.take<uint64_t>(nn);
     w.k1 = a.take<uint64_t>(nn);
     w.v0 = a.take<uint32_t>(nn);
@@ -2093,11 +2269,14 @@ static int db_sorted_keys(const DbRun& r, const DbGrid& g, int cellbits, int nbi
     PCH_HIP_TRY(hipMemsetAsync(w.meta + 4, 0, (bytes + 15) & ~size_t(15), s));
     // One workgroup per chunk only pays with enough chunks to fill the GPU (measured break-even near
     // 100 chunks of 50 000 rows); PCH_DBSCAN_SORT=chunk / global forces a path (tests compare them)
-    if (!compressed && cellbits <= 32 && r.chunk_size <= CS_MAX_CHUNK && sort_mode != 2 &&
+    if (!compressed && cellbits <= 31 && r.chunk_size <= CS_MAX_CHUNK && sort_mode != 2 &&
         (sort_mode == 1 || nchunks >= CS_MIN_CHUNKS)) {
-        // chunk-local path: one workgroup per chunk builds keys, sorts and gathers
+        // chunk-local path: one workgroup per chunk builds keys, groups the rows by cell and writes them; a chunk with
+        // more cells than db_cellscatter_k's table takes goes through db_chunksort_k (gated by chunk_ovf: no host read)
+        PCH_LAUNCH("db_cellscatter", db_cellscatter_k, dim3((unsigned)nchunks), dim3(CS_THREADS), 0, s, r.xyz, n, g,
+                   w.chunk_bad, w.chunk_ovf, w.pts, w.k1, w.meta + 6);
         PCH_LAUNCH("db_chunksort", db_chunksort_k, dim3((unsigned)nchunks), dim3(CS_THREADS), 0, s, r.xyz, n, g,
-                   w.chunk_bad, w.xbuf, w.pts, w.k1, w.meta + 6, (unsigned long long*)w.cell_box);
+                   w.chunk_ovf, w.chunk_bad, w.xbuf, w.pts, w.k1, w.meta + 6, (unsigned long long*)w.cell_box);
 #ifdef PCH_CS_STAMPS
         {
             unsigned long long t[11];                    // start | sweep B | sweep H | one per pass | heads
