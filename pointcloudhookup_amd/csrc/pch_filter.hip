@@ -568,9 +568,9 @@ static int select_lerp(int64_t n, const float* sub, double q_percent, float add1
     return PCH_OK;
 }
 static int select_percentile(const float* base, int64_t n, int64_t stride, const float* sub,
-                             double q_percent, float add1, float add2, SelWs& w, hipStream_t s) {
+                             double q_percent, SelWs& w, hipStream_t s) {
     PCH_TRY(select_passes(base, n, stride, q_percent, w, s));
-    return select_lerp(n, sub, q_percent, add1, add2, w, s);
+    return select_lerp(n, sub, q_percent, 0.0f, 0.0f, w, s);
 }
 
 // per-thread side stream + events: the select passes only need the raw z values, so they run
@@ -646,6 +646,83 @@ __device__ __forceinline__ bool gf_cand_ok(const float* __restrict__ tcand, cons
     return t <= nextafter(ta, -INFINITY) && t <= nextafter(tb, -INFINITY);
 }
 
+// ---- what the two sweeps share (gf_compact_k over the z column, gf_cand_k over the candidate slots): the tile order,
+// the tile's output offset, what becomes of a survivor, and the fold of the tile's bounding box
+// The look-back waits for every tile in front of this one, so the tile order must be an
+// order in which workgroups START: HIP promises nothing about blockIdx dispatch order, and a
+// resident workgroup spinning on a tile that was never scheduled would hang the GPU.  The logical
+// tile is therefore a ticket drawn on arrival (as rocPRIM's look-back scan does): every tile with
+// a smaller ticket belongs to a workgroup that is already running.
+// false: this sweep does not run (the fallback sweep without use_b).  The caller's next barrier publishes *tile_sh.
+template <int WHICH>
+__device__ __forceinline__ bool gf_take_tile(GfState* __restrict__ st, uint32_t* tile_sh) {
+    if (WHICH == 1 && st->use_b == 0) return false;
+    if (threadIdx.x == 0) *tile_sh = atomicAdd(&st->ticket[WHICH], 1u);
+    return true;
+}
+// Wave 0 obtains the tile's exclusive prefix (T = the tile's count) and leaves it in *excl_sh for the caller's next
+// barrier; the last tile records the sweep's total.
+template <int WHICH>
+__device__ __forceinline__ void gf_tile_prefix(GfState* __restrict__ st, uint64_t* __restrict__ status, int64_t tile,
+                                               uint32_t T, long long min_keep, uint32_t* excl_sh) {
+    if (wave_id() != 0) return;
+    const uint32_t e0 = gf_lookback(status, tile, T);
+    const bool lb_failed = e0 == GF_LB_FAILED;
+    const uint32_t e = lb_failed ? 0u : e0;                  // prefix 0 keeps the survivors' writes inside the output
+    if (lane_id() == 0) {
+        *excl_sh = e;
+        if (lb_failed) {
+            atomicOr(&st->failed, 1u);
+        } else if (tile == (int64_t)gridDim.x - 1) {         // the last tile knows the total: it also decides
+            st->total[WHICH] = e + T;                        // whether the fallback threshold applies
+            if (WHICH == 0) st->use_b = ((long long)(e + T) < min_keep) ? 1u : 0u;
+        }
+    }
+}
+// first output row of wave w: the tile's prefix plus the survivors of the waves in front
+__device__ __forceinline__ uint32_t gf_wave_offset(uint32_t excl, const uint32_t (&wtot)[GF_THREADS / 64], int w) {
+    uint32_t woff = excl;
+    for (int w2 = 0; w2 < w; ++w2) woff += wtot[w2];
+    return woff;
+}
+// survivor (x, y, z) = input row `row` becomes output row o, centred; lo / hi collect the box (lo holds ~ordered(min))
+__device__ __forceinline__ void gf_emit(float x, float y, float z, const float (&c)[3], int64_t o, int64_t row,
+                                        float* __restrict__ out_points, int32_t* __restrict__ out_index,
+                                        uint32_t (&lo)[3], uint32_t (&hi)[3]) {
+    const float v[3] = {x - c[0], y - c[1], z - c[2]};       // points = raw_points - centroid (float32)
+    out_points[3 * o + 0] = v[0];
+    out_points[3 * o + 1] = v[1];
+    out_points[3 * o + 2] = v[2];
+    if (out_index) out_index[o] = (int32_t)row;
+    if (fabsf(v[0]) < INFINITY && fabsf(v[1]) < INFINITY && fabsf(v[2]) < INFINITY) {   // NaN/inf rows
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const uint32_t kk = f32_ordered(v[a]);
+            lo[a] = ~kk > lo[a] ? ~kk : lo[a];
+            hi[a] = kk > hi[a] ? kk : hi[a];
+        }
+    }
+}
+// the tile's box: over the wave, over the waves, into one of the sweep's slot sets
+template <int WHICH>
+__device__ __forceinline__ void gf_fold_box(GfState* __restrict__ st, int64_t tile, uint32_t (&lo)[3], uint32_t (&hi)[3],
+                                            uint32_t (&box)[GF_THREADS / 64][6]) {
+    const int w = wave_id();
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = wave_reduce_max(lo[a]);
+        hi[a] = wave_reduce_max(hi[a]);
+        if (lane_id() == 0) { box[w][a] = lo[a]; box[w][3 + a] = hi[a]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const int a = threadIdx.x;
+        uint32_t v = box[0][a];
+        for (int w2 = 1; w2 < GF_THREADS / 64; ++w2) v = box[w2][a] > v ? box[w2][a] : v;
+        if (v) atomicMax(&st->slots[WHICH][tile % GF_SLOTS][a], v);
+    }
+}
+
 template <int WHICH>
 __global__ __launch_bounds__(GF_THREADS) void gf_compact_k(
     const float* __restrict__ raw, const float* __restrict__ zcol, int64_t n,
@@ -659,17 +736,11 @@ __global__ __launch_bounds__(GF_THREADS) void gf_compact_k(
     __shared__ unsigned long long masks[GF_THREADS / 64][GF_ROUNDS];      // survivors of every 64-point round
     __shared__ uint32_t cum[GF_THREADS / 64][GF_ROUNDS + 1];
     __shared__ uint32_t tile_sh;
-    if (WHICH == 1 && st->use_b == 0) return;
-    // The look-back below waits for every tile in front of this one, so the tile order must be an
-    // order in which workgroups START: HIP promises nothing about blockIdx dispatch order, and a
-    // resident workgroup spinning on a tile that was never scheduled would hang the GPU.  The logical
-    // tile is therefore a ticket drawn on arrival (as rocPRIM's look-back scan does): every tile with
-    // a smaller ticket belongs to a workgroup that is already running.
-    if (threadIdx.x == 0) tile_sh = atomicAdd(&st->ticket[WHICH], 1u);
+    if (!gf_take_tile<WHICH>(st, &tile_sh)) return;
     __syncthreads();
     const int64_t tile = tile_sh;
-    const float cx = centroid[0], cy = centroid[1], cz = centroid[2];
-    const float thr = scal[1 + WHICH];
+    const float cen[3] = {centroid[0], centroid[1], centroid[2]};
+    const float cz = cen[2], thr = scal[1 + WHICH];
     const int w = wave_id(), l = lane_id();
     const int64_t seg = tile * GF_TILE + (int64_t)w * (64 * GF_ROUNDS);
     // ---- sweep over the z column: survivor masks and the tile's count
@@ -693,20 +764,7 @@ __global__ __launch_bounds__(GF_THREADS) void gf_compact_k(
     }
     __syncthreads();
     const uint32_t T = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    if (w == 0) {
-        const uint32_t e0 = gf_lookback(status, tile, T);
-        const bool lb_failed = e0 == GF_LB_FAILED;
-        const uint32_t e = lb_failed ? 0u : e0;              // prefix 0 keeps the writes below inside the output
-        if (l == 0) {
-            excl_sh = e;
-            if (lb_failed) {
-                atomicOr(&st->failed, 1u);
-            } else if (tile == (int64_t)gridDim.x - 1) {         // the last tile knows the total: it also decides
-                st->total[WHICH] = e + T;                     // whether the fallback threshold applies
-                if (WHICH == 0) st->use_b = ((long long)(e + T) < min_keep) ? 1u : 0u;
-            }
-        }
-    }
+    gf_tile_prefix<WHICH>(st, status, tile, T, min_keep, &excl_sh);
     __syncthreads();
     if (T == 0) return;                                       // workgroup-uniform
     // ---- survivors: the row (one 12-byte load) is only fetched for them.  The wave's survivors are taken
@@ -715,9 +773,8 @@ __global__ __launch_bounds__(GF_THREADS) void gf_compact_k(
     // consecutive lanes write consecutive output rows (a pass over the 64 rounds with the ~10 % surviving
     // lanes active would leave most lanes idle and scatter the writes)
     struct Row3 { float x, y, z; };
-    uint32_t woff = excl_sh;
-    for (int w2 = 0; w2 < w; ++w2) woff += wtot[w2];
-    uint32_t lo[3] = {0u, 0u, 0u}, hi[3] = {0u, 0u, 0u};      // lo holds ~ordered(min)
+    const uint32_t woff = gf_wave_offset(excl_sh, wtot, w);
+    uint32_t lo[3] = {0u, 0u, 0u}, hi[3] = {0u, 0u, 0u};
     const uint32_t nw = wtot[w];
 #pragma unroll 2
     for (uint32_t j = l; j < nw; j += 64) {
@@ -740,34 +797,9 @@ __global__ __launch_bounds__(GF_THREADS) void gf_compact_k(
         }
         const int64_t i = seg + r * 64 + bit;
         const Row3 q = reinterpret_cast<const Row3*>(raw)[i];
-        const float v[3] = {q.x - cx, q.y - cy, q.z - cz};
-        const int64_t o = (int64_t)woff + j;
-        out_points[3 * o + 0] = v[0];
-        out_points[3 * o + 1] = v[1];
-        out_points[3 * o + 2] = v[2];
-        if (out_index) out_index[o] = (int32_t)i;
-        if (fabsf(v[0]) < INFINITY && fabsf(v[1]) < INFINITY && fabsf(v[2]) < INFINITY) {   // NaN/inf rows
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const uint32_t kk = f32_ordered(v[a]);
-                lo[a] = ~kk > lo[a] ? ~kk : lo[a];
-                hi[a] = kk > hi[a] ? kk : hi[a];
-            }
-        }
+        gf_emit(q.x, q.y, q.z, cen, (int64_t)woff + j, i, out_points, out_index, lo, hi);
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = wave_reduce_max(lo[a]);
-        hi[a] = wave_reduce_max(hi[a]);
-        if (l == 0) { box[w][a] = lo[a]; box[w][3 + a] = hi[a]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int a = threadIdx.x;
-        uint32_t v = box[0][a];
-        for (int w2 = 1; w2 < GF_THREADS / 64; ++w2) v = box[w2][a] > v ? box[w2][a] : v;
-        if (v) atomicMax(&st->slots[WHICH][tile % GF_SLOTS][a], v);
-    }
+    gf_fold_box<WHICH>(st, tile, lo, hi, box);
 }
 
 // The same sweep from the candidate slots (MsCand, pch_mean.h: four planes per 1024-row block): a workgroup takes 64
@@ -797,19 +829,14 @@ __global__ __launch_bounds__(GF_THREADS, 6) void gf_cand_k(     // six waves per
     __shared__ uint32_t tile_sh;
     static_assert(NE == 128, "two (slot, round) pairs per lane in the prefix below");
     if (!gf_cand_ok(tcand, centroid, scal)) return;        // gf_compact_k runs instead
-    if (WHICH == 1 && st->use_b == 0) return;
-#ifdef PCH_GF_STAMPS
-    const unsigned long long ts0 = wall_clock64();
-    unsigned long long ts1 = 0, ts2 = 0, ts3 = 0;
-#endif
-    if (threadIdx.x == 0) tile_sh = atomicAdd(&st->ticket[WHICH], 1u);     // tile order = order of arrival (look-back)
+    if (!gf_take_tile<WHICH>(st, &tile_sh)) return;
     const int w = wave_id(), l = lane_id();
     masks[w][2 * l] = 0ull;
     masks[w][2 * l + 1] = 0ull;
     __syncthreads();
     const int64_t tile = tile_sh;
-    const float cx = centroid[0], cy = centroid[1], cz = centroid[2];
-    const float thr = scal[1 + WHICH];
+    const float cen[3] = {centroid[0], centroid[1], centroid[2]};
+    const float cz = cen[2], thr = scal[1 + WHICH];
     const int64_t b0 = tile * GF_CT_BLKS + (int64_t)w * GF_CW_BLKS;
     // Candidates come in runs: blocks next to a tower hold hundreds, most blocks fewer than 64 or none.  A slot after
     // the other is a chain of dependent memory round trips (the kernel waited 86 % of its wave cycles that way), so
@@ -844,15 +871,12 @@ __global__ __launch_bounds__(GF_THREADS, 6) void gf_cand_k(     // six waves per
     }
     if (l == 0) wtot[w] = run;
     __syncthreads();
-#ifdef PCH_GF_STAMPS
-    ts1 = wall_clock64();
-#endif
     const uint32_t T = wtot[0] + wtot[1] + wtot[2] + wtot[3];
     // eight slots at a time: with all sixteen rows in registers the kernel needs 130 VGPRs, and at three waves per
     // SIMD only half of the tiles are resident - two rounds of workgroups that each wait on the look-back
     constexpr int HB = GF_CW_BLKS / 2;
     const uint64_t lt = lanemask_lt();
-    uint32_t lo[3] = {0u, 0u, 0u}, hi[3] = {0u, 0u, 0u};  // lo holds ~ordered(min)
+    uint32_t lo[3] = {0u, 0u, 0u}, hi[3] = {0u, 0u, 0u};
     auto load_half = [&](int r, int half, float4 (&q)[HB], unsigned long long (&ms)[HB]) {
         const uint32_t i = r * 64 + l;
 #pragma unroll
@@ -873,20 +897,8 @@ __global__ __launch_bounds__(GF_THREADS, 6) void gf_cand_k(     // six waves per
             const unsigned long long m = ms[k];
             if ((m >> l) & 1ull) {
                 const float4 c4 = q[k];
-                const float v[3] = {c4.x - cx, c4.y - cy, c4.z - cz};
-                const int64_t o = (int64_t)woff + cum[w][kb * NR + r] + (uint32_t)__popcll(m & lt);
-                out_points[3 * o + 0] = v[0];
-                out_points[3 * o + 1] = v[1];
-                out_points[3 * o + 2] = v[2];
-                if (out_index) out_index[o] = (int32_t)((b0 + kb) * GF_CBLK + (int64_t)__float_as_uint(c4.w));
-                if (fabsf(v[0]) < INFINITY && fabsf(v[1]) < INFINITY && fabsf(v[2]) < INFINITY) {   // NaN/inf rows
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) {
-                        const uint32_t kk = f32_ordered(v[a]);
-                        lo[a] = ~kk > lo[a] ? ~kk : lo[a];
-                        hi[a] = kk > hi[a] ? kk : hi[a];
-                    }
-                }
+                gf_emit(c4.x, c4.y, c4.z, cen, (int64_t)woff + cum[w][kb * NR + r] + (uint32_t)__popcll(m & lt),
+                        (b0 + kb) * GF_CBLK + (int64_t)__float_as_uint(c4.w), out_points, out_index, lo, hi);
             }
         }
     };
@@ -895,23 +907,7 @@ __global__ __launch_bounds__(GF_THREADS, 6) void gf_cand_k(     // six waves per
     float4 q0[HB];
     unsigned long long ms0[HB];
     if (T != 0 && maxnc != 0) load_half(0, 0, q0, ms0);
-    if (w == 0) {
-        const uint32_t e0 = gf_lookback(status, tile, T);
-        const bool lb_failed = e0 == GF_LB_FAILED;
-        const uint32_t e = lb_failed ? 0u : e0;              // prefix 0 keeps the writes below inside the output
-        if (l == 0) {
-            excl_sh = e;
-            if (lb_failed) {
-                atomicOr(&st->failed, 1u);
-            } else if (tile == (int64_t)gridDim.x - 1) {     // the last tile knows the total: it also decides
-                st->total[WHICH] = e + T;                    // whether the fallback threshold applies
-                if (WHICH == 0) st->use_b = ((long long)(e + T) < min_keep) ? 1u : 0u;
-            }
-        }
-#ifdef PCH_GF_STAMPS
-        ts2 = wall_clock64();
-#endif
-    }
+    gf_tile_prefix<WHICH>(st, status, tile, T, min_keep, &excl_sh);
     {   // survivors of the wave in front of every (slot, round) pair, in file order = slot-major
         const uint32_t c0 = (uint32_t)__popcll(masks[w][2 * l]), c1 = (uint32_t)__popcll(masks[w][2 * l + 1]);
         const uint32_t incl = wave_scan_incl(c0 + c1);
@@ -920,8 +916,7 @@ __global__ __launch_bounds__(GF_THREADS, 6) void gf_cand_k(     // six waves per
     }
     __syncthreads();
     if (T == 0) return;                                    // workgroup-uniform
-    uint32_t woff = excl_sh;
-    for (int w2 = 0; w2 < w; ++w2) woff += wtot[w2];
+    const uint32_t woff = gf_wave_offset(excl_sh, wtot, w);
     if (maxnc != 0) {
         emit_half(0, 0, q0, ms0, woff);
         {
@@ -942,26 +937,7 @@ __global__ __launch_bounds__(GF_THREADS, 6) void gf_cand_k(     // six waves per
             }
         }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = wave_reduce_max(lo[a]);
-        hi[a] = wave_reduce_max(hi[a]);
-        if (l == 0) { box[w][a] = lo[a]; box[w][3 + a] = hi[a]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int a = threadIdx.x;
-        uint32_t v = box[0][a];
-        for (int w2 = 1; w2 < GF_THREADS / 64; ++w2) v = box[w2][a] > v ? box[w2][a] : v;
-        if (v) atomicMax(&st->slots[WHICH][tile % GF_SLOTS][a], v);
-    }
-#ifdef PCH_GF_STAMPS
-    ts3 = wall_clock64();
-    if (WHICH == 0 && threadIdx.x == 0 && (tile % 190 == 0 || tile == gridDim.x - 1))
-        printf("gf_cand tile %4lld (block %4u): start %8.2f us, count %6.2f, look-back %6.2f, rows %6.2f, end %8.2f us\n",
-               (long long)tile, blockIdx.x, (double)(ts0 % 100000000ull) / 100.0, (double)(ts1 - ts0) / 100.0,
-               (double)(ts2 - ts1) / 100.0, (double)(ts3 - ts2) / 100.0, (double)(ts3 % 100000000ull) / 100.0);
-#endif
+    gf_fold_box<WHICH>(st, tile, lo, hi, box);
 }
 
 // publishes the scalars, the count and the bounding box of the sweep that counts
@@ -1022,48 +998,6 @@ static void gf_plan(Arena& a, int64_t n, GfWs& w) {
 
 using namespace pch;
 
-extern "C" size_t pch_mean_seq_f32_ws_bytes(int64_t n) {
-    if (n < 0) return 0;
-    Arena a;
-    MsWs w;
-    ms_plan(a, n, w);
-    return a.off;
-}
-
-extern "C" int pch_mean_seq_f32(const float* xyz, int64_t n, float* out_centroid, void* ws,
-                                size_t ws_bytes, void* stream) {
-    PCH_DEVICE_GUARD(xyz ? (const void*)xyz : (const void*)out_centroid);
-    PCH_REQUIRE(n >= 0 && out_centroid && ws, "bad argument");
-    PCH_REQUIRE(n == 0 || xyz, "null input");
-    Arena a(ws, ws_bytes);
-    MsWs w;
-    ms_plan(a, n, w);
-    if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
-    return mean_seq_launch(xyz, n, out_centroid, w, nullptr, (hipStream_t)stream);
-}
-
-extern "C" int pch_mean_seq_partial_f32(const float* xyz, int64_t n, const float* sum_in3, int64_t total_n,
-                                        float* out3, float* zcol_out, int32_t phase, void* ws, size_t ws_bytes,
-                                        void* stream) {
-    PCH_DEVICE_GUARD(ws);
-    PCH_REQUIRE(n >= 0 && total_n >= 0 && ws && phase >= 0 && phase <= 2, "bad argument");
-    PCH_REQUIRE(phase == MS_PHASE_TABLES || out3, "null output");
-    PCH_REQUIRE(n == 0 || xyz, "null input");
-    Arena a(ws, ws_bytes, phase == MS_PHASE_WALK);       // the walk continues the tables of the call before
-    MsWs w;
-    ms_plan(a, n, w);
-    if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
-    return mean_seq_launch(xyz, n, out3, w, zcol_out, (hipStream_t)stream, nullptr, sum_in3,
-                           total_n > 0 ? total_n : MS_NO_DIVIDE, phase);
-}
-
-extern "C" int pch_mean_seq_serial_f32(const float* xyz, int64_t n, float* out_centroid, void* stream) {
-    PCH_DEVICE_GUARD(xyz ? (const void*)xyz : (const void*)out_centroid);
-    PCH_REQUIRE(n >= 0 && out_centroid, "bad argument");
-    PCH_REQUIRE(n == 0 || xyz, "null input");
-    return mean_seq_serial_launch(xyz, n, out_centroid, (hipStream_t)stream);
-}
-
 extern "C" size_t pch_percentile_f32_ws_bytes(int64_t n) {
     Arena a;
     SelWs w;
@@ -1083,7 +1017,7 @@ extern "C" int pch_percentile_f32(const float* base, int64_t n, int64_t stride, 
     SelWs w;
     sel_plan(a, w, n);
     if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
-    PCH_TRY(select_percentile(base, n, stride, sub, q_percent, 0.0f, 0.0f, w, s));
+    PCH_TRY(select_percentile(base, n, stride, sub, q_percent, w, s));
     PCH_HIP_TRY(hipMemcpyAsync(out, w.scal, sizeof(float), hipMemcpyDeviceToDevice, s));
     return PCH_OK;
 }
@@ -1157,27 +1091,16 @@ extern "C" int pch_select_min_above_f32(const float* base, int64_t n, int64_t st
 }
 
 // ---- keep = (z - cz) > threshold with GIVEN centroid and threshold (the shared values of a tiled run);
-// same sweep as the fused filter
+// same sweep and same finish as the fused filter
+constexpr int FGT_FLOATS = 16;    // first block of the workspace: centroid[4], scal[4], gf_finalize_k's scalars[8]
 extern "C" size_t pch_filter_gt_ws_bytes(int64_t n) {
     if (n < 0) return 0;
     Arena a;
-    a.take<float>(8);
+    a.take<float>(FGT_FLOATS);
     a.take<GfState>(1);
     a.take<uint64_t>(2 * ceil_div(n > 0 ? n : 1, GF_TILE));
     return a.off;
 }
-
-namespace pch {
-__global__ void gf_count_out_k(const GfState* __restrict__ st, int64_t* __restrict__ out_count, float* __restrict__ out_aabb) {
-    if (threadIdx.x == 0) *out_count = st->failed ? (int64_t)-1 : (int64_t)st->total[0];
-    if (threadIdx.x < 6 && out_aabb) {
-        const int a = threadIdx.x;
-        uint32_t v = 0;
-        for (int k = 0; k < GF_SLOTS; ++k) { const uint32_t u = st->slots[0][k][a]; v = u > v ? u : v; }
-        out_aabb[a] = v == 0u ? 0.0f : f32_unordered(a < 3 ? ~v : v);
-    }
-}
-}  // namespace pch
 
 extern "C" int pch_filter_gt_f32(const float* raw, int64_t n, const float* centroid3_host, float threshold,
                                  float* out_points, int32_t* out_index, int64_t* out_count, float* out_aabb,
@@ -1191,21 +1114,25 @@ extern "C" int pch_filter_gt_f32(const float* raw, int64_t n, const float* centr
     }
     PCH_REQUIRE(raw && out_points, "null buffer");
     Arena a(ws, ws_bytes);
-    float* scal = a.take<float>(8);                  // [0..2] centroid, [5] threshold (gf_compact_k<0> reads scal[4 + 1])
+    float* f = a.take<float>(FGT_FLOATS);
     const size_t st_off = a.off;
     GfState* st = a.take<GfState>(1);
     const int64_t nb = ceil_div(n, GF_TILE);
     uint64_t* status = a.take<uint64_t>(2 * nb);
     if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
-    float hs[8] = {centroid3_host[0], centroid3_host[1], centroid3_host[2], 0.0f, 0.0f, threshold, threshold, 0.0f};
-    PCH_HIP_TRY(hipMemcpyAsync(scal, hs, sizeof(hs), hipMemcpyHostToDevice, s));
+    // the words the fused filter computes on the device: centroid[3], -, then scal = base, threshold A, threshold B, -.
+    // With min_keep 0 sweep A never raises use_b, so gf_finalize_k reports sweep A; its scalars land in the workspace
+    const float hs[8] = {centroid3_host[0], centroid3_host[1], centroid3_host[2], 0.0f, 0.0f, threshold, threshold, 0.0f};
+    PCH_HIP_TRY(hipMemcpyAsync(f, hs, sizeof(hs), hipMemcpyHostToDevice, s));
     PCH_HIP_TRY(hipMemsetAsync(st, 0, a.off - st_off, s));
+    const float* centroid = f;
+    const float* scal = f + 4;
     // the sweep reads z straight from the rows (a pass that first copied the z column out - 16 B per point of traffic
     // for a 12 B per point sweep - is gone)
     PCH_LAUNCH("gf_compact", gf_compact_k<0>, dim3((unsigned)nb), dim3(GF_THREADS), 0, s, raw, (const float*)nullptr, n,
-               (const float*)scal, (const float*)(scal + 4), st, status, (long long)0, out_points, out_index,
-               (const float*)nullptr);
-    PCH_LAUNCH("gf_count_out", gf_count_out_k, dim3(1), dim3(64), 0, s, (const GfState*)st, out_count, out_aabb);
+               centroid, scal, st, status, (long long)0, out_points, out_index, (const float*)nullptr);
+    PCH_LAUNCH("gf_finalize", gf_finalize_k, dim3(1), dim3(64), 0, s, (const GfState*)st, centroid, scal,
+               f + 8, out_count, out_aabb);
     PCH_HIP_TRY(hipStreamSynchronize(s));               // `hs` lives on this stack frame
     return PCH_OK;
 }
@@ -1248,28 +1175,25 @@ int pch::ground_filter_run(const float* raw, int64_t n, double pct, float offset
     w.sel.also_zero = reinterpret_cast<uint32_t*>(w.st);
     w.sel.also_words = (int64_t)(w.clear_bytes / 4);
     SideStream& ss = side_stream();
+    // Two strands.  `s`: summary, level 2, walk - no cross-stream hop inside the chain.  Side stream: at once the
+    // sample half of the percentile (it reads the z of the raw rows, so it does not wait for the z column and
+    // runs beside the summary), then - behind the summary - the percentile's sweep and exact select; joined in
+    // front of the interpolation.  With the sample half out of the way both strands end within a few us of each
+    // other (measured: the other assignment, select on `s` and walk on the side stream, loses 45 us to the hops).
+    // Without a side stream the select follows the walk on `s` and takes its own sample.
+    const bool sample_early = ss.ok && select_is_bracketed(w.sel, n, 1);
+    if (sample_early) {
+        PCH_HIP_TRY(hipEventRecord(ss.ev_start, s));            // everything the caller queued before this call
+        PCH_HIP_TRY(hipStreamWaitEvent(ss.s, ss.ev_start, 0));   // (the rows; the previous user of the workspace)
+        PCH_TRY(select_sample_passes(raw + 2, 3, n, pct, w.sel, ss.s));
+    }
+    PCH_TRY(mean_seq_launch(raw, n, w.centroid, w.ms, w.zcol, s, ss.ok ? ss.ev_fork : nullptr, nullptr, MS_DIVIDE_BY_N,
+                            MS_PHASE_BOTH, &w.cand, &cand_made));
+    if (ss.ok) PCH_HIP_TRY(hipStreamWaitEvent(ss.s, ss.ev_fork, 0));
+    PCH_TRY(select_passes(w.zcol, n, 1, pct, w.sel, ss.ok ? ss.s : s, sample_early));
     if (ss.ok) {
-        // Two strands.  `s`: summary, level 2, walk - no cross-stream hop inside the chain.  Side stream: at once the
-        // sample half of the percentile (it reads the z of the raw rows, so it does not wait for the z column and
-        // runs beside the summary), then - behind the summary - the percentile's sweep and exact select; joined in
-        // front of the interpolation.  With the sample half out of the way both strands end within a few us of each
-        // other (measured: the other assignment, select on `s` and walk on the side stream, loses 45 us to the hops).
-        const bool sample_early = select_is_bracketed(w.sel, n, 1);
-        if (sample_early) {
-            PCH_HIP_TRY(hipEventRecord(ss.ev_start, s));            // everything the caller queued before this call
-            PCH_HIP_TRY(hipStreamWaitEvent(ss.s, ss.ev_start, 0));   // (the rows; the previous user of the workspace)
-            PCH_TRY(select_sample_passes(raw + 2, 3, n, pct, w.sel, ss.s));
-        }
-        PCH_TRY(mean_seq_launch(raw, n, w.centroid, w.ms, w.zcol, s, ss.ev_fork, nullptr, MS_DIVIDE_BY_N, MS_PHASE_BOTH,
-                                &w.cand, &cand_made));
-        PCH_HIP_TRY(hipStreamWaitEvent(ss.s, ss.ev_fork, 0));
-        PCH_TRY(select_passes(w.zcol, n, 1, pct, w.sel, ss.s, sample_early));
         PCH_HIP_TRY(hipEventRecord(ss.ev_join, ss.s));
         PCH_HIP_TRY(hipStreamWaitEvent(s, ss.ev_join, 0));
-    } else {
-        PCH_TRY(mean_seq_launch(raw, n, w.centroid, w.ms, w.zcol, s, nullptr, nullptr, MS_DIVIDE_BY_N, MS_PHASE_BOTH,
-                                &w.cand, &cand_made));
-        PCH_TRY(select_passes(w.zcol, n, 1, pct, w.sel, s));
     }
     PCH_TRY(select_lerp(n, w.centroid + 2, pct, offset, fallback_offset, w.sel, s));
     const dim3 grid((unsigned)nb), blk(GF_THREADS);

@@ -191,21 +191,24 @@ __device__ void ms_zestimate(const float* __restrict__ zs, int64_t ns, double pc
     // every 16th sample is plenty for an estimate (6 k values at 100 M points, and the margin is 0.5 m); 8 loads in flight
     constexpr int EST_STRIDE = 16, EST_BATCH = 8;
     const int64_t ne = (ns + EST_STRIDE - 1) / EST_STRIDE;
+    auto for_samples = [&](auto&& f) {                        // f(z) for this thread's samples, NaN past the end
+        for (int64_t i0 = 0; i0 < ne; i0 += 1024 * EST_BATCH) {   // workgroup-uniform trip count (ballots inside f)
+            float zb[EST_BATCH];
+#pragma unroll
+            for (int u = 0; u < EST_BATCH; ++u) {
+                const int64_t i = i0 + u * 1024 + threadIdx.x;
+                zb[u] = i < ne ? zs[i * EST_STRIDE] : NAN;
+            }
+#pragma unroll
+            for (int u = 0; u < EST_BATCH; ++u) f(zb[u]);
+        }
+    };
     uint32_t mine = 0;
-    for (int64_t i0 = 0; i0 < ne; i0 += 1024 * EST_BATCH) {   // workgroup-uniform trip count (ballots inside)
-        float zb[EST_BATCH];
-#pragma unroll
-        for (int u = 0; u < EST_BATCH; ++u) {
-            const int64_t i = i0 + u * 1024 + threadIdx.x;
-            zb[u] = i < ne ? zs[i * EST_STRIDE] : NAN;
-        }
-#pragma unroll
-        for (int u = 0; u < EST_BATCH; ++u) {
-            const bool in = zb[u] == zb[u];
-            add_bin(in, f32_ordered(zb[u]) >> 21);
-            mine += in ? 1u : 0u;
-        }
-    }
+    for_samples([&](float z) {
+        const bool in = z == z;
+        add_bin(in, f32_ordered(z) >> 21);
+        mine += in ? 1u : 0u;
+    });
     mine = wave_reduce_add(mine);
     if (l == 0) atomicAdd(&total_sh, mine);
     __syncthreads();
@@ -220,19 +223,10 @@ __device__ void ms_zestimate(const float* __restrict__ zs, int64_t ns, double pc
     for (int j = threadIdx.x; j < 2048; j += 1024) hist[j] = 0;
     if (threadIdx.x == 0) { pick_bin = 2047; pick_below = 0; }
     __syncthreads();
-    for (int64_t i0 = 0; i0 < ne; i0 += 1024 * EST_BATCH) {
-        float zb[EST_BATCH];
-#pragma unroll
-        for (int u = 0; u < EST_BATCH; ++u) {
-            const int64_t i = i0 + u * 1024 + threadIdx.x;
-            zb[u] = i < ne ? zs[i * EST_STRIDE] : NAN;
-        }
-#pragma unroll
-        for (int u = 0; u < EST_BATCH; ++u) {
-            const uint32_t k = f32_ordered(zb[u]);
-            add_bin(zb[u] == zb[u] && (k >> 21) == top, (k >> 10) & 2047u);
-        }
-    }
+    for_samples([&](float z) {
+        const uint32_t k = f32_ordered(z);
+        add_bin(z == z && (k >> 21) == top, (k >> 10) & 2047u);
+    });
     scan_pick(rank);
     if (threadIdx.x == 0) {
         const uint32_t key = (top << 21) | (pick_bin << 10);       // lower edge of the bin
@@ -1163,9 +1157,8 @@ void ms_plan(Arena& a, int64_t n, MsWs& w) {
 
 int mean_seq_launch(const float* xyz, int64_t n, float* out, MsWs& w, float* zcol, hipStream_t s,
                     hipEvent_t ev_zcol, const float* sum_in, int64_t divide_n, int phase, const MsCand* cand,
-                    bool* cand_made, hipStream_t walk_stream) {
+                    bool* cand_made) {
     if (cand_made) *cand_made = false;
-    hipStream_t ws = s;                                  // stream of level 2 and the walk
     const int64_t nb = n > 0 ? ceil_div(n, MSB) : 0;
     const int64_t nb2 = ceil_div(nb, 64);
     if (n > 0 && phase != MS_PHASE_WALK) {
@@ -1189,11 +1182,7 @@ int mean_seq_launch(const float* xyz, int64_t n, float* out, MsWs& w, float* zco
                    0, s, xyz, n, nb, w.rec, zcol, pred, nb2, emit ? cand->slots : (float*)nullptr,
                    emit ? cand->counts : (uint32_t*)nullptr, emit ? (const float*)cand->tcand : (const float*)nullptr);
         if (ev_zcol) PCH_HIP_TRY(hipEventRecord(ev_zcol, s));
-        if (walk_stream && ev_zcol) {
-            PCH_HIP_TRY(hipStreamWaitEvent(walk_stream, ev_zcol, 0));
-            ws = walk_stream;
-        }
-        PCH_LAUNCH("mean_level2", ms_level2_k, dim3((unsigned)(3 * nb2)), dim3(256), 0, ws,
+        PCH_LAUNCH("mean_level2", ms_level2_k, dim3((unsigned)(3 * nb2)), dim3(256), 0, s,
                    (const MsRec*)w.rec, nb, nb2, w.hdr2, w.rows2);
     }
     if (phase == MS_PHASE_TABLES) return PCH_OK;
@@ -1201,14 +1190,54 @@ int mean_seq_launch(const float* xyz, int64_t n, float* out, MsWs& w, float* zco
     T.rec = w.rec; T.nb = nb;
     T.hdr2 = w.hdr2; T.rows2 = w.rows2; T.nb2 = nb2;
     const int divide = divide_n != MS_NO_DIVIDE;
-    PCH_LAUNCH("mean_walk", ms_walk_k, dim3(3), dim3(64 * MS_XW), 0, ws, xyz, n, T, sum_in,
+    PCH_LAUNCH("mean_walk", ms_walk_k, dim3(3), dim3(64 * MS_XW), 0, s, xyz, n, T, sum_in,
                divide_n == MS_DIVIDE_BY_N ? n : divide_n, divide, out, w.stats);
     return PCH_OK;
 }
 
-int mean_seq_serial_launch(const float* xyz, int64_t n, float* out, hipStream_t s) {
-    PCH_LAUNCH("mean_seq_serial", mean_seq_k, dim3(1), dim3(256), 0, s, xyz, n, out);
-    return PCH_OK;
+}  // namespace pch
+
+using namespace pch;
+
+extern "C" size_t pch_mean_seq_f32_ws_bytes(int64_t n) {
+    if (n < 0) return 0;
+    Arena a;
+    MsWs w;
+    ms_plan(a, n, w);
+    return a.off;
 }
 
-}  // namespace pch
+extern "C" int pch_mean_seq_f32(const float* xyz, int64_t n, float* out_centroid, void* ws,
+                                size_t ws_bytes, void* stream) {
+    PCH_DEVICE_GUARD(xyz ? (const void*)xyz : (const void*)out_centroid);
+    PCH_REQUIRE(n >= 0 && out_centroid && ws, "bad argument");
+    PCH_REQUIRE(n == 0 || xyz, "null input");
+    Arena a(ws, ws_bytes);
+    MsWs w;
+    ms_plan(a, n, w);
+    if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
+    return mean_seq_launch(xyz, n, out_centroid, w, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int pch_mean_seq_partial_f32(const float* xyz, int64_t n, const float* sum_in3, int64_t total_n,
+                                        float* out3, float* zcol_out, int32_t phase, void* ws, size_t ws_bytes,
+                                        void* stream) {
+    PCH_DEVICE_GUARD(ws);
+    PCH_REQUIRE(n >= 0 && total_n >= 0 && ws && phase >= 0 && phase <= 2, "bad argument");
+    PCH_REQUIRE(phase == MS_PHASE_TABLES || out3, "null output");
+    PCH_REQUIRE(n == 0 || xyz, "null input");
+    Arena a(ws, ws_bytes, phase == MS_PHASE_WALK);       // the walk continues the tables of the call before
+    MsWs w;
+    ms_plan(a, n, w);
+    if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
+    return mean_seq_launch(xyz, n, out3, w, zcol_out, (hipStream_t)stream, nullptr, sum_in3,
+                           total_n > 0 ? total_n : MS_NO_DIVIDE, phase);
+}
+
+extern "C" int pch_mean_seq_serial_f32(const float* xyz, int64_t n, float* out_centroid, void* stream) {
+    PCH_DEVICE_GUARD(xyz ? (const void*)xyz : (const void*)out_centroid);
+    PCH_REQUIRE(n >= 0 && out_centroid, "bad argument");
+    PCH_REQUIRE(n == 0 || xyz, "null input");
+    PCH_LAUNCH("mean_seq_serial", mean_seq_k, dim3(1), dim3(256), 0, (hipStream_t)stream, xyz, n, out_centroid);
+    return PCH_OK;
+}

@@ -58,6 +58,11 @@ def release_workspace():
     _tls.ws = {}
 
 
+def _double3(v):
+    import ctypes as C
+    return (C.c_double * 3)(*[float(x) for x in v])
+
+
 def set_profiling(enable, only=None):
     """Enables per-kernel hipEvent timing inside the library; ``only`` (iterable of kernel names)
     restricts the recording so that the host cost of the event records stays negligible."""
@@ -114,8 +119,7 @@ def las_scale(XYZ_i32, scales, offsets):
     L = _lib.lib()
     X = _need_cuda(XYZ_i32, torch.int32, "XYZ").reshape(-1, 3)
     out = torch.empty(X.shape, dtype=torch.float64, device=X.device)
-    sc = (C.c_double * 3)(*[float(v) for v in scales])
-    of = (C.c_double * 3)(*[float(v) for v in offsets])
+    sc, of = _double3(scales), _double3(offsets)
     with torch.cuda.device(X.device):
         _lib.check(L.pch_las_scale_i32_f64(_ptr(X), X.shape[0], C.cast(sc, C.c_void_p),
                                            C.cast(of, C.c_void_p), _ptr(out), _stream()))
@@ -128,8 +132,7 @@ def las_unscale(xyz_f64, scales, offsets):
     L = _lib.lib()
     x = _need_cuda(xyz_f64, torch.float64, "xyz").reshape(-1, 3)
     out = torch.empty(x.shape, dtype=torch.int32, device=x.device)
-    sc = (C.c_double * 3)(*[float(v) for v in scales])
-    of = (C.c_double * 3)(*[float(v) for v in offsets])
+    sc, of = _double3(scales), _double3(offsets)
     with torch.cuda.device(x.device):
         _lib.check(L.pch_las_unscale_f64_i32(_ptr(x), x.shape[0], C.cast(sc, C.c_void_p),
                                              C.cast(of, C.c_void_p), _ptr(out), _stream()))
@@ -202,10 +205,7 @@ class MeanShard:
 def percentile_f32(values, q_percent, sub=None):
     """np.percentile(values - sub, q) for a float32 vector (any stride).  Returns float32 [1]."""
     L = _lib.lib()
-    if not values.is_cuda or values.dtype != torch.float32 or values.dim() != 1:
-        raise TypeError("values must be a 1-D float32 CUDA tensor")
-    n = values.shape[0]
-    stride = values.stride(0) if n > 1 else 1
+    n, stride = _strided_1d(values)
     out = torch.empty((1,), dtype=torch.float32, device=values.device)
     with torch.cuda.device(values.device):
         nb = L.pch_percentile_f32_ws_bytes(n)
@@ -273,6 +273,15 @@ def filter_gt(raw, centroid, threshold, want_index=True):
                 aabb=aabb.cpu().numpy())
 
 
+def _ground_result(points, index, nf, centroid, base, threshold, used_fallback, count_at_offset, aabb):
+    """The stage-B result of ground_filter and tower_clusters: device rows, host scalars as numpy float32."""
+    import numpy as np
+    return dict(points=points[:nf], index=None if index is None else index[:nf],
+                centroid=np.array(centroid, dtype=np.float32), base=np.float32(base), threshold=np.float32(threshold),
+                used_fallback=bool(used_fallback), count_at_offset=int(count_at_offset),
+                aabb=np.array(aabb, dtype=np.float32), count=nf)
+
+
 def ground_filter(raw, pct=25.0, offset=3.0, fallback_offset=1.0, min_keep=1000, want_index=True):
     """Fused stage B on float32 [n,3].  Returns dict(points [n_f,3] f32 (centred, file
     order), index int32 [n_f] | None, centroid f32[3] (host np), base, threshold,
@@ -293,10 +302,8 @@ def ground_filter(raw, pct=25.0, offset=3.0, fallback_offset=1.0, min_keep=1000,
                                            _stream()))
         host = scal.cpu().numpy()           # one D2H copy, synchronises the stream
         nf = _lib.check_count(host[16:18].view("<i8")[0], "ground_filter")
-    return dict(points=out_points[:nf], index=None if out_index is None else out_index[:nf],
-                centroid=host[0:3].copy(), base=host[3], threshold=host[4],
-                used_fallback=bool(host[5] != 0.0), count_at_offset=int(host[6:7].view("<u4")[0]),
-                aabb=host[8:14].copy(), count=nf)
+    return _ground_result(out_points, out_index, nf, host[0:3], host[3], host[4], host[5] != 0.0,
+                          host[6:7].view("<u4")[0], host[8:14])
 
 
 # ---------------------------------------------------------------------------- stage C
@@ -428,7 +435,6 @@ def tower_clusters(raw, eps=8.0, min_samples=80, chunk_size=50000, pct=25.0, off
     Returns (ground dict as ops.ground_filter, labels int32 [n_f], nclusters,
     perm | None, offsets | None, stats | None)."""
     import ctypes as C
-    import numpy as np
     L = _lib.lib()
     raw = _need_cuda(raw, torch.float32, "raw").reshape(-1, 3)
     n = raw.shape[0]
@@ -463,10 +469,8 @@ def tower_clusters(raw, eps=8.0, min_samples=80, chunk_size=50000, pct=25.0, off
             rc = 0
         _lib.check(rc)
     _nf_hint[key] = nf / max(n, 1)
-    ground = dict(points=out_points[:nf], index=None if out_index is None else out_index[:nf],
-                  centroid=np.array(info.centroid, dtype=np.float32), base=np.float32(info.base),
-                  threshold=np.float32(info.threshold), used_fallback=bool(info.used_fallback),
-                  count_at_offset=int(info.count_at_offset), aabb=np.array(info.aabb, dtype=np.float32), count=nf)
+    ground = _ground_result(out_points, out_index, nf, info.centroid, info.base, info.threshold, info.used_fallback,
+                            info.count_at_offset, info.aabb)
     if not segment:
         return ground, labels[:nf], k, None, None, None
     return ground, labels[:nf], k, perm[:nf], offsets[:k + 1], stats[:k]
@@ -614,8 +618,7 @@ def crop_aabb(xyz, lo, hi, want_index=False):
     xyz = _need_cuda(xyz, torch.float64, "xyz").reshape(-1, 3)
     n = xyz.shape[0]
     dev = xyz.device
-    mn = (C.c_double * 3)(*[float(v) for v in lo])
-    mx = (C.c_double * 3)(*[float(v) for v in hi])
+    mn, mx = _double3(lo), _double3(hi)
     with torch.cuda.device(dev):
         out = torch.empty((n, 3), dtype=torch.float64, device=dev)
         idx = torch.empty((n,), dtype=torch.int64, device=dev) if want_index else None

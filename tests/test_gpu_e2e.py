@@ -562,6 +562,24 @@ def test_filter_gt_equals_the_fused_filter(cuda):
     np.testing.assert_array_equal(got["aabb"], gf["aabb"])
     thr = tiles_shared_threshold(raw, gf)
     assert thr.view(np.uint32) == np.float32(gf["threshold"]).view(np.uint32)
+    # two inputs the tiled runs never give it: no row index wanted, and a threshold above every z (nothing kept,
+    # all-zero box); each against the reference expression in float32, bit for bit
+    centred = raw.cpu().numpy() - gf["centroid"]
+    assert centred.dtype == np.float32
+    for t, want_index in ((np.float32(gf["threshold"]), False), (np.float32(centred[:, 2].max() + 1.0), True)):
+        keep = centred[:, 2] > t
+        want = centred[keep]
+        got = ops.filter_gt(raw, gf["centroid"], t, want_index=want_index)
+        assert got["count"] == len(want)
+        assert got["points"].shape == want.shape
+        assert np.array_equal(got["points"].cpu().numpy().view(np.uint32), want.view(np.uint32))
+        if want_index:
+            assert np.array_equal(got["index"].cpu().numpy(), np.flatnonzero(keep))
+        else:
+            assert got["index"] is None
+        box = np.concatenate([want.min(axis=0), want.max(axis=0)]) if len(want) else np.zeros(6, np.float32)
+        np.testing.assert_array_equal(got["aabb"], box)
+    assert got["count"] == 0 and not got["aabb"].any()
 
 
 def tiles_shared_threshold(raw, gf):
