@@ -5,6 +5,8 @@ committed files.  Nothing from /root/reference is copied: fixtures hold numbers 
 
   dbscan_*.npz      inputs (float32) + labels / core mask of the REAL sklearn call the reference
                     makes (utils/tower_extraction.py:107-112)
+  dbscan_lattice_ties.npz  the same call on the lattices of tests/dbscan_cases.py, whose pairs sit exactly at eps
+                    (outputs only; run with the argument "lattice")
   numpy_stats.json  np.mean(axis=0) (float32, sequential) and np.percentile(z,25) of seeded
                     EPSG:4547-scale arrays (utils/tower_extraction.py:63,83)
   kuangxuan_boxes.json  boxes of the reference's own example tower (ui/extract.py:460-464);
@@ -86,6 +88,41 @@ def dbscan_cases():
         np.savez_compressed(os.path.join(HERE, f"dbscan_{name}.npz"), X=X, labels=labels, core=core,
                             eps=eps, min_samples=ms, chunk=chunk)
         print(name, len(X), "clusters", labels.max() + 1, "noise", (labels == -1).sum())
+
+
+def dbscan_lattice_ties():
+    """sklearn's labels and core mask for the lattices of tests/dbscan_cases.py (pairs exactly at eps) at eps and at
+    nextafter(eps, 0), for the three min_samples read off the distance matrix.  Inputs are rebuilt from seeds; a
+    lattice on which the ball tree disagrees with the per-pair rule is left out and reported."""
+    import hashlib
+    from sklearn.cluster import DBSCAN
+    sys.path.insert(0, os.path.dirname(HERE))
+    import dbscan_cases as dc
+    from oracle import dbscan as odb
+    out, names = {}, []
+    for name in sorted(dc.LATTICES):
+        X, eps, em, mss, p = dc.lattice_case(name)
+        labels = np.empty((len(mss), 2, len(X)), np.int16)
+        core = np.zeros((len(mss), 2, len(X)), np.uint8)
+        agrees = True
+        for i, ms in enumerate(mss):
+            for j, e in enumerate((eps, em)):
+                cl = DBSCAN(eps=e, min_samples=ms, n_jobs=-1, algorithm="ball_tree").fit(X)
+                assert cl.labels_.max() < 32767
+                labels[i, j] = cl.labels_
+                core[i, j, cl.core_sample_indices_] = 1
+                rl, rc = odb.dbscan_fit_c(X, e, ms)
+                same = np.array_equal(rl, cl.labels_) and np.array_equal(rc, core[i, j])
+                agrees &= same
+                print(name, "min_samples", ms, "eps" if j == 0 else "nextafter(eps,0)", "core", int(core[i, j].sum()),
+                      "clusters", int(cl.labels_.max()) + 1, "agrees with the per-pair rule" if same else "DISAGREES")
+        if not agrees:
+            continue
+        names.append(name)
+        out[f"{name}_labels"], out[f"{name}_core"] = labels, core
+        out[f"{name}_eps"], out[f"{name}_min_samples"] = eps, np.asarray(mss)
+        out[f"{name}_sha"] = hashlib.sha256(np.ascontiguousarray(X).tobytes()).hexdigest()
+    np.savez_compressed(os.path.join(HERE, "dbscan_lattice_ties.npz"), names=np.asarray(names), **out)
 
 
 def numpy_stats():
@@ -497,9 +534,11 @@ def gim_match_contract():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["dbscan", "numpy", "boxes", "e2e", "refrun", "gim"]
+    which = sys.argv[1:] or ["dbscan", "lattice", "numpy", "boxes", "e2e", "refrun", "gim"]
     if "dbscan" in which:
         dbscan_cases()
+    if "lattice" in which:
+        dbscan_lattice_ties()
     if "numpy" in which:
         numpy_stats()
     if "boxes" in which:
