@@ -72,7 +72,8 @@ int         pch_device_count(void);
  * Order inside a chunk: Open3D emits unordered_map iteration order, i.e. unspecified; parity is the SET of
  * (index, mean, count) per chunk.  This library emits coarse grid cells (the top bits of [ix|iy|iz]) in ascending
  * order and, inside a cell, the voxels in the order of their first points - or sorted by (ix,iy,iz) where a cell
- * takes the sorting path (dense cells, wide keys).  Deterministic for a given input.
+ * takes the sorting path (dense cells, wide keys).  Deterministic for a given input and build, but not stable across
+ * versions of this library; pch_voxel_canonical_order below gives an order that depends on the input alone.
  * out_chunk_offsets [nchunks+1] int64 (may be NULL): slice of each chunk in the output
  * out_m      [1] int64 number of voxels
  */
@@ -82,6 +83,27 @@ int pch_voxel_downsample_f64(const double* xyz, int64_t n, double voxel_size,
                              int32_t* out_idx, double* out_mean, int32_t* out_count,
                              int64_t* out_chunk_offsets, int64_t* out_m,
                              void* ws, size_t ws_bytes, void* stream);
+
+/* Opt-in canonical order: the rows pch_voxel_downsample_f64 wrote, with every chunk's slice sorted ascending by
+ * (ix, iy, iz) - the order of oracle/voxel.py, a function of the input alone.  Everything downstream that depends on
+ * row order (the sequential float32 centroid and the DBSCAN chunk split of stage B/C, read from point_2.las) is then
+ * the same for every version and tuning of the voxel stage.
+ * idx [m,3] int32 (every index >= 0), mean [m,3] float64, count [m] int32, chunk_offsets [nchunks+1] int64 with
+ * chunk_offsets[0] == 0 and chunk_offsets[nchunks] == m (anything else: PCH_ERR_ARG), nchunks >= 1.
+ * out_idx / out_mean / out_count: the same rows reordered; buffers distinct from the inputs, 16-byte aligned.
+ * out_perm [m] int32 (may be NULL): source row of every output row.  chunk_offsets holds for the outputs unchanged.
+ * No voxel index repeats inside a chunk of the stage's output; if one does, the repeats keep their input order.
+ * One device-wide stable radix sort on the bits in use of [chunk | ix | iy | iz]; two sorts (the voxel fields, then
+ * the chunk of the permuted rows) where that key is wider than 64 bits.  m == 0 is success; m >= 2^31 is
+ * PCH_ERR_RANGE.  Host reads: ONE - four words behind the reduction over idx (the largest index per axis, which
+ * fixes the number of sort passes, and the check of chunk_offsets); the host waits for that copy only, everything
+ * behind it is enqueued without synchronising. */
+size_t pch_voxel_canonical_order_ws_bytes(int64_t m, int64_t nchunks);
+int pch_voxel_canonical_order(const int32_t* idx, const double* mean, const int32_t* count,
+                              const int64_t* chunk_offsets, int64_t nchunks, int64_t m,
+                              int32_t* out_idx, double* out_mean, int32_t* out_count,
+                              int32_t* out_perm /* may be NULL: source row of every output row */,
+                              void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ LAS files (native reader / writer)
  * What laspy does for the reference on the hot path, done by the library itself (host C++ + one decode

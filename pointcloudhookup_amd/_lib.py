@@ -31,6 +31,8 @@ _SIGS = {
     "pch_device_count": (C.c_int, []),
     "pch_voxel_downsample_ws_bytes": (_sz, [_i64, _i64]),
     "pch_voxel_downsample_f64": (C.c_int, [_vp, _i64, _f64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pch_voxel_canonical_order_ws_bytes": (_sz, [_i64, _i64]),
+    "pch_voxel_canonical_order": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pch_las_read_header": (C.c_int, [C.c_char_p, _vp]),
     "pch_las_read_ws_bytes": (_sz, []),
     "pch_las_read_xyz_i32": (C.c_int, [C.c_char_p, _i64, _i64, _vp, _vp, _sz, _vp]),

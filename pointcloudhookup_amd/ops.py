@@ -76,10 +76,14 @@ def get_profile():
 
 
 # ---------------------------------------------------------------------------- stage A
-def voxel_downsample(xyz, voxel_size, chunk_size=0):
+def voxel_downsample(xyz, voxel_size, chunk_size=0, order="library"):
     """Per-chunk voxel-grid downsample.  Returns (idx int32 [m,3], mean f64 [m,3],
     count int32 [m], chunk_offsets int64 [nchunks+1]); rows grouped by chunk; the order inside a
-    chunk is deterministic but not sorted (include/pch_hip.h; Open3D's own is unspecified).  Synchronises (reads m)."""
+    chunk is deterministic but not sorted (include/pch_hip.h; Open3D's own is unspecified).  Synchronises (reads m).
+    ``order="canonical"`` sorts every chunk's rows by (ix, iy, iz) behind the stage (voxel_canonical_order): that
+    order depends on the input alone, the default one also on the build."""
+    if order not in ("library", "canonical"):
+        raise ValueError(f"order must be 'library' or 'canonical', got {order!r}")
     L = _lib.lib()
     xyz = _need_cuda(xyz, torch.float64, "xyz").reshape(-1, 3)
     n = xyz.shape[0]
@@ -98,7 +102,34 @@ def voxel_downsample(xyz, voxel_size, chunk_size=0):
                                               _ptr(count), _ptr(offs), _ptr(m_dev), _ptr(ws), ws.numel(),
                                               _stream()))
         m = _lib.check_count(m_dev.item(), "voxel_downsample")
+    if order == "canonical":
+        return voxel_canonical_order(idx[:m], mean[:m], count[:m], offs) + (offs,)
     return idx[:m], mean[:m], count[:m], offs
+
+
+def voxel_canonical_order(idx, mean, count, chunk_offsets, want_perm=False):
+    """The rows voxel_downsample returned, every chunk's slice sorted ascending by (ix, iy, iz): new tensors
+    (idx, mean, count) and, with ``want_perm``, the source row of every output row (int32 [m]).  chunk_offsets holds
+    for the result unchanged.  Runs on the current stream in the shared workspace."""
+    L = _lib.lib()
+    idx = _need_cuda(idx, torch.int32, "idx").reshape(-1, 3)
+    mean = _need_cuda(mean, torch.float64, "mean").reshape(-1, 3)
+    count = _need_cuda(count, torch.int32, "count").reshape(-1)
+    offs = _need_cuda(chunk_offsets, torch.int64, "chunk_offsets").reshape(-1)
+    m = idx.shape[0]
+    if mean.shape[0] != m or count.shape[0] != m or offs.shape[0] < 2:
+        raise ValueError("idx, mean and count must have the same number of rows; chunk_offsets at least two entries")
+    dev = idx.device
+    nchunks = offs.shape[0] - 1
+    with torch.cuda.device(dev):
+        out_idx, out_mean, out_count = torch.empty_like(idx), torch.empty_like(mean), torch.empty_like(count)
+        perm = torch.empty((m,), dtype=torch.int32, device=dev) if want_perm else None
+        if m:
+            ws = _workspace(L.pch_voxel_canonical_order_ws_bytes(m, nchunks), dev)
+            _lib.check(L.pch_voxel_canonical_order(_ptr(idx), _ptr(mean), _ptr(count), _ptr(offs), nchunks, m,
+                                                   _ptr(out_idx), _ptr(out_mean), _ptr(out_count), _ptr(perm),
+                                                   _ptr(ws), ws.numel(), _stream()))
+    return (out_idx, out_mean, out_count, perm) if want_perm else (out_idx, out_mean, out_count)
 
 
 def las_records_xyz(records_u8, n, record_len):

@@ -1,6 +1,7 @@
 """Drop-in for the reference's ``ui/Sampling.py`` - the CLI twin of ui/import_PC.py
 (/root/reference/ui/Sampling.py:10-18,21-80): same function names and arguments, progress on
-stdout (tqdm when installed), every error caught and printed."""
+stdout (tqdm when installed), every error caught and printed.  Both functions run the code of ui/import_PC.py and
+so honour its ``OUTPUT_ORDER`` switch (env PCH_VOXEL_ORDER), read at call time."""
 from __future__ import annotations
 
 import os

@@ -8,7 +8,10 @@ arithmetic (X*scale+offset, rint((v-offset)/scale)) also runs on the device.
 
 Output order differs from Open3D's (hash-map iteration order there; here: chunks in file order, inside a
 chunk coarse grid cells in index order and the voxels of a cell in the order of their first points -
-deterministic); the set of output points per chunk is the same.
+deterministic for a given build, but not stable across versions of the library); the set of output points per chunk
+is the same.  ``OUTPUT_ORDER`` (env PCH_VOXEL_ORDER=library|canonical, default library; read at call time) switches
+to every chunk's voxels sorted by (ix, iy, iz): a function of the input alone, so that the tower table computed from
+the output file is the same across versions.
 
 Hand-off to tower extraction (pyGUI_towers_test.py:344-368 calls the two back to back): the int32 records of the
 output file stay registered on the device (pointcloudhookup_amd/resident.py), so ``extract_towers`` on that path
@@ -26,6 +29,7 @@ import numpy as np
 
 DEVICE = os.environ.get("PCH_DEVICE", "cuda:0")
 ASYNC_WRITE = os.environ.get("PCH_ASYNC_LAS_WRITE", "0") == "1"
+OUTPUT_ORDER = os.environ.get("PCH_VOXEL_ORDER", "library")
 
 
 def process_chunk(points_chunk, voxel_size):
@@ -36,7 +40,7 @@ def process_chunk(points_chunk, voxel_size):
     pts = np.ascontiguousarray(np.asarray(points_chunk).astype(np.float64)).reshape(-1, 3)
     if pts.shape[0] == 0:
         return np.zeros((0, 3), dtype=np.float64)
-    _, mean, _, _ = ops.voxel_downsample(torch.from_numpy(pts).to(DEVICE), float(voxel_size), 0)
+    _, mean, _, _ = ops.voxel_downsample(torch.from_numpy(pts).to(DEVICE), float(voxel_size), 0, order=OUTPUT_ORDER)
     return mean.cpu().numpy()
 
 
@@ -57,6 +61,9 @@ def run_voxel_downsampling(
     from .. import las as _las
     from .. import ops, stages
 
+    order = OUTPUT_ORDER
+    if order not in ("library", "canonical"):
+        raise ValueError(f"OUTPUT_ORDER / PCH_VOXEL_ORDER must be 'library' or 'canonical', got {order!r}")
     clock = stages.Clock("run_voxel_downsampling")
     dev = torch.device(DEVICE)
     hdr, XYZ = _las.read_device(input_path, dev)                      # records decoded on the GPU
@@ -71,9 +78,13 @@ def run_voxel_downsampling(
         xyz = ops.las_scale(XYZ, hdr.scales, hdr.offsets)            # chunk.x/.y/.z  (:47-48)
         del XYZ
         clock.mark("int32 -> float64 scaled view")
-        _, mean, _, offs = ops.voxel_downsample(xyz, float(voxel_size), int(chunk_size))
+        idx, mean, count, offs = ops.voxel_downsample(xyz, float(voxel_size), int(chunk_size))
         del xyz
         clock.mark("voxel grids (all chunks)")
+        if order == "canonical":
+            _, mean, _ = ops.voxel_canonical_order(idx, mean, count, offs)
+            clock.mark("canonical order (sort by voxel index per chunk)")
+        del idx, count
         out_XYZ = ops.las_unscale(mean, hdr.scales, hdr.offsets)                 # :61-63
         n_out = int(mean.shape[0])
         del mean
