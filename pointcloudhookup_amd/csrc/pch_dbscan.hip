@@ -13,6 +13,7 @@
 // x-neighbour cells are one contiguous run of the sorted point array: 25 runs per cell.
 // Cluster numbering reproduces sklearn's sweep: id = rank of the component's smallest core
 // index; a border point takes the smallest id among its core neighbours.
+#include <assert.h>
 #include "pch_prims.h"
 
 namespace pch {
@@ -349,6 +350,42 @@ __device__ __forceinline__ uint32_t cs_cell_key(const DbGrid& g, float x, float 
     return (((cz << g.by) | cy) << g.bx) | cx;
 }
 
+// ---- what db_chunksort_k and db_cellscatter_k must agree on for the overflow hand-over.  One asymmetry stays:
+// db_cellscatter_k stops sweeping once it has seen too many cells, so a NaN behind that point is found only by
+// db_chunksort_k's sweep B - which is why the overflow kernel keeps the bad-chunk path of cs_rows_in_place.
+constexpr int CS_HU = 8;                      // rows per thread in flight
+// rows i0 + u * CS_THREADS + tid of the chunk, all loads issued before any is used; a row past the end repeats row 0
+__device__ __forceinline__ void cs_load_rows(const Row3* __restrict__ rows, int i0, int cn, Row3 (&q)[CS_HU]) {
+#pragma unroll
+    for (int u = 0; u < CS_HU; ++u) {
+        const int i = i0 + u * CS_THREADS + (int)threadIdx.x;
+        q[u] = rows[i < cn ? i : 0];
+    }
+}
+// row check: is q finite?  A row of the chunk (in) sets flags[0] if not, else flags[1] if outside the grid (!ok)
+__device__ __forceinline__ bool cs_row_check(const Row3& q, bool in, bool ok, uint32_t* flags) {
+    const bool fin = fabsf(q.x) < INFINITY && fabsf(q.y) < INFINITY && fabsf(q.z) < INFINITY;
+    if (in && !fin) flags[0] = 1u;
+    else if (in && !ok) flags[1] = 1u;
+    return fin;
+}
+__device__ __forceinline__ uint64_t cs_chunk_field(const DbGrid& g, int64_t c) {    // of the keys of chunk c
+    const int sh = g.bx + g.by + g.bz;
+    return sh < 64 ? ((uint64_t)c << sh) : 0ull;
+}
+// a NaN/inf chunk (isbad: every key is cell 0) or a one-cell chunk: the rows stay where they are
+__device__ __forceinline__ void cs_rows_in_place(const DbGrid& g, const Row3* __restrict__ rows, int cn, int64_t lo,
+        uint64_t hi, bool isbad, float4* __restrict__ pts, uint64_t* __restrict__ keys_out) {
+    for (int i = threadIdx.x; i < cn; i += CS_THREADS) {
+        const Row3 q = rows[i];
+        float4 o4;
+        o4.x = q.x; o4.y = q.y; o4.z = q.z; o4.w = __uint_as_float((uint32_t)(lo + i));
+        pts[lo + i] = o4;
+        bool ok;
+        keys_out[lo + i] = isbad ? hi : (hi | cs_cell_key(g, q.x, q.y, q.z, ok));
+    }
+}
+
 // gate: runs only the chunks whose word is set (those db_cellscatter_k handed over); the others return at once
 __global__ __launch_bounds__(CS_THREADS) void db_chunksort_k(
     const float* __restrict__ xyz, int64_t n, DbGrid g, const uint32_t* __restrict__ gate, uint32_t* __restrict__ bad,
@@ -383,25 +420,18 @@ __global__ __launch_bounds__(CS_THREADS) void db_chunksort_k(
     if (tid < 2) flags[tid] = 0;
     if (tid < 6) cbox[tid] = tid < 3 ? 0xFFFFFFFFu : 0u;
     __syncthreads();
-    constexpr int HU = 8;                               // rows per thread in flight
     // ---- sweep B: NaN/inf and range checks, the chunk's box in cell coordinates
     {
         uint32_t mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0u, 0u, 0u};
-        for (int i0 = 0; i0 < cn; i0 += HU * CS_THREADS) {
-            Row3 q[HU];
+        for (int i0 = 0; i0 < cn; i0 += CS_HU * CS_THREADS) {
+            Row3 q[CS_HU];
+            cs_load_rows(rows, i0, cn, q);
 #pragma unroll
-            for (int u = 0; u < HU; ++u) {
-                const int i = i0 + u * CS_THREADS + tid;
-                q[u] = rows[i < cn ? i : 0];
-            }
-#pragma unroll
-            for (int u = 0; u < HU; ++u) {
+            for (int u = 0; u < CS_HU; ++u) {
                 const bool in = i0 + u * CS_THREADS + tid < cn;
-                const bool fin = fabsf(q[u].x) < INFINITY && fabsf(q[u].y) < INFINITY && fabsf(q[u].z) < INFINITY;
                 uint32_t cc[3];
                 const bool ok = db_cell_coords(g, q[u].x, q[u].y, q[u].z, cc[0], cc[1], cc[2]);
-                if (in && !fin) flags[0] = 1u;
-                else if (in && !ok) flags[1] = 1u;
+                const bool fin = cs_row_check(q[u], in, ok, flags);
                 if (in && fin && ok) {
 #pragma unroll
                     for (int a = 0; a < 3; ++a) { mn[a] = cc[a] < mn[a] ? cc[a] : mn[a]; mx[a] = cc[a] > mx[a] ? cc[a] : mx[a]; }
@@ -432,15 +462,11 @@ __global__ __launch_bounds__(CS_THREADS) void db_chunksort_k(
         return (uint32_t)((((((uint64_t)(cz - oz)) << wy) | (uint64_t)(cy - oy)) << wx) | (uint64_t)(cx - ox));   // tb <= 32
     };
     // ---- sweep H: digit histograms of every pass
-    for (int i0 = 0; i0 < cn; i0 += HU * CS_THREADS) {  // workgroup-uniform trip count
-        Row3 q[HU];
+    for (int i0 = 0; i0 < cn; i0 += CS_HU * CS_THREADS) {  // workgroup-uniform trip count
+        Row3 q[CS_HU];
+        cs_load_rows(rows, i0, cn, q);
 #pragma unroll
-        for (int u = 0; u < HU; ++u) {
-            const int i = i0 + u * CS_THREADS + tid;
-            q[u] = rows[i < cn ? i : 0];
-        }
-#pragma unroll
-        for (int u = 0; u < HU; ++u) {
+        for (int u = 0; u < CS_HU; ++u) {
             const bool in = i0 + u * CS_THREADS + tid < cn;
             bool ok;
             const uint32_t k = relkey(cs_cell_key(g, q[u].x, q[u].y, q[u].z, ok));
@@ -455,19 +481,8 @@ __global__ __launch_bounds__(CS_THREADS) void db_chunksort_k(
         bad[c] = isbad ? 1u : 0u;
         if (!isbad && flags[1]) atomicOr(status, 1u);
     }
-    const int sh = g.bx + g.by + g.bz;
-    const uint64_t hi = sh < 64 ? ((uint64_t)c << sh) : 0ull;
-    if (isbad || passes == 0) {                         // rows stay where they are: one cell (cell 0 if bad)
-        for (int i = tid; i < cn; i += CS_THREADS) {
-            const Row3 q = rows[i];
-            float4 o4;
-            o4.x = q.x; o4.y = q.y; o4.z = q.z; o4.w = __uint_as_float((uint32_t)(lo + i));
-            pts[lo + i] = o4;
-            bool ok;
-            keys_out[lo + i] = isbad ? hi : (hi | cs_cell_key(g, q.x, q.y, q.z, ok));
-        }
-        return;
-    }
+    const uint64_t hi = cs_chunk_field(g, c);
+    if (isbad || passes == 0) { cs_rows_in_place(g, rows, cn, lo, hi, isbad, pts, keys_out); return; }   // one cell
     // One pass, unswitched on what the compiler has to know statically: FIRST (the source rows are 12-byte input
     // rows), LAST (the full keys are written too) and, per tile, FULL (every lane holds a row).  In a full tile the
     // scattered stores are unconditional, so their number is a constant - and with it the wait for the NEXT tile's
@@ -623,26 +638,19 @@ __global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
     for (int j = tid; j < CT_SLOTS; j += CS_THREADS) { tkey[j] = CT_EMPTY; tcnt[j] = 0u; }
     if (tid < 5) flags[tid] = 0u;
     __syncthreads();
-    constexpr int HU = 8;                               // rows per thread in flight
     // ---- sweep 1: checks, cell counts.  A row inserts only while flags[3] is clear, and at most one new key per
     // thread can be in flight when it is set, so the table holds at most CT_CELLS + CS_THREADS keys: a probe always
     // ends at its key or at an empty slot (the bound on the probe loop is never reached)
-    for (int i0 = 0; i0 < cn; i0 += HU * CS_THREADS) {
+    for (int i0 = 0; i0 < cn; i0 += CS_HU * CS_THREADS) {
         if (__hip_atomic_load(&flags[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;   // too many cells
-        Row3 q[HU];
+        Row3 q[CS_HU];
+        cs_load_rows(rows, i0, cn, q);
 #pragma unroll
-        for (int u = 0; u < HU; ++u) {
-            const int i = i0 + u * CS_THREADS + tid;
-            q[u] = rows[i < cn ? i : 0];
-        }
-#pragma unroll
-        for (int u = 0; u < HU; ++u) {
+        for (int u = 0; u < CS_HU; ++u) {
             const bool in = i0 + u * CS_THREADS + tid < cn;
-            const bool fin = fabsf(q[u].x) < INFINITY && fabsf(q[u].y) < INFINITY && fabsf(q[u].z) < INFINITY;
             bool ok;
             const uint32_t k = cs_cell_key(g, q[u].x, q[u].y, q[u].z, ok);
-            if (in && !fin) flags[0] = 1u;
-            else if (in && !ok) flags[1] = 1u;
+            const bool fin = cs_row_check(q[u], in, ok, flags);
             if (in && fin && __hip_atomic_load(&flags[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) {
                 uint32_t h = ct_hash(k);
                 for (int p = 0; p < CT_SLOTS; ++p, h = (h + 1u) & (CT_SLOTS - 1)) {
@@ -665,19 +673,8 @@ __global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
         }
     }
     if (over) return;                                   // db_chunksort_k takes this chunk
-    const int sh = g.bx + g.by + g.bz;
-    const uint64_t hi = sh < 64 ? ((uint64_t)c << sh) : 0ull;
-    if (isbad || ncell == 1u) {                         // rows stay where they are: one cell (cell 0 if bad)
-        for (int i = tid; i < cn; i += CS_THREADS) {
-            const Row3 q = rows[i];
-            float4 o4;
-            o4.x = q.x; o4.y = q.y; o4.z = q.z; o4.w = __uint_as_float((uint32_t)(lo + i));
-            pts[lo + i] = o4;
-            bool ok;
-            keys_out[lo + i] = isbad ? hi : (hi | cs_cell_key(g, q.x, q.y, q.z, ok));
-        }
-        return;
-    }
+    const uint64_t hi = cs_chunk_field(g, c);
+    if (isbad || ncell == 1u) { cs_rows_in_place(g, rows, cn, lo, hi, isbad, pts, keys_out); return; }   // one cell
     // ---- the occupied slots, compacted (in any order) and padded to a power of two ...
     const int P = 1 << (32 - __clz((int)ncell - 1));    // 2 <= P <= CT_CELLS
     for (int j0 = 0; j0 < CT_SLOTS; j0 += CS_THREADS) {
@@ -731,15 +728,11 @@ __global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
     }
     __syncthreads();
     // ---- sweep 2: every row to its cell's next position
-    for (int i0 = 0; i0 < cn; i0 += HU * CS_THREADS) {
-        Row3 q[HU];
+    for (int i0 = 0; i0 < cn; i0 += CS_HU * CS_THREADS) {
+        Row3 q[CS_HU];
+        cs_load_rows(rows, i0, cn, q);
 #pragma unroll
-        for (int u = 0; u < HU; ++u) {
-            const int i = i0 + u * CS_THREADS + tid;
-            q[u] = rows[i < cn ? i : 0];
-        }
-#pragma unroll
-        for (int u = 0; u < HU; ++u) {
+        for (int u = 0; u < CS_HU; ++u) {
             const int i = i0 + u * CS_THREADS + tid;
             if (i < cn) {
                 bool ok;
@@ -1991,10 +1984,24 @@ __global__ void db_prelabel_k(const uint32_t* __restrict__ total, int32_t* __res
     if (box_acc && i < box_words) box_acc[i] = 0u;
 }
 
+// The 256-byte head of the workspace.  Kernels take pointers to single fields; the host reads fields of a copy.
+struct DbMeta {
+    uint32_t box_key[6];    // db_aabb_in_k: ordered keys of the finite rows' box, min xyz | max xyz; db_bounds reads
+                            // them.  DbWs::clear_from starts at [4] for its 16-byte alignment: nobody reads [4..5] then
+    uint32_t status;        // bit 0: a finite row outside the grid, bit 1: compressed coordinate out of range
+    uint32_t ncells, nclusters;
+    uint32_t comp_max[3];   // dbc_comp_k: largest compressed index per axis
+    int64_t  first_bad;     // db_compress: first NaN/inf row, -1 if none
+    uint32_t pad[50];
+};
+static_assert(sizeof(DbMeta) == 256 && offsetof(DbMeta, box_key) == 0 && offsetof(DbMeta, status) == 24 &&
+              offsetof(DbMeta, ncells) == 28 && offsetof(DbMeta, nclusters) == 32 && offsetof(DbMeta, comp_max) == 36 &&
+              offsetof(DbMeta, first_bad) == 48 && offsetof(DbMeta, pad) == 56, "the layout every build so far had");
+
 struct DbWs {
-    uint32_t* meta;         // [0..5] aabb ordered keys, [6] status, [7] m, [8] nclusters
+    DbMeta*   meta;
     uint64_t *k0, *k1, *cell_key;
-    uint32_t *v0, *v1, *head, *cid, *cell_start, *cell_ncore, *flag, *radix_ws, *scan_ws;
+    uint32_t *v0, *v1, *head, *cid, *cell_start, *cell_ncore, *radix_ws, *scan_ws;
     float4   *pts, *xbuf;
     uint8_t*  core_s;
     float*    cell_box;
@@ -2003,21 +2010,34 @@ struct DbWs {
     int      *parent, *root, *comp_min, *cell_label;
     int2*     rowtab;
     int64_t   rowtab_cells;
-    uint32_t* chunk_bad;
+    uint32_t *chunk_bad, *chunk_cells;
     uint32_t* chunk_ovf;     // one word per chunk: db_cellscatter_k handed the chunk to db_chunksort_k
-    uint32_t* chunk_cells;
     uint32_t* comp;          // [n][3] compressed cell coordinates (fallback for grids beyond the 64-bit key)
     uint32_t* flag2;         // [n + 8] head flags kept beside their scan
     unsigned long long* core_stats;   // [4] tallies of db_core_k<true> (pch_dbscan_set_pair_counting)
     uint32_t* scan1_b;                // zeroed words of the single-pass scan of the cluster ranks
+    uint32_t* bits;         // bitmap over the rows: db_cellstats_k clears it, db_mark_k sets the clusters' first core rows
+    // Views that db_plan carves into the arrays above:
+    uint32_t* wrank;        // bits' array from the next multiple of 64 words on: db_labels' scan of the bitmap's word
+                            // counts.  Both are kept for pch_dbscan_first_core_rows_i32; the array has no other use
+    uint8_t*  face_todo;    // root as bytes: db_union_pairs_k writes the face pairs it leaves to db_union_face_k.  root
+                            // itself is first written by db_compmin_k, behind both
+    unsigned long long* cs_stamps = nullptr;     // cell_box (first written by db_cellfin_k), PCH_CS_STAMPS builds only
+    // One 16-byte aligned fill zeroes status / ncells / nclusters, scan1_b and the first-cell word of every chunk
+    // (db_cells_k writes it at a chunk's first cell; the zeros make a chunk without a cell an empty range)
+    void*  clear_from() const { return &meta->box_key[4]; }
+    size_t clear_bytes(int64_t nchunks) const {
+        return ((size_t)((char*)(chunk_cells + nchunks + 1) - (char*)clear_from()) + 15) & ~size_t(15);
+    }
 };
 
 static void db_plan(Arena& a, int64_t n, DbWs& w) {
     const int64_t nn = n > 0 ? n : 1;
-    w.meta = a.take<uint32_t>(64);                       // exactly one 256-byte arena block ...
-    w.scan1_b = a.take<uint32_t>(scan1_ws_u32(nn / 32 + 1));   // ... directly followed by the zero-initialised words
-                                                         // of the single-pass scan and by the per-chunk table:
-    w.chunk_cells = a.take<uint32_t>(nn + 8);            // ONE fill clears them all (db_plan keeps them adjacent)
+    w.meta = a.take<DbMeta>(1);                          // DbWs::clear_from runs across these three: nothing may be
+    w.scan1_b = a.take<uint32_t>(scan1_ws_u32(nn / 32 + 1));   // carved between them
+    w.chunk_cells = a.take<uint32_t>(nn + 8);
+    assert(!w.chunk_cells || ((void*)(w.meta + 1) == w.scan1_b && (char*)w.chunk_cells - (char*)w.scan1_b ==
+                              (ptrdiff_t)((scan1_ws_u32(nn / 32 + 1) * sizeof(uint32_t) + 255) & ~size_t(255))));
     w.core_stats = a.take<unsigned long long>(4);
     w.chunk_bad = a.take<uint32_t>(nn + 8);              // one word per chunk (chunk_size >= 1)
     w.chunk_ovf = a.take<uint32_t>(nn + 8);              // (written for every chunk by db_cellscatter_k)
@@ -2040,7 +2060,7 @@ static void db_plan(Arena& a, int64_t n, DbWs& w) {
     w.root = a.take<int>(nn);
     w.comp_min = a.take<int>(nn);
     w.cell_label = a.take<int>(nn);
-    w.flag = a.take<uint32_t>(nn / 16 + 256);             // row bitmap (n/32 words) + its scanned word counts
+    w.bits = a.take<uint32_t>(nn / 16 + 256);             // row bitmap (n/32 words) + its scanned word counts (wrank)
     w.radix_ws = a.take<uint32_t>(radix_ws_u32(nn));
     w.scan_ws = a.take<uint32_t>(scan_ws_u32(nn));
     // neighbour-row table (200 B per cell) for up to max(n/4, 64Ki) cells; beyond that the rows are
@@ -2049,6 +2069,11 @@ static void db_plan(Arena& a, int64_t n, DbWs& w) {
     w.rowtab = a.take<int2>((size_t)w.rowtab_cells * DB_ROWS);
     w.comp = a.take<uint32_t>(3 * nn);
     w.flag2 = a.take<uint32_t>(nn + 8);
+    w.wrank = w.bits ? w.bits + ((ceil_div(nn, 32) + 63) & ~int64_t(63)) : nullptr;
+    w.face_todo = reinterpret_cast<uint8_t*>(w.root);
+#ifdef PCH_CS_STAMPS
+    w.cs_stamps = reinterpret_cast<unsigned long long*>(w.cell_box);
+#endif
 }
 
 // The cell table in the parameter order of the neighbour kernels: db_core_k takes DB_GRID_ARGS (and writes core_s /
@@ -2134,18 +2159,18 @@ static int db_bounds(const DbRun& r, const float* aabb_host, float (&box)[6], bo
     if (aabb_host) {
         memcpy(box, aabb_host, sizeof(box));
     } else {
-        uint32_t* meta = r.w.meta;
-        PCH_HIP_TRY(hipMemsetAsync(meta, 0xFF, 3 * sizeof(uint32_t), r.s));
-        PCH_HIP_TRY(hipMemsetAsync(meta + 3, 0, 3 * sizeof(uint32_t), r.s));
-        PCH_LAUNCH("db_aabb_in", db_aabb_in_k, dim3(db_stride_blocks(r.n)), dim3(DB_THREADS), 0, r.s, r.xyz, r.n, meta);
-        uint32_t mm[6];
-        PCH_HIP_TRY(hipMemcpyAsync(mm, meta, sizeof(mm), hipMemcpyDeviceToHost, r.s));
+        uint32_t* key = r.w.meta->box_key;
+        PCH_HIP_TRY(hipMemsetAsync(key, 0xFF, 3 * sizeof(uint32_t), r.s));
+        PCH_HIP_TRY(hipMemsetAsync(key + 3, 0, 3 * sizeof(uint32_t), r.s));
+        PCH_LAUNCH("db_aabb_in", db_aabb_in_k, dim3(db_stride_blocks(r.n)), dim3(DB_THREADS), 0, r.s, r.xyz, r.n, key);
+        DbMeta back;
+        PCH_HIP_TRY(hipMemcpyAsync(back.box_key, key, sizeof(back.box_key), hipMemcpyDeviceToHost, r.s));
         PCH_HIP_TRY(hipStreamSynchronize(r.s));
-        if (mm[0] == 0xFFFFFFFFu) {                        // not a single finite point: every chunk fails
+        if (back.box_key[0] == 0xFFFFFFFFu) {              // not a single finite point: every chunk fails
             done = true;
             return db_all_noise(r);
         }
-        for (int k = 0; k < 6; ++k) box[k] = host_unordered(mm[k]);
+        for (int k = 0; k < 6; ++k) box[k] = host_unordered(back.box_key[k]);
     }
     for (int k = 0; k < 6; ++k) {
         if (!(box[k] == box[k]) || box[k] > 3.0e38f || box[k] < -3.0e38f) {
@@ -2216,11 +2241,10 @@ static int db_run_chunks(const DbRun& r, double eps, int32_t min_samples, void* 
 static int db_compress(const DbRun& r, DbGrid& g, int& cellbits, bool& done) {
     const DbWs& w = r.w; const hipStream_t s = r.s; const int64_t n = r.n;
     const unsigned gn = (unsigned)ceil_div(n, DB_THREADS);
-    int64_t* first_bad = reinterpret_cast<int64_t*>(w.meta + 12);
-    PCH_HIP_TRY(hipMemsetAsync(first_bad, 0xFF, sizeof(int64_t), s));
+    PCH_HIP_TRY(hipMemsetAsync(&w.meta->first_bad, 0xFF, sizeof(int64_t), s));
     PCH_LAUNCH("db_first_bad", db_first_bad_k, dim3(db_stride_blocks(n)), dim3(DB_THREADS), 0, s, r.xyz, n,
-               reinterpret_cast<unsigned long long*>(first_bad));
-    PCH_HIP_TRY(hipMemsetAsync(w.meta + 6, 0, 6 * sizeof(uint32_t), s));
+               reinterpret_cast<unsigned long long*>(&w.meta->first_bad));
+    PCH_HIP_TRY(hipMemsetAsync(&w.meta->status, 0, offsetof(DbMeta, first_bad) - offsetof(DbMeta, status), s));
     for (int axis = 0; axis < 3; ++axis) {
         PCH_LAUNCH("dbc_axis_keys", dbc_axis_keys_k, dim3(gn), dim3(DB_THREADS), 0, s, r.xyz, n, axis, w.k0, w.v0);
         PCH_TRY(radix_sort_pairs(w.k0, w.v0, w.k1, w.v1, n, 32, w.radix_ws, s));
@@ -2232,24 +2256,23 @@ static int db_compress(const DbRun& r, DbGrid& g, int& cellbits, bool& done) {
         PCH_HIP_TRY(hipMemsetAsync(w.cell_start, 0, sizeof(uint32_t) * (size_t)(n + 8), s));
         for (int phase = 0; phase < 2; ++phase)
             PCH_LAUNCH("dbc_local", dbc_local_k, dim3(gn), dim3(DB_THREADS), 0, s, ksa, w.flag2, w.head, n, g.inv_cell,
-                       w.cell_box, phase, w.cid, w.cell_start, w.meta + 6);
+                       w.cell_box, phase, w.cid, w.cell_start, &w.meta->status);
         PCH_TRY(scan_exclusive_u32(w.cell_start, w.cell_start, n, w.scan_ws, nullptr, s));
         PCH_LAUNCH("dbc_comp", dbc_comp_k, dim3(gn), dim3(DB_THREADS), 0, s, vsa, w.flag2, w.head, w.cid, w.cell_start,
-                   n, axis, w.comp, w.meta + 9);
+                   n, axis, w.comp, w.meta->comp_max);
     }
-    uint32_t back[8];                        // [0] status, [3..5] largest compressed index per axis, [6..7] first bad row
-    PCH_HIP_TRY(hipMemcpyAsync(back, w.meta + 6, sizeof(back), hipMemcpyDeviceToHost, s));
+    DbMeta back;                             // status .. first_bad
+    PCH_HIP_TRY(hipMemcpyAsync(&back.status, &w.meta->status, offsetof(DbMeta, pad) - offsetof(DbMeta, status),
+                               hipMemcpyDeviceToHost, s));
     PCH_HIP_TRY(hipStreamSynchronize(s));
-    int64_t bad_row;
-    memcpy(&bad_row, &back[6], sizeof(bad_row));
-    if (bad_row >= 0) {                      // NaN / inf in a single fit: sklearn rejects it, everything stays noise
+    if (back.first_bad >= 0) {               // NaN / inf in a single fit: sklearn rejects it, everything stays noise
         PCH_TRY(db_all_noise(r));
         g_last.ws = nullptr;
         done = true;
         return PCH_OK;
     }
-    if (back[0] != 0) { set_error("compressed cell coordinates out of range"); return PCH_ERR_RANGE; }
-    cellbits = db_cell_bits(g, (int)back[3], (int)back[4], (int)back[5]);
+    if (back.status != 0) { set_error("compressed cell coordinates out of range"); return PCH_ERR_RANGE; }
+    cellbits = db_cell_bits(g, (int)back.comp_max[0], (int)back.comp_max[1], (int)back.comp_max[2]);
     if (cellbits > 64) {
         set_error("cell key needs %d bits even with compressed coordinates (%lld isolated points?)", cellbits, (long long)n);
         return PCH_ERR_RANGE;
@@ -2262,11 +2285,7 @@ static int db_sorted_keys(const DbRun& r, const DbGrid& g, int cellbits, int nbi
                           const uint64_t*& ks) {
     const DbWs& w = r.w; const hipStream_t s = r.s; const int64_t n = r.n, nchunks = r.nchunks;
     const unsigned gn = (unsigned)ceil_div(n, DB_THREADS);
-    // status / cell count / cluster count words and the per-chunk first-cell table, in one 16-byte aligned fill
-    // (meta[4..5] are bounding-box keys nobody reads any more; chunk_cells is written at the first cell of every
-    // chunk by db_cells_k, the zeros make a chunk without a cell an empty range)
-    const size_t bytes = (size_t)(reinterpret_cast<char*>(w.chunk_cells + nchunks + 1) - reinterpret_cast<char*>(w.meta + 4));
-    PCH_HIP_TRY(hipMemsetAsync(w.meta + 4, 0, (bytes + 15) & ~size_t(15), s));
+    PCH_HIP_TRY(hipMemsetAsync(w.clear_from(), 0, w.clear_bytes(nchunks), s));
     // One workgroup per chunk only pays with enough chunks to fill the GPU (measured break-even near
     // 100 chunks of 50 000 rows); PCH_DBSCAN_SORT=chunk / global forces a path (tests compare them)
     if (!compressed && cellbits <= 31 && r.chunk_size <= CS_MAX_CHUNK && sort_mode != 2 &&
@@ -2274,14 +2293,14 @@ static int db_sorted_keys(const DbRun& r, const DbGrid& g, int cellbits, int nbi
         // chunk-local path: one workgroup per chunk builds keys, groups the rows by cell and writes them; a chunk with
         // more cells than db_cellscatter_k's table takes goes through db_chunksort_k (gated by chunk_ovf: no host read)
         PCH_LAUNCH("db_cellscatter", db_cellscatter_k, dim3((unsigned)nchunks), dim3(CS_THREADS), 0, s, r.xyz, n, g,
-                   w.chunk_bad, w.chunk_ovf, w.pts, w.k1, w.meta + 6);
+                   w.chunk_bad, w.chunk_ovf, w.pts, w.k1, &w.meta->status);
         PCH_LAUNCH("db_chunksort", db_chunksort_k, dim3((unsigned)nchunks), dim3(CS_THREADS), 0, s, r.xyz, n, g,
-                   w.chunk_ovf, w.chunk_bad, w.xbuf, w.pts, w.k1, w.meta + 6, (unsigned long long*)w.cell_box);
+                   w.chunk_ovf, w.chunk_bad, w.xbuf, w.pts, w.k1, &w.meta->status, w.cs_stamps);
 #ifdef PCH_CS_STAMPS
         {
             unsigned long long t[11];                    // start | sweep B | sweep H | one per pass | heads
             PCH_HIP_TRY(hipStreamSynchronize(s));
-            PCH_HIP_TRY(hipMemcpy(t, w.cell_box, sizeof(t), hipMemcpyDeviceToHost));
+            PCH_HIP_TRY(hipMemcpy(t, w.cs_stamps, sizeof(t), hipMemcpyDeviceToHost));
             for (int q = 1; q <= 6; ++q)
                 fprintf(stderr, "chunksort phase %d: %.2f us\n", q, (double)(long long)(t[q] - t[q - 1]) / 100.0);
             fprintf(stderr, "chunksort tiles: rank %.2f us, offsets %.2f us, scatter %.2f us\n", (double)t[8] / 100.0,
@@ -2299,7 +2318,7 @@ static int db_sorted_keys(const DbRun& r, const DbGrid& g, int cellbits, int nbi
         PCH_LAUNCH("db_chunkbad", db_chunkbad_k, dim3(db_stride_blocks(n)), dim3(DB_THREADS), 0, s, r.xyz, n,
                    r.chunk_size, w.chunk_bad);
         PCH_LAUNCH("db_keys", db_keys_k, dim3(gn), dim3(DB_THREADS), 0, s, r.xyz, n, g, w.chunk_bad, w.k0, w.v0,
-                   w.meta + 6);
+                   &w.meta->status);
     }
     PCH_TRY(radix_sort_pairs(w.k0, w.v0, w.k1, w.v1, n, nbits, w.radix_ws, s));
     const bool in1 = radix_sort_result_buffer(nbits) == 1;
@@ -2314,18 +2333,18 @@ static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const ui
     const DbWs& w = r.w; const hipStream_t s = r.s; const int64_t n = r.n;
     const int64_t ntile = ceil_div(n, (int64_t)SCAN_TILE);
     PCH_LAUNCH("db_heads", db_heads_k, dim3((unsigned)ntile), dim3(DB_THREADS), 0, s, ks, n, w.scan_ws);
-    PCH_TRY(scan_tile_sums_u32(w.scan_ws, ntile, w.meta + 7, s));
+    PCH_TRY(scan_tile_sums_u32(w.scan_ws, ntile, &w.meta->ncells, s));
     // the cell count sizes the next grids: fetch it while db_cells_k (sized by n) runs
-    uint32_t st_m[2];
-    PCH_TRY(peek_enqueue(w.meta + 6, sizeof(st_m), s));
+    DbMeta back;                             // status, ncells
+    PCH_TRY(peek_enqueue(&w.meta->status, 2 * sizeof(uint32_t), s));
     PCH_LAUNCH("db_cells", db_cells_k, dim3((unsigned)ntile), dim3(DB_THREADS), 0, s, ks, w.scan_ws, n, cellbits,
                r.nchunks, w.cid, w.cell_start, w.cell_key, w.chunk_cells, w.cell_acc);
-    PCH_TRY(peek_wait(st_m, sizeof(st_m)));
-    if (st_m[0] != 0) {
+    PCH_TRY(peek_wait(&back.status, 2 * sizeof(uint32_t)));
+    if (back.status != 0) {
         set_error("finite coordinates outside the supplied bounding box");
         return PCH_ERR_ARG;
     }
-    const int m = (int)st_m[1];
+    const int m = (int)back.ncells;
     const unsigned gc = (unsigned)ceil_div(m, DB_WAVES);
     c = {g, w.pts, w.cell_start, w.cell_key, m, m <= w.rowtab_cells ? w.rowtab : nullptr, w.core_s, w.cell_ncore,
          w.cell_box};
@@ -2341,7 +2360,7 @@ static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const ui
                    w.cell_ncore, nullptr);
     }
     PCH_LAUNCH("db_cellstats", db_cellstats_k, dim3((unsigned)ceil_div(n, (int64_t)DB_WAVES * 64 * DB_CS_ROUNDS)),
-               dim3(DB_THREADS), 0, s, w.pts, w.cid, w.core_s, n, w.cell_acc, w.flag, ceil_div(n, 32));
+               dim3(DB_THREADS), 0, s, w.pts, w.cid, w.core_s, n, w.cell_acc, w.bits, ceil_div(n, 32));
     PCH_LAUNCH("db_cellfin", db_cellfin_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
                w.cell_acc, m, w.cell_box, w.cell_min, w.parent, w.comp_min);
     return PCH_OK;
@@ -2351,15 +2370,12 @@ static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const ui
 static int db_union(const DbRun& r, const DbCells& c) {
     const DbWs& w = r.w; const hipStream_t s = r.s; const int m = c.m;
     const unsigned gc = (unsigned)ceil_div(m, DB_WAVES);
-    // face neighbours: lane-per-pair first (needs the row table), the wave-wide search for what that left open;
-    // the flags live in w.root, which nobody needs before db_compmin_k
-    const uint8_t* face_todo = nullptr;
-    if (c.rowtab) {
+    // face neighbours: lane-per-pair first (needs the row table), the wave-wide search for what that left open
+    if (c.rowtab)
         PCH_LAUNCH("db_union_pairs", db_union_pairs_k, dim3((unsigned)ceil_div(4 * (int64_t)m, DB_THREADS)),
-                   dim3(DB_THREADS), 0, s, DB_CELL_ARGS(c), w.parent, reinterpret_cast<uint8_t*>(w.root));
-        face_todo = reinterpret_cast<const uint8_t*>(w.root);
-    }
-    PCH_LAUNCH("db_union0", db_union_face_k, dim3(gc), dim3(DB_THREADS), 0, s, DB_CELL_ARGS(c), w.parent, face_todo);
+                   dim3(DB_THREADS), 0, s, DB_CELL_ARGS(c), w.parent, w.face_todo);
+    PCH_LAUNCH("db_union0", db_union_face_k, dim3(gc), dim3(DB_THREADS), 0, s, DB_CELL_ARGS(c), w.parent,
+               c.rowtab ? (const uint8_t*)w.face_todo : nullptr);
     PCH_LAUNCH("db_flatten", db_flatten_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
                w.parent, m);
     PCH_LAUNCH("db_union1", db_union_k, dim3(gc), dim3(DB_THREADS), 0, s, DB_CELL_ARGS(c), w.parent);
@@ -2374,24 +2390,22 @@ static int db_labels(const DbRun& r, const DbCells& c, const DbTuning& tune, int
     // cluster id = rank of the cluster's smallest core row: a bitmap over the rows + a scan of its
     // word counts (n/32 elements instead of n)
     const int64_t nw = ceil_div(n, 32);
-    uint32_t* bits = w.flag;
-    uint32_t* wrank = w.flag + ((nw + 63) & ~int64_t(63));
     static_assert(DB_CS_ROUNDS * 64 * DB_WAVES / DB_THREADS <= 32, "db_cellstats_k's grid has a thread per bitmap word");
     PCH_LAUNCH("db_mark", db_mark_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
-               w.root, w.comp_min, m, bits);
+               w.root, w.comp_min, m, w.bits);
     // word ranks: popcount on load
-    if (scan1_pays(nw)) PCH_TRY(scan1_exclusive_popc_u32(bits, wrank, nw, w.scan1_b, w.meta + 8, s));
-    else PCH_TRY(scan_exclusive_popc_u32(bits, wrank, nw, w.scan_ws, w.meta + 8, s));
+    if (scan1_pays(nw)) PCH_TRY(scan1_exclusive_popc_u32(w.bits, w.wrank, nw, w.scan1_b, &w.meta->nclusters, s));
+    else PCH_TRY(scan_exclusive_popc_u32(w.bits, w.wrank, nw, w.scan_ws, &w.meta->nclusters, s));
     uint32_t* box_acc = (boxes && boxes->acc && boxes->cap > 0 && !tune.no_boxfold) ? boxes->acc : nullptr;
     const int32_t box_cap = box_acc ? boxes->cap : 0;
     PCH_LAUNCH("db_prelabel", db_prelabel_k, dim3((unsigned)(box_acc ? ceil_div(8 * (int64_t)box_cap, 256) : 1)),
-               dim3(256), 0, s, w.meta + 8, r.out_nclusters, box_acc, 8 * (int64_t)box_cap);
+               dim3(256), 0, s, &w.meta->nclusters, r.out_nclusters, box_acc, 8 * (int64_t)box_cap);
     if (k_host) PCH_TRY(peek_enqueue(r.out_nclusters, sizeof(int32_t), s));    // read while the labels are written
     // many chunks: the blocks of one chunk share an XCD (see db_label_k); otherwise blocks in sorted order
     const int bpc = (nchunks >= 16 && !tune.no_xcd) ? (int)ceil_div(r.chunk_size, DB_LAB_TILE) : 0;
     const unsigned gl = bpc > 0 ? (unsigned)(8 * ceil_div(nchunks, 8) * bpc) : (unsigned)ceil_div(n, DB_LAB_TILE);
     PCH_LAUNCH("db_label", db_label_k, dim3(gl), dim3(DB_THREADS), 0, s, w.pts, w.cid, w.core_s, w.root, w.comp_min,
-               bits, wrank, n, w.cell_start, w.cell_label, r.labels, r.core, r.chunk_size, bpc, nchunks, box_acc,
+               w.bits, w.wrank, n, w.cell_start, w.cell_label, r.labels, r.core, r.chunk_size, bpc, nchunks, box_acc,
                box_cap);
     PCH_LAUNCH("db_border", db_border_k, dim3((unsigned)ceil_div(m, DB_WAVES)), dim3(DB_THREADS), 0, s,
                DB_CELL_ARGS(c), w.cell_label, r.labels, box_acc, box_cap);
@@ -2488,10 +2502,8 @@ extern "C" int pch_dbscan_first_core_rows_i32(int64_t n, int32_t* out_rows, void
     PCH_TRY(db_continue(__func__, n, ws, ws_bytes, w));
     PCH_REQUIRE(out_rows != nullptr, "null output");
     const int64_t nw = ceil_div(n, 32);
-    const uint32_t* bits = w.flag;
-    const uint32_t* wrank = w.flag + ((nw + 63) & ~int64_t(63));
     PCH_LAUNCH("db_first_rows", db_first_rows_k, dim3((unsigned)ceil_div(nw, DB_THREADS)), dim3(DB_THREADS), 0,
-               (hipStream_t)stream, bits, wrank, nw, out_rows);
+               (hipStream_t)stream, w.bits, w.wrank, nw, out_rows);
     return PCH_OK;
 }
 

@@ -338,28 +338,27 @@ def ground_filter(raw, pct=25.0, offset=3.0, fallback_offset=1.0, min_keep=1000,
 
 
 # ---------------------------------------------------------------------------- stage C
+def _dbscan_call(xyz, ws, eps, min_samples, chunk_size, aabb, want_core):
+    """pch_dbscan_f32 on float32 [n,3] of the current device, in the workspace tensor ws: (labels, core | None, k)"""
+    import ctypes as C
+    n, dev = xyz.shape[0], xyz.device
+    labels = torch.empty((n,), dtype=torch.int32, device=dev)
+    core = torch.empty((n,), dtype=torch.uint8, device=dev) if want_core else None
+    ncl = torch.zeros((1,), dtype=torch.int32, device=dev)
+    box = None if aabb is None else (C.c_float * 6)(*[float(v) for v in aabb])
+    _lib.check(_lib.lib().pch_dbscan_f32(_ptr(xyz), n, float(eps), int(min_samples), int(chunk_size),
+                                         None if box is None else C.cast(box, C.c_void_p), _ptr(labels),
+                                         _ptr(core), _ptr(ncl), _ptr(ws), ws.numel(), _stream()))
+    return labels, core, _lib.check_count(ncl.item(), "dbscan")
+
+
 def dbscan(xyz, eps=8.0, min_samples=80, chunk_size=50000, aabb=None, want_core=False):
     """Chunked exact DBSCAN on float32 [n,3].  Returns (labels int32 [n], core uint8 [n] | None,
     nclusters int).  Synchronises."""
-    import ctypes as C
-    L = _lib.lib()
     xyz = _need_cuda(xyz, torch.float32, "xyz").reshape(-1, 3)
-    n = xyz.shape[0]
-    dev = xyz.device
-    with torch.cuda.device(dev):
-        labels = torch.empty((n,), dtype=torch.int32, device=dev)
-        core = torch.empty((n,), dtype=torch.uint8, device=dev) if want_core else None
-        ncl = torch.zeros((1,), dtype=torch.int32, device=dev)
-        nb = L.pch_dbscan_ws_bytes(n)
-        ws = _workspace(nb, dev)
-        box = None
-        if aabb is not None:
-            box = (C.c_float * 6)(*[float(v) for v in aabb])
-        _lib.check(L.pch_dbscan_f32(_ptr(xyz), n, float(eps), int(min_samples), int(chunk_size),
-                                    None if box is None else C.cast(box, C.c_void_p), _ptr(labels),
-                                    _ptr(core), _ptr(ncl), _ptr(ws), ws.numel(), _stream()))
-        k = _lib.check_count(ncl.item(), "dbscan")
-    return labels, core, k
+    with torch.cuda.device(xyz.device):
+        ws = _workspace(_lib.lib().pch_dbscan_ws_bytes(xyz.shape[0]), xyz.device)
+        return _dbscan_call(xyz, ws, eps, min_samples, chunk_size, aabb, want_core)
 
 
 class DbscanFit:
@@ -370,23 +369,12 @@ class DbscanFit:
     continuation calls raise (PCH_ERR_ARG) instead of reading another run's grid."""
 
     def __init__(self, xyz, eps=8.0, min_samples=80, chunk_size=0, aabb=None):
-        import ctypes as C
-        L = _lib.lib()
         xyz = _need_cuda(xyz, torch.float32, "xyz").reshape(-1, 3)
-        n = xyz.shape[0]
-        dev = xyz.device
-        self.n, self.device = n, dev
-        with torch.cuda.device(dev):
-            self.labels = torch.empty((n,), dtype=torch.int32, device=dev)
-            self.core = torch.empty((n,), dtype=torch.uint8, device=dev)
-            ncl = torch.zeros((1,), dtype=torch.int32, device=dev)
-            self.workspace = torch.empty(int(L.pch_dbscan_ws_bytes(n)) + 256, dtype=torch.uint8, device=dev)
-            box = None if aabb is None else (C.c_float * 6)(*[float(v) for v in aabb])
-            _lib.check(L.pch_dbscan_f32(_ptr(xyz), n, float(eps), int(min_samples), int(chunk_size),
-                                        None if box is None else C.cast(box, C.c_void_p), _ptr(self.labels),
-                                        _ptr(self.core), _ptr(ncl), _ptr(self.workspace), self.workspace.numel(),
-                                        _stream()))
-            self.nclusters = _lib.check_count(ncl.item(), "dbscan")
+        self.n, self.device = xyz.shape[0], xyz.device
+        with torch.cuda.device(self.device):
+            nb = int(_lib.lib().pch_dbscan_ws_bytes(self.n)) + 256
+            ws = self.workspace = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            self.labels, self.core, self.nclusters = _dbscan_call(xyz, ws, eps, min_samples, chunk_size, aabb, True)
 
     def first_core_rows(self):
         """Smallest core row of every cluster (int32 [nclusters], ascending with the cluster id)."""

@@ -108,3 +108,62 @@ def test_largest_chunk_size(cuda, cells):
     chunk = 131072
     X = _cloud(4, chunk, cells, last_rows=60001)
     _check(X, cuda, 50, chunk)
+
+
+# The middle chunk of three takes every route of the two chunk kernels: rows per chunk, cells of the middle chunk, row
+# of that chunk that holds a NaN.  The last case repeats the one before it with chunks of three row batches per thread:
+# db_cellscatter_k stops sweeping behind the first batch, so only db_chunksort_k's own sweep meets the NaN.
+CHUNK_SHAPES = {
+    "few cells": (4096, 300, None),
+    "above the table limit": (4096, LIMIT + 500, None),
+    "one cell": (4096, 1, None),
+    "NaN in the first rows": (4096, 300, 5),
+    "above the limit, NaN in the last 64 rows": (4096, LIMIT + 500, 4096 - 10),
+    "above the limit, NaN in the last 64 rows, swept in batches": (20000, LIMIT + 500, 20000 - 10),
+}
+
+
+@pytest.mark.parametrize("shape", list(CHUNK_SHAPES))
+def test_chunk_shapes_of_the_shared_prologue(cuda, shape):
+    """three chunks, the middle one of the shape under test: labels, core flags and cluster count of the chunk-local
+    route equal the global sort's; a NaN chunk is noise as a whole, and a chunk above the limit went to db_chunksort"""
+    chunk, cells, nan_row = CHUNK_SHAPES[shape]
+    X = _cloud(5, chunk, [200, cells, 600])
+    if nan_row is not None:
+        X[chunk + nan_row, 1] = np.nan
+    ops.set_profiling(True)
+    try:
+        la, ca, ka = _run(X, cuda, 4, chunk, "chunk")
+        ran = {name for name, _, launches in ops.get_profile() if launches > 0}
+    finally:
+        ops.set_profiling(False)
+    lb, cb, kb = _run(X, cuda, 4, chunk, "global")
+    np.testing.assert_array_equal(la, lb)
+    np.testing.assert_array_equal(ca, cb)
+    assert ka == kb and ka > 0
+    assert "db_cellscatter" in ran
+    if cells > LIMIT:
+        assert "db_chunksort" in ran
+    if nan_row is not None:
+        assert (la[chunk:2 * chunk] == -1).all() and not ca[chunk:2 * chunk].any()
+    for c in (0, 2):
+        assert (la[c * chunk:(c + 1) * chunk] >= 0).any() and ca[c * chunk:(c + 1) * chunk].any()
+
+
+@pytest.mark.parametrize("n", [1, 31, 32, 33, 2017, 2048, 2049])
+def test_first_core_rows_and_identity_relabel_at_the_bitmap_boundaries(cuda, n):
+    """n at the word and 64-word boundaries of the row bitmap and of its scanned word counts, which the fit and its
+    continuation calls take from one carving.  Two blobs far apart, the second one in the last word: the first core
+    row of every cluster is read back from the fit's own labels and core flags, and the identity map leaves the
+    labels as they are"""
+    rng = np.random.default_rng(n)
+    nb = min((n - 1) % 32 + 1, n - 1)                     # the second blob starts with the bitmap's last word
+    X = rng.uniform(-0.4, 0.4, (n, 3)) + np.where(np.arange(n)[:, None] >= n - nb, 50.0, 0.0)
+    fit = ops.DbscanFit(torch.from_numpy(X.astype(np.float32)).to(cuda), 2.0, 1, 0)
+    assert fit.nclusters == min(n, 2)
+    labels, core = fit.labels.clone(), fit.core.bool()
+    rows = torch.arange(n, device=cuda)
+    want = [int(rows[core & (labels == k)].min()) for k in range(fit.nclusters)]
+    assert fit.first_core_rows().cpu().tolist() == want
+    ident = torch.arange(fit.nclusters, dtype=torch.int32, device=cuda)
+    assert torch.equal(fit.relabel(ident), labels)

@@ -33,6 +33,16 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert L.pch_mean_seq_f32_ws_bytes(10 ** 8) < 2e8          # summary tables: < 2 B/point
 
 
+def test_dbscan_workspace_bytes_are_what_they_were():
+    """pch_dbscan_ws_bytes at the carving's boundaries, against the figures of the build before DbMeta and the
+    carved views (recorded from that build): the workspace layout did not move"""
+    from pointcloudhookup_amd import _lib
+    L = _lib.lib()
+    was = {0: 10496, 1: 10496, 31: 18944, 32: 18944, 33: 20992, 2047: 794624, 2048: 794624, 2049: 800512,
+           50000: 19294976, 2 ** 20: 247208192, 2 ** 31 - 1: 506274254848}
+    assert {n: L.pch_dbscan_ws_bytes(n) for n in was} == was
+
+
 def test_product_path_fails_loudly_without_gpu_tensors():
     import torch
     from pointcloudhookup_amd import ops
