@@ -1,5 +1,9 @@
 """Parity of every C-ABI operator against the CPU oracle on the same seeded inputs
 (bit-exact for indices, counts, labels and for every float the reference computes)."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -22,37 +26,28 @@ def _dev(a, cuda, dtype=None):
 
 
 # ------------------------------------------------------------------------------ stage A
-@pytest.mark.parametrize("n,voxel,chunk", [(1, 0.1, 0), (5, 0.5, 2), (1000, 0.5, 0), (1000, 0.5, 300),
-                                           (20000, 0.2, 7000), (200000, 0.1, 50000),
-                                           (300000, 0.2, 0)])
-def test_voxel_matches_oracle(cuda, n, voxel, chunk):
+VOXEL_UNIFORM = [(1, 0.1, 0), (5, 0.5, 2), (1000, 0.5, 0), (1000, 0.5, 300), (20000, 0.2, 7000), (200000, 0.1, 50000),
+                 (300000, 0.2, 0)]
+# path case -> seed of its generator (fixed integers: the same bytes in every process)
+VOXEL_PATHS = {"dense_core": 101, "one_voxel_20000": 102, "wide_keys_u64": 103, "huge_keys_general": 104,
+               "ragged_tiles": 105, "tower_like": 106, "all_equal_points": 107, "lds_sort_32bit_keys": 108,
+               "grouped_overflow": 109}
+GOLDEN_ORDER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "voxel_default_order.json")
+
+
+def _uniform_name(n, voxel, chunk):
+    return f"uniform_{n}_{voxel}_{chunk}"
+
+
+def _voxel_uniform_input(n, voxel, chunk):
     rng = np.random.default_rng(n)
     pts = rng.random((n, 3)) * [60.0, 25.0, 8.0] + OFFSET
     pts[: n // 3] = np.round(pts[: n // 3], 1)              # many exact duplicates / shared voxels
-    idx, mean, count, offs = ops.voxel_downsample(_dev(pts, cuda), voxel, chunk)
-    ridx, rmean, rcount, roffs = ovx.voxel_down_sample_chunked(pts, voxel, chunk if chunk else n)
-    assert idx.shape[0] == ridx.shape[0]
-    _voxel_sets_equal(idx, mean, count, offs, ridx, rmean, rcount, roffs)
+    return pts, voxel, chunk
 
 
-def _voxel_sets_equal(idx, mean, count, offs, ridx, rmean, rcount, roffs):
-    """stage-A parity (SURVEY 8c): per chunk the same SET of (voxel index, mean, count) - the library's order
-    inside a chunk is its own (Open3D's is unordered_map order), so both sides are compared sorted by index"""
-    offs = offs.cpu().numpy()
-    np.testing.assert_array_equal(offs, roffs)
-    gi, gm, gc = ovx.canonical(idx.cpu().numpy(), mean.cpu().numpy(), count.cpu().numpy(), offs)
-    np.testing.assert_array_equal(gi, ridx)                          # voxel indices bit exact
-    np.testing.assert_array_equal(gc, rcount)
-    np.testing.assert_array_equal(gm.view(np.uint64), rmean.view(np.uint64))   # in-order f64 sums: bit exact
-
-
-@pytest.mark.parametrize("case", ["dense_core", "one_voxel_20000", "wide_keys_u64", "huge_keys_general",
-                                  "ragged_tiles", "tower_like", "all_equal_points"])
-def test_voxel_paths_match_oracle(cuda, case):
-    """Every path of the voxel finisher: units sorted inside LDS on 32-bit keys, units too large for LDS
-    (LSD passes in global memory), keys too wide for an LDS key (also sorted in global memory), one voxel
-    holding more rows than an LDS tile (in-order sum across tiles), ragged partition tiles."""
-    rng = np.random.default_rng(hash(case) % 2**32)
+def _voxel_path_input(case):
+    rng = np.random.default_rng(VOXEL_PATHS[case])
     if case == "dense_core":              # 60 000 points inside 2 m: level-1 units far above the LDS capacity
         pts, voxel, chunk = rng.normal(0, 0.6, (60000, 3)) + OFFSET, 0.05, 0
     elif case == "one_voxel_20000":       # a single voxel with 20 000 rows + scattered others
@@ -69,11 +64,94 @@ def test_voxel_paths_match_oracle(cuda, case):
         t = rng.normal([25, 50, 22], [2.5, 2.5, 9], (150000, 3))
         pts = np.vstack([g, t])
         pts, voxel, chunk = pts[rng.permutation(len(pts))] + OFFSET, 0.2, 200000
+    elif case == "lds_sort_32bit_keys":   # 120 m x 120 m x 60 m at 1 cm: 14+14+13 = 41 key bits, 9 of them level 1
+        pts, voxel, chunk = rng.random((5000, 3)) * [120.0, 120.0, 60.0] + OFFSET, 0.01, 0
+    elif case == "grouped_overflow":      # 5 900 voxels of one row and one voxel of 100 rows, shuffled
+        voxel, chunk = 0.5, 0
+        cells = rng.choice(200 * 200 * 50, 5901, replace=False)
+        cells = np.column_stack([cells // (200 * 50), (cells // 50) % 200, cells % 50]).astype(np.float64)
+        full = np.repeat(cells[:1], 100, axis=0) + rng.uniform(-0.2, 0.2, (100, 3))
+        pts = (np.vstack([cells[1:], full]) + 0.5) * voxel
+        pts = pts[rng.permutation(len(pts))] + OFFSET
     else:                                 # all_equal_points: zero key bits
         pts, voxel, chunk = np.tile(OFFSET + [1.0, 2.0, 3.0], (9000, 1)), 0.1, 4000
-    idx, mean, count, offs = ops.voxel_downsample(_dev(pts, cuda), voxel, chunk)
-    ridx, rmean, rcount, roffs = ovx.voxel_down_sample_chunked(pts, voxel, chunk if chunk else len(pts))
+    return pts, voxel, chunk
+
+
+VOXEL_CASES = {_uniform_name(*c): (lambda c=c: _voxel_uniform_input(*c)) for c in VOXEL_UNIFORM}
+VOXEL_CASES.update({c: (lambda c=c: _voxel_path_input(c)) for c in VOXEL_PATHS})
+_voxel_runs = {}
+
+
+def _voxel_run(cuda, name):
+    """input and default-order output (numpy) of a named case, computed once per session"""
+    if name not in _voxel_runs:
+        pts, voxel, chunk = VOXEL_CASES[name]()
+        out = ops.voxel_downsample(_dev(pts, cuda), voxel, chunk)
+        _voxel_runs[name] = (pts, voxel, chunk, tuple(o.cpu().numpy() for o in out))
+    return _voxel_runs[name]
+
+
+def _voxel_digests(idx, mean, count, offs):
+    """SHA-256 of the raw bytes of every output array"""
+    return {k: hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest()
+            for k, v in (("idx", idx), ("mean", mean), ("count", count), ("chunk_offsets", offs))}
+
+
+@pytest.mark.parametrize("n,voxel,chunk", VOXEL_UNIFORM)
+def test_voxel_matches_oracle(cuda, n, voxel, chunk):
+    pts, voxel, chunk, (idx, mean, count, offs) = _voxel_run(cuda, _uniform_name(n, voxel, chunk))
+    ridx, rmean, rcount, roffs = ovx.voxel_down_sample_chunked(pts, voxel, chunk if chunk else n)
+    assert idx.shape[0] == ridx.shape[0]
     _voxel_sets_equal(idx, mean, count, offs, ridx, rmean, rcount, roffs)
+
+
+def _voxel_sets_equal(idx, mean, count, offs, ridx, rmean, rcount, roffs):
+    """stage-A parity (SURVEY 8c): per chunk the same SET of (voxel index, mean, count) - the library's order
+    inside a chunk is its own (Open3D's is unordered_map order), so both sides are compared sorted by index"""
+    idx, mean, count, offs = (torch.as_tensor(a).cpu().numpy() for a in (idx, mean, count, offs))
+    np.testing.assert_array_equal(offs, roffs)
+    gi, gm, gc = ovx.canonical(idx, mean, count, offs)
+    np.testing.assert_array_equal(gi, ridx)                          # voxel indices bit exact
+    np.testing.assert_array_equal(gc, rcount)
+    np.testing.assert_array_equal(gm.view(np.uint64), rmean.view(np.uint64))   # in-order f64 sums: bit exact
+
+
+@pytest.mark.parametrize("case", list(VOXEL_PATHS))
+def test_voxel_paths_match_oracle(cuda, case):
+    """Every path of the voxel finisher: units sorted inside LDS on 32-bit keys, units too large for LDS
+    (LSD passes in global memory), keys too wide for an LDS key (also sorted in global memory), one voxel
+    holding more rows than an LDS tile (in-order sum across tiles), ragged partition tiles.
+
+    lds_sort_32bit_keys: the largest indices are about 12 000, 12 000 and 6 000, so the axes take 14 + 14 + 13 = 41
+    key bits; level 1 takes 9 and leaves 32, a batch then spans one level-1 digit and sorts on exactly 32 bits:
+    the LDS sort of a batch whose voxel count is NOT announced before the sort (that needs <= 31 bits).
+
+    grouped_overflow: 200 x 200 x 50 cells take 8 + 8 + 6 = 22 key bits, 13 of them below level 1, so a batch spans
+    up to 256 level-1 digits, sorts on at most 13 + 8 = 21 <= 31 bits, holds at most 4 096 rows (VF_CAP) and is
+    announced.  A level-1 digit holds about 6 000 / 400 = 15 rows, so the greedy grouping fills the batch around the
+    full voxel to nearly 4 096 rows (at least the 2 000 that remain when the first batch took 4 096).  With R rows the
+    batch has R - 99 voxels, and 10 * (R - 99) >= 7 * R from R = 330 on: the 0.7 voxels-per-row rule would keep it
+    grouped.  The 33rd row that arrives on the full voxel's slot trips the 32-row limit, so the batch is sorted in
+    LDS after it has announced."""
+    pts, voxel, chunk, (idx, mean, count, offs) = _voxel_run(cuda, case)
+    ridx, rmean, rcount, roffs = ovx.voxel_down_sample_chunked(pts, voxel, chunk if chunk else len(pts))
+    if case == "lds_sort_32bit_keys":
+        assert [int(m).bit_length() for m in ridx.max(0)] == [14, 14, 13]
+    if case == "grouped_overflow":
+        assert [int(m).bit_length() for m in ridx.max(0)] == [8, 8, 6]
+        assert len(rcount) == 5901 and np.sort(rcount)[-2:].tolist() == [1, 100]
+    _voxel_sets_equal(idx, mean, count, offs, ridx, rmean, rcount, roffs)
+
+
+@pytest.mark.parametrize("name", list(VOXEL_CASES))
+def test_voxel_default_order_is_pinned(cuda, name):
+    """The order of the default output inside a chunk is the library's own, but what follows depends on it (stage B's
+    sequential float32 mean, the 50 000-row chunk split), so it is pinned: the digests of the four output arrays are
+    those of the commit named in the fixture."""
+    with open(GOLDEN_ORDER) as f:
+        want = json.load(f)["cases"][name]
+    assert _voxel_digests(*_voxel_run(cuda, name)[3]) == want
 
 
 def test_voxel_single_voxel_and_negative_coords(cuda):
@@ -857,16 +935,8 @@ def test_percentile_bracketed_select_is_exact(cuda, case, q):
     assert (np.isnan(want) and np.isnan(got)) or got.view(np.uint32) == want.view(np.uint32), (case, q, got, want)
 
 
-def test_voxel_scatter_staged_through_lds_equals_the_direct_form(cuda):
-    """Large inputs take the partition whose tiles are put in digit order inside LDS before they are copied out
-    (vx_scatter_lds_k; chosen by size, PCH_VX_SCATTER=lds forces it).  A child process with the switch set runs ragged
-    tiles, two chunks with a dense column, and a 3 M-row corridor against the oracle (set equality per chunk)."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    script = r'''
-import sys, numpy as np, torch
+STAGED_SCRIPT = r'''
+import hashlib, json, sys, numpy as np, torch
 sys.path.insert(0, sys.argv[1])
 from oracle import voxel as ovx
 from pointcloudhookup_amd import ops, synth
@@ -878,14 +948,32 @@ tower = np.vstack([g, t])
 cases = [(rng.random((50001, 3)) * [50.0, 20.0, 5.0] + OFF, 0.25, 12345),
          (tower[rng.permutation(len(tower))] + OFF, 0.2, 200000),
          (synth.corridor_numpy(3_000_000, seed=synth.SEED0 + 9, kind="corridor", offset=True, towers=6), 0.1, 500000)]
-for pts, voxel, chunk in cases:
-    idx, mean, count, offs = ops.voxel_downsample(torch.from_numpy(np.ascontiguousarray(pts)).cuda(), voxel, chunk)
+for k, (pts, voxel, chunk) in enumerate(cases):
+    out = [o.cpu().numpy() for o in ops.voxel_downsample(torch.from_numpy(np.ascontiguousarray(pts)).cuda(), voxel, chunk)]
+    idx, mean, count, offs = out
     ridx, rmean, rcount, roffs = ovx.voxel_down_sample_chunked(pts, voxel, chunk)
-    assert np.array_equal(offs.cpu().numpy(), roffs)
-    gi, gm, gc = ovx.canonical(idx.cpu().numpy(), mean.cpu().numpy(), count.cpu().numpy(), roffs)
+    assert np.array_equal(offs, roffs)
+    gi, gm, gc = ovx.canonical(idx, mean, count, roffs)
     assert np.array_equal(gi, ridx) and np.array_equal(gc, rcount) and np.array_equal(gm.view(np.uint64), rmean.view(np.uint64))
+    if k < 2:
+        print("digest", json.dumps([hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest() for a in out]))
 print("staged scatter ok", len(cases))
 '''
+
+
+def test_voxel_scatter_staged_through_lds_equals_the_direct_form(cuda):
+    """Large inputs take the partition whose tiles are put in digit order inside LDS before they are copied out
+    (vx_scatter_lds_k; chosen by size, PCH_VX_SCATTER=lds forces it).  A child process with the switch set runs ragged
+    tiles, two chunks with a dense column, and a 3 M-row corridor against the oracle (set equality per chunk)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PCH_VX_SCATTER="lds")
-    r = subprocess.run([sys.executable, "-c", script, root], env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "-c", STAGED_SCRIPT, root], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "staged scatter ok 3" in r.stdout, r.stdout[-500:] + r.stderr[-2000:]
+    # the default order of the first two cases is pinned like that of the in-process cases (test_voxel_default_order_is_pinned)
+    got = [json.loads(ln[len("digest "):]) for ln in r.stdout.splitlines() if ln.startswith("digest ")]
+    with open(GOLDEN_ORDER) as f:
+        want = json.load(f)["cases"]
+    keys = ("idx", "mean", "count", "chunk_offsets")
+    assert [dict(zip(keys, g)) for g in got] == [want["staged_ragged_tiles"], want["staged_tower_like"]]

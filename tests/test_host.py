@@ -43,6 +43,15 @@ def test_dbscan_workspace_bytes_are_what_they_were():
     assert {n: L.pch_dbscan_ws_bytes(n) for n in was} == was
 
 
+def test_voxel_workspace_bytes_are_what_they_were():
+    """pch_voxel_downsample_ws_bytes for three (n, chunk) pairs, against the figures of the build before the finisher
+    was cut into steps (recorded from that build): the workspace layout, VoxelBatch's 24 bytes included, did not move"""
+    from pointcloudhookup_amd import _lib
+    L = _lib.lib()
+    was = {(1000, 100): 299776, (50001, 12345): 2755584, (100_000_000, 500_000): 5254903552}
+    assert {k: L.pch_voxel_downsample_ws_bytes(*k) for k in was} == was
+
+
 def test_product_path_fails_loudly_without_gpu_tensors():
     import torch
     from pointcloudhookup_amd import ops
