@@ -298,6 +298,33 @@ int pch_dbscan_pair_stats(int64_t n, uint64_t* out4_host, void* ws, size_t ws_by
 int pch_dbscan_strip_pairs_i32(int64_t n, float x_lo, float x_hi, int32_t cap, int32_t* out_pairs,
                                int32_t* out_count, void* ws, size_t ws_bytes, void* stream);
 
+/* Assigns points that were NOT part of the fit to the clusters of that same last fit: "which rows of my original
+ * cloud belong to tower k?" - a second flight line, the rows the height filter removed (tower feet), the cloud before
+ * it was thinned.  The rule is the one the fit applies to its own non-core rows:
+ *   q = fl32(query[i] - sub3) per component (a float32 subtraction, the arithmetic of raw - centroid; sub3_host ==
+ *       NULL: no subtraction);
+ *   out_labels[i] = the smallest label among the fit's core points p within eps of q under the library's predicate
+ *       (float64 sum_j((double)q_j - (double)p_j)^2 <= eps*eps behind the float32 guard-band pre-filter), -1 if no
+ *       core point is in reach; a query holding NaN or +-inf gets -1.
+ * Applied to the fit's own rows it reproduces the fit's labels, core rows included (core points within eps of each
+ * other share a cluster).
+ * query [nq,3] float32, out_labels [nq] int32 (device); sub3_host 3 floats on the host or NULL.
+ * query_chunk [nq] int32 (device): the chunk whose fit query i is held against (one fit per chunk, as sklearn is
+ *       called); an index outside [0, nchunks) or a chunk that held NaN/inf gives -1 for that query.  NULL is allowed
+ *       only for a single-chunk fit (else PCH_ERR_ARG).
+ * n, ws, ws_bytes name the fit (same workspace rule as the relabel call: PCH_ERR_ARG, "untouched workspace").  The
+ * fit's workspace and labels are only read, so the call may be repeated, before or after pch_dbscan_relabel_i32; after
+ * a relabel it reports the new ids, and a cell whose cluster was dropped attracts nothing.
+ * qws: a query workspace of its own, >= pch_dbscan_assign_ws_bytes(nq) bytes (smaller: PCH_ERR_WORKSPACE); it must
+ * not overlap ws (PCH_ERR_ARG - the fit stays remembered).  nq == 0 is success, nq >= 2^31 PCH_ERR_ARG.
+ * A fit that took the compressed-coordinate path (grid beyond the 64-bit cell key) keeps no map from a coordinate to
+ * a cell: PCH_ERR_RANGE.  Per-chunk refits and all-noise early returns leave no grid: PCH_ERR_ARG, as for the other
+ * continuation calls.  Enqueues its work and returns; no host reads. */
+size_t pch_dbscan_assign_ws_bytes(int64_t nq);
+int pch_dbscan_assign_f32(const float* query, int64_t nq, const float* sub3_host, const int32_t* query_chunk,
+                          int64_t n, int32_t* out_labels, void* qws, size_t qws_bytes,
+                          void* ws, size_t ws_bytes, void* stream);
+
 /* One representative per LATTICE cell of up to two strips of a tile: the smallest row among the core points of the
  * cell whose x lies in the strip.  The lattice is shared by all ranks (cell = floor(coordinate / side) per axis, side =
  * eps / sqrt(3) * (1 - 2^-16), anchored at the origin of the common frame), so the two tiles on either side of an edge

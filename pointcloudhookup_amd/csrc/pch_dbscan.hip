@@ -1895,6 +1895,192 @@ __global__ __launch_bounds__(DB_THREADS) void db_border_k(DbGrid g, const float4
     }
 }
 
+// ---- points that were NOT part of the fit, held against it (pch_dbscan_assign_f32): db_border_k's rule - smallest
+// cluster id among the fit's core points within eps, else -1 - for query points the caller brings.  The queries are
+// binned into the fit's own cells, sorted by cell and cut into pieces; one wave per piece walks the 5x5x5 block around
+// the piece's cell exactly as db_border_k walks it around a cell of the fit.
+struct DbQuery {
+    const float* xyz; int64_t nq;    // [nq][3] query rows
+    float sx, sy, sz;                // q = fl32(row - s) per component (0: x - 0.0f is x, bit for bit, -0.0 and NaN too)
+    const int32_t* chunk;            // [nq] chunk whose fit a query is held against; null: chunk 0
+    int64_t nchunks;
+};
+constexpr uint32_t DQ_OUT   = 0x80000000u;   // in a query's value word (nq < 2^31): the answer is -1 whatever its cell holds
+#ifndef PCH_DQ_PIECE
+#define PCH_DQ_PIECE 64                      // tuning builds: make EXTRA=-DPCH_DQ_PIECE=256 (DESIGN.md section 5 has the figures)
+#endif
+constexpr int      DQ_PIECE = PCH_DQ_PIECE;  // queries a wave takes at most: one crowded cell does not serialise the launch
+
+__device__ __forceinline__ float4 dq_point(const DbQuery& Q, int64_t i) {
+    float4 q;
+    q.x = Q.xyz[3 * i + 0] - Q.sx; q.y = Q.xyz[3 * i + 1] - Q.sy; q.z = Q.xyz[3 * i + 2] - Q.sz; q.w = 0.0f;
+    return q;
+}
+
+// Query keys: [chunk | cz | cy | cx] in the fit's bit widths, the cell by db_cell_coords' expression.  Every point of
+// the fit lies in a cell of [0, m] per axis, and a point within eps of the query lies at most two cells from the
+// query's cell t (eps < 2 cell sides).  So a query with t < -2 or t > m + 2 on some axis has nobody in reach: -1 at
+// once.  Any other t is clamped to c = min(max(t, 0), m), and that is exact: a valid cell v with |v - t| <= 2 has
+// |v - c| <= 2 as well (c lies between t and v, or is t), so the block around c holds every cell the block around t
+// would have offered, and the distance test decides as before.  The comparison and the clamp run in double: a
+// coordinate of 1e30 has no integer cell.  NaN fails every comparison, inf the upper one.
+__global__ __launch_bounds__(DB_THREADS) void dq_keys_k(DbQuery Q, DbGrid g, uint64_t* __restrict__ keys,
+                                                        uint32_t* __restrict__ vals) {
+    const int64_t i = (int64_t)blockIdx.x * DB_THREADS + threadIdx.x;
+    if (i >= Q.nq) return;
+    const float4 q = dq_point(Q, i);
+    const int64_t c = Q.chunk ? (int64_t)Q.chunk[i] : 0;
+    bool ok = c >= 0 && c < Q.nchunks;
+    if (ok) ok = g.chunk_bad[c] == 0u;                     // a NaN/inf chunk has no fit
+    const double fx = floor(((double)q.x - (double)g.ox) * g.inv_cell);
+    const double fy = floor(((double)q.y - (double)g.oy) * g.inv_cell);
+    const double fz = floor(((double)q.z - (double)g.oz) * g.inv_cell);
+    const double mx = (double)g.mx, my = (double)g.my, mz = (double)g.mz;
+    ok = ok && fx >= -2.0 && fx <= mx + 2.0 && fy >= -2.0 && fy <= my + 2.0 && fz >= -2.0 && fz <= mz + 2.0;
+    uint64_t key = 0;
+    if (ok)
+        key = db_pack(g, (uint64_t)c, (uint64_t)fmin(fmax(fz, 0.0), mz), (uint64_t)fmin(fmax(fy, 0.0), my),
+                      (uint64_t)fmin(fmax(fx, 0.0), mx));
+    keys[i] = key;
+    vals[i] = (uint32_t)i | (ok ? 0u : DQ_OUT);
+}
+
+// Pieces of the sorted queries: a piece starts where the key changes and at every multiple of DQ_PIECE, so it lies
+// inside one cell and holds at most DQ_PIECE queries (64: one query per lane; measured against 256 and 1024).  dq_heads_k writes the start flags (scanned in place),
+// dq_pieces_k the first query of every piece and, behind the last one, nq.
+__device__ __forceinline__ bool dq_head(const uint64_t* __restrict__ keys, int64_t i) {
+    return i % DQ_PIECE == 0 || keys[i] != keys[i - 1];
+}
+__global__ __launch_bounds__(DB_THREADS) void dq_heads_k(const uint64_t* __restrict__ keys, int64_t nq,
+                                                         uint32_t* __restrict__ flag) {
+    const int64_t i = (int64_t)blockIdx.x * DB_THREADS + threadIdx.x;
+    if (i < nq) flag[i] = dq_head(keys, i) ? 1u : 0u;
+}
+__global__ __launch_bounds__(DB_THREADS) void dq_pieces_k(const uint64_t* __restrict__ keys, int64_t nq,
+                                                          const uint32_t* __restrict__ excl,
+                                                          uint32_t* __restrict__ piece_start) {
+    const int64_t i = (int64_t)blockIdx.x * DB_THREADS + threadIdx.x;
+    if (i >= nq) return;
+    const bool h = dq_head(keys, i);
+    if (h) piece_start[excl[i]] = (uint32_t)i;
+    if (i == nq - 1) piece_start[excl[i] + (h ? 1u : 0u)] = (uint32_t)nq;
+}
+
+// One wave per piece (the grid is sized on the host from nq alone, so the waves stride over the piece count the
+// device holds).  Rows of the piece's cell with db_row_run - not the row table: the query's cell need not exist in the
+// fit -, the core cells of those rows one per lane as in db_border_k, then query after query: smallest label first,
+// reject by core box, db_within2 over the cell's core rows, the first hit decides.  The queries are loaded 64 at a time,
+// one per lane, and handed round; every lane stores the answer of its own query.
+__global__ __launch_bounds__(DB_THREADS) void dq_assign_k(DbQuery Q, DbGrid g, const float4* __restrict__ pts,
+                                                          const uint32_t* __restrict__ cell_start,
+                                                          const uint64_t* __restrict__ cell_key,
+                                                          const uint8_t* __restrict__ core_s,
+                                                          const uint32_t* __restrict__ cell_ncore,
+                                                          const float* __restrict__ cell_box,
+                                                          const int* __restrict__ cell_label,
+                                                          const uint64_t* __restrict__ keys,
+                                                          const uint32_t* __restrict__ vals,
+                                                          const uint32_t* __restrict__ piece_start,
+                                                          const uint32_t* __restrict__ npieces,
+                                                          int32_t* __restrict__ out) {
+    __shared__ RowSet rows[DB_WAVES];
+    const int l = lane_id();
+    RowSet* rs = &rows[wave_id()];
+    const uint32_t np = *npieces;
+    for (uint32_t p = blockIdx.x * DB_WAVES + wave_id(); p < np; p += gridDim.x * DB_WAVES) {   // wave-uniform
+        const uint32_t ps = piece_start[p], pe = piece_start[p + 1];
+        const uint64_t key = keys[ps];
+        __builtin_amdgcn_wave_barrier();                   // the piece before this one has read its rows
+        if (l < DB_ROWS) {
+            const int2 v = db_row_run(g, cell_key, key, l);
+            rs->ca[l] = v.x;
+            rs->cb[l] = v.y;
+        }
+        __builtin_amdgcn_wave_barrier();
+        int any = 0;
+        if (l < DB_ROWS)
+            for (int B = rs->ca[l]; B < rs->cb[l]; ++B) any |= (cell_ncore[B] != 0);
+        const bool none = !__ballot(any != 0);             // no core cell in reach: the whole piece is -1
+        constexpr int BR = 3, BROWS = 12;                  // db_border_k's gather: 12 rows x 5 cells per round
+        int Bc[BR], Bl[BR];
+        bool Bd[BR];
+        float Bx[BR][6];
+#pragma unroll
+        for (int rd = 0; rd < BR; ++rd) {
+            const int row = rd * BROWS + l / 5, k = l % 5;
+            Bc[rd] = -1; Bl[rd] = INT_BIG; Bd[rd] = false;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) Bx[rd][a] = 0.0f;
+            if (!none && l < 5 * BROWS && row < DB_ROWS) {
+                const int B = rs->ca[row] + k;
+                if (B < rs->cb[row]) {
+                    const uint32_t nb = cell_ncore[B];
+                    if (nb != 0) {
+                        Bc[rd] = B;
+                        Bl[rd] = cell_label[B];
+                        Bd[rd] = nb == cell_start[B + 1] - cell_start[B];
+#pragma unroll
+                        for (int a = 0; a < 6; ++a) Bx[rd][a] = cell_box[6 * (int64_t)B + a];
+                    }
+                }
+            }
+        }
+        for (uint32_t q0 = ps; q0 < pe; q0 += 64) {
+            const bool have = q0 + l < pe;
+            const uint32_t v = have ? vals[q0 + l] : DQ_OUT;
+            float4 mine;
+            mine.x = mine.y = mine.z = mine.w = 0.0f;
+            if (have && !none && !(v & DQ_OUT)) mine = dq_point(Q, (int64_t)v);
+            int res = -1;
+            const int cnt = (int)(pe - q0 < 64u ? pe - q0 : 64u);
+            for (int j = 0; j < cnt && !none; ++j) {
+                if ((uint32_t)__builtin_amdgcn_readlane((int)v, j) & DQ_OUT) continue;          // wave-uniform
+                float4 qp;
+                qp.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.x), j));
+                qp.y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.y), j));
+                qp.z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.z), j));
+                qp.w = 0.0f;
+                bool cand[BR];
+#pragma unroll
+                for (int rd = 0; rd < BR; ++rd) cand[rd] = Bc[rd] >= 0 && !(db_box_d2(qp, Bx[rd]) > g.eps2);
+                int best = INT_BIG;
+                for (;;) {                                  // every turn ends the loop or strikes one candidate cell
+                    int lab = INT_BIG, sel = -1;
+#pragma unroll
+                    for (int rd = 0; rd < BR; ++rd)
+                        if (cand[rd] && Bl[rd] < lab) { lab = Bl[rd]; sel = rd; }
+                    const int lo = wave_reduce_min(lab);
+                    if (lo == INT_BIG) break;               // a cell whose cluster was dropped attracts nothing
+                    const int owner = (int)__builtin_ctzll(__ballot(lab == lo));
+                    int Bsel = -1;
+                    bool dsel = false;
+#pragma unroll
+                    for (int rd = 0; rd < BR; ++rd)
+                        if (sel == rd) { Bsel = Bc[rd]; dsel = Bd[rd]; }
+                    const int B = __builtin_amdgcn_readlane(Bsel, owner);
+                    const bool b_dense = __builtin_amdgcn_readlane((int)dsel, owner) != 0;
+                    const uint32_t bs = cell_start[B], be = cell_start[B + 1];
+                    bool found = false;
+                    for (uint32_t j0 = bs; j0 < be; j0 += 64) {
+                        const uint32_t jj = j0 + l;
+                        bool hit = false;
+                        if (jj < be && (b_dense || core_s[jj])) hit = db_within2(qp, pts[jj], g);
+                        if (__ballot(hit)) { found = true; break; }
+                    }
+                    if (found) { best = lo; break; }
+                    if (l == owner) {
+#pragma unroll
+                        for (int rd = 0; rd < BR; ++rd)
+                            if (sel == rd) cand[rd] = false;
+                    }
+                }
+                if (l == j && best != INT_BIG) res = best;
+            }
+            if (have) out[v & ~DQ_OUT] = res;
+        }
+    }
+}
+
 // ---- relabelling with an external cluster map (cross-tile reconciliation, tiles.py): core points and
 // cells take map[old id], every other point goes back to -1 and is assigned again by db_border_k, so
 // that a border point takes the smallest NEW id among its core neighbours
@@ -2105,8 +2291,9 @@ static DbTuning db_tuning() {
 }
 
 // the run whose workspace the entries below continue, and its cell table
-struct DbLastRun { void* ws; size_t ws_bytes; int64_t n; DbCells c; };
-static thread_local DbLastRun g_last = {nullptr, 0, 0, {}};
+// (nchunks and compressed: what pch_dbscan_assign_f32 needs to know about the grid beyond the cell table)
+struct DbLastRun { void* ws; size_t ws_bytes; int64_t n; DbCells c; int64_t nchunks; bool compressed; };
+static thread_local DbLastRun g_last = {nullptr, 0, 0, {}, 0, false};
 
 void ws_touched(const void* base, size_t bytes) {
     if (!g_last.ws) return;
@@ -2490,7 +2677,7 @@ int pch::dbscan_run(const float* xyz, int64_t n, double eps, int32_t min_samples
     PCH_TRY(db_cells_core(r, g, cellbits, ks, tune.count_pairs, c));
     PCH_TRY(db_union(r, c));
     PCH_TRY(db_labels(r, c, tune, k_host, boxes));
-    g_last = {ws, ws_bytes, n, c};
+    g_last = {ws, ws_bytes, n, c, r.nchunks, overflow};
     return PCH_OK;
 }
 
@@ -2552,6 +2739,76 @@ extern "C" int pch_dbscan_relabel_i32(const int32_t* map, int32_t nmap, int64_t 
                w.cell_label, w.cell_ncore, c.m, map, nmap);
     PCH_LAUNCH("db_border", db_border_k, dim3((unsigned)ceil_div(c.m, DB_WAVES)), dim3(DB_THREADS), 0, s,
                DB_CELL_ARGS(c), w.cell_label, labels, nullptr, 0);
+    return PCH_OK;
+}
+
+// the query workspace of pch_dbscan_assign_f32
+struct DqWs { uint64_t *k0, *k1; uint32_t *v0, *v1, *flag, *piece_start, *radix_ws, *scan_ws, *npieces; };
+static void dq_plan(Arena& a, int64_t nq, DqWs& w) {
+    const int64_t nn = nq > 0 ? nq : 1;
+    w.npieces = a.take<uint32_t>(64);
+    w.k0 = a.take<uint64_t>(nn);
+    w.k1 = a.take<uint64_t>(nn);
+    w.v0 = a.take<uint32_t>(nn);
+    w.v1 = a.take<uint32_t>(nn);
+    w.flag = a.take<uint32_t>(nn + 8);            // start flags of the pieces, scanned in place
+    w.piece_start = a.take<uint32_t>(nn + 8);     // one more entry than pieces
+    w.radix_ws = a.take<uint32_t>(radix_ws_u32(nn));
+    w.scan_ws = a.take<uint32_t>(scan_ws_u32(nn));
+}
+
+extern "C" size_t pch_dbscan_assign_ws_bytes(int64_t nq) {
+    if (nq < 0) return 0;
+    Arena a;
+    DqWs w;
+    dq_plan(a, nq, w);
+    return a.off;
+}
+
+extern "C" int pch_dbscan_assign_f32(const float* query, int64_t nq, const float* sub3_host, const int32_t* query_chunk,
+                                     int64_t n, int32_t* out_labels, void* qws, size_t qws_bytes, void* ws,
+                                     size_t ws_bytes, void* stream) {
+    PCH_DEVICE_GUARD(out_labels ? (const void*)out_labels : (const void*)ws);
+    hipStream_t s = (hipStream_t)stream;
+    PCH_REQUIRE(nq >= 0 && nq < (int64_t(1) << 31), "nq out of range [0, 2^31)");
+    PCH_REQUIRE(n >= 0, "bad argument");
+    if (nq == 0) return PCH_OK;
+    DbWs w;
+    PCH_TRY(db_continue(__func__, n, ws, ws_bytes, w));
+    PCH_REQUIRE(query && out_labels && qws, "null buffer");
+    if (g_last.compressed) {
+        set_error("%s: the fit took the compressed-coordinate path, which keeps no map from a coordinate to a cell",
+                  __func__);
+        return PCH_ERR_RANGE;
+    }
+    PCH_REQUIRE(query_chunk || g_last.nchunks == 1, "query_chunk is null but the fit has several chunks");
+    {
+        const char* a0 = static_cast<const char*>(qws);
+        const char* b0 = static_cast<const char*>(ws);
+        PCH_REQUIRE(!(a0 < b0 + ws_bytes && b0 < a0 + qws_bytes), "the query workspace overlaps the fit's workspace");
+    }
+    Arena qa(qws, qws_bytes);                     // (disjoint from the fit's workspace: the fit stays remembered)
+    DqWs qw;
+    dq_plan(qa, nq, qw);
+    if (qa.overflow) { set_error("query workspace too small: need %zu bytes", qa.off); return PCH_ERR_WORKSPACE; }
+    const DbCells& c = g_last.c;
+    const DbQuery Q = {query, nq, sub3_host ? sub3_host[0] : 0.0f, sub3_host ? sub3_host[1] : 0.0f,
+                       sub3_host ? sub3_host[2] : 0.0f, query_chunk, g_last.nchunks};
+    const unsigned gq = (unsigned)ceil_div(nq, DB_THREADS);
+    const int nbits = c.g.bx + c.g.by + c.g.bz + bits_for((uint64_t)g_last.nchunks);     // <= 64: not compressed
+    PCH_LAUNCH("dq_keys", dq_keys_k, dim3(gq), dim3(DB_THREADS), 0, s, Q, c.g, qw.k0, qw.v0);
+    PCH_TRY(radix_sort_pairs(qw.k0, qw.v0, qw.k1, qw.v1, nq, nbits, qw.radix_ws, s));
+    const bool in1 = radix_sort_result_buffer(nbits) == 1;
+    const uint64_t* ks = in1 ? qw.k1 : qw.k0;
+    const uint32_t* vs = in1 ? qw.v1 : qw.v0;
+    PCH_LAUNCH("dq_heads", dq_heads_k, dim3(gq), dim3(DB_THREADS), 0, s, ks, nq, qw.flag);
+    PCH_TRY(scan_exclusive_u32(qw.flag, qw.flag, nq, qw.scan_ws, qw.npieces, s));
+    PCH_LAUNCH("dq_pieces", dq_pieces_k, dim3(gq), dim3(DB_THREADS), 0, s, ks, nq, qw.flag, qw.piece_start);
+    // pieces <= cells with queries + nq / DQ_PIECE; the host does not read the count: the waves stride over it
+    const unsigned ga = (unsigned)std::min(ceil_div(nq, (int64_t)DB_WAVES * 8), int64_t(16384));
+    PCH_LAUNCH("dq_assign", dq_assign_k, dim3(ga), dim3(DB_THREADS), 0, s, Q, c.g, c.pts, c.cell_start, c.cell_key,
+               c.core_s, c.cell_ncore, c.cell_box, (const int*)w.cell_label, ks, vs, qw.piece_start, qw.npieces,
+               out_labels);
     return PCH_OK;
 }
 

@@ -371,6 +371,7 @@ class DbscanFit:
     def __init__(self, xyz, eps=8.0, min_samples=80, chunk_size=0, aabb=None):
         xyz = _need_cuda(xyz, torch.float32, "xyz").reshape(-1, 3)
         self.n, self.device = xyz.shape[0], xyz.device
+        self.chunk_size = int(chunk_size) if 0 < int(chunk_size) < self.n else 0      # 0: one fit over all rows
         with torch.cuda.device(self.device):
             nb = int(_lib.lib().pch_dbscan_ws_bytes(self.n)) + 256
             ws = self.workspace = torch.empty(nb, dtype=torch.uint8, device=self.device)
@@ -419,6 +420,35 @@ class DbscanFit:
             _lib.check(L.pch_dbscan_relabel_i32(_ptr(cmap), cmap.numel(), self.n, _ptr(self.labels),
                                                 _ptr(self.workspace), self.workspace.numel(), _stream()))
         return self.labels
+
+    def assign(self, query, sub=None, chunk=None):
+        """Labels (int32 [nq], device) of float32 [nq,3] points that were not part of the fit: the smallest cluster
+        id among the fit's core points within eps of ``fl32(query - sub)``, else -1 - the rule the fit applies to its
+        own non-core rows (pch_dbscan_assign_f32).  ``sub``: three floats subtracted in float32, e.g. the centroid
+        the fitted rows were centred with.  ``chunk``: int32 [nq] device tensor naming the chunk whose fit each query
+        is held against; required when the fit has several chunks (``chunk_size``).  Reads the fit only: call it as
+        often as needed, before or after ``relabel`` (then it reports the new ids).  Asynchronous."""
+        import ctypes as C
+        import numpy as np
+        query = _need_cuda(query, torch.float32, "query").reshape(-1, 3)
+        if chunk is not None:
+            chunk = _need_cuda(chunk, torch.int32, "chunk").reshape(-1)
+            if chunk.numel() != query.shape[0]:
+                raise ValueError("chunk must name one chunk per query row")
+        nq = query.shape[0]
+        with torch.cuda.device(self.device):
+            if self.nclusters == 0:                   # nothing to join, and an all-noise fit may have left no grid
+                return torch.full((nq,), -1, dtype=torch.int32, device=self.device)
+            out = torch.empty((nq,), dtype=torch.int32, device=self.device)
+            if nq == 0:
+                return out
+            L = _lib.lib()
+            s3 = None if sub is None else (C.c_float * 3)(*[float(np.float32(v)) for v in sub])
+            qws = torch.empty(int(L.pch_dbscan_assign_ws_bytes(nq)) + 256, dtype=torch.uint8, device=self.device)
+            _lib.check(L.pch_dbscan_assign_f32(_ptr(query), nq, None if s3 is None else C.cast(s3, C.c_void_p),
+                                               _ptr(chunk), self.n, _ptr(out), _ptr(qws), qws.numel(),
+                                               _ptr(self.workspace), self.workspace.numel(), _stream()))
+        return out
 
 
 def set_pair_counting(enable):

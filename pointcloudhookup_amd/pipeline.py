@@ -32,6 +32,44 @@ def cluster_points(raw, eps=8.0, min_points=80, chunk_size=REF_CHUNK, pct=25.0, 
     return out
 
 
+def label_full_cloud(sampled_raw, full_raw, eps=8.0, min_points=80, chunk_size=0, pct=25.0, offset=3.0,
+                     fallback_offset=1.0, min_keep=1000, segment=False):
+    """Which rows of ``full_raw`` belong to which tower of ``sampled_raw``: stage B (``ops.ground_filter``) on the
+    sampled cloud, one ``ops.DbscanFit`` on the rows it kept, then ``fit.assign(full_raw, sub=centroid)`` - every row
+    of the full cloud takes the smallest cluster id among the fit's core points within eps, else -1.
+
+    Both clouds are float32 [N,3] device tensors in the same (uncentred) frame.  ``full_raw`` may be the cloud before
+    it was thinned, a second flight line, or ``sampled_raw`` itself.  Rows BELOW the height threshold may be labelled,
+    and that is intended: a tower's feet lie within eps of its core points although the filter removed them.
+
+    ``chunk_size`` > 0 fits the kept rows in file-order chunks as the reference does (one fit per chunk); a row of
+    the full cloud can then be held against a chunk only through its own place in that file order, so this needs
+    ``full_raw is sampled_raw`` (a kept row meets the chunk it was fitted in, a dropped row the chunk of the next kept
+    row) and raises ValueError otherwise.
+
+    Returns dict: ground (ops.ground_filter result), labels int32 [N_f] of the kept rows, nclusters, cloud_labels int32
+    [N_full]; with ``segment`` also perm / offsets of ``ops.segment_by_label`` over cloud_labels."""
+    if int(chunk_size) > 0 and full_raw is not sampled_raw:
+        raise ValueError("chunk_size > 0 fits the kept rows chunk by chunk in file order; rows of another cloud have no "
+                         "place in that order - pass full_raw is sampled_raw, or chunk_size=0 for one global fit")
+    gf = ops.ground_filter(sampled_raw, pct, offset, fallback_offset, min_keep, want_index=True)
+    fit = ops.DbscanFit(gf["points"], eps, min_points, int(chunk_size), aabb=gf["aabb"] if gf["count"] else None)
+    chunk = None
+    if fit.chunk_size:
+        n = full_raw.reshape(-1, 3).shape[0]
+        kept = torch.zeros((n,), dtype=torch.int64, device=full_raw.device)
+        kept[gf["index"].long()] = 1
+        before = torch.cumsum(kept, 0) - kept                  # kept rows in front of every row
+        last = (fit.n + fit.chunk_size - 1) // fit.chunk_size - 1
+        chunk = torch.clamp(before // fit.chunk_size, max=last).to(torch.int32)
+    cloud_labels = fit.assign(full_raw, sub=gf["centroid"], chunk=chunk)
+    out = dict(ground=gf, labels=fit.labels, nclusters=fit.nclusters, cloud_labels=cloud_labels)
+    if segment:
+        perm, offsets, _ = ops.segment_by_label(cloud_labels, full_raw, fit.nclusters)
+        out.update(perm=perm, offsets=offsets)
+    return out
+
+
 def north_angle_deg(rotation):
     """utils/tower_extraction.py:165-177."""
     hx, hy = float(rotation[0, 0]), float(rotation[1, 0])
