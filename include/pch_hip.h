@@ -45,7 +45,7 @@ extern "C" {
 #define PCH_ERR_TIMEOUT     -6   /* a device-side wait between workgroups ran out of its budget (see below) */
 
 /* Device-side waits are bounded.  The order-preserving compactions (pch_ground_filter_f32, pch_filter_gt_f32,
- * pch_crop_aabb_f64) and the voxel finisher (pch_voxel_downsample_f64) chain their workgroups by a single-pass
+ * pch_crop_aabb_f64, pch_crop_boxes_f64) and the voxel finisher (pch_voxel_downsample_f64) chain their workgroups by a single-pass
  * look-back: a workgroup polls the status words of the workgroups in front of it.  Every such poll loop has a
  * wall-clock budget (4 s); a workgroup that exceeds it gives up, the kernel drains, and the call's count word
  * (*out_count / *out_m, device memory) reads NEGATIVE instead of holding a count - the outputs are then
@@ -412,6 +412,57 @@ size_t pch_crop_aabb_ws_bytes(int64_t n);
 int pch_crop_aabb_f64(const double* xyz, int64_t n, const double* min3_host, const double* max3_host,
                       double* out_points, int64_t* out_index, int64_t* out_count,
                       void* ws, size_t ws_bytes, void* stream);
+
+/* Crop by MANY boxes in one sweep of the cloud, axis-aligned and oriented ones mixed: the points of every tower box of
+ * a tile at once, instead of one pch_crop_aabb_f64 call (one sweep, one [n,3] buffer, one host read) per tower.
+ * Replaces: the per-tower mask + gather of test/kuangxuan.py:60-79, and the same over the scaled oriented boxes of
+ * ui/extract.py:345-420 (the tower dict's center / rotation / extent, which the non-default wire frame draws).
+ *
+ * kind 0  the predicate of pch_crop_aabb_f64: six inclusive comparisons of the raw float64 coordinates with lo / hi.  A
+ *         row or a bound holding NaN fails them; lo > hi is an empty box, not an error.
+ * kind 1  float64, no contraction, in exactly this order: d = p - center per component;
+ *         u_k = (d_x*R[0][k] + d_y*R[1][k]) + d_z*R[2][k] with R = axes, row-major, whose COLUMNS are the box axes;
+ *         inside iff -half_k <= u_k <= half_k for k = 0, 1, 2.  A NaN anywhere gives not inside.  We believe this is
+ *         what Open3D's OrientedBoundingBox::GetPointIndicesWithinBoundingBox computes; Open3D was not at hand when
+ *         this was written, so parity is with this formula, not with Open3D.
+ * Output, grouped by box, boxes ascending, inside a box rows ascending (the order of points[mask]); a row inside
+ * several boxes appears once in each:
+ *   out_offsets [nboxes+1] int64 (device): box t owns [offsets[t], offsets[t+1]) of out_points / out_index
+ *   out_points  [cap,3] float64, out_index [cap] int64 (may be NULL): the rows and their source rows
+ *   out_count   [1] int64: the total number of hits
+ * cap is a capacity, not a promise: if there are more hits than cap, *out_count still holds the true total and
+ * out_offsets the complete, true table, nothing is written at or beyond cap, and what lies below cap is undefined -
+ * call again with cap >= *out_count (pch_strip_lattice_reps_f32 works the same way; ops.crop_boxes retries once).
+ * Limits: n < 2^32; nboxes <= 4096 - more, or a kind other than 0 and 1: PCH_ERR_ARG; n == 0 or nboxes == 0: success,
+ * offsets and count zeroed.  The hits must number fewer than 2^31: cap >= 2^31 gives PCH_ERR_RANGE at once; the
+ * call reads nothing back, so a total of 2^31 or more shows in *out_count only (offsets and count are kept in 64
+ * bits and stay true), and whoever reads the count reports PCH_ERR_RANGE (ops.crop_boxes does).  A workspace
+ * below the ws_bytes function's figure for the same (n, nboxes, cap): PCH_ERR_WORKSPACE.  Enqueues and returns: no host
+ * read.  boxes_host has been copied when the call returns.  A bounded wait that ran out (above, PCH_ERR_TIMEOUT)
+ * leaves *out_count negative, as pch_crop_aabb_f64 does.
+ *
+ * The sweep takes the cloud in tiles of 2048 rows and tests a tile only against the boxes whose cull bounds meet the
+ * bounding box of the tile's finite rows.  pch_crop_box_bounds_f64 - a HOST function, no device work, all pointers
+ * host pointers - returns those bounds, [nboxes,6] = lo xyz, hi xyz: for kind 0 the box itself; for kind 1
+ * center_j -+ (sum_k |R[j][k]|*|half_k| + 8e-6*max|half|)*(1 + 1e-9), two floats further out (the margin is derived in
+ * pch_crop.hip: every row the predicate accepts lies inside, for an R orthonormal to 1e-6), and -inf / +inf for an R
+ * further from orthonormal or a box with NaN / inf fields.  A box whose bounds are not all finite is never skipped,
+ * so the cull never changes the result.  A file-order LAS cloud is spatially coherent and most tiles meet no or few
+ * boxes; a shuffled cloud tests every box for every tile. */
+typedef struct PchCropBox {
+    int32_t kind;        /* 0 = axis-aligned, 1 = oriented */
+    int32_t reserved;
+    double  lo[3], hi[3];   /* kind 0: inclusive bounds on the raw coordinates; kind 1: unused */
+    double  center[3];      /* kind 1 */
+    double  axes[9];        /* kind 1: row-major 3x3 R, COLUMNS are the box axes (the tower dict's 'rotation') */
+    double  half[3];        /* kind 1: half extents */
+} PchCropBox;
+size_t pch_crop_boxes_ws_bytes(int64_t n, int32_t nboxes, int64_t cap);
+int pch_crop_boxes_f64(const double* xyz, int64_t n, const PchCropBox* boxes_host, int32_t nboxes, int64_t cap,
+                       double* out_points, int64_t* out_index, int64_t* out_offsets, int64_t* out_count,
+                       void* ws, size_t ws_bytes, void* stream);
+int pch_crop_box_bounds_f64(const PchCropBox* boxes_host, int32_t nboxes, double* out_lo3_hi3);
+
 /* Self-test of the bounded wait: launches eight look-back tiles of which the second never publishes and returns
  * PCH_ERR_TIMEOUT when the six tiles behind it gave up within budget_ms (1..2000) as designed AND the count word they
  * marked (sign bit, as the data-path kernels mark theirs) reads negative; PCH_ERR_HIP when not.  dev_scratch: >= 256 bytes of device memory.  Synchronises.  Not part of the data path (tests only). */

@@ -71,6 +71,9 @@ _SIGS = {
     "pch_segment_by_label": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pch_crop_aabb_ws_bytes": (_sz, [_i64]),
     "pch_crop_aabb_f64": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pch_crop_boxes_ws_bytes": (_sz, [_i64, _i32, _i64]),
+    "pch_crop_boxes_f64": (C.c_int, [_vp, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pch_crop_box_bounds_f64": (C.c_int, [_vp, _i32, _vp]),
     "pch_decimate_f64": (C.c_int, [_vp, _i64, _i64, C.c_uint64, _vp, _vp, _vp]),
     "pch_selftest_lookback_timeout": (C.c_int, [C.c_int, _vp, _sz, _vp]),
     "pch_obb_shell_ws_bytes": (_sz, [_i32]),
@@ -84,7 +87,6 @@ _SIGS = {
     "pch_set_profiling_filter": (None, [C.c_char_p]),
     "pch_get_profile": (C.c_int, [C.c_int, _vp, _vp, _vp]),
 }
-
 
 
 class LasHeaderC(C.Structure):
@@ -101,6 +103,12 @@ class TowerClustersInfo(C.Structure):
     _fields_ = [("centroid", C.c_float * 3), ("base", C.c_float), ("threshold", C.c_float),
                 ("used_fallback", C.c_int32), ("count_at_offset", C.c_int64), ("aabb", C.c_float * 6),
                 ("count", C.c_int64), ("nclusters", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CropBoxC(C.Structure):
+    """PchCropBox (include/pch_hip.h)."""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("lo", C.c_double * 3), ("hi", C.c_double * 3),
+                ("center", C.c_double * 3), ("axes", C.c_double * 9), ("half", C.c_double * 3)]
 
 
 _lib = None

@@ -11,6 +11,7 @@ One function per reference library call:
   ground_filter     <- centring + percentile filter          utils/tower_extraction.py:63-64,82-89
   dbscan            <- chunked sklearn DBSCAN + label offset utils/tower_extraction.py:96-117
   segment_by_label  <- per-label boolean masks               utils/tower_extraction.py:125,131-134
+  crop_boxes        <- per-tower box masks over the cloud    test/kuangxuan.py:60-79, ui/extract.py:345-420
 """
 from __future__ import annotations
 
@@ -692,3 +693,90 @@ def decimate(xyz, k, seed=0, want_index=False):
         idx = torch.empty((k,), dtype=torch.int64, device=dev) if want_index else None
         _lib.check(L.pch_decimate_f64(_ptr(xyz), n, k, int(seed) & (2**64 - 1), _ptr(out), _ptr(idx), _stream()))
     return (out, idx) if want_index else out
+
+
+MAX_CROP_BOXES = 4096
+
+
+def crop_box_table(boxes):
+    """The PchCropBox table of ``boxes`` as a numpy structured array (host): a list of ("aabb", lo, hi) and
+    ("obb", center, rotation, extent) - rotation 3x3 with the box axes in its COLUMNS, extent the FULL side lengths,
+    as in a tower dict - or an array this function returned.  Pure host code.  ValueError: more than 4096 boxes, an
+    unknown kind, a field of the wrong shape."""
+    import numpy as np
+    dt = np.dtype(_lib.CropBoxC)
+    if isinstance(boxes, np.ndarray) and boxes.dtype.fields is not None:
+        if boxes.dtype != dt or boxes.ndim != 1:
+            raise ValueError("a prepared box table must be a one-dimensional array of PchCropBox records")
+        tab = np.ascontiguousarray(boxes)
+    else:
+        boxes = list(boxes)
+        tab = np.zeros((len(boxes),), dtype=dt)
+        for t, box in enumerate(boxes):
+            kind = box[0] if len(box) else None
+            try:
+                if kind == "aabb" and len(box) == 3:
+                    tab[t]["lo"] = np.asarray(box[1], dtype=np.float64).reshape(3)
+                    tab[t]["hi"] = np.asarray(box[2], dtype=np.float64).reshape(3)
+                elif kind == "obb" and len(box) == 4:
+                    tab[t]["kind"] = 1
+                    tab[t]["center"] = np.asarray(box[1], dtype=np.float64).reshape(3)
+                    tab[t]["axes"] = np.asarray(box[2], dtype=np.float64).reshape(9)
+                    tab[t]["half"] = np.asarray(box[3], dtype=np.float64).reshape(3) * 0.5
+                else:
+                    raise ValueError(f"box {t}: unknown kind {kind!r} (\"aabb\", lo, hi / \"obb\", center, rotation, "
+                                     "extent)")
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"box {t}: {e}") from None
+    if len(tab) > MAX_CROP_BOXES:
+        raise ValueError(f"crop_boxes takes at most {MAX_CROP_BOXES} boxes per call, got {len(tab)}")
+    if len(tab) and not np.isin(tab["kind"], (0, 1)).all():
+        raise ValueError("box table: unknown kind (0 = axis-aligned, 1 = oriented)")
+    return tab
+
+
+def crop_box_bounds(boxes):
+    """float64 [T,6] (lo xyz, hi xyz), host: the axis-aligned bounds the sweep of crop_boxes uses to skip a box for a
+    tile of rows (pch_crop_box_bounds_f64).  Pure host code."""
+    import numpy as np
+    tab = crop_box_table(boxes)
+    out = np.zeros((len(tab), 6), dtype=np.float64)
+    if len(tab):
+        _lib.check(_lib.lib().pch_crop_box_bounds_f64(tab.ctypes.data, len(tab), out.ctypes.data))
+    return out
+
+
+def crop_boxes(xyz, boxes, want_index=False, cap=None):
+    """The points of float64 [n,3] inside each of up to 4096 boxes, in one sweep of the cloud (pch_crop_boxes_f64):
+    (points [M,3] float64, offsets int64 [T+1]) and, with want_index, the source rows int64 [M] - device tensors; box t
+    owns points[offsets[t]:offsets[t+1]], rows ascending as in points[mask], a row inside several boxes once in each.
+    boxes: see crop_box_table.  cap: capacity for the hits (default max(n // 8, 65536)); if there are more, the call
+    is repeated once with the reported number.  Synchronises (reads the count)."""
+    L = _lib.lib()
+    tab = crop_box_table(boxes)
+    if isinstance(xyz, torch.Tensor) and xyz.dtype != torch.float64:
+        raise ValueError(f"xyz must be torch.float64, got {xyz.dtype}")
+    xyz = _need_cuda(xyz, torch.float64, "xyz").reshape(-1, 3)
+    n, T, dev = xyz.shape[0], len(tab), xyz.device
+    cap = max(n // 8, 1 << 16) if cap is None else int(cap)
+    if cap < 0:
+        raise ValueError("cap must not be negative")
+    with torch.cuda.device(dev):
+        offsets = torch.empty((T + 1,), dtype=torch.int64, device=dev)
+        cnt = torch.empty((1,), dtype=torch.int64, device=dev)
+        for attempt in range(2):
+            if cap >= 1 << 31:
+                raise _lib.PchError(-4, "crop_boxes: 2^31 or more hits")
+            out = torch.empty((cap, 3), dtype=torch.float64, device=dev)
+            idx = torch.empty((cap,), dtype=torch.int64, device=dev) if want_index else None
+            ws = _workspace(L.pch_crop_boxes_ws_bytes(n, T, cap), dev)
+            _lib.check(L.pch_crop_boxes_f64(_ptr(xyz), n, tab.ctypes.data, T, cap, _ptr(out), _ptr(idx),
+                                            _ptr(offsets), _ptr(cnt), _ptr(ws), ws.numel(), _stream()))
+            m = _lib.check_count(cnt.item(), "crop_boxes")
+            if m <= cap:
+                break
+            del out, idx
+            cap = m                                        # more hits than the buffer holds: once more, with room
+        else:
+            raise RuntimeError("crop_boxes: the hit count grew between two calls on the same cloud")
+    return (out[:m], offsets, idx[:m]) if want_index else (out[:m], offsets)

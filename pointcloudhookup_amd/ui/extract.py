@@ -165,6 +165,11 @@ def _obb_line_points(center, rotation, extent):
     return np.array([pts[i] for e in _OBB_EDGES for i in e])
 
 
+def _adaptive_scale(height):
+    """scale table of the oriented branch (reference :372-380): by the tower's own height"""
+    return [3.2, 3.2, 5.0] if height < 20 else ([3.0, 3.0, 4.8] if height < 40 else [2.8, 2.8, 4.5])
+
+
 def extract_and_visualize_towers_original(las_path: str, tower_obbs: list,
                                           scale_factors: list = None,
                                           line_color: tuple = (1.0, 0.0, 0.0),
@@ -180,7 +185,7 @@ def extract_and_visualize_towers_original(las_path: str, tower_obbs: list,
             ext = np.array(tower_info['extent'])
             if adaptive_scaling:
                 h = ext[2]
-                scale = [3.2, 3.2, 5.0] if h < 20 else ([3.0, 3.0, 4.8] if h < 40 else [2.8, 2.8, 4.5])
+                scale = _adaptive_scale(h)
                 print(f"📏 杆塔{i}: 高度{h:.1f}m, 自适应缩放{scale}")
             else:
                 scale = scale_factors
@@ -210,3 +215,66 @@ def extract_and_visualize_towers(las_path: str, tower_obbs: list,
                                                       line_color)
     return extract_and_visualize_towers_original(las_path, tower_obbs, scale_factors, line_color,
                                                  adaptive_scaling)
+
+
+def tower_crop_boxes(tower_obbs: list, scale_factors: list = None, adaptive_scaling: bool = True,
+                     use_kuangxuan_method: bool = True, kuangxuan_preset: str = "kuangxuan_original"):
+    """One crop box per tower dict, in the form ops.crop_boxes takes - the very box extract_and_visualize_towers draws
+    with the same arguments: ("aabb", lo, hi) for the kuangxuan and symmetric presets, ("obb", center, rotation,
+    extent * scale) for the oriented branch.  None for a tower whose dict is malformed (a warning is printed).  Pure
+    host code."""
+    if scale_factors is None:
+        scale_factors = [2.8, 2.8, 4.5]
+    if use_kuangxuan_method:
+        bbox_method, bbox_params = get_bbox_preset(kuangxuan_preset)
+    boxes = []
+    for i, tower_info in enumerate(tower_obbs):
+        try:
+            if use_kuangxuan_method:
+                width, height = _tower_size(tower_info)
+                lo, hi = _bounds_for(tower_info['center'], width, height, bbox_method, bbox_params)
+                box = ("aabb", np.asarray(lo, dtype=np.float64).reshape(3), np.asarray(hi, dtype=np.float64).reshape(3))
+            else:
+                ext = np.array(tower_info['extent'])
+                scale = _adaptive_scale(ext[2]) if adaptive_scaling else scale_factors
+                box = ("obb", np.asarray(tower_info['center'], dtype=np.float64).reshape(3),
+                       np.asarray(tower_info['rotation'], dtype=np.float64).reshape(3, 3),
+                       np.asarray(ext * np.array(scale), dtype=np.float64).reshape(3))
+        except Exception as e:
+            print(f"⚠️ 杆塔{i}裁剪失败: {str(e)}")
+            box = None
+        boxes.append(box)
+    return boxes
+
+
+def crop_tower_points(las_path: str, tower_obbs: list, scale_factors: list = None, adaptive_scaling: bool = True,
+                      use_kuangxuan_method: bool = True, kuangxuan_preset: str = "kuangxuan_original",
+                      want_index: bool = False):
+    """The points of every tower: one (m_i, 3) float64 array per tower dict (and, with want_index, the int64 rows of
+    the cloud they came from) - the points inside the box extract_and_visualize_towers draws with the same arguments.
+    Not in the reference, which leaves the cropping to the viewer (one mask over the cloud per tower,
+    test/kuangxuan.py:60-79).  The cloud is decoded and cropped on the GPU in one sweep for all towers
+    (ops.crop_boxes); only the cropped rows come back to the host.  A malformed tower dict gives an empty array."""
+    if not os.path.exists(las_path):
+        raise FileNotFoundError(f"未找到文件: {las_path}")
+    boxes = tower_crop_boxes(tower_obbs, scale_factors, adaptive_scaling, use_kuangxuan_method, kuangxuan_preset)
+    good = [t for t, b in enumerate(boxes) if b is not None]
+    points = [np.zeros((0, 3)) for _ in boxes]
+    rows = [np.zeros((0,), dtype=np.int64) for _ in boxes]
+    if good:
+        from .. import las as _las
+        from .. import ops
+        dev = os.environ.get("PCH_DEVICE", "cuda:0")
+        hdr, XYZ = _las.read_device(las_path, dev)
+        if XYZ.shape[0]:
+            xyz = ops.las_scale(XYZ, hdr.scales, hdr.offsets)
+            for s in range(0, len(good), ops.MAX_CROP_BOXES):
+                part = good[s:s + ops.MAX_CROP_BOXES]
+                got = ops.crop_boxes(xyz, [boxes[t] for t in part], want_index=want_index)
+                pts, offs = got[0].cpu().numpy(), got[1].cpu().numpy()
+                idx = got[2].cpu().numpy() if want_index else None
+                for k, t in enumerate(part):
+                    points[t] = pts[offs[k]:offs[k + 1]]
+                    if want_index:
+                        rows[t] = idx[offs[k]:offs[k + 1]]
+    return (points, rows) if want_index else points
