@@ -919,6 +919,40 @@ __global__ __launch_bounds__(DB_THREADS) void db_rowtab_k(DbGrid g, const uint64
 }
 
 // ---- core points ---------------------------------------------------------------------
+// A straggler of db_core_k's phase 2: one query against what is left of the candidate segments sa[r] .. sb[r],
+// r < DB_SEGS, from row j0 of segment r on.  The lanes take 64 candidates each per group, AHEAD groups per trip, and
+// the sweep leaves at min_samples, checked per trip.  Returns the count.  COUNT: the tallies of db_core_k<true>, 64
+// lane slots per group that holds a candidate.
+// AHEAD: a lone point beside a tower core that is NOT core passes every candidate of its neighbourhood (13 585 in the
+// bench tile) - one dependent load per 64 candidates made such a wave the tail of the kernel.  Where the neighbourhood
+// is that large (DB_LONG_TOT) the callers sweep DB_AHEAD groups per trip, their loads in flight together, else one:
+// the same candidates in the same order, and a sweep leaves at min_samples either way.
+template <bool COUNT, int AHEAD>
+__device__ __forceinline__ int db_query_sweep(const DbGrid& g, const float4* __restrict__ pts, const float4 qp,
+                                              int count, int r, uint32_t j0, const uint32_t* sa, const uint32_t* sb,
+                                              unsigned long long& n_useful, unsigned long long& n_slots) {
+    const int l = lane_id();
+    while (r < DB_SEGS && count < g.min_samples) {
+        const uint32_t pb = sb[r];
+        if (j0 >= pb) { ++r; if (r < DB_SEGS) j0 = sa[r]; continue; }
+        float4 P[AHEAD];
+#pragma unroll
+        for (int u = 0; u < AHEAD; ++u) {
+            const uint32_t j = j0 + 64u * u + l;
+            P[u] = pts[j < pb ? j : pb - 1];               // past the end: the last row again, not counted below
+        }
+#pragma unroll
+        for (int u = 0; u < AHEAD; ++u) {
+            const uint32_t jb = j0 + 64u * u;
+            const bool hit = jb + l < pb && db_within2(qp, P[u], g);
+            count += (int)__popcll(__ballot(hit));
+            if (COUNT && jb < pb) { n_useful += (pb - jb) < 64u ? (pb - jb) : 64u; n_slots += 64; }
+        }
+        j0 += 64u * AHEAD;
+    }
+    return count;
+}
+
 // one wave per cell.  Dense cell: all core.  Sparse cell: n-body tile loop - every lane owns one
 // query point of the cell, candidate tiles (64 points of the sorted neighbour runs) are staged
 // once in LDS and broadcast to all queries; the wave leaves as soon as every query has reached
@@ -1002,15 +1036,14 @@ __global__ __launch_bounds__(DB_THREADS) void db_core_k(DbGrid g, const float4* 
     const bool long_sweep = tot >= DB_LONG_TOT;            // wave-uniform
     if (cnt < DB_FEW_QUERIES) {
         // a handful of queries (cluster fringe): lanes sweep the candidates of one query at a
-        // time and leave at min_samples - usually within the first tile of a dense neighbour
+        // time and leave at min_samples - usually within the first tile of a dense neighbour.  The two sweeps are
+        // db_query_sweep's from (0, sa[0]), written out: through that function db_core took 0.126 ms on the bench tile
+        // against 0.120 (measured in three forms of the function; registers and LDS the same).
         for (uint32_t q = s; q < e; ++q) {
             const float4 qp = pts[q];
             int count = 0;
             if (long_sweep) {
-                // A lone point beside a tower core that is NOT core passes every candidate of its neighbourhood (13 585
-                // in the bench tile) - one dependent load per 64 candidates made such a wave the tail of the kernel.
-                // Where the neighbourhood is that large, DB_AHEAD groups per trip, their loads in flight together (the
-                // same candidates in the same order; a sweep leaves at min_samples either way).
+                // DB_AHEAD groups per trip, their loads in flight together (db_query_sweep has the reason)
                 for (int r = 0; r < DB_SEGS && count < g.min_samples; ++r) {
                     const uint32_t pa = sa[r], pb = sb[r];
                     for (uint32_t j0 = pa; j0 < pb && count < g.min_samples; j0 += 64u * DB_AHEAD) {
@@ -1086,40 +1119,10 @@ __global__ __launch_bounds__(DB_THREADS) void db_core_k(DbGrid g, const float4* 
             active &= active - 1;
             float4 qp;
             qp.x = __shfl(Q.x, ql, 64); qp.y = __shfl(Q.y, ql, 64); qp.z = __shfl(Q.z, ql, 64); qp.w = 0.0f;
-            int cq = __shfl(count, ql, 64);
-            int rr = r;
-            uint32_t jj = j0;
-            if (long_sweep) {                              // (as above)
-                while (rr < DB_SEGS && cq < g.min_samples) {
-                    const uint32_t pb = sb[rr];
-                    if (jj >= pb) { ++rr; if (rr < DB_SEGS) jj = sa[rr]; continue; }
-                    float4 P[DB_AHEAD];
-#pragma unroll
-                    for (int u = 0; u < DB_AHEAD; ++u) {
-                        const uint32_t j = jj + 64u * u + l;
-                        P[u] = pts[j < pb ? j : pb - 1];
-                    }
-#pragma unroll
-                    for (int u = 0; u < DB_AHEAD; ++u) {
-                        const uint32_t jb = jj + 64u * u;
-                        const bool hit = jb + l < pb && db_within2(qp, P[u], g);
-                        cq += (int)__popcll(__ballot(hit));
-                        if (COUNT && jb < pb) { n_useful += (pb - jb) < 64u ? (pb - jb) : 64u; n_slots += 64; }
-                    }
-                    jj += 64u * DB_AHEAD;
-                }
-            } else {
-                while (rr < DB_SEGS && cq < g.min_samples) {
-                    const uint32_t pb = sb[rr];
-                    if (jj >= pb) { ++rr; if (rr < DB_SEGS) jj = sa[rr]; continue; }
-                    const uint32_t j = jj + l;
-                    bool hit = false;
-                    if (j < pb) hit = db_within2(qp, pts[j], g);
-                    cq += (int)__popcll(__ballot(hit));
-                    if (COUNT) { n_useful += (pb - jj) < 64u ? (pb - jj) : 64u; n_slots += 64; }
-                    jj += 64;
-                }
-            }
+            const int c0 = __shfl(count, ql, 64);
+            const int cq = long_sweep
+                ? db_query_sweep<COUNT, DB_AHEAD>(g, pts, qp, c0, r, j0, sa, sb, n_useful, n_slots)
+                : db_query_sweep<COUNT, 1>(g, pts, qp, c0, r, j0, sa, sb, n_useful, n_slots);
             if (l == ql) count = cq;
         }
         const bool is_core = valid && count >= g.min_samples;
@@ -1793,6 +1796,90 @@ __global__ __launch_bounds__(DB_THREADS) void db_label_k(const float4* __restric
     db_box_flush(box_acc, cur, m);
 }
 
+// ---- the border rule: smallest cluster id among the core points within eps, else none (db_border_k, dq_assign_k) ----
+// The neighbour cells with core points, ONE PER LANE (three rounds of twelve rows x five cells - a row holds the
+// cells x-2 .. x+2 of one (y, z)): count, label and core box are read once per cell of the fit, side by side.  One cell
+// after the other - count, label, six box words, each a dependent load, for up to 125 cells and every query again - was
+// db_border_k: a lone noise point beside a tower tested ~100 boxes at ~0.4 us each, 51 us for 2.6 MB of traffic.
+// A row never holds more than five cells: the keys of x-2 .. x+2 in one (chunk, y, z) are unique (db_row_run).
+constexpr int DB_BR = 3, DB_BROWS = 12;
+struct DbCoreCells {
+    int cell[DB_BR], label[DB_BR];     // -1 / INT_BIG: this lane holds no core cell in that round
+    bool dense[DB_BR];                 // every row of the cell is core: core_s need not be read
+    float box[DB_BR][6];               // box of the cell's core points
+};
+
+// the core cells among the rows of rs, one per lane; `on` is wave-uniform, false: nothing is read and no lane holds a cell
+__device__ __forceinline__ void db_gather_core_cells(DbCoreCells& cc, const RowSet* __restrict__ rs, bool on,
+                                                     const uint32_t* __restrict__ cell_start,
+                                                     const uint32_t* __restrict__ cell_ncore,
+                                                     const float* __restrict__ cell_box,
+                                                     const int* __restrict__ cell_label) {
+    const int l = lane_id();
+#pragma unroll
+    for (int rd = 0; rd < DB_BR; ++rd) {
+        const int row = rd * DB_BROWS + l / 5, k = l % 5;
+        cc.cell[rd] = -1; cc.label[rd] = INT_BIG; cc.dense[rd] = false;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) cc.box[rd][a] = 0.0f;
+        if (on && l < 5 * DB_BROWS && row < DB_ROWS) {
+            const int B = rs->ca[row] + k;
+            if (B < rs->cb[row]) {
+                const uint32_t nb = cell_ncore[B];
+                if (nb != 0) {
+                    cc.cell[rd] = B;
+                    cc.label[rd] = cell_label[B];
+                    cc.dense[rd] = nb == cell_start[B + 1] - cell_start[B];
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) cc.box[rd][a] = cell_box[6 * (int64_t)B + a];
+                }
+            }
+        }
+    }
+}
+
+// The smallest label among the gathered cells that hold a core point within eps of qp, INT_BIG if there is none.
+// Cells whose core box reaches the query, then: smallest label first - the first cell that really holds a core point
+// within eps decides (what is asked for is the smallest label among such cells; the order of the cells with larger
+// labels does not matter).  A cell whose cluster was dropped (label INT_BIG) attracts nothing.
+__device__ __forceinline__ int db_border_label(const DbGrid& g, const float4 qp, const DbCoreCells& cc,
+                                               const float4* __restrict__ pts,
+                                               const uint32_t* __restrict__ cell_start,
+                                               const uint8_t* __restrict__ core_s) {
+    const int l = lane_id();
+    bool cand[DB_BR];
+#pragma unroll
+    for (int rd = 0; rd < DB_BR; ++rd) cand[rd] = cc.cell[rd] >= 0 && !(db_box_d2(qp, cc.box[rd]) > g.eps2);
+    for (;;) {                                             // every turn ends the loop or strikes one candidate cell
+        int mine = INT_BIG, sel = -1;
+#pragma unroll
+        for (int rd = 0; rd < DB_BR; ++rd)
+            if (cand[rd] && cc.label[rd] < mine) { mine = cc.label[rd]; sel = rd; }
+        const int lo = wave_reduce_min(mine);
+        if (lo == INT_BIG) return INT_BIG;
+        const int owner = (int)__builtin_ctzll(__ballot(mine == lo));
+        int Bsel = -1;
+        bool dsel = false;
+#pragma unroll
+        for (int rd = 0; rd < DB_BR; ++rd)
+            if (sel == rd) { Bsel = cc.cell[rd]; dsel = cc.dense[rd]; }
+        const int B = __builtin_amdgcn_readlane(Bsel, owner);
+        const bool b_dense = __builtin_amdgcn_readlane((int)dsel, owner) != 0;
+        const uint32_t bs = cell_start[B], be = cell_start[B + 1];
+        for (uint32_t j0 = bs; j0 < be; j0 += 64) {
+            const uint32_t j = j0 + l;
+            bool hit = false;
+            if (j < be && (b_dense || core_s[j])) hit = db_within2(qp, pts[j], g);
+            if (__ballot(hit)) return lo;
+        }
+        if (l == owner) {
+#pragma unroll
+            for (int rd = 0; rd < DB_BR; ++rd)
+                if (sel == rd) cand[rd] = false;
+        }
+    }
+}
+
 // border points: smallest cluster id among the core points within eps
 __global__ __launch_bounds__(DB_THREADS) void db_border_k(DbGrid g, const float4* __restrict__ pts,
                                                           const uint32_t* __restrict__ cell_start,
@@ -1817,75 +1904,12 @@ __global__ __launch_bounds__(DB_THREADS) void db_border_k(DbGrid g, const float4
     if (l < DB_ROWS)
         for (int B = rs->ca[l]; B < rs->cb[l]; ++B) any |= (cell_ncore[B] != 0);
     if (!__ballot(any != 0)) return;
-    // The neighbour cells with core points, ONE PER LANE (three rounds of twelve rows x five cells - a row holds the
-    // cells x-2 .. x+2 of one (y, z)): count, label and core box are read once per cell A, side by side.  One cell after
-    // the other - count, label, six box words, each a dependent load, for up to 125 cells and every query again - was
-    // this kernel: a lone noise point beside a tower tested ~100 boxes at ~0.4 us each, 51 us for 2.6 MB of traffic.
-    // A row never holds more than five cells: the keys of x-2 .. x+2 in one (chunk, y, z) are unique (db_row_run).
-    constexpr int BR = 3, BROWS = 12;
-    int Bc[BR], Bl[BR];
-    bool Bd[BR];
-    float Bx[BR][6];
-#pragma unroll
-    for (int rd = 0; rd < BR; ++rd) {
-        const int row = rd * BROWS + l / 5, k = l % 5;
-        Bc[rd] = -1; Bl[rd] = INT_BIG; Bd[rd] = false;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) Bx[rd][a] = 0.0f;
-        if (l < 5 * BROWS && row < DB_ROWS) {
-            const int B = rs->ca[row] + k;
-            if (B < rs->cb[row]) {
-                const uint32_t nb = cell_ncore[B];
-                if (nb != 0) {
-                    Bc[rd] = B;
-                    Bl[rd] = cell_label[B];
-                    Bd[rd] = nb == cell_start[B + 1] - cell_start[B];
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) Bx[rd][a] = cell_box[6 * (int64_t)B + a];
-                }
-            }
-        }
-    }
+    DbCoreCells cc;
+    db_gather_core_cells(cc, rs, true, cell_start, cell_ncore, cell_box, cell_label);
     for (uint32_t q = as; q < ae; ++q) {
         if (core_s[q]) continue;
         const float4 qp = pts[q];
-        // cells whose core box reaches the query, then: smallest label first - the first cell that really holds a core
-        // point within eps decides (what is asked for is the smallest label among such cells; the order of the cells
-        // with larger labels does not matter)
-        bool cand[BR];
-#pragma unroll
-        for (int rd = 0; rd < BR; ++rd) cand[rd] = Bc[rd] >= 0 && !(db_box_d2(qp, Bx[rd]) > g.eps2);
-        int best = INT_BIG;
-        for (;;) {
-            int mine = INT_BIG, sel = -1;
-#pragma unroll
-            for (int rd = 0; rd < BR; ++rd)
-                if (cand[rd] && Bl[rd] < mine) { mine = Bl[rd]; sel = rd; }
-            const int lo = wave_reduce_min(mine);
-            if (lo == INT_BIG) break;
-            const int owner = (int)__builtin_ctzll(__ballot(mine == lo));
-            int Bsel = -1;
-            bool dsel = false;
-#pragma unroll
-            for (int rd = 0; rd < BR; ++rd)
-                if (sel == rd) { Bsel = Bc[rd]; dsel = Bd[rd]; }
-            const int B = __builtin_amdgcn_readlane(Bsel, owner);
-            const bool b_dense = __builtin_amdgcn_readlane((int)dsel, owner) != 0;
-            const uint32_t bs = cell_start[B], be = cell_start[B + 1];
-            bool found = false;
-            for (uint32_t j0 = bs; j0 < be; j0 += 64) {
-                const uint32_t j = j0 + l;
-                bool hit = false;
-                if (j < be && (b_dense || core_s[j])) hit = db_within2(qp, pts[j], g);
-                if (__ballot(hit)) { found = true; break; }
-            }
-            if (found) { best = lo; break; }
-            if (l == owner) {
-#pragma unroll
-                for (int rd = 0; rd < BR; ++rd)
-                    if (sel == rd) cand[rd] = false;
-            }
-        }
+        const int best = db_border_label(g, qp, cc, pts, cell_start, core_s);
         if (l == 0 && best != INT_BIG) labels[__float_as_uint(qp.w)] = best;
         if (box_acc && best != INT_BIG && best >= 0 && best < box_cap && l < 6) {     // a border point joins its box
             const float v = l % 3 == 0 ? qp.x : (l % 3 == 1 ? qp.y : qp.z);
@@ -1898,7 +1922,8 @@ __global__ __launch_bounds__(DB_THREADS) void db_border_k(DbGrid g, const float4
 // ---- points that were NOT part of the fit, held against it (pch_dbscan_assign_f32): db_border_k's rule - smallest
 // cluster id among the fit's core points within eps, else -1 - for query points the caller brings.  The queries are
 // binned into the fit's own cells, sorted by cell and cut into pieces; one wave per piece walks the 5x5x5 block around
-// the piece's cell exactly as db_border_k walks it around a cell of the fit.
+// the piece's cell with the functions db_border_k walks it with around a cell of the fit (db_gather_core_cells,
+// db_border_label).
 struct DbQuery {
     const float* xyz; int64_t nq;    // [nq][3] query rows
     float sx, sy, sz;                // q = fl32(row - s) per component (0: x - 0.0f is x, bit for bit, -0.0 and NaN too)
@@ -1968,9 +1993,9 @@ __global__ __launch_bounds__(DB_THREADS) void dq_pieces_k(const uint64_t* __rest
 
 // One wave per piece (the grid is sized on the host from nq alone, so the waves stride over the piece count the
 // device holds).  Rows of the piece's cell with db_row_run - not the row table: the query's cell need not exist in the
-// fit -, the core cells of those rows one per lane as in db_border_k, then query after query: smallest label first,
-// reject by core box, db_within2 over the cell's core rows, the first hit decides.  The queries are loaded 64 at a time,
-// one per lane, and handed round; every lane stores the answer of its own query.
+// fit -, the core cells of those rows one per lane (db_gather_core_cells), then query after query through
+// db_border_label.  The queries are loaded 64 at a time, one per lane, and handed round; every lane stores the answer of
+// its own query.
 __global__ __launch_bounds__(DB_THREADS) void dq_assign_k(DbQuery Q, DbGrid g, const float4* __restrict__ pts,
                                                           const uint32_t* __restrict__ cell_start,
                                                           const uint64_t* __restrict__ cell_key,
@@ -2001,30 +2026,8 @@ __global__ __launch_bounds__(DB_THREADS) void dq_assign_k(DbQuery Q, DbGrid g, c
         if (l < DB_ROWS)
             for (int B = rs->ca[l]; B < rs->cb[l]; ++B) any |= (cell_ncore[B] != 0);
         const bool none = !__ballot(any != 0);             // no core cell in reach: the whole piece is -1
-        constexpr int BR = 3, BROWS = 12;                  // db_border_k's gather: 12 rows x 5 cells per round
-        int Bc[BR], Bl[BR];
-        bool Bd[BR];
-        float Bx[BR][6];
-#pragma unroll
-        for (int rd = 0; rd < BR; ++rd) {
-            const int row = rd * BROWS + l / 5, k = l % 5;
-            Bc[rd] = -1; Bl[rd] = INT_BIG; Bd[rd] = false;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) Bx[rd][a] = 0.0f;
-            if (!none && l < 5 * BROWS && row < DB_ROWS) {
-                const int B = rs->ca[row] + k;
-                if (B < rs->cb[row]) {
-                    const uint32_t nb = cell_ncore[B];
-                    if (nb != 0) {
-                        Bc[rd] = B;
-                        Bl[rd] = cell_label[B];
-                        Bd[rd] = nb == cell_start[B + 1] - cell_start[B];
-#pragma unroll
-                        for (int a = 0; a < 6; ++a) Bx[rd][a] = cell_box[6 * (int64_t)B + a];
-                    }
-                }
-            }
-        }
+        DbCoreCells cc;
+        db_gather_core_cells(cc, rs, !none, cell_start, cell_ncore, cell_box, cell_label);
         for (uint32_t q0 = ps; q0 < pe; q0 += 64) {
             const bool have = q0 + l < pe;
             const uint32_t v = have ? vals[q0 + l] : DQ_OUT;
@@ -2040,40 +2043,7 @@ __global__ __launch_bounds__(DB_THREADS) void dq_assign_k(DbQuery Q, DbGrid g, c
                 qp.y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.y), j));
                 qp.z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.z), j));
                 qp.w = 0.0f;
-                bool cand[BR];
-#pragma unroll
-                for (int rd = 0; rd < BR; ++rd) cand[rd] = Bc[rd] >= 0 && !(db_box_d2(qp, Bx[rd]) > g.eps2);
-                int best = INT_BIG;
-                for (;;) {                                  // every turn ends the loop or strikes one candidate cell
-                    int lab = INT_BIG, sel = -1;
-#pragma unroll
-                    for (int rd = 0; rd < BR; ++rd)
-                        if (cand[rd] && Bl[rd] < lab) { lab = Bl[rd]; sel = rd; }
-                    const int lo = wave_reduce_min(lab);
-                    if (lo == INT_BIG) break;               // a cell whose cluster was dropped attracts nothing
-                    const int owner = (int)__builtin_ctzll(__ballot(lab == lo));
-                    int Bsel = -1;
-                    bool dsel = false;
-#pragma unroll
-                    for (int rd = 0; rd < BR; ++rd)
-                        if (sel == rd) { Bsel = Bc[rd]; dsel = Bd[rd]; }
-                    const int B = __builtin_amdgcn_readlane(Bsel, owner);
-                    const bool b_dense = __builtin_amdgcn_readlane((int)dsel, owner) != 0;
-                    const uint32_t bs = cell_start[B], be = cell_start[B + 1];
-                    bool found = false;
-                    for (uint32_t j0 = bs; j0 < be; j0 += 64) {
-                        const uint32_t jj = j0 + l;
-                        bool hit = false;
-                        if (jj < be && (b_dense || core_s[jj])) hit = db_within2(qp, pts[jj], g);
-                        if (__ballot(hit)) { found = true; break; }
-                    }
-                    if (found) { best = lo; break; }
-                    if (l == owner) {
-#pragma unroll
-                        for (int rd = 0; rd < BR; ++rd)
-                            if (sel == rd) cand[rd] = false;
-                    }
-                }
+                const int best = db_border_label(g, qp, cc, pts, cell_start, core_s);
                 if (l == j && best != INT_BIG) res = best;
             }
             if (have) out[v & ~DQ_OUT] = res;
@@ -2274,20 +2244,18 @@ struct DbCells {
 
 // Stage C's tuning switches, read here only, once per process.  PCH_DBSCAN_SORT=chunk|global: the cell sort (0
 // automatic, 1 chunk-local, 2 global), which pch_dbscan_set_sort_mode() overrides for the whole process.
-// PCH_DB_NO_BOXFOLD: no cluster boxes folded into the label kernels.  PCH_DB_NO_XCD: db_label_k's blocks in sorted
-// order, not by XCD.  Pair counting (pch_dbscan_set_pair_counting) is set per thread.
-struct DbTuning { int sort_mode; bool no_boxfold, no_xcd, count_pairs; };
+// Pair counting (pch_dbscan_set_pair_counting) is set per thread.
+struct DbTuning { int sort_mode; bool count_pairs; };
 static int g_sort_mode = -1;
 static thread_local bool g_count_pairs = false;
 static DbTuning db_tuning() {
-    static const bool no_boxfold = getenv("PCH_DB_NO_BOXFOLD") != nullptr, no_xcd = getenv("PCH_DB_NO_XCD") != nullptr;
     int m = __atomic_load_n(&g_sort_mode, __ATOMIC_RELAXED);
     if (m < 0) {
         const char* e = getenv("PCH_DBSCAN_SORT");
         m = (e && strcmp(e, "chunk") == 0) ? 1 : (e && strcmp(e, "global") == 0) ? 2 : 0;
         __atomic_store_n(&g_sort_mode, m, __ATOMIC_RELAXED);
     }
-    return {m, no_boxfold, no_xcd, g_count_pairs};
+    return {m, g_count_pairs};
 }
 
 // the run whose workspace the entries below continue, and its cell table
@@ -2572,7 +2540,7 @@ static int db_union(const DbRun& r, const DbCells& c) {
 }
 
 // the labels of core and border rows (and, with `boxes`, the cluster boxes folded in); k_host: the cluster count
-static int db_labels(const DbRun& r, const DbCells& c, const DbTuning& tune, int32_t* k_host, DbBoxOut* boxes) {
+static int db_labels(const DbRun& r, const DbCells& c, int32_t* k_host, DbBoxOut* boxes) {
     const DbWs& w = r.w; const hipStream_t s = r.s; const int64_t n = r.n, nchunks = r.nchunks; const int m = c.m;
     // cluster id = rank of the cluster's smallest core row: a bitmap over the rows + a scan of its
     // word counts (n/32 elements instead of n)
@@ -2583,13 +2551,13 @@ static int db_labels(const DbRun& r, const DbCells& c, const DbTuning& tune, int
     // word ranks: popcount on load
     if (scan1_pays(nw)) PCH_TRY(scan1_exclusive_popc_u32(w.bits, w.wrank, nw, w.scan1_b, &w.meta->nclusters, s));
     else PCH_TRY(scan_exclusive_popc_u32(w.bits, w.wrank, nw, w.scan_ws, &w.meta->nclusters, s));
-    uint32_t* box_acc = (boxes && boxes->acc && boxes->cap > 0 && !tune.no_boxfold) ? boxes->acc : nullptr;
+    uint32_t* box_acc = (boxes && boxes->acc && boxes->cap > 0) ? boxes->acc : nullptr;
     const int32_t box_cap = box_acc ? boxes->cap : 0;
     PCH_LAUNCH("db_prelabel", db_prelabel_k, dim3((unsigned)(box_acc ? ceil_div(8 * (int64_t)box_cap, 256) : 1)),
                dim3(256), 0, s, &w.meta->nclusters, r.out_nclusters, box_acc, 8 * (int64_t)box_cap);
     if (k_host) PCH_TRY(peek_enqueue(r.out_nclusters, sizeof(int32_t), s));    // read while the labels are written
     // many chunks: the blocks of one chunk share an XCD (see db_label_k); otherwise blocks in sorted order
-    const int bpc = (nchunks >= 16 && !tune.no_xcd) ? (int)ceil_div(r.chunk_size, DB_LAB_TILE) : 0;
+    const int bpc = nchunks >= 16 ? (int)ceil_div(r.chunk_size, DB_LAB_TILE) : 0;
     const unsigned gl = bpc > 0 ? (unsigned)(8 * ceil_div(nchunks, 8) * bpc) : (unsigned)ceil_div(n, DB_LAB_TILE);
     PCH_LAUNCH("db_label", db_label_k, dim3(gl), dim3(DB_THREADS), 0, s, w.pts, w.cid, w.core_s, w.root, w.comp_min,
                w.bits, w.wrank, n, w.cell_start, w.cell_label, r.labels, r.core, r.chunk_size, bpc, nchunks, box_acc,
@@ -2676,7 +2644,7 @@ int pch::dbscan_run(const float* xyz, int64_t n, double eps, int32_t min_samples
     PCH_TRY(db_sorted_keys(r, g, cellbits, nbits, overflow, tune.sort_mode, ks));
     PCH_TRY(db_cells_core(r, g, cellbits, ks, tune.count_pairs, c));
     PCH_TRY(db_union(r, c));
-    PCH_TRY(db_labels(r, c, tune, k_host, boxes));
+    PCH_TRY(db_labels(r, c, k_host, boxes));
     g_last = {ws, ws_bytes, n, c, r.nchunks, overflow};
     return PCH_OK;
 }
