@@ -373,7 +373,8 @@ __device__ __forceinline__ uint64_t cs_chunk_field(const DbGrid& g, int64_t c) {
     const int sh = g.bx + g.by + g.bz;
     return sh < 64 ? ((uint64_t)c << sh) : 0ull;
 }
-// a NaN/inf chunk (isbad: every key is cell 0) or a one-cell chunk: the rows stay where they are
+// a NaN/inf chunk (isbad: every key is cell 0) or a one-cell chunk: the rows stay where they are.  keys_out may be
+// null (db_cellscatter_k on the table route: the chunk's single cell is staged instead)
 __device__ __forceinline__ void cs_rows_in_place(const DbGrid& g, const Row3* __restrict__ rows, int cn, int64_t lo,
         uint64_t hi, bool isbad, float4* __restrict__ pts, uint64_t* __restrict__ keys_out) {
     for (int i = threadIdx.x; i < cn; i += CS_THREADS) {
@@ -382,7 +383,7 @@ __device__ __forceinline__ void cs_rows_in_place(const DbGrid& g, const Row3* __
         o4.x = q.x; o4.y = q.y; o4.z = q.z; o4.w = __uint_as_float((uint32_t)(lo + i));
         pts[lo + i] = o4;
         bool ok;
-        keys_out[lo + i] = isbad ? hi : (hi | cs_cell_key(g, q.x, q.y, q.z, ok));
+        if (keys_out) keys_out[lo + i] = isbad ? hi : (hi | cs_cell_key(g, q.x, q.y, q.z, ok));
     }
 }
 
@@ -612,6 +613,17 @@ __global__ __launch_bounds__(CS_THREADS) void db_chunksort_k(
 // their order can change from run to run; no reader of the sorted rows depends on it.
 // A chunk with more than CT_CELLS cells stops counting, sets ovf[c] and writes nothing else: db_chunksort_k, launched
 // right behind with ovf as its gate, sorts it.  NaN/inf and one-cell chunks keep their rows in place, as db_chunksort_k does.
+// TABLE (the run has at most DB_TABLE_MAX_CHUNKS chunks): the sorted cell list that the scan works on IS the chunk's
+// part of the cell table, so it is staged - st.ncell[c], and at [lo, lo + ncell) the full keys in ascending order and
+// every cell's first sorted position - and no key is written per row: 16 bytes written per row instead of 24, one
+// scattered store instead of two.  db_chunkcells_k and db_celltab_k (below) turn the staged lists into the table.
+// Every chunk writes st.ncell[c] on every run (the workspace is not cleared): 0 for a chunk handed to db_chunksort_k.
+// !TABLE: a full key per sorted row (keys_out), the table is read off those by db_heads_k / db_cells_k.
+struct DbStage {
+    uint32_t* ncell;        // [nchunks] cells of chunk c; 0: the chunk overflowed, its keys come from db_chunksort_k
+    uint64_t* key;          // [n] at lo + j: key of the chunk's j-th cell, ascending
+    uint32_t* start;        // [n] at lo + j: first sorted row of that cell (an index into pts)
+};
 constexpr int CT_SLOTS = 4096;                  // table slots (key + count: 32 KiB)
 constexpr int CT_BITS  = 12;                    // log2(CT_SLOTS)
 constexpr int CT_CELLS = 1024;                  // cells a chunk may hold here (measured: a uniform-cloud chunk of ~1 600
@@ -621,9 +633,10 @@ static_assert(CT_SLOTS == 1 << CT_BITS && CT_CELLS + CS_THREADS < CT_SLOTS, "the
 
 __device__ __forceinline__ uint32_t ct_hash(uint32_t k) { return (k * 0x9E3779B1u) >> (32 - CT_BITS); }
 
+template <bool TABLE>
 __global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
     const float* __restrict__ xyz, int64_t n, DbGrid g, uint32_t* __restrict__ bad, uint32_t* __restrict__ ovf,
-    float4* __restrict__ pts, uint64_t* __restrict__ keys_out, uint32_t* __restrict__ status) {
+    float4* __restrict__ pts, uint64_t* __restrict__ keys_out, DbStage st, uint32_t* __restrict__ status) {
     __shared__ uint32_t tkey[CT_SLOTS];
     __shared__ uint32_t tcnt[CT_SLOTS];         // sweep 1: rows per cell; sweep 2: the cell's next position
     __shared__ uint32_t skey[CT_CELLS];         // the chunk's cell keys, sorted
@@ -667,6 +680,7 @@ __global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
     const bool over = !isbad && ncell > (uint32_t)CT_CELLS;
     if (tid == 0) {
         ovf[c] = over ? 1u : 0u;                        // written for every chunk: db_chunksort_k's gate
+        if constexpr (TABLE) st.ncell[c] = over ? 0u : (isbad ? 1u : ncell);
         if (!over) {
             bad[c] = isbad ? 1u : 0u;
             if (!isbad && flags[1]) atomicOr(status, 1u);
@@ -674,7 +688,16 @@ __global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
     }
     if (over) return;                                   // db_chunksort_k takes this chunk
     const uint64_t hi = cs_chunk_field(g, c);
-    if (isbad || ncell == 1u) { cs_rows_in_place(g, rows, cn, lo, hi, isbad, pts, keys_out); return; }   // one cell
+    if (isbad || ncell == 1u) {                         // one cell
+        if constexpr (TABLE) {
+            // its key: cell 0 of a NaN/inf chunk, else the table's only key
+            if (isbad) { if (tid == 0) st.key[lo] = hi; }
+            else for (int j = tid; j < CT_SLOTS; j += CS_THREADS) if (tkey[j] != CT_EMPTY) st.key[lo] = hi | tkey[j];
+            if (tid == 0) st.start[lo] = (uint32_t)lo;
+        }
+        cs_rows_in_place(g, rows, cn, lo, hi, isbad, pts, TABLE ? nullptr : keys_out);
+        return;
+    }
     // ---- the occupied slots, compacted (in any order) and padded to a power of two ...
     const int P = 1 << (32 - __clz((int)ncell - 1));    // 2 <= P <= CT_CELLS
     for (int j0 = 0; j0 < CT_SLOTS; j0 += CS_THREADS) {
@@ -722,7 +745,13 @@ __global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
         for (int w2 = 0; w2 < w; ++w2) run += wsum[w2];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            if (4 * tid + u < (int)ncell) tcnt[slot[u]] = run;    // only this thread touches these slots
+            if (4 * tid + u < (int)ncell) {
+                tcnt[slot[u]] = run;                    // only this thread touches these slots
+                if constexpr (TABLE) {                  // ncell <= cn: the chunk's own part of the staging arrays
+                    st.key[lo + 4 * tid + u] = hi | skey[4 * tid + u];
+                    st.start[lo + 4 * tid + u] = (uint32_t)(lo + run);
+                }
+            }
             run += cnt[u];
         }
     }
@@ -744,7 +773,7 @@ __global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
                 float4 o4;
                 o4.x = q[u].x; o4.y = q[u].y; o4.z = q[u].z; o4.w = __uint_as_float((uint32_t)(lo + i));
                 pts[lo + pos] = o4;
-                keys_out[lo + pos] = hi | k;
+                if constexpr (!TABLE) keys_out[lo + pos] = hi | k;
             }
         }
     }
@@ -847,6 +876,126 @@ __global__ __launch_bounds__(DB_THREADS) void db_cells_k(const uint64_t* __restr
             if (base + j < n) cid[base + j] = cc[j];
     }
 }
+// ---- the cell table from the lists that db_cellscatter_k<true> staged: no key per row is written or read ----------
+// db_chunkcells_k (one workgroup) scans the chunks' cell counts into chunk_cells, which makes every staged cell's
+// global index chunk_cells[c] + j, and says in *route whether a chunk overflowed.  db_celltab_k then runs over the rows in
+// db_cells_k's shape.  *route clear: it writes what db_cells_k writes, finding a row's cell in its chunk's staged starts.
+// *route set (some chunk went through db_chunksort_k, which writes keys): it writes the keys of all OTHER chunks' rows
+// instead, and the host, which reads the word in the wait it makes anyway, launches db_heads_k / db_cells_k on them.
+constexpr int64_t DB_TABLE_MAX_CHUNKS = 16384;  // beyond: db_cellscatter_k<false>, the table is read off the keys
+constexpr int CC_THREADS = 1024;
+constexpr int CC_ITEMS = (int)(DB_TABLE_MAX_CHUNKS / CC_THREADS);     // consecutive chunks per thread
+
+// cells staged for chunk c of cn rows.  db_cellscatter_k<true> writes the word for every chunk on every run and a chunk
+// has at most one cell per row, so the minimum never changes a value: it is purely a guard that keeps the reads of the
+// staging arrays and the writes of the table inside them should a writer ever break that
+__device__ __forceinline__ uint32_t ct_staged_cells(const uint32_t* __restrict__ ncell, int64_t c, int64_t cn) {
+    const uint32_t v = ncell[c];
+    return v < (uint32_t)cn ? v : (uint32_t)cn;
+}
+
+__global__ __launch_bounds__(CC_THREADS) void db_chunkcells_k(
+    const uint32_t* __restrict__ ncell, const uint32_t* __restrict__ ovf, int nchunks, int64_t n, int64_t chunk_size,
+    uint32_t* __restrict__ chunk_cells, uint32_t* __restrict__ cell_start, uint32_t* __restrict__ ncells,
+    uint32_t* __restrict__ route) {
+    __shared__ uint32_t wsum[CC_THREADS / 64];
+    const int tid = threadIdx.x, c0 = tid * CC_ITEMS;
+    uint32_t v[CC_ITEMS], sum = 0;
+    int over = 0;
+#pragma unroll
+    for (int u = 0; u < CC_ITEMS; ++u) {
+        const int c = c0 + u;
+        v[u] = 0u;
+        if (c < nchunks) {
+            const int64_t lo = (int64_t)c * chunk_size;
+            v[u] = ct_staged_cells(ncell, c, (n - lo) < chunk_size ? (n - lo) : chunk_size);
+            over |= ovf[c] != 0u;
+        }
+        sum += v[u];
+    }
+    over = __syncthreads_or(over);
+    const uint32_t incl = wave_scan_incl(sum);
+    if (lane_id() == 63) wsum[wave_id()] = incl;
+    __syncthreads();
+    uint32_t run = incl - sum, total = 0;
+    for (int w = 0; w < CC_THREADS / 64; ++w) { if (w < wave_id()) run += wsum[w]; total += wsum[w]; }
+#pragma unroll
+    for (int u = 0; u < CC_ITEMS; ++u) {
+        if (c0 + u < nchunks) chunk_cells[c0 + u] = run;
+        run += v[u];
+    }
+    if (tid == 0) {
+        *route = over ? 1u : 0u;
+        if (!over) {                                    // else db_cells_k's to write
+            chunk_cells[nchunks] = total;
+            cell_start[total] = (uint32_t)n;            // total <= n
+            *ncells = total;
+        }
+    }
+}
+
+__global__ __launch_bounds__(DB_THREADS) void db_celltab_k(
+    const uint32_t* __restrict__ route, DbStage st, const uint32_t* __restrict__ ovf,
+    const uint32_t* __restrict__ chunk_cells, int64_t n, int64_t chunk_size, uint32_t* __restrict__ cid,
+    uint32_t* __restrict__ cell_start, uint64_t* __restrict__ cell_key, uint32_t* __restrict__ cell_acc,
+    uint64_t* __restrict__ keys_out) {
+    const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * DC_ITEMS;
+    if (base >= n) return;
+    const bool fill = *route != 0u;                     // uniform over the grid
+    // the chunk of row `base`, and the last of its staged cells that starts at or before it.  lo <= base < end, and
+    // the chunk's first cell starts at lo
+    int64_t c = (uint32_t)base / (uint32_t)chunk_size;  // n < 2^31
+    int64_t lo = c * chunk_size, end = lo + chunk_size < n ? lo + chunk_size : n;
+    uint32_t nc = ct_staged_cells(st.ncell, c, end - lo), j = 0;
+    for (uint32_t a = 1, b = nc; a < b;) {              // j = the largest index in [0, nc) with start <= base
+        const uint32_t mid = a + (b - a) / 2;
+        if (st.start[lo + mid] <= (uint32_t)base) { j = mid; a = mid + 1; } else b = mid;
+    }
+    int64_t next = j + 1 < nc ? (int64_t)st.start[lo + j + 1] : end;      // first row of the cell behind j
+    uint32_t cell0 = chunk_cells[c];
+    bool skip = fill && ovf[c] != 0u;                   // (fill) db_chunksort_k wrote this chunk's keys
+    uint32_t cc[DC_ITEMS];
+#pragma unroll
+    for (int u = 0; u < DC_ITEMS; ++u) {
+        const int64_t i = base + u;
+        cc[u] = 0u;
+        if (i >= n) continue;
+        bool head = i == base && nc != 0u && (int64_t)st.start[lo + j] == i;
+        if (i == end) {                                 // the next chunk: chunk_size may be anything from 1 up
+            ++c; lo = end; end = lo + chunk_size < n ? lo + chunk_size : n;
+            nc = ct_staged_cells(st.ncell, c, end - lo); j = 0;
+            next = 1 < nc ? (int64_t)st.start[lo + 1] : end;
+            cell0 = chunk_cells[c];
+            skip = fill && ovf[c] != 0u;
+            head = nc != 0u;
+        } else if (i == next) {                         // the next cell of this chunk (next < end here: j + 1 < nc)
+            ++j;
+            next = j + 1 < nc ? (int64_t)st.start[lo + j + 1] : end;
+            head = true;
+        }
+        cc[u] = cell0 + j;
+        if (fill) {
+            if (!skip) keys_out[i] = st.key[lo + j];
+        } else if (head) {
+            cell_start[cc[u]] = (uint32_t)i;
+            cell_key[cc[u]] = st.key[lo + j];
+            uint4* a4 = reinterpret_cast<uint4*>(cell_acc + 8 * (int64_t)cc[u]);   // neutral start of db_cellstats_k
+            a4[0] = make_uint4(0u, 0u, 0u, 0u);
+            a4[1] = make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+    if (fill) return;
+    if (base + DC_ITEMS <= n) {
+        uint4* o = reinterpret_cast<uint4*>(cid + base);
+        o[0] = make_uint4(cc[0], cc[1], cc[2], cc[3]);
+        o[1] = make_uint4(cc[4], cc[5], cc[6], cc[7]);
+    } else {
+#pragma unroll
+        for (int u = 0; u < DC_ITEMS; ++u)
+            if (base + u < n) cid[base + u] = cc[u];
+    }
+}
+
 // ---- neighbour rows of one cell: lanes 0..24 each find one (dy,dz) row ------------------
 struct RowSet {
     int ca[DB_ROWS], cb[DB_ROWS];      // cell index range of every row
@@ -2148,7 +2297,7 @@ struct DbMeta {
     uint32_t ncells, nclusters;
     uint32_t comp_max[3];   // dbc_comp_k: largest compressed index per axis
     int64_t  first_bad;     // db_compress: first NaN/inf row, -1 if none
-    uint32_t pad[50];
+    uint32_t pad[50];       // [0]: DbWs::cell_route
 };
 static_assert(sizeof(DbMeta) == 256 && offsetof(DbMeta, box_key) == 0 && offsetof(DbMeta, status) == 24 &&
               offsetof(DbMeta, ncells) == 28 && offsetof(DbMeta, nclusters) == 32 && offsetof(DbMeta, comp_max) == 36 &&
@@ -2178,6 +2327,10 @@ struct DbWs {
                             // counts.  Both are kept for pch_dbscan_first_core_rows_i32; the array has no other use
     uint8_t*  face_todo;    // root as bytes: db_union_pairs_k writes the face pairs it leaves to db_union_face_k.  root
                             // itself is first written by db_compmin_k, behind both
+    DbStage   stage;        // the chunk route's staged cell lists (db_cellscatter_k<true>) in arrays that only the global
+                            // sort uses: ncell = v1, key = k0, start = v0
+    uint32_t* cell_route;   // meta->pad[0]: db_chunkcells_k says that a chunk overflowed, so the table comes from keys.
+                            // One copy from meta->status up to here brings the host status, ncells and this word
     unsigned long long* cs_stamps = nullptr;     // cell_box (first written by db_cellfin_k), PCH_CS_STAMPS builds only
     // One 16-byte aligned fill zeroes status / ncells / nclusters, scan1_b and the first-cell word of every chunk
     // (db_cells_k writes it at a chunk's first cell; the zeros make a chunk without a cell an empty range)
@@ -2227,6 +2380,8 @@ static void db_plan(Arena& a, int64_t n, DbWs& w) {
     w.flag2 = a.take<uint32_t>(nn + 8);
     w.wrank = w.bits ? w.bits + ((ceil_div(nn, 32) + 63) & ~int64_t(63)) : nullptr;
     w.face_todo = reinterpret_cast<uint8_t*>(w.root);
+    w.stage = {w.v1, w.k0, w.v0};
+    w.cell_route = w.meta ? &w.meta->pad[0] : nullptr;
 #ifdef PCH_CS_STAMPS
     w.cs_stamps = reinterpret_cast<unsigned long long*>(w.cell_box);
 #endif
@@ -2437,20 +2592,28 @@ static int db_compress(const DbRun& r, DbGrid& g, int& cellbits, bool& done) {
 
 // the cell keys in sorted order (ks) and the points in that order (w.pts)
 static int db_sorted_keys(const DbRun& r, const DbGrid& g, int cellbits, int nbits, bool compressed, int sort_mode,
-                          const uint64_t*& ks) {
+                          const uint64_t*& ks, bool& staged) {
     const DbWs& w = r.w; const hipStream_t s = r.s; const int64_t n = r.n, nchunks = r.nchunks;
     const unsigned gn = (unsigned)ceil_div(n, DB_THREADS);
     PCH_HIP_TRY(hipMemsetAsync(w.clear_from(), 0, w.clear_bytes(nchunks), s));
+    staged = false;
     // One workgroup per chunk only pays with enough chunks to fill the GPU (measured break-even near
     // 100 chunks of 50 000 rows); PCH_DBSCAN_SORT=chunk / global forces a path (tests compare them)
     if (!compressed && cellbits <= 31 && r.chunk_size <= CS_MAX_CHUNK && sort_mode != 2 &&
         (sort_mode == 1 || nchunks >= CS_MIN_CHUNKS)) {
         // chunk-local path: one workgroup per chunk builds keys, groups the rows by cell and writes them; a chunk with
-        // more cells than db_cellscatter_k's table takes goes through db_chunksort_k (gated by chunk_ovf: no host read)
-        PCH_LAUNCH("db_cellscatter", db_cellscatter_k, dim3((unsigned)nchunks), dim3(CS_THREADS), 0, s, r.xyz, n, g,
-                   w.chunk_bad, w.chunk_ovf, w.pts, w.k1, &w.meta->status);
+        // more cells than db_cellscatter_k's table takes goes through db_chunksort_k (gated by chunk_ovf: no host read).
+        // staged: the chunks leave their cell lists instead of a key per row (db_chunkcells_k's single workgroup
+        // bounds the number of chunks); db_cells_core takes the table from them unless a chunk overflowed
+        staged = nchunks <= DB_TABLE_MAX_CHUNKS;
+        const auto cellscatter = staged ? db_cellscatter_k<true> : db_cellscatter_k<false>;
+        PCH_LAUNCH("db_cellscatter", cellscatter, dim3((unsigned)nchunks), dim3(CS_THREADS), 0, s, r.xyz, n, g,
+                   w.chunk_bad, w.chunk_ovf, w.pts, w.k1, w.stage, &w.meta->status);
         PCH_LAUNCH("db_chunksort", db_chunksort_k, dim3((unsigned)nchunks), dim3(CS_THREADS), 0, s, r.xyz, n, g,
                    w.chunk_ovf, w.chunk_bad, w.xbuf, w.pts, w.k1, &w.meta->status, w.cs_stamps);
+        if (staged)
+            PCH_LAUNCH("db_chunkcells", db_chunkcells_k, dim3(1), dim3(CC_THREADS), 0, s, w.stage.ncell, w.chunk_ovf,
+                       (int)nchunks, n, r.chunk_size, w.chunk_cells, w.cell_start, &w.meta->ncells, w.cell_route);
 #ifdef PCH_CS_STAMPS
         {
             unsigned long long t[11];                    // start | sweep B | sweep H | one per pass | heads
@@ -2483,18 +2646,30 @@ static int db_sorted_keys(const DbRun& r, const DbGrid& g, int cellbits, int nbi
 }
 
 // the cells of the sorted keys, their row table, the core flags and the per-cell statistics; c: the cell table
-static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const uint64_t* ks, bool count_pairs,
-                         DbCells& c) {
+static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const uint64_t* ks, bool staged,
+                         bool count_pairs, DbCells& c) {
     const DbWs& w = r.w; const hipStream_t s = r.s; const int64_t n = r.n;
     const int64_t ntile = ceil_div(n, (int64_t)SCAN_TILE);
-    PCH_LAUNCH("db_heads", db_heads_k, dim3((unsigned)ntile), dim3(DB_THREADS), 0, s, ks, n, w.scan_ws);
-    PCH_TRY(scan_tile_sums_u32(w.scan_ws, ntile, &w.meta->ncells, s));
-    // the cell count sizes the next grids: fetch it while db_cells_k (sized by n) runs
-    DbMeta back;                             // status, ncells
-    PCH_TRY(peek_enqueue(&w.meta->status, 2 * sizeof(uint32_t), s));
-    PCH_LAUNCH("db_cells", db_cells_k, dim3((unsigned)ntile), dim3(DB_THREADS), 0, s, ks, w.scan_ws, n, cellbits,
-               r.nchunks, w.cid, w.cell_start, w.cell_key, w.chunk_cells, w.cell_acc);
-    PCH_TRY(peek_wait(&back.status, 2 * sizeof(uint32_t)));
+    // the cell count sizes the next grids: fetch it while the kernel that writes the table (sized by n) runs
+    DbMeta back;                             // status, ncells ... the route word
+    constexpr size_t peek_bytes = offsetof(DbMeta, pad) + sizeof(uint32_t) - offsetof(DbMeta, status);
+    back.pad[0] = 1u;
+    if (staged) {
+        // db_chunkcells_k left ncells and the route word; db_celltab_k reads the word itself and writes either the
+        // table or the keys that db_chunksort_k did not (then the table is read off the keys below, as ever)
+        PCH_TRY(peek_enqueue(&w.meta->status, peek_bytes, s));
+        PCH_LAUNCH("db_celltab", db_celltab_k, dim3((unsigned)ntile), dim3(DB_THREADS), 0, s, w.cell_route, w.stage,
+                   w.chunk_ovf, w.chunk_cells, n, r.chunk_size, w.cid, w.cell_start, w.cell_key, w.cell_acc, w.k1);
+        PCH_TRY(peek_wait(&back.status, peek_bytes));
+    }
+    if (back.pad[0] != 0u) {
+        PCH_LAUNCH("db_heads", db_heads_k, dim3((unsigned)ntile), dim3(DB_THREADS), 0, s, ks, n, w.scan_ws);
+        PCH_TRY(scan_tile_sums_u32(w.scan_ws, ntile, &w.meta->ncells, s));
+        PCH_TRY(peek_enqueue(&w.meta->status, 2 * sizeof(uint32_t), s));
+        PCH_LAUNCH("db_cells", db_cells_k, dim3((unsigned)ntile), dim3(DB_THREADS), 0, s, ks, w.scan_ws, n, cellbits,
+                   r.nchunks, w.cid, w.cell_start, w.cell_key, w.chunk_cells, w.cell_acc);
+        PCH_TRY(peek_wait(&back.status, 2 * sizeof(uint32_t)));
+    }
     if (back.status != 0) {
         set_error("finite coordinates outside the supplied bounding box");
         return PCH_ERR_ARG;
@@ -2641,8 +2816,9 @@ int pch::dbscan_run(const float* xyz, int64_t n, double eps, int32_t min_samples
     }
     const uint64_t* ks;
     DbCells c;
-    PCH_TRY(db_sorted_keys(r, g, cellbits, nbits, overflow, tune.sort_mode, ks));
-    PCH_TRY(db_cells_core(r, g, cellbits, ks, tune.count_pairs, c));
+    bool staged;
+    PCH_TRY(db_sorted_keys(r, g, cellbits, nbits, overflow, tune.sort_mode, ks, staged));
+    PCH_TRY(db_cells_core(r, g, cellbits, ks, staged, tune.count_pairs, c));
     PCH_TRY(db_union(r, c));
     PCH_TRY(db_labels(r, c, k_host, boxes));
     g_last = {ws, ws_bytes, n, c, r.nchunks, overflow};

@@ -55,6 +55,8 @@ names = {"ms_summary_k": "mean_summary", "ms_walk_k": "mean_walk", "ms_level2_k"
          "db_union_pairs_k": "db_union_pairs", "db_mark_k": "db_mark", "sel_bracket_k": "sel_bracket",
          "sg_hist_k": "seg_hist", "sg_scatter_k": "seg_scatter", "db_union_k": "db_union", "db_border_k": "db_border",
          "gf_compact_k<0>": "gf_compact", "gf_compact_k<1>": "gf_compact_fb", "db_chunksort_k": "db_chunksort", "db_cellscatter_k": "db_cellscatter",
+         "db_cellscatter_k<true>": "db_cellscatter", "db_cellscatter_k<false>": "db_cellscatter",
+         "db_chunkcells_k": "db_chunkcells", "db_celltab_k": "db_celltab",
          "sel_hist_k<0, 1, true>": "sel_hist0",
          "sel_hist_k<1, 1, true>": "sel_hist1", "sel_hist_k<2, 1, true>": "sel_hist2", "rs_scatter_k": "radix_scatter",
          "rs_hist_k": "radix_hist", "db_gather_k": "db_gather", "db_keys_k": "db_keys",
