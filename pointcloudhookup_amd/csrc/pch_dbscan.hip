@@ -1001,38 +1001,56 @@ struct RowSet {
     int ca[DB_ROWS], cb[DB_ROWS];      // cell index range of every row
 };
 
-__device__ __forceinline__ int db_lower(const uint64_t* __restrict__ a, int m, uint64_t k) {
+template <typename K>
+__device__ __forceinline__ int db_lower(const K* __restrict__ a, int m, K k) {
     int lo = 0, hi = m;
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < k) lo = mid + 1; else hi = mid; }
     return lo;
 }
-// cell-index range [x, y) of neighbour row `row` (cells x-2 .. x+2 at (dy, dz) = DB_ROW_DY/DZ[row]) of the cell `key`
-__device__ __forceinline__ int2 db_row_run(const DbGrid& g, const uint64_t* __restrict__ cell_key, uint64_t key,
-                                           int row) {
+// neighbour row `row` (cells x-2 .. x+2 at (dy, dz) = DB_ROW_DY/DZ[row]) of the cell `key`: its y and z and the x range
+// it covers inside the grid; false: the row lies outside
+struct DbRowAt { int xlo, xhi, ny, nz; };
+__device__ __forceinline__ bool db_row_at(const DbGrid& g, uint64_t key, int row, DbRowAt& at) {
     const uint64_t cx = key & ((1ull << g.bx) - 1);
     const uint64_t cy = (key >> g.bx) & ((1ull << g.by) - 1);
     const uint64_t cz = (key >> (g.bx + g.by)) & ((1ull << g.bz) - 1);
+    at.ny = (int)cy + DB_ROW_DY[row];
+    at.nz = (int)cz + DB_ROW_DZ[row];
+    at.xlo = (int)cx - 2 < 0 ? 0 : (int)cx - 2;
+    at.xhi = (int)cx + 2 > g.mx ? g.mx : (int)cx + 2;
+    return at.ny >= 0 && at.ny <= g.my && at.nz >= 0 && at.nz <= g.mz;
+}
+// index range [x, y) of the keys klo .. khi among the sorted, unique a[0 .. n): the five cells of a neighbour row at most
+template <typename K>
+__device__ __forceinline__ int2 db_run_in(const K* __restrict__ a, int n, K klo, K khi) {
+    int2 v;
+    v.x = db_lower(a, n, klo);
+    // the end of the run: cell keys are unique, so at most five cells (x - 2 .. x + 2) follow v.x, their keys
+    // ascending - five loads side by side instead of a second binary search (fourteen dependent loads in a chunk
+    // of 11 000 cells)
+    K kk[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) kk[i] = v.x + i < n ? a[v.x + i] : ~K(0);
+    int cntx = 0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) cntx += kk[i] <= khi ? 1 : 0;
+    v.y = v.x + cntx;
+    return v;
+}
+// cell-index range [x, y) of neighbour row `row` of the cell `key`
+__device__ __forceinline__ int2 db_row_run(const DbGrid& g, const uint64_t* __restrict__ cell_key, uint64_t key,
+                                           int row) {
     const int sh = g.bx + g.by + g.bz;
     const uint64_t chunk = sh < 64 ? (key >> sh) : 0;
-    const int ny = (int)cy + DB_ROW_DY[row], nz = (int)cz + DB_ROW_DZ[row];
     int2 v;
     v.x = 0; v.y = 0;
-    if (ny >= 0 && ny <= g.my && nz >= 0 && nz <= g.mz) {
-        const int xlo = (int)cx - 2 < 0 ? 0 : (int)cx - 2;
-        const int xhi = (int)cx + 2 > g.mx ? g.mx : (int)cx + 2;
+    DbRowAt at;
+    if (db_row_at(g, key, row, at)) {
         const int c0 = (int)g.chunk_cells[chunk], c1 = (int)g.chunk_cells[chunk + 1];   // neighbours share the chunk
-        v.x = c0 + db_lower(cell_key + c0, c1 - c0, db_pack(g, chunk, (uint64_t)nz, (uint64_t)ny, (uint64_t)xlo));
-        // the end of the run: cell keys are unique, so at most five cells (x - 2 .. x + 2) follow v.x, their keys
-        // ascending - five loads side by side instead of a second binary search (fourteen dependent loads in a chunk
-        // of 11 000 cells)
-        const uint64_t khi = db_pack(g, chunk, (uint64_t)nz, (uint64_t)ny, (uint64_t)xhi);
-        uint64_t kk[5];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) kk[i] = v.x + i < c1 ? cell_key[v.x + i] : ~0ull;
-        int cntx = 0;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) cntx += kk[i] <= khi ? 1 : 0;
-        v.y = v.x + cntx;
+        v = db_run_in(cell_key + c0, c1 - c0, db_pack(g, chunk, (uint64_t)at.nz, (uint64_t)at.ny, (uint64_t)at.xlo),
+                      db_pack(g, chunk, (uint64_t)at.nz, (uint64_t)at.ny, (uint64_t)at.xhi));
+        v.x += c0;
+        v.y += c0;
     }
     return v;
 }
@@ -1388,19 +1406,12 @@ __global__ __launch_bounds__(DB_THREADS) void db_cellstats_k(const float4* __res
     }
 }
 
-// accumulators -> bounding box floats (no core point: +inf / -inf) and smallest core row; also
-// resets the union-find forest
-__global__ __launch_bounds__(DB_THREADS) void db_cellfin_k(const uint32_t* __restrict__ acc, int m,
-                                                           float* __restrict__ cell_box,
-                                                           int* __restrict__ cell_min,
-                                                           int* __restrict__ parent,
-                                                           int* __restrict__ comp_min) {
-    const int c = blockIdx.x * DB_THREADS + threadIdx.x;
-    if (c >= m) return;
+// a cell's accumulators -> bounding box floats of its core points (none: +inf / -inf); returns their smallest row
+// (none: INT_BIG)
+__device__ __forceinline__ int db_cell_decode(const uint32_t* __restrict__ acc, int64_t c, float (&box)[6]) {
     uint32_t a[7];
 #pragma unroll
-    for (int k = 0; k < 7; ++k) a[k] = acc[8 * (int64_t)c + k];
-    float box[6];
+    for (int k = 0; k < 7; ++k) a[k] = acc[8 * c + k];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         box[k] = INFINITY;
@@ -1408,10 +1419,21 @@ __global__ __launch_bounds__(DB_THREADS) void db_cellfin_k(const uint32_t* __res
         if (a[k] != 0u) box[k] = f32_unordered(~a[k]);
         if (a[3 + k] != 0u) box[3 + k] = f32_unordered(a[3 + k]);
     }
+    return a[6] != 0u ? (int)(~a[6]) : INT_BIG;
+}
+
+// the decoded accumulators of every cell; also resets the union-find forest (db_chunkunion_k does both for its chunk)
+__global__ __launch_bounds__(DB_THREADS) void db_cellfin_k(const uint32_t* __restrict__ acc, int m,
+                                                           float* __restrict__ cell_box,
+                                                           int* __restrict__ cell_min,
+                                                           int* __restrict__ parent,
+                                                           int* __restrict__ comp_min) {
+    const int c = blockIdx.x * DB_THREADS + threadIdx.x;
+    if (c >= m) return;
+    float box[6];
+    const int mn = db_cell_decode(acc, c, box);
 #pragma unroll
     for (int k = 0; k < 6; ++k) cell_box[6 * (int64_t)c + k] = box[k];
-    int mn = INT_BIG;
-    if (a[6] != 0u) mn = (int)(~a[6]);
     cell_min[c] = mn;
     parent[c] = c;
     comp_min[c] = INT_BIG;
@@ -1544,15 +1566,70 @@ __device__ __forceinline__ DbFace db_face(const DbGrid& g, uint64_t key, int dir
 // parents were in one set at some time, and sets only ever merge
 __device__ __forceinline__ bool db_link_open(const DbGrid& g, const float* __restrict__ cell_box,
                                              const float* __restrict__ boxB, const int* parent, int A, int B) {
-    return !(db_boxbox_d2(cell_box + 6 * (int64_t)A, boxB) > g.eps2) && parent[A] != parent[B];
+    return parent[A] != parent[B] && !(db_boxbox_d2(cell_box + 6 * (int64_t)A, boxB) > g.eps2);
 }
 
-// one wave per core cell A.  Phase 1 (64 candidate cells at a time, one per lane): neighbour core
-// cells B > A whose core boxes are within eps and whose root differs from A's survive.
+// The per-cell words the union rounds read and their forest.  Either the global arrays, indexed by cell (db_union_pairs_k,
+// db_union_face_k, db_union_k), or one chunk's copies in LDS, indexed from the chunk's first cell (db_chunkunion_k).
+// cell_start holds rows of pts either way, so the bodies below are the same code on both.
+struct DbForest {
+    const uint32_t* cell_start; const uint32_t* cell_ncore; const float* cell_box; int* parent;
+};
+
+// may core cell A still need a link to cell B: B core, db_link_open, and the roots differ now
+__device__ __forceinline__ bool db_link_live(const DbGrid& g, const DbForest& f, int A, int B) {
+    bool live = f.cell_ncore[B] != 0 && db_link_open(g, f.cell_box, f.cell_box + 6 * (int64_t)B, f.parent, A, B);
+    if (live) live = uf_find(f.parent, A) != uf_find(f.parent, B);
+    return live;
+}
+
+// The general round for one core cell A, wave-wide; rs: its neighbour rows.  Phase 1 (64 candidate cells at a time,
+// one per lane): neighbour core cells B > A whose core boxes are within eps and whose root differs from A's survive.
 // Phase 2 (wave-wide per survivor): look for one core pair within eps (lanes over B's points,
 // scalar loop over A's points, leave at the first hit), then unite.
-// db_union_face_k has looked at the (up to 3) face-adjacent cells with a larger index before: for
+// The face round has looked at the (up to 3) face-adjacent cells with a larger index before: for
 // dense data they connect at the first tile and leave almost nothing but root comparisons here.
+__device__ __forceinline__ void db_union_cell(const DbGrid& g, const float4* __restrict__ pts,
+                                              const uint8_t* __restrict__ core_s, const DbForest& f, int A,
+                                              const RowSet* rs, int* cd) {
+    const int l = lane_id();
+    int total;
+    {
+        // flatten the <= 25 runs of <= 5 cells into one candidate list (prefix over the run lengths)
+        int len = 0;
+        if (l < DB_ROWS) { len = rs->cb[l] - rs->ca[l]; len = len < 0 ? 0 : len; }
+        const int incl = wave_scan_incl(len);
+        total = __shfl(incl, 63, 64);
+        if (l < DB_ROWS)
+            for (int k = 0; k < len; ++k) cd[incl - len + k] = rs->ca[l] + k;
+    }
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t as = f.cell_start[A], ae = f.cell_start[A + 1];
+    const bool a_dense = f.cell_ncore[A] == (ae - as);
+    for (int base = 0; base < total; base += 64) {
+        int B = -1;
+        if (base + l < total) B = cd[base + l];
+        const bool live = B > A && db_link_live(g, f, A, B);          // every unordered pair once
+        unsigned long long todo = __ballot(live);
+        while (todo) {
+            const int src = (int)__builtin_ctzll(todo);
+            todo &= todo - 1;
+            const int Bs = __builtin_amdgcn_readlane(B, src);
+            {                                              // united meanwhile through another cell?
+                int same = 0;
+                if (l == 0) same = uf_find(f.parent, A) == uf_find(f.parent, Bs);
+                if (__builtin_amdgcn_readfirstlane(same)) continue;
+            }
+            const uint32_t bs = f.cell_start[Bs], be = f.cell_start[Bs + 1];
+            const bool b_dense = f.cell_ncore[Bs] == (be - bs);
+            const float* boxB = f.cell_box + 6 * (int64_t)Bs;
+            const bool connected = db_cells_connected(g, pts, core_s, as, ae, a_dense, bs, be, b_dense, boxB, as);
+            if (connected && l == 0) uf_union(f.parent, A, Bs);
+        }
+    }
+}
+
+// one wave per core cell A
 __global__ __launch_bounds__(DB_THREADS) void db_union_k(DbGrid g, const float4* __restrict__ pts,
                                                          const uint32_t* __restrict__ cell_start,
                                                          const uint64_t* __restrict__ cell_key, int m,
@@ -1566,49 +1643,9 @@ __global__ __launch_bounds__(DB_THREADS) void db_union_k(DbGrid g, const float4*
     const int A = blockIdx.x * DB_WAVES + wave_id();
     if (A >= m) return;
     if (cell_ncore[A] == 0) return;
-    const int l = lane_id();
     RowSet* rs = &rows[wave_id()];
-    int* cd = cand[wave_id()];
-    const uint64_t keyA = cell_key[A];
-    db_rows(g, cell_key, keyA, rs, rowtab, A);
-    int total;
-    {
-        // flatten the <= 25 runs of <= 5 cells into one candidate list (prefix over the run lengths)
-        int len = 0;
-        if (l < DB_ROWS) { len = rs->cb[l] - rs->ca[l]; len = len < 0 ? 0 : len; }
-        const int incl = wave_scan_incl(len);
-        total = __shfl(incl, 63, 64);
-        if (l < DB_ROWS)
-            for (int k = 0; k < len; ++k) cd[incl - len + k] = rs->ca[l] + k;
-    }
-    __builtin_amdgcn_wave_barrier();
-    const uint32_t as = cell_start[A], ae = cell_start[A + 1];
-    const bool a_dense = cell_ncore[A] == (ae - as);
-    for (int base = 0; base < total; base += 64) {
-        int B = -1;
-        if (base + l < total) B = cd[base + l];
-        bool live = false;
-        if (B > A) {                                       // every unordered pair once
-            live = cell_ncore[B] != 0 && db_link_open(g, cell_box, cell_box + 6 * (int64_t)B, parent, A, B);
-            if (live) live = uf_find(parent, A) != uf_find(parent, B);
-        }
-        unsigned long long todo = __ballot(live);
-        while (todo) {
-            const int src = (int)__builtin_ctzll(todo);
-            todo &= todo - 1;
-            const int Bs = __builtin_amdgcn_readlane(B, src);
-            {                                              // united meanwhile through another cell?
-                int same = 0;
-                if (l == 0) same = uf_find(parent, A) == uf_find(parent, Bs);
-                if (__builtin_amdgcn_readfirstlane(same)) continue;
-            }
-            const uint32_t bs = cell_start[Bs], be = cell_start[Bs + 1];
-            const bool b_dense = cell_ncore[Bs] == (be - bs);
-            const float* boxB = cell_box + 6 * (int64_t)Bs;
-            const bool connected = db_cells_connected(g, pts, core_s, as, ae, a_dense, bs, be, b_dense, boxB, as);
-            if (connected && l == 0) uf_union(parent, A, Bs);
-        }
-    }
+    db_rows(g, cell_key, cell_key[A], rs, rowtab, A);
+    db_union_cell(g, pts, core_s, DbForest{cell_start, cell_ncore, cell_box, parent}, A, rs, cand[wave_id()]);
 }
 
 // ROUND 0, first half: one LANE per (cell, face direction).  A wave per cell walks one chain of dependent loads
@@ -1616,8 +1653,53 @@ __global__ __launch_bounds__(DB_THREADS) void db_union_k(DbGrid g, const float4*
 // a few dozen points) that chain, not arithmetic, is the whole cost.  Here 64 such chains are in flight per wave:
 // the lane finds its neighbour, compares boxes and parents and tries the first DB_PAIR_TRIES core points of either
 // cell against each other - adjacent cells almost always connect there - and unites on a hit.  Pairs it cannot
-// decide are flagged in face_todo[cell]; only those cells are looked at by the wave-wide db_union_face_k.
+// decide are flagged in face_todo[cell]; only those cells are looked at by the wave-wide face round.
 constexpr int DB_PAIR_TRIES = 3;
+
+// one lane: core cell A (ncoreA core points) against its face neighbour B (-1: none).  true: undecided
+__device__ __forceinline__ bool db_pair_lane(const DbGrid& g, const float4* __restrict__ pts,
+                                             const uint8_t* __restrict__ core_s, const DbForest& f, int A,
+                                             uint32_t ncoreA, int B) {
+    if (B <= A) return false;
+    const uint32_t nB = f.cell_ncore[B];
+    if (nB == 0) return false;
+    float boxB[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) boxB[a] = f.cell_box[6 * (int64_t)B + a];
+    if (!db_link_open(g, f.cell_box, boxB, f.parent, A, B)) return false;
+    const int rootA = uf_find(f.parent, A), rootB = uf_find(f.parent, B);
+    if (rootA == rootB) return false;
+    const uint32_t as = f.cell_start[A], ae = f.cell_start[A + 1];
+    const uint32_t bs = f.cell_start[B], be = f.cell_start[B + 1];
+    const bool a_dense = ncoreA == (ae - as), b_dense = nB == (be - bs);
+    float4 pb[DB_PAIR_TRIES];
+    int nb = 0;
+    for (uint32_t j = bs; j < be && nb < DB_PAIR_TRIES; ++j) {
+        if (!b_dense && !core_s[j]) continue;
+        const float4 p = pts[j];
+#pragma unroll
+        for (int u = 0; u < DB_PAIR_TRIES; ++u)            // pb stays in registers: no slot indexed by a variable
+            if (u == nb) pb[u] = p;
+        ++nb;
+    }
+    bool connected = false;
+    int na = 0;
+    for (uint32_t i = as; i < ae && na < DB_PAIR_TRIES && !connected; ++i) {
+        if (!a_dense && !core_s[i]) continue;
+        ++na;
+        const float4 pa = pts[i];
+        if (db_box_d2(pa, boxB) > g.eps2) continue;
+#pragma unroll
+        for (int j = 0; j < DB_PAIR_TRIES; ++j)
+            if (j < nb && db_within2(pa, pb[j], g)) connected = true;
+    }
+    if (connected) uf_union(f.parent, rootA, rootB);
+    return !connected;
+}
+// the three face bits of a cell from its four lanes' `undecided` (lanes 4 k .. 4 k + 3 hold cell k's +x, +y, +z, idle)
+__device__ __forceinline__ uint32_t db_pair_bits(bool undecided) {
+    return (uint32_t)((__ballot(undecided) >> (lane_id() & ~3)) & 7ull);
+}
 
 __global__ __launch_bounds__(DB_THREADS) void db_union_pairs_k(DbGrid g, const float4* __restrict__ pts,
                                                                const uint32_t* __restrict__ cell_start,
@@ -1644,114 +1726,55 @@ __global__ __launch_bounds__(DB_THREADS) void db_union_pairs_k(DbGrid g, const f
                 for (int k = run.x; k < run.y; ++k)
                     if (cell_key[k] == f.want) { B = k; break; }
             }
-            if (B > A) {
-                const uint32_t nB = cell_ncore[B];
-                if (nB != 0) {
-                    float boxB[6];
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) boxB[a] = cell_box[6 * (int64_t)B + a];
-                    bool pend = db_link_open(g, cell_box, boxB, parent, A, B);
-                    int rootA = A, rootB = B;
-                    if (pend) {
-                        rootA = uf_find(parent, A);
-                        rootB = uf_find(parent, B);
-                        pend = rootA != rootB;
-                    }
-                    if (pend) {
-                        const uint32_t as = cell_start[A], ae = cell_start[A + 1];
-                        const uint32_t bs = cell_start[B], be = cell_start[B + 1];
-                        const bool a_dense = ncoreA == (ae - as), b_dense = nB == (be - bs);
-                        float4 pb[DB_PAIR_TRIES];
-                        int nb = 0;
-                        for (uint32_t j = bs; j < be && nb < DB_PAIR_TRIES; ++j)
-                            if (b_dense || core_s[j]) pb[nb++] = pts[j];
-                        bool connected = false;
-                        int na = 0;
-                        for (uint32_t i = as; i < ae && na < DB_PAIR_TRIES && !connected; ++i) {
-                            if (!a_dense && !core_s[i]) continue;
-                            ++na;
-                            const float4 pa = pts[i];
-                            if (db_box_d2(pa, boxB) > g.eps2) continue;
-#pragma unroll
-                            for (int j = 0; j < DB_PAIR_TRIES; ++j)
-                                if (j < nb && db_within2(pa, pb[j], g)) connected = true;
-                        }
-                        if (connected) uf_union(parent, rootA, rootB);
-                        else undecided = true;
-                    }
-                }
-            }
+            undecided = db_pair_lane(g, pts, core_s, DbForest{cell_start, cell_ncore, cell_box, parent}, A, ncoreA, B);
         }
     }
-    const unsigned long long um = __ballot(undecided);
-    if (A < m && dir == 0) face_todo[A] = (uint8_t)((um >> (lane_id() & ~3)) & 7ull);
+    const uint32_t bits = db_pair_bits(undecided);
+    if (A < m && dir == 0) face_todo[A] = (uint8_t)bits;
 }
 
-// ROUND 0 as its own kernel: the (up to) three face neighbours with a larger key are examined side
+// ROUND 0, wave-wide: the (up to) three face neighbours with a larger key are examined side
 // by side, 21 lanes each, so that the chain of dependent loads (neighbour lookup, roots, first
 // points) is walked once per cell instead of once per neighbour.  Adjacent dense cells connect at
 // the first point pair; a pair that is still undecided after DB_FACE_TRIES points of A is handed
 // to the full-wave search of the general round.
 constexpr int DB_FACE_TRIES = 8;
 
-__global__ __launch_bounds__(DB_THREADS) void db_union_face_k(DbGrid g, const float4* __restrict__ pts,
-                                                              const uint32_t* __restrict__ cell_start,
-                                                              const uint64_t* __restrict__ cell_key, int m,
-                                                              const int2* __restrict__ rowtab,
-                                                              const uint8_t* __restrict__ core_s,
-                                                              const uint32_t* __restrict__ cell_ncore,
-                                                              const float* __restrict__ cell_box,
-                                                              int* __restrict__ parent,
-                                                              const uint8_t* __restrict__ face_todo) {
-    __shared__ RowSet rows[DB_WAVES];
-    const int A = blockIdx.x * DB_WAVES + wave_id();
-    if (A >= m) return;
-    if (face_todo && face_todo[A] == 0) return;            // db_union_pairs_k has settled this cell's faces
-    const uint32_t ncoreA = cell_ncore[A];
-    if (ncoreA == 0) return;
+// lanes 21 k .. 21 k + 20 are group k (0: +x, 1: +y, 2: +z); lane 63: group 3, idle
+struct DbFaceLane { int grp, gl; unsigned long long gmask; };
+__device__ __forceinline__ DbFaceLane db_face_lane() {
+    const int l = lane_id(), grp = l / 21;
+    return {grp, l - 21 * grp, grp < 3 ? (0x1FFFFFull << (21 * grp)) : 0ull};
+}
+
+// one wave: core cell A (ncoreA core points) against B, its group's face neighbour (-1: none)
+__device__ __forceinline__ void db_face_cell(const DbGrid& g, const float4* __restrict__ pts,
+                                             const uint8_t* __restrict__ core_s, const DbForest& f, int A,
+                                             uint32_t ncoreA, int B) {
     const int l = lane_id();
-    const int grp = l / 21, gl = l - 21 * grp;             // lane 63: group 3, idle
-    const unsigned long long gmask = grp < 3 ? (0x1FFFFFull << (21 * grp)) : 0ull;
-    RowSet* rs = &rows[wave_id()];
-    const uint64_t keyA = cell_key[A];
-    db_rows(g, cell_key, keyA, rs, rowtab, A);
-    int B = -1;
-    {
-        bool found = false;
-        int k = -1;
-        if (grp < 3) {
-            const DbFace f = db_face(g, keyA, grp);
-            if (grp == 0) {
-                k = A + 1;
-                found = gl == 0 && k < m && cell_key[k] == f.want;
-            } else {
-                k = rs->ca[f.row] + gl;
-                found = k < rs->cb[f.row] && cell_key[k] == f.want;
-            }
-        }
-        const unsigned long long fm = __ballot(found) & gmask;
-        if (fm) B = __shfl(k, (int)__builtin_ctzll(fm), 64);
-    }
-    const uint32_t as = cell_start[A], ae = cell_start[A + 1];
+    const DbFaceLane fl = db_face_lane();
+    const int grp = fl.grp, gl = fl.gl;
+    const unsigned long long gmask = fl.gmask;
+    const uint32_t as = f.cell_start[A], ae = f.cell_start[A + 1];
     const bool a_dense = ncoreA == (ae - as);
     const float4 pa0 = pts[as];                            // in flight with the neighbour look-ups below
     uint32_t bs = 0, be = 0;
     bool b_dense = false, pend = false;
     float boxB[6] = {0, 0, 0, 0, 0, 0};
     if (B > A) {
-        const uint32_t nB = cell_ncore[B];
-        bs = cell_start[B];
-        be = cell_start[B + 1];
+        const uint32_t nB = f.cell_ncore[B];
+        bs = f.cell_start[B];
+        be = f.cell_start[B + 1];
         b_dense = nB == (be - bs);
 #pragma unroll
-        for (int a = 0; a < 6; ++a) boxB[a] = cell_box[6 * (int64_t)B + a];
-        pend = nB != 0 && db_link_open(g, cell_box, boxB, parent, A, B);
+        for (int a = 0; a < 6; ++a) boxB[a] = f.cell_box[6 * (int64_t)B + a];
+        pend = nB != 0 && db_link_open(g, f.cell_box, boxB, f.parent, A, B);
     }
     if (gl != 0) pend = false;                             // one lane per group looks the roots up
     int rootA = A, rootB = B;
     if (pend) {
-        rootA = uf_find(parent, A);
-        rootB = uf_find(parent, B);
+        rootA = uf_find(f.parent, A);
+        rootB = uf_find(f.parent, B);
         pend = rootA != rootB;
     }
     pend = __shfl((int)pend, grp < 3 ? 21 * grp : 0, 64) != 0 && grp < 3;
@@ -1772,19 +1795,59 @@ __global__ __launch_bounds__(DB_THREADS) void db_union_face_k(DbGrid g, const fl
             if (__ballot(near) == 0) break;
         }
     }
-    if (connected && gl == 0) uf_union(parent, rootA, rootB);      // starts from the roots found above
+    if (connected && gl == 0) uf_union(f.parent, rootA, rootB);    // starts from the roots found above
     // undecided pairs (rare): the full-wave search, one pair after the other
     unsigned long long todo = __ballot(pend && gl == 0);
     while (todo) {
         const int src = (int)__builtin_ctzll(todo);
         todo &= todo - 1;
         const int Bs = __shfl(B, src, 64);
-        const uint32_t bs2 = cell_start[Bs], be2 = cell_start[Bs + 1];
-        const bool b_dense2 = cell_ncore[Bs] == (be2 - bs2);
-        const float* boxB2 = cell_box + 6 * (int64_t)Bs;
+        const uint32_t bs2 = f.cell_start[Bs], be2 = f.cell_start[Bs + 1];
+        const bool b_dense2 = f.cell_ncore[Bs] == (be2 - bs2);
+        const float* boxB2 = f.cell_box + 6 * (int64_t)Bs;
         const bool conn = db_cells_connected(g, pts, core_s, as, ae, a_dense, bs2, be2, b_dense2, boxB2, ia);
-        if (conn && l == 0) uf_union(parent, A, Bs);
+        if (conn && l == 0) uf_union(f.parent, A, Bs);
     }
+}
+
+__global__ __launch_bounds__(DB_THREADS) void db_union_face_k(DbGrid g, const float4* __restrict__ pts,
+                                                              const uint32_t* __restrict__ cell_start,
+                                                              const uint64_t* __restrict__ cell_key, int m,
+                                                              const int2* __restrict__ rowtab,
+                                                              const uint8_t* __restrict__ core_s,
+                                                              const uint32_t* __restrict__ cell_ncore,
+                                                              const float* __restrict__ cell_box,
+                                                              int* __restrict__ parent,
+                                                              const uint8_t* __restrict__ face_todo) {
+    __shared__ RowSet rows[DB_WAVES];
+    const int A = blockIdx.x * DB_WAVES + wave_id();
+    if (A >= m) return;
+    if (face_todo && face_todo[A] == 0) return;            // db_union_pairs_k has settled this cell's faces
+    const uint32_t ncoreA = cell_ncore[A];
+    if (ncoreA == 0) return;
+    const DbFaceLane fl = db_face_lane();
+    const int grp = fl.grp, gl = fl.gl;
+    RowSet* rs = &rows[wave_id()];
+    const uint64_t keyA = cell_key[A];
+    db_rows(g, cell_key, keyA, rs, rowtab, A);
+    int B = -1;
+    {
+        bool found = false;
+        int k = -1;
+        if (grp < 3) {
+            const DbFace f = db_face(g, keyA, grp);
+            if (grp == 0) {
+                k = A + 1;
+                found = gl == 0 && k < m && cell_key[k] == f.want;
+            } else {
+                k = rs->ca[f.row] + gl;
+                found = k < rs->cb[f.row] && cell_key[k] == f.want;
+            }
+        }
+        const unsigned long long fm = __ballot(found) & fl.gmask;
+        if (fm) B = __shfl(k, (int)__builtin_ctzll(fm), 64);
+    }
+    db_face_cell(g, pts, core_s, DbForest{cell_start, cell_ncore, cell_box, parent}, A, ncoreA, B);
 }
 
 // path compression between the union rounds: afterwards parent[c] is the root of c
@@ -1817,6 +1880,175 @@ __global__ __launch_bounds__(DB_THREADS) void db_mark_k(const int* __restrict__ 
     if (root[c] == c) {                                    // one bit per original row: the smallest core row of a cluster
         const uint32_t r = (uint32_t)comp_min[c];
         atomicOr(&flag[r >> 5], 1u << (r & 31u));
+    }
+}
+
+// ---- the staged route: all of the above for one chunk, in LDS ------------------------------------
+// Neighbours share the chunk, so a chunk's cells [chunk_cells[c], chunk_cells[c + 1]) are a union-find problem of
+// their own, and where the cell table came from the staged lists a chunk holds at most CT_CELLS of them: one
+// workgroup per chunk keeps the cell keys, first rows, core counts, core boxes, smallest core rows and the forest in
+// LDS, indexed from the chunk's first cell, and runs db_cellfin_k, the face round (db_pair_lane, db_face_cell), the
+// flattening, the general round (db_union_cell), db_compmin_k and db_mark_k on them.  A uf_find hop, a neighbour
+// look-up (binary search over the chunk's keys: no row table) and the whole candidate filter then cost LDS
+// latency; global loads are left for the point pairs that prove a link.  Workgroups never wait for one another,
+// and inside one the forest stays lock free (CAS retry only); every barrier below is reached by all threads.
+// The results are the words the seven kernels leave: whether two cells link does not depend on the order of the
+// tests, and the larger root hooks under the smaller, so a component's root is its smallest cell.
+constexpr int CU_THREADS = 1024;
+constexpr int CU_WAVES   = CU_THREADS / 64;
+static_assert(CU_THREADS == CT_CELLS, "a thread per cell of the chunk");
+
+// local index of the cell with key `want` among the chunk's nc sorted keys; -1: no such cell
+__device__ __forceinline__ int cu_cell(const uint32_t* key, int nc, uint32_t want) {
+    const int k = db_lower(key, nc, want);
+    return k < nc && key[k] == want ? k : -1;
+}
+// face neighbour dir of local cell A (db_face; the grid's edge has none)
+__device__ __forceinline__ int cu_face(const DbGrid& g, const uint32_t* key, int nc, int A, int dir) {
+    const uint32_t k = key[A];
+    const DbFace f = db_face(g, k, dir);
+    if (dir == 0) return A + 1 < nc && key[A + 1] == (uint32_t)f.want ? A + 1 : -1;
+    const int at = dir == 1 ? (int)((k >> g.bx) & ((1u << g.by) - 1)) : (int)((k >> (g.bx + g.by)) & ((1u << g.bz) - 1));
+    return at < (dir == 1 ? g.my : g.mz) ? cu_cell(key, nc, (uint32_t)f.want) : -1;
+}
+// db_row_run on the chunk's keys: local range of neighbour row `row` of the cell with key k
+__device__ __forceinline__ int2 cu_row_run(const DbGrid& g, const uint32_t* key, int nc, uint32_t k, int row) {
+    int2 v;
+    v.x = 0; v.y = 0;
+    DbRowAt at;
+    if (db_row_at(g, k, row, at))
+        v = db_run_in(key, nc, (uint32_t)db_pack(g, 0, (uint64_t)at.nz, (uint64_t)at.ny, (uint64_t)at.xlo),
+                      (uint32_t)db_pack(g, 0, (uint64_t)at.nz, (uint64_t)at.ny, (uint64_t)at.xhi));
+    return v;
+}
+
+__global__ __launch_bounds__(CU_THREADS) void db_chunkunion_k(DbGrid g, const float4* __restrict__ pts,
+                                                              const uint32_t* __restrict__ cell_start,
+                                                              const uint64_t* __restrict__ cell_key, int m,
+                                                              const uint8_t* __restrict__ core_s,
+                                                              const uint32_t* __restrict__ cell_ncore,
+                                                              const uint32_t* __restrict__ acc,
+                                                              float* __restrict__ cell_box,
+                                                              int* __restrict__ root,
+                                                              int* __restrict__ comp_min,
+                                                              uint32_t* __restrict__ flag, int64_t n) {
+    __shared__ uint32_t key[CT_CELLS], start[CT_CELLS + 1], ncore[CT_CELLS];
+    __shared__ uint32_t todo[CT_CELLS];                    // face bits of the face round, then row bits of the general one
+    __shared__ float box[6 * CT_CELLS];
+    __shared__ int cmin[CT_CELLS], parent[CT_CELLS];
+    __shared__ RowSet rows[CU_WAVES];
+    __shared__ int cand[CU_WAVES][128];
+    const int tid = threadIdx.x, l = lane_id();
+    // a chunk_cells that is not what db_chunkcells_k writes must neither leave LDS nor the table
+    int first = (int)g.chunk_cells[blockIdx.x], nc = (int)g.chunk_cells[blockIdx.x + 1] - first;
+    first = first < 0 ? 0 : (first > m ? m : first);
+    nc = nc < 0 ? 0 : (nc > CT_CELLS ? CT_CELLS : nc);
+    nc = nc > m - first ? m - first : nc;
+    const DbForest f = {start, ncore, box, parent};
+
+    // db_cellfin_k: the cell's words, its decoded accumulators (cell_box also for db_border_k and later queries)
+    if (tid < nc) {
+        const int64_t c = first + tid;
+        const int sh = g.bx + g.by + g.bz;                 // <= 31 on this route
+        key[tid] = (uint32_t)cell_key[c] & ((1u << sh) - 1u);
+        start[tid] = cell_start[c];
+        if (tid == nc - 1) start[nc] = cell_start[c + 1];
+        ncore[tid] = cell_ncore[c];
+        float b[6];
+        cmin[tid] = db_cell_decode(acc, c, b);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) { box[6 * tid + k] = b[k]; cell_box[6 * c + k] = b[k]; }
+        parent[tid] = tid;
+    }
+    __syncthreads();
+
+    // db_union_pairs_k: four lanes per cell
+    for (int t0 = 0; t0 < 4 * nc; t0 += CU_THREADS) {
+        const int A = (t0 + tid) >> 2, dir = tid & 3;
+        bool undecided = false;
+        if (A < nc && dir < 3) {
+            const uint32_t ncoreA = ncore[A];
+            if (ncoreA != 0) undecided = db_pair_lane(g, pts, core_s, f, A, ncoreA, cu_face(g, key, nc, A, dir));
+        }
+        const uint32_t bits = db_pair_bits(undecided);
+        if (A < nc && dir == 0) todo[A] = bits;
+    }
+    __syncthreads();
+
+    // db_union_face_k: a wave per cell that has a face left
+    for (int A = wave_id(); A < nc; A += CU_WAVES) {
+        const uint32_t ncoreA = ncore[A];
+        if (todo[A] == 0 || ncoreA == 0) continue;
+        const int grp = db_face_lane().grp;
+        db_face_cell(g, pts, core_s, f, A, ncoreA, grp < 3 ? cu_face(g, key, nc, A, grp) : -1);
+    }
+    __syncthreads();
+
+    // db_flatten_k
+    if (tid < nc) {
+        const int r = uf_find(parent, tid);
+        if (r != tid) parent[tid] = r;
+        todo[tid] = 0u;
+    }
+    __syncthreads();
+
+    // db_union_k, its filter first: a lane per (cell, neighbour row) notes the rows that hold a live candidate.  Every
+    // pair is taken from its smaller cell, and the cells are sorted by (z, y, x): only the row of the cell itself and
+    // the 12 rows with dz > 0 or dz == 0 < dy - the odd ones of DB_ROW_DY/DZ - hold a larger cell
+    for (int t0 = 0; t0 < 16 * nc; t0 += CU_THREADS) {
+        const int A = (t0 + tid) >> 4, u = tid & 15, row = u == 0 ? 0 : 2 * u - 1;
+        if (A < nc && u < 13 && ncore[A] != 0) {
+            const int2 run = cu_row_run(g, key, nc, key[A], row);
+            const int pA = parent[A];
+            uint32_t open = 0u;                            // what the parents alone leave of the (up to) five, side by side
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                const int B = run.x + i;
+                if (B < run.y && B > A && parent[B] != pA) open |= 1u << i;
+            }
+            bool live = false;
+            while (open != 0u && !live) {
+                const int i = __builtin_ctz(open);
+                open &= open - 1u;
+                live = db_link_live(g, f, A, run.x + i);
+            }
+            if (live) atomicOr(&todo[A], 1u << row);
+        }
+    }
+    __syncthreads();
+    // ... then a wave per cell with such rows, on those rows
+    for (int A = wave_id(); A < nc; A += CU_WAVES) {
+        const uint32_t live_rows = todo[A];
+        if (live_rows == 0) continue;
+        RowSet* rs = &rows[wave_id()];
+        if (l < DB_ROWS) {
+            int2 v;
+            v.x = 0; v.y = 0;
+            if ((live_rows >> l) & 1u) v = cu_row_run(g, key, nc, key[A], l);
+            rs->ca[l] = v.x;
+            rs->cb[l] = v.y;
+        }
+        __builtin_amdgcn_wave_barrier();
+        db_union_cell(g, pts, core_s, f, A, rs, cand[wave_id()]);
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+
+    // db_compmin_k and db_mark_k: every core cell's root, the component's smallest core row on it, its bit
+    int r = -1;
+    if (tid < nc && ncore[tid] != 0) {
+        r = uf_find(parent, tid);
+        if (r != tid) atomicMin(&cmin[r], cmin[tid]);      // only roots are written, only other cells write
+    }
+    __syncthreads();
+    if (tid < nc) {
+        const int64_t c = first + tid;
+        root[c] = r < 0 ? -1 : first + r;
+        comp_min[c] = r == tid ? cmin[tid] : INT_BIG;
+        if (r == tid) {
+            const uint32_t row = (uint32_t)cmin[tid];  // a core cell's smallest core row: below n
+            if ((int64_t)row < n) atomicOr(&flag[row >> 5], 1u << (row & 31u));
+        }
     }
 }
 
@@ -2393,6 +2625,8 @@ struct DbCells {
     DbGrid g; const float4* pts; const uint32_t* cell_start; const uint64_t* cell_key; int m;
     const int2* rowtab;          // null: more cells than the row table holds, rows are searched on the fly
     const uint8_t* core_s; const uint32_t* cell_ncore; const float* cell_box;
+    bool chunk_union;            // the table came from the staged lists (no chunk beyond CT_CELLS cells): db_union runs
+                                 // db_chunkunion_k, which also does db_cellfin_k's and db_mark_k's work
 };
 #define DB_GRID_ARGS(c) (c).g, (c).pts, (c).cell_start, (c).cell_key, (c).m, (c).rowtab
 #define DB_CELL_ARGS(c) DB_GRID_ARGS(c), (c).core_s, (c).cell_ncore, (c).cell_box
@@ -2677,7 +2911,7 @@ static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const ui
     const int m = (int)back.ncells;
     const unsigned gc = (unsigned)ceil_div(m, DB_WAVES);
     c = {g, w.pts, w.cell_start, w.cell_key, m, m <= w.rowtab_cells ? w.rowtab : nullptr, w.core_s, w.cell_ncore,
-         w.cell_box};
+         w.cell_box, staged && back.pad[0] == 0u};
     if (c.rowtab)
         PCH_LAUNCH("db_rowtab", db_rowtab_k, dim3((unsigned)ceil_div(m, 2 * DB_WAVES)), dim3(DB_THREADS), 0, s, g,
                    w.cell_key, m, w.rowtab);
@@ -2691,8 +2925,9 @@ static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const ui
     }
     PCH_LAUNCH("db_cellstats", db_cellstats_k, dim3((unsigned)ceil_div(n, (int64_t)DB_WAVES * 64 * DB_CS_ROUNDS)),
                dim3(DB_THREADS), 0, s, w.pts, w.cid, w.core_s, n, w.cell_acc, w.bits, ceil_div(n, 32));
-    PCH_LAUNCH("db_cellfin", db_cellfin_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
-               w.cell_acc, m, w.cell_box, w.cell_min, w.parent, w.comp_min);
+    if (!c.chunk_union)
+        PCH_LAUNCH("db_cellfin", db_cellfin_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
+                   w.cell_acc, m, w.cell_box, w.cell_min, w.parent, w.comp_min);
     return PCH_OK;
 }
 
@@ -2700,6 +2935,12 @@ static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const ui
 static int db_union(const DbRun& r, const DbCells& c) {
     const DbWs& w = r.w; const hipStream_t s = r.s; const int m = c.m;
     const unsigned gc = (unsigned)ceil_div(m, DB_WAVES);
+    if (c.chunk_union) {                                 // every chunk on its own, in LDS; parent and cell_min stay unused
+        PCH_LAUNCH("db_chunkunion", db_chunkunion_k, dim3((unsigned)r.nchunks), dim3(CU_THREADS), 0, s, c.g, c.pts,
+                   c.cell_start, c.cell_key, m, c.core_s, c.cell_ncore, w.cell_acc, w.cell_box, w.root, w.comp_min,
+                   w.bits, r.n);
+        return PCH_OK;
+    }
     // face neighbours: lane-per-pair first (needs the row table), the wave-wide search for what that left open
     if (c.rowtab)
         PCH_LAUNCH("db_union_pairs", db_union_pairs_k, dim3((unsigned)ceil_div(4 * (int64_t)m, DB_THREADS)),
@@ -2721,8 +2962,9 @@ static int db_labels(const DbRun& r, const DbCells& c, int32_t* k_host, DbBoxOut
     // word counts (n/32 elements instead of n)
     const int64_t nw = ceil_div(n, 32);
     static_assert(DB_CS_ROUNDS * 64 * DB_WAVES / DB_THREADS <= 32, "db_cellstats_k's grid has a thread per bitmap word");
-    PCH_LAUNCH("db_mark", db_mark_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
-               w.root, w.comp_min, m, w.bits);
+    if (!c.chunk_union)
+        PCH_LAUNCH("db_mark", db_mark_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
+                   w.root, w.comp_min, m, w.bits);
     // word ranks: popcount on load
     if (scan1_pays(nw)) PCH_TRY(scan1_exclusive_popc_u32(w.bits, w.wrank, nw, w.scan1_b, &w.meta->nclusters, s));
     else PCH_TRY(scan_exclusive_popc_u32(w.bits, w.wrank, nw, w.scan_ws, &w.meta->nclusters, s));
