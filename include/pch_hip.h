@@ -45,7 +45,7 @@ extern "C" {
 #define PCH_ERR_TIMEOUT     -6   /* a device-side wait between workgroups ran out of its budget (see below) */
 
 /* Device-side waits are bounded.  The order-preserving compactions (pch_ground_filter_f32, pch_filter_gt_f32,
- * pch_crop_aabb_f64, pch_crop_boxes_f64) and the voxel finisher (pch_voxel_downsample_f64) chain their workgroups by a single-pass
+ * pch_filter_plane_f32, pch_crop_aabb_f64, pch_crop_boxes_f64) and the voxel finisher (pch_voxel_downsample_f64) chain their workgroups by a single-pass
  * look-back: a workgroup polls the status words of the workgroups in front of it.  Every such poll loop has a
  * wall-clock budget (4 s); a workgroup that exceeds it gives up, the kernel drains, and the call's count word
  * (*out_count / *out_m, device memory) reads NEGATIVE instead of holding a count - the outputs are then
@@ -229,6 +229,47 @@ int pch_ground_filter_f32(const float* raw, int64_t n, double pct, float offset,
                           float* out_points, int32_t* out_index, float* out_scalars,
                           int64_t* out_count, float* out_aabb,
                           void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------ stage B, opt-in: one RANSAC ground plane
+ * The second ground rule, for sloped terrain: a plane z = a x + b y + c fitted by RANSAC on z ~ (x, y) instead of one
+ * global percentile.  Replaces: test/main_ground.py:8-32 (remove_ground_ransac; RANSACRegressor with
+ * residual_threshold 0.1).  Frame: P = fl32(raw - centroid) as in stage B; everything below is float64 on (double)P
+ * in exactly the written association, without FMA.
+ *   plane of hypothesis h from p0, p1, p2 = P[rows[h]]:  u = p1 - p0, v = p2 - p0,
+ *     nx = u.y v.z - u.z v.y, ny = u.z v.x - u.x v.z, nz = u.x v.y - u.y v.x, nn = (nx nx + ny ny) + nz nz;
+ *     valid iff nn is finite, nz != 0 and nz nz >= cos2_max_slope nn (the slope gate: a tower face is no ground);
+ *     a = -nx / nz, b = -ny / nz, c = p0.z - (a p0.x + b p0.y); a non-finite a, b or c invalidates it too, and so does
+ *     a row outside [0, n).  Repeats in a triple are not rejected: such a triple is degenerate, hence invalid.
+ *   residual of row i: r = z - ((a x + b y) + c); inlier iff |r| <= residual_threshold (a NaN row never is)
+ *   best: the valid hypothesis with the most inliers, the smallest h on a tie; -1 if none is valid.  No refit.
+ * pch_plane_fit_f32 (test/main_ground.py:21-28):
+ *   raw [n,3] float32, 0 <= n < 2^31; centroid3_dev [3] float32 (DEVICE: what pch_mean_seq_f32 wrote);
+ *   rows_dev [nhyp,3] int64 (device), 1 <= nhyp <= 4096
+ *   out_planes [nhyp,4] float64: a, b, c, valid (1.0 / 0.0); an invalid hypothesis is four zeros
+ *   out_counts [nhyp] int64: inliers over all n rows, 0 for an invalid hypothesis
+ *   out_best_dev: DEVICE record; a = b = c = 0, count = 0, best = -1 when no hypothesis is valid (always so for n == 0)
+ *   Asynchronous: enqueues and returns, fit and filter chain through out_best_dev without a host read.  The inlier
+ *   count takes the cloud in passes of 1024 rows per workgroup.  The workspace is reserved (0 bytes today).
+ * pch_filter_plane_f32 (test/main_ground.py:28-30): the order-preserving compaction of pch_filter_gt_f32 with the
+ *   plane of best_dev as the rule - keep_mode 0: keep r > offset_or_threshold (height above the fitted ground, the
+ *   analogue of z > base + offset); keep_mode 1: keep !(|r| <= offset_or_threshold), i.e. ~inlier_mask_, NaN rows
+ *   included.  best < 0 keeps nothing.  Outputs as pch_filter_gt_f32 (out_aabb over the finite kept rows, zeros if
+ *   there are none); *out_count reads negative after a bounded wait that ran out (above).  Asynchronous. */
+typedef struct PchPlaneBest {
+    double  a, b, c;          /* z = a x + b y + c in the centred frame */
+    int64_t count;            /* inliers of the best hypothesis */
+    int32_t best;             /* its index, -1: no valid hypothesis */
+    int32_t nvalid;           /* valid hypotheses */
+} PchPlaneBest;
+size_t pch_plane_fit_ws_bytes(int64_t n, int32_t nhyp);
+int pch_plane_fit_f32(const float* raw, int64_t n, const float* centroid3_dev, const int64_t* rows_dev, int32_t nhyp,
+                      double residual_threshold, double cos2_max_slope, double* out_planes /*[nhyp,4]: a,b,c,valid*/,
+                      int64_t* out_counts /*[nhyp]*/, PchPlaneBest* out_best_dev, void* ws, size_t ws_bytes,
+                      void* stream);
+size_t pch_filter_plane_ws_bytes(int64_t n);
+int pch_filter_plane_f32(const float* raw, int64_t n, const float* centroid3_dev, const PchPlaneBest* best_dev,
+                         int32_t keep_mode, double offset_or_threshold, float* out_points, int32_t* out_index,
+                         int64_t* out_count, float* out_aabb, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ stage C
  * sklearn.cluster.DBSCAN(eps, min_samples, algorithm='ball_tree').fit(chunk).labels_ for

@@ -54,6 +54,10 @@ _SIGS = {
     "pch_ground_filter_ws_bytes": (_sz, [_i64]),
     "pch_ground_filter_f32": (C.c_int, [_vp, _i64, _f64, _f32, _f32, _i64, _vp, _vp, _vp, _vp, _vp,
                                         _vp, _sz, _vp]),
+    "pch_plane_fit_ws_bytes": (_sz, [_i64, _i32]),
+    "pch_plane_fit_f32": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pch_filter_plane_ws_bytes": (_sz, [_i64]),
+    "pch_filter_plane_f32": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pch_dbscan_set_sort_mode": (None, [C.c_int]),
     "pch_first_nonfinite_row_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
     "pch_dbscan_relabel_i32": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _sz, _vp]),
@@ -109,6 +113,12 @@ class CropBoxC(C.Structure):
     """PchCropBox (include/pch_hip.h)."""
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("lo", C.c_double * 3), ("hi", C.c_double * 3),
                 ("center", C.c_double * 3), ("axes", C.c_double * 9), ("half", C.c_double * 3)]
+
+
+class PlaneBestC(C.Structure):
+    """PchPlaneBest (include/pch_hip.h)."""
+    _fields_ = [("a", C.c_double), ("b", C.c_double), ("c", C.c_double), ("count", C.c_int64),
+                ("best", C.c_int32), ("nvalid", C.c_int32)]
 
 
 _lib = None

@@ -1,0 +1,326 @@
+// Opt-in second ground rule of stage B: one global RANSAC plane z ~ (x, y) instead of one global percentile.
+// Reference: test/main_ground.py:8-32 (remove_ground_ransac: RANSACRegressor on z ~ (x, y), residual_threshold 0.1,
+// the rows off the plane are "non-ground").  The rule, in the frame of stage B (P = fl32(raw - centroid), then
+// float64 in exactly the written association, no FMA: the library is built with -ffp-contract=off):
+//   plane of the triple (p0, p1, p2):  u = p1 - p0, v = p2 - p0, n = u x v, nn = (nx nx + ny ny) + nz nz
+//       valid iff nn finite, nz != 0, nz nz >= cos2 nn (slope gate), and a, b, c below finite
+//       a = -nx / nz, b = -ny / nz, c = p0.z - (a p0.x + b p0.y)
+//   residual of a row:  r = z - ((a x + b y) + c);  inlier iff |r| <= residual_threshold (NaN: never)
+//   best: the valid hypothesis with the most inliers, the smallest index on a tie; none valid: -1
+//   filter: keep r > offset ("above"), or keep !(|r| <= residual_threshold) ("off_plane", ~inlier_mask_)
+// No refit on the inliers (sklearn's inlier_mask_ is the best trial's mask too).
+#include "pch_common.h"
+#include "pch_lookback.h"
+
+namespace pch {
+
+constexpr int PL_THREADS = 256;
+constexpr int PL_ROWS    = 4;                           // rows a lane keeps as centred doubles
+constexpr int PL_TILE    = PL_THREADS * PL_ROWS;        // 1024 rows per workgroup pass of pl_count_k
+constexpr int PL_MAX_HYP = 4096;
+constexpr int PL_GRID    = 2048;                        // workgroups of pl_count_k at most (grid-stride beyond)
+
+struct PlPlane { double a, b, c, valid; };              // out_planes row; an invalid hypothesis is four zeros
+struct PlRow3 { float x, y, z; };
+typedef double PlVec4 __attribute__((ext_vector_type(4)));   // a PlPlane read as ONE 32-byte load
+
+// ---- step 2: one thread per hypothesis
+__global__ void pl_planes_k(const float* __restrict__ raw, int64_t n, const float* __restrict__ centroid,
+                            const int64_t* __restrict__ rows, int nhyp, double cos2, PlPlane* __restrict__ planes) {
+    const int h = blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= nhyp) return;
+    PlPlane out = {0.0, 0.0, 0.0, 0.0};
+    const int64_t i0 = rows[3 * h], i1 = rows[3 * h + 1], i2 = rows[3 * h + 2];
+    if (i0 >= 0 && i0 < n && i1 >= 0 && i1 < n && i2 >= 0 && i2 < n) {      // a row outside the cloud: invalid
+        const float cen[3] = {centroid[0], centroid[1], centroid[2]};
+        const PlRow3* __restrict__ r3 = reinterpret_cast<const PlRow3*>(raw);
+        const PlRow3 q0 = r3[i0], q1 = r3[i1], q2 = r3[i2];
+        const double p0x = (double)(q0.x - cen[0]), p0y = (double)(q0.y - cen[1]), p0z = (double)(q0.z - cen[2]);
+        const double ux = (double)(q1.x - cen[0]) - p0x, uy = (double)(q1.y - cen[1]) - p0y,
+                     uz = (double)(q1.z - cen[2]) - p0z;
+        const double vx = (double)(q2.x - cen[0]) - p0x, vy = (double)(q2.y - cen[1]) - p0y,
+                     vz = (double)(q2.z - cen[2]) - p0z;
+        const double nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
+        const double nn = (nx * nx + ny * ny) + nz * nz;
+        if (fabs(nn) < INFINITY && nz != 0.0 && nz * nz >= cos2 * nn) {
+            const double a = -nx / nz, b = -ny / nz;
+            const double c = p0z - (a * p0x + b * p0y);
+            if (fabs(a) < INFINITY && fabs(b) < INFINITY && fabs(c) < INFINITY) out = {a, b, c, 1.0};
+        }
+    }
+    planes[h] = out;
+}
+
+// ---- step 3, the hot kernel: nhyp x n residual tests in float64.  A lane keeps PL_ROWS rows as centred doubles; the
+// loop over the hypotheses reads the plane wave-uniformly (scalar loads) and skips an invalid one with a uniform
+// branch; a ballot per row round gives a wave-uniform count, which lands in lane (h & 63) of one accumulator register
+// and goes to the workgroup's LDS counters once per 64 hypotheses, to the global counters once per workgroup.
+// Nothing waits on another workgroup.  Rows beyond n are NaN: never inliers.
+__global__ __launch_bounds__(PL_THREADS) void pl_count_k(const float* __restrict__ raw, int64_t n,
+                                                         const float* __restrict__ centroid,
+                                                         const PlPlane* __restrict__ planes, int nhyp, double thr,
+                                                         unsigned long long* __restrict__ counts) {
+    __shared__ uint32_t cnt_sh[PL_MAX_HYP];             // < 2^31 rows in all: 32 bits hold a workgroup's share
+    for (int h = threadIdx.x; h < nhyp; h += PL_THREADS) cnt_sh[h] = 0u;
+    __syncthreads();
+    const float cen[3] = {centroid[0], centroid[1], centroid[2]};
+    const PlRow3* __restrict__ r3 = reinterpret_cast<const PlRow3*>(raw);
+    const int l = lane_id();
+    const int64_t ntiles = (n + PL_TILE - 1) / PL_TILE;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t seg = tile * PL_TILE + (int64_t)wave_id() * (64 * PL_ROWS);
+        if (seg >= n) continue;                         // wave-uniform: nothing of this wave's share exists
+        double x[PL_ROWS], y[PL_ROWS], z[PL_ROWS];
+#pragma unroll
+        for (int r = 0; r < PL_ROWS; ++r) {
+            const int64_t i = seg + r * 64 + l;
+            const PlRow3 q = r3[i < n ? i : n - 1];
+            const double nan = __longlong_as_double(0x7ff8000000000000ll);
+            x[r] = i < n ? (double)(q.x - cen[0]) : nan;
+            y[r] = i < n ? (double)(q.y - cen[1]) : nan;
+            z[r] = i < n ? (double)(q.z - cen[2]) : nan;
+        }
+        for (int hb = 0; hb < nhyp; hb += 64) {
+            uint32_t acc = 0u;
+            const int he = nhyp - hb < 64 ? nhyp - hb : 64;
+            for (int j = 0; j < he; ++j) {
+                const PlVec4 p = reinterpret_cast<const PlVec4*>(planes)[hb + j];      // a, b, c, valid
+                if (p.w != 0.0) {
+                    uint32_t c = 0u;
+#pragma unroll
+                    for (int r = 0; r < PL_ROWS; ++r) {
+                        const double res = z[r] - ((p.x * x[r] + p.y * y[r]) + p.z);
+                        c += (uint32_t)__popcll(__ballot(fabs(res) <= thr));
+                    }
+                    acc = l == j ? c : acc;
+                }
+            }
+            if (acc) atomicAdd(&cnt_sh[hb + l], acc);
+        }
+    }
+    __syncthreads();
+    for (int h = threadIdx.x; h < nhyp; h += PL_THREADS) {
+        const uint32_t c = cnt_sh[h];
+        if (c) atomicAdd(&counts[h], (unsigned long long)c);
+    }
+}
+
+// ---- step 4: one workgroup; the key orders by count first and by the LOWER index second, 0 = no valid hypothesis
+__global__ __launch_bounds__(PL_THREADS) void pl_best_k(const PlPlane* __restrict__ planes,
+                                                        const int64_t* __restrict__ counts, int nhyp,
+                                                        PchPlaneBest* __restrict__ best) {
+    __shared__ unsigned long long key_sh[PL_THREADS / 64];
+    __shared__ uint32_t nv_sh[PL_THREADS / 64];
+    unsigned long long key = 0ull;
+    uint32_t nv = 0u;
+    for (int h = threadIdx.x; h < nhyp; h += PL_THREADS) {
+        if (planes[h].valid == 0.0) continue;
+        ++nv;
+        const unsigned long long k = ((unsigned long long)(counts[h] + 1) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)h);
+        key = k > key ? k : key;
+    }
+    key = wave_reduce_max(key);
+    nv = wave_reduce_add(nv);
+    if (lane_id() == 0) { key_sh[wave_id()] = key; nv_sh[wave_id()] = nv; }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int w = 1; w < PL_THREADS / 64; ++w) {
+        key = key_sh[w] > key ? key_sh[w] : key;
+        nv += nv_sh[w];
+    }
+    PchPlaneBest out = {0.0, 0.0, 0.0, 0, -1, (int32_t)nv};
+    if (key) {
+        const int h = (int)(0xFFFFFFFFu - (uint32_t)key);
+        out.a = planes[h].a;
+        out.b = planes[h].b;
+        out.c = planes[h].c;
+        out.count = counts[h];
+        out.best = h;
+    }
+    *best = out;
+}
+
+// ---- step 5: order-preserving compaction in one sweep, the skeleton of crop_aabb_k (pch_view.hip): tiles by ticket,
+// the tile's offset from the look-back, the count word with the sign-bit failure mark; what is emitted and how the
+// box is folded follows gf_emit / gf_fold_box (pch_filter.hip)
+constexpr int PF_ROUNDS = 8;
+constexpr int PF_TILE   = PL_THREADS * PF_ROUNDS;       // 2048 rows per workgroup
+constexpr int PF_SLOTS  = 64;
+
+struct PfState {
+    uint32_t ticket, pad[3];
+    uint32_t slots[PF_SLOTS][6];                        // ~ordered(min xyz) / ordered(max xyz), folded with atomicMax
+};
+
+__global__ __launch_bounds__(PL_THREADS) void pl_filter_k(const float* __restrict__ raw, int64_t n,
+                                                          const float* __restrict__ centroid,
+                                                          const PchPlaneBest* __restrict__ best, int keep_mode,
+                                                          double val, PfState* __restrict__ st,
+                                                          uint64_t* __restrict__ status, float* __restrict__ out_points,
+                                                          int32_t* __restrict__ out_index,
+                                                          int64_t* __restrict__ out_count) {
+    __shared__ uint32_t wtot[PL_THREADS / 64];
+    __shared__ uint32_t tile_sh, excl_sh;
+    __shared__ uint32_t box[PL_THREADS / 64][6];
+    if (best->best < 0) return;                         // no plane: nothing is kept, the count word stays 0
+    if (threadIdx.x == 0) tile_sh = atomicAdd(&st->ticket, 1u);
+    __syncthreads();
+    const int64_t tile = tile_sh;
+    const double pa = best->a, pb = best->b, pc = best->c;
+    const float cen[3] = {centroid[0], centroid[1], centroid[2]};
+    const int w = wave_id(), l = lane_id();
+    const int64_t seg = tile * PF_TILE + (int64_t)w * (64 * PF_ROUNDS);
+    const PlRow3* __restrict__ r3 = reinterpret_cast<const PlRow3*>(raw);
+    PlRow3 q[PF_ROUNDS];
+    unsigned long long m[PF_ROUNDS];
+    uint32_t run = 0;
+#pragma unroll
+    for (int r = 0; r < PF_ROUNDS; ++r) {
+        const int64_t i = seg + r * 64 + l;
+        q[r] = r3[i < n ? i : 0];
+    }
+#pragma unroll
+    for (int r = 0; r < PF_ROUNDS; ++r) {
+        const int64_t i = seg + r * 64 + l;
+        q[r].x -= cen[0];                               // points = raw_points - centroid (float32)
+        q[r].y -= cen[1];
+        q[r].z -= cen[2];
+        const double res = (double)q[r].z - ((pa * (double)q[r].x + pb * (double)q[r].y) + pc);
+        const bool keep = i < n && (keep_mode == 0 ? res > val : !(fabs(res) <= val));
+        m[r] = __ballot(keep);
+        run += (uint32_t)__popcll(m[r]);
+    }
+    if (l == 0) wtot[w] = run;
+    __syncthreads();
+    const uint32_t T = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    if (w == 0) {
+        const uint32_t e0 = gf_lookback(status, tile, T);
+        const bool lb_failed = e0 == GF_LB_FAILED;
+        const uint32_t e = lb_failed ? 0u : e0;              // prefix 0 keeps the writes below inside the output
+        if (l == 0) {
+            excl_sh = e;
+            // out_count starts at 0: the last tile adds the total, a tile whose wait ran out sets the sign bit
+            unsigned long long* oc = reinterpret_cast<unsigned long long*>(out_count);
+            if (lb_failed) atomicOr(oc, 1ull << 63);
+            else if (tile == (int64_t)gridDim.x - 1) atomicAdd(oc, (unsigned long long)e + T);
+        }
+    }
+    __syncthreads();
+    if (T == 0) return;
+    uint32_t woff = excl_sh;
+    for (int w2 = 0; w2 < w; ++w2) woff += wtot[w2];
+    const uint64_t lt = lanemask_lt();
+    uint32_t lo[3] = {0u, 0u, 0u}, hi[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int r = 0; r < PF_ROUNDS; ++r) {
+        if ((m[r] >> l) & 1ull) {
+            const int64_t o = (int64_t)woff + (uint32_t)__popcll(m[r] & lt);
+            const float v[3] = {q[r].x, q[r].y, q[r].z};
+            out_points[3 * o + 0] = v[0];
+            out_points[3 * o + 1] = v[1];
+            out_points[3 * o + 2] = v[2];
+            if (out_index) out_index[o] = (int32_t)(seg + r * 64 + l);
+            if (fabsf(v[0]) < INFINITY && fabsf(v[1]) < INFINITY && fabsf(v[2]) < INFINITY) {   // NaN/inf rows
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const uint32_t kk = f32_ordered(v[a]);
+                    lo[a] = ~kk > lo[a] ? ~kk : lo[a];
+                    hi[a] = kk > hi[a] ? kk : hi[a];
+                }
+            }
+        }
+        woff += (uint32_t)__popcll(m[r]);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = wave_reduce_max(lo[a]);
+        hi[a] = wave_reduce_max(hi[a]);
+        if (l == 0) { box[w][a] = lo[a]; box[w][3 + a] = hi[a]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const int a = threadIdx.x;
+        uint32_t v = box[0][a];
+        for (int w2 = 1; w2 < PL_THREADS / 64; ++w2) v = box[w2][a] > v ? box[w2][a] : v;
+        if (v) atomicMax(&st->slots[tile % PF_SLOTS][a], v);
+    }
+}
+
+// the bounding box of the finite kept rows; zeros when there are none (as gf_finalize_k reports it)
+__global__ void pl_box_k(const PfState* __restrict__ st, float* __restrict__ out_aabb) {
+    const int a = threadIdx.x;
+    if (a >= 6) return;
+    uint32_t v = 0u;
+    for (int k = 0; k < PF_SLOTS; ++k) { const uint32_t u = st->slots[k][a]; v = u > v ? u : v; }
+    out_aabb[a] = v == 0u ? 0.0f : f32_unordered(a < 3 ? ~v : v);
+}
+
+}  // namespace pch
+
+using namespace pch;
+
+extern "C" size_t pch_plane_fit_ws_bytes(int64_t n, int32_t nhyp) {
+    (void)n;
+    (void)nhyp;
+    return 0;                                           // the counters live in LDS and in out_counts
+}
+
+extern "C" int pch_plane_fit_f32(const float* raw, int64_t n, const float* centroid3_dev, const int64_t* rows_dev,
+                                 int32_t nhyp, double residual_threshold, double cos2_max_slope, double* out_planes,
+                                 int64_t* out_counts, PchPlaneBest* out_best_dev, void* ws, size_t ws_bytes,
+                                 void* stream) {
+    (void)ws;
+    (void)ws_bytes;
+    PCH_DEVICE_GUARD(out_best_dev);
+    hipStream_t s = (hipStream_t)stream;
+    PCH_REQUIRE(n >= 0 && n < (int64_t(1) << 31) && nhyp >= 1 && nhyp <= PL_MAX_HYP, "bad argument");
+    PCH_REQUIRE(out_planes && out_counts && out_best_dev, "null output");
+    static_assert(sizeof(PlPlane) == 4 * sizeof(double), "out_planes is [nhyp,4] float64");
+    PlPlane* planes = reinterpret_cast<PlPlane*>(out_planes);
+    PCH_HIP_TRY(hipMemsetAsync(out_counts, 0, (size_t)nhyp * sizeof(int64_t), s));
+    if (n == 0) {                                       // no row to draw from: every hypothesis is invalid
+        PCH_HIP_TRY(hipMemsetAsync(out_planes, 0, (size_t)nhyp * sizeof(PlPlane), s));
+    } else {
+        PCH_REQUIRE(raw && centroid3_dev && rows_dev, "null input");
+        PCH_LAUNCH("pl_planes", pl_planes_k, dim3((unsigned)ceil_div(nhyp, 64)), dim3(64), 0, s, raw, n, centroid3_dev,
+                   rows_dev, (int)nhyp, cos2_max_slope, planes);
+        const int64_t nt = ceil_div(n, PL_TILE);
+        PCH_LAUNCH("pl_count", pl_count_k, dim3((unsigned)(nt < PL_GRID ? nt : PL_GRID)), dim3(PL_THREADS), 0, s, raw,
+                   n, centroid3_dev, (const PlPlane*)planes, (int)nhyp, residual_threshold,
+                   reinterpret_cast<unsigned long long*>(out_counts));
+    }
+    PCH_LAUNCH("pl_best", pl_best_k, dim3(1), dim3(PL_THREADS), 0, s, (const PlPlane*)planes,
+               (const int64_t*)out_counts, (int)nhyp, out_best_dev);
+    return PCH_OK;
+}
+
+extern "C" size_t pch_filter_plane_ws_bytes(int64_t n) {
+    if (n < 0) return 0;
+    Arena a;
+    a.take<PfState>(1);
+    a.take<uint64_t>(ceil_div(n > 0 ? n : 1, PF_TILE));
+    return a.off;
+}
+
+extern "C" int pch_filter_plane_f32(const float* raw, int64_t n, const float* centroid3_dev,
+                                    const PchPlaneBest* best_dev, int32_t keep_mode, double offset_or_threshold,
+                                    float* out_points, int32_t* out_index, int64_t* out_count, float* out_aabb,
+                                    void* ws, size_t ws_bytes, void* stream) {
+    PCH_DEVICE_GUARD(out_count);
+    hipStream_t s = (hipStream_t)stream;
+    PCH_REQUIRE(n >= 0 && n < (int64_t(1) << 31) && out_count && (keep_mode == 0 || keep_mode == 1), "bad argument");
+    PCH_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(int64_t), s));
+    if (out_aabb) PCH_HIP_TRY(hipMemsetAsync(out_aabb, 0, 6 * sizeof(float), s));
+    if (n == 0) return PCH_OK;
+    PCH_REQUIRE(raw && centroid3_dev && best_dev && out_points && ws, "null buffer");
+    Arena a(ws, ws_bytes);
+    PfState* st = a.take<PfState>(1);
+    const int64_t nt = ceil_div(n, PF_TILE);
+    uint64_t* status = a.take<uint64_t>(nt);
+    if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
+    PCH_HIP_TRY(hipMemsetAsync(ws, 0, a.off, s));
+    PCH_LAUNCH("pl_filter", pl_filter_k, dim3((unsigned)nt), dim3(PL_THREADS), 0, s, raw, n, centroid3_dev, best_dev,
+               (int)keep_mode, offset_or_threshold, st, status, out_points, out_index, out_count);
+    if (out_aabb) PCH_LAUNCH("pl_box", pl_box_k, dim3(1), dim3(64), 0, s, (const PfState*)st, out_aabb);
+    return PCH_OK;
+}

@@ -9,6 +9,7 @@ One function per reference library call:
   mean_seq_f32      <- np.mean(raw, axis=0)                  utils/tower_extraction.py:63
   percentile_f32    <- np.percentile(z, 25)                  utils/tower_extraction.py:83
   ground_filter     <- centring + percentile filter          utils/tower_extraction.py:63-64,82-89
+  ground_filter_plane <- RANSAC ground plane (opt-in)      test/main_ground.py:8-32
   dbscan            <- chunked sklearn DBSCAN + label offset utils/tower_extraction.py:96-117
   segment_by_label  <- per-label boolean masks               utils/tower_extraction.py:125,131-134
   crop_boxes        <- per-tower box masks over the cloud    test/kuangxuan.py:60-79, ui/extract.py:345-420
@@ -336,6 +337,181 @@ def ground_filter(raw, pct=25.0, offset=3.0, fallback_offset=1.0, min_keep=1000,
         nf = _lib.check_count(host[16:18].view("<i8")[0], "ground_filter")
     return _ground_result(out_points, out_index, nf, host[0:3], host[3], host[4], host[5] != 0.0,
                           host[6:7].view("<u4")[0], host[8:14])
+
+
+# ------------------------------------------------------------- stage B, opt-in: one RANSAC ground plane
+PLANE_MAX_HYPOTHESES = 4096
+PLANE_COUNT_TILE = 1024        # rows per workgroup pass of the inlier count (pl_count_k): the sizes tests straddle
+_PLANE_KEEP = {"above": 0, "off_plane": 1}
+
+
+def plane_hypothesis_rows(n, H=256, seed=0):
+    """The row triples of H plane hypotheses over a cloud of n rows: host int64 [H,3], drawn with replacement (a
+    triple with a repeat is simply an invalid hypothesis).  The first H of a longer draw with the same seed."""
+    import numpy as np
+    n, H = int(n), int(H)
+    if n < 1:
+        raise ValueError("plane_hypothesis_rows needs a cloud with at least one row")
+    if not 1 <= H <= PLANE_MAX_HYPOTHESES:
+        raise ValueError(f"between 1 and {PLANE_MAX_HYPOTHESES} hypotheses, got {H}")
+    return np.random.Generator(np.random.PCG64(int(seed))).integers(0, n, size=(H, 3), dtype=np.int64)
+
+
+def _centroid_dev(centroid, dev):
+    """float32 [3] on the device: a device tensor as it is, host values rounded to float32 and uploaded"""
+    import numpy as np
+    if isinstance(centroid, torch.Tensor):
+        return centroid.to(device=dev, dtype=torch.float32).reshape(3).contiguous()
+    return torch.from_numpy(np.array(centroid, dtype=np.float32).reshape(3)).to(dev)
+
+
+def _plane_rows_dev(rows, n, dev):
+    """int64 [H,3] hypothesis table on the device, checked on the host when it comes from there"""
+    import numpy as np
+    if isinstance(rows, torch.Tensor) and rows.is_cuda:
+        rows = _need_cuda(rows, torch.int64, "rows").reshape(-1, 3)
+    else:
+        host = np.ascontiguousarray(np.asarray(rows, dtype=np.int64)).reshape(-1, 3)
+        if n and host.size and (host.min() < 0 or host.max() >= n):
+            raise ValueError("rows: every entry must lie in [0, n)")
+        rows = torch.from_numpy(host).to(dev)
+    if not 1 <= rows.shape[0] <= PLANE_MAX_HYPOTHESES:
+        raise ValueError(f"between 1 and {PLANE_MAX_HYPOTHESES} hypotheses, got {rows.shape[0]}")
+    return rows
+
+
+def _plane_fit_launch(raw, cen_dev, rows_dev, residual_threshold, max_slope_deg, best_ptr):
+    """pch_plane_fit_f32, enqueued: (planes float64 [H,4], counts int64 [H]) device tensors, the best record at
+    best_ptr (device)"""
+    import math
+    L = _lib.lib()
+    n, H, dev = raw.shape[0], rows_dev.shape[0], raw.device
+    planes = torch.empty((H, 4), dtype=torch.float64, device=dev)
+    counts = torch.empty((H,), dtype=torch.int64, device=dev)
+    cos2 = math.cos(math.radians(float(max_slope_deg))) ** 2
+    ws = _workspace(L.pch_plane_fit_ws_bytes(n, H), dev)
+    _lib.check(L.pch_plane_fit_f32(_ptr(raw), n, _ptr(cen_dev), _ptr(rows_dev), H, float(residual_threshold), cos2,
+                                   _ptr(planes), _ptr(counts), best_ptr, _ptr(ws), ws.numel(), _stream()))
+    return planes, counts
+
+
+def _plane_best(words):
+    """PchPlaneBest from its 40 bytes (numpy uint8)"""
+    return _lib.PlaneBestC.from_buffer_copy(words.tobytes())
+
+
+def plane_fit(raw, centroid, rows, residual_threshold=0.1, max_slope_deg=45.0):
+    """RANSAC ground plane z = a x + b y + c of fl32(raw - centroid) over GIVEN hypotheses (test/main_ground.py:21-28;
+    the rule is stated in include/pch_hip.h).  raw float32 [n,3] (device), centroid float32 [3] (host values or a
+    device tensor), rows int64 [H,3] (plane_hypothesis_rows).  Returns dict(planes float64 [H,4] = a, b, c, valid and
+    counts int64 [H] as host arrays, best (-1: no valid hypothesis), plane float64 [3] | None, inliers, nvalid).
+    Synchronises once."""
+    import numpy as np
+    raw = _need_cuda(raw, torch.float32, "raw").reshape(-1, 3)
+    dev = raw.device
+    with torch.cuda.device(dev):
+        rows_dev = _plane_rows_dev(rows, raw.shape[0], dev)
+        H = rows_dev.shape[0]
+        best = torch.empty((40,), dtype=torch.uint8, device=dev)
+        planes, counts = _plane_fit_launch(raw, _centroid_dev(centroid, dev), rows_dev, residual_threshold,
+                                           max_slope_deg, _ptr(best))
+        host = torch.cat([planes.view(torch.uint8).reshape(-1), counts.view(torch.uint8), best]).cpu().numpy()
+    rec = _plane_best(host[40 * H:])
+    return dict(planes=host[:32 * H].view(np.float64).reshape(H, 4).copy(),
+                counts=host[32 * H:40 * H].view(np.int64).copy(), best=int(rec.best),
+                plane=None if rec.best < 0 else np.array([rec.a, rec.b, rec.c], dtype=np.float64),
+                inliers=int(rec.count), nvalid=int(rec.nvalid))
+
+
+def _filter_plane_launch(raw, cen_dev, best_ptr, keep, value, out_points, out_index, cnt_ptr, aabb_ptr):
+    L = _lib.lib()
+    n = raw.shape[0]
+    ws = _workspace(L.pch_filter_plane_ws_bytes(n), raw.device)
+    _lib.check(L.pch_filter_plane_f32(_ptr(raw), n, _ptr(cen_dev), best_ptr, _PLANE_KEEP[keep], float(value),
+                                      _ptr(out_points), _ptr(out_index), cnt_ptr, aabb_ptr, _ptr(ws), ws.numel(),
+                                      _stream()))
+
+
+def _plane_keep_value(keep, offset, residual_threshold):
+    if keep not in _PLANE_KEEP:
+        raise ValueError(f"keep must be 'above' or 'off_plane', got {keep!r}")
+    return offset if keep == "above" else residual_threshold
+
+
+def filter_plane(raw, centroid, plane_or_fit, keep="above", offset=3.0, residual_threshold=0.1, want_index=True):
+    """points = fl32(raw - centroid), kept by their residual r = z - ((a x + b y) + c) to a GIVEN plane, order
+    preserving (test/main_ground.py:28-30): keep="above" keeps r > offset, keep="off_plane" keeps
+    !(|r| <= residual_threshold), remove_ground_ransac's own non-ground set.  plane_or_fit: (a, b, c), or what
+    plane_fit returned (a fit without a valid hypothesis keeps nothing).  Returns the dict of filter_gt.
+    Synchronises."""
+    import numpy as np
+    value = _plane_keep_value(keep, offset, residual_threshold)
+    raw = _need_cuda(raw, torch.float32, "raw").reshape(-1, 3)
+    n, dev = raw.shape[0], raw.device
+    plane = plane_or_fit["plane"] if isinstance(plane_or_fit, dict) else plane_or_fit
+    rec = _lib.PlaneBestC(0.0, 0.0, 0.0, 0, -1, 0)
+    if plane is not None:
+        a, b, c = (float(v) for v in plane)
+        rec = _lib.PlaneBestC(a, b, c, 0, 0, 1)
+    with torch.cuda.device(dev):
+        best = torch.from_numpy(np.frombuffer(bytes(rec), dtype=np.uint8).copy()).to(dev)
+        out_points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        out_index = torch.empty((n,), dtype=torch.int32, device=dev) if want_index else None
+        cnt = torch.zeros((1,), dtype=torch.int64, device=dev)
+        aabb = torch.zeros((6,), dtype=torch.float32, device=dev)
+        _filter_plane_launch(raw, _centroid_dev(centroid, dev), _ptr(best), keep, value, out_points, out_index,
+                             _ptr(cnt), _ptr(aabb))
+        m = _lib.check_count(cnt.item(), "filter_plane")
+    return dict(points=out_points[:m], index=None if out_index is None else out_index[:m], count=m,
+                aabb=aabb.cpu().numpy())
+
+
+def ground_filter_plane(raw, hypotheses=256, seed=0, residual_threshold=0.1, max_slope_deg=45.0, offset=3.0,
+                        fallback_offset=1.0, min_keep=1000, keep="above", want_index=True, rows=None):
+    """Stage B with the plane rule, for sloped terrain: centroid (mean_seq_f32), plane_fit over ``rows`` (default:
+    plane_hypothesis_rows(n, hypotheses, seed)), filter_plane, and in "above" mode the reference's fallback - fewer
+    than min_keep rows above ``offset``: the rows above ``fallback_offset`` instead.  Returns the dict of
+    ground_filter - base = float32(c), the plane's height under the centroid; threshold = the offset used - plus
+    plane (float64 [3]), inliers, nvalid, best.  ValueError when no hypothesis is valid.  Fit and filter chain on the
+    device; one host read, a second after a fallback."""
+    import numpy as np
+    value = _plane_keep_value(keep, offset, residual_threshold)
+    L = _lib.lib()
+    raw = _need_cuda(raw, torch.float32, "raw").reshape(-1, 3)
+    n, dev = raw.shape[0], raw.device
+    if n == 0:
+        raise ValueError("no valid ground plane: the cloud is empty")
+    with torch.cuda.device(dev):
+        rows_dev = _plane_rows_dev(plane_hypothesis_rows(n, hypotheses, seed) if rows is None else rows, n, dev)
+        out_points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        out_index = torch.empty((n,), dtype=torch.int32, device=dev) if want_index else None
+        # one block for the host: [0:40] best record, [48:56] count, [64:88] aabb, [96:108] centroid
+        scal = torch.zeros((112,), dtype=torch.uint8, device=dev)
+        base = scal.data_ptr()
+        cen = scal[96:108].view(torch.float32)
+        ws = _workspace(L.pch_mean_seq_f32_ws_bytes(n), dev)
+        _lib.check(L.pch_mean_seq_f32(_ptr(raw), n, _ptr(cen), _ptr(ws), ws.numel(), _stream()))
+        _plane_fit_launch(raw, cen, rows_dev, residual_threshold, max_slope_deg, base)
+
+        def sweep(v):
+            _filter_plane_launch(raw, cen, base, keep, v, out_points, out_index, base + 48, base + 64)
+            host = scal.cpu().numpy()
+            return host, _lib.check_count(host[48:56].view("<i8")[0], "ground_filter_plane")
+
+        host, nf = sweep(value)
+        rec = _plane_best(host[:40])
+        if rec.best < 0:
+            raise ValueError(f"no valid ground plane among {rows_dev.shape[0]} hypotheses (degenerate triples, or "
+                             f"none within {max_slope_deg} degrees of level)")
+        first, used_fallback = nf, False
+        if keep == "above" and nf < int(min_keep):
+            used_fallback, value = True, fallback_offset
+            host, nf = sweep(value)
+    out = _ground_result(out_points, out_index, nf, host[96:108].view(np.float32), np.float32(rec.c), value,
+                         used_fallback, first, host[64:88].view(np.float32))
+    out.update(plane=np.array([rec.a, rec.b, rec.c], dtype=np.float64), inliers=int(rec.count),
+               nvalid=int(rec.nvalid), best=int(rec.best))
+    return out
 
 
 # ---------------------------------------------------------------------------- stage C

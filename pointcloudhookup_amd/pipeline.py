@@ -17,12 +17,34 @@ REF_CHUNK = 50000          # utils/tower_extraction.py:96
 
 
 def cluster_points(raw, eps=8.0, min_points=80, chunk_size=REF_CHUNK, pct=25.0, offset=3.0,
-                   fallback_offset=1.0, min_keep=1000, want_index=False, segment=True):
+                   fallback_offset=1.0, min_keep=1000, want_index=False, segment=True, ground="percentile",
+                   plane=None):
     """Stages B + C + D0 on a float32 [N,3] device tensor.
 
     Returns dict: ground (ops.ground_filter result), labels int32 [N_f] (device), nclusters,
     perm / offsets / stats (ops.segment_by_label) when ``segment``.
+
+    ``ground`` selects the ground rule of stage B: "percentile" (the reference's, the default: one fused library
+    call) or "plane" (opt-in, for sloped terrain: ops.ground_filter_plane, then ops.dbscan and ops.segment_by_label;
+    ``plane`` is a dict of keyword arguments for it - hypotheses, seed, residual_threshold, max_slope_deg, keep, ...
+    - whose offset / fallback_offset / min_keep / want_index default to this call's).
     """
+    if ground == "plane":
+        kw = dict(offset=offset, fallback_offset=fallback_offset, min_keep=min_keep, want_index=want_index)
+        kw.update(plane or {})
+        gf = ops.ground_filter_plane(raw, **kw)
+        points = gf["points"]
+        if gf["count"]:
+            labels, _, k = ops.dbscan(points, eps, min_points, chunk_size, aabb=gf["aabb"])
+        else:
+            labels, k = torch.empty((0,), dtype=torch.int32, device=points.device), 0
+        out = dict(ground=gf, labels=labels, nclusters=k)
+        if segment:
+            perm, offsets, stats = ops.segment_by_label(labels, points, k)
+            out.update(perm=perm, offsets=offsets, stats=stats)
+        return out
+    if ground != "percentile":
+        raise ValueError(f"ground must be 'percentile' or 'plane', got {ground!r}")
     gf, labels, k, perm, offsets, stats = ops.tower_clusters(
         raw, eps, min_points, chunk_size, pct, offset, fallback_offset, min_keep,
         want_index=want_index, segment=segment)

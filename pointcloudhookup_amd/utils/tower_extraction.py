@@ -21,6 +21,10 @@ of extract_towers, because ``clustering`` was never bound.  "noise" is the behav
 (what trimesh does); "fast" filters the clusters on the device down to the points that can be hull vertices
 and searches the box natively (pointcloudhookup_amd/obb.py:boxes_fast) - same procedure, but qhull may merge
 facets differently on the reduced input, so a box can differ in the centimetres; see DESIGN.md section 11.
+``GROUND_MODE`` ("percentile" | "plane", env PCH_GROUND_MODE): "percentile" is the reference's height filter;
+"plane" removes the ground by one RANSAC plane instead (ops.ground_filter_plane, the remedy of the reference's own
+test/main_ground.py:8-32) - for sloped terrain, where one global percentile keeps the ground uphill and cuts the
+towers downhill.  It logs one extra line with the plane.
 """
 from __future__ import annotations
 
@@ -35,6 +39,7 @@ OBB_EXTENT_ORDER = os.environ.get("PCH_OBB_EXTENT_ORDER", "unsorted")
 DEVICE = os.environ.get("PCH_DEVICE", "cuda:0")
 CHUNK_FAILURE = os.environ.get("PCH_CHUNK_FAILURE", "reference")
 OBB_MODE = os.environ.get("PCH_OBB_MODE", "exact")
+GROUND_MODE = os.environ.get("PCH_GROUND_MODE", "percentile")
 PRESTART_BYTES = 100 << 20                             # LAS files from here on get worker processes early
 CHUNK_SIZE = 50000                                     # utils/tower_extraction.py:96
 
@@ -119,14 +124,23 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
         progress(10)
         if raw.shape[0] == 0:
             raise IndexError("index -1 is out of bounds for axis 0 with size 0")
-        gf = ops.ground_filter(raw, 25.0, 3.0, 1.0, 1000, want_index=False)
-        clock.mark("centroid + percentile filter")
+        if GROUND_MODE == "plane":
+            gf = ops.ground_filter_plane(raw, want_index=False)
+            clock.mark("centroid + plane fit + plane filter")
+        elif GROUND_MODE == "percentile":
+            gf = ops.ground_filter(raw, 25.0, 3.0, 1.0, 1000, want_index=False)
+            clock.mark("centroid + percentile filter")
+        else:
+            raise ValueError("GROUND_MODE must be 'percentile' or 'plane'")
         header_info["centroid"] = gf["centroid"]
         if gf["used_fallback"]:
             log(f"✅ 高度过滤完成，保留点数: {gf['count_at_offset']}")
             log("⚠️ 过滤后点数太少，尝试降低过滤阈值")
         else:
             log(f"✅ 高度过滤完成，保留点数: {gf['count']}")
+        if GROUND_MODE == "plane":
+            a, b, c = gf["plane"]
+            log(f"📐 地面平面: z = {a:.6f}·x + {b:.6f}·y + {c:.3f}（内点 {gf['inliers']}/{raw.shape[0]}）")
     except Exception as e:
         log(f"⚠️ 高度过滤失败: {str(e)}")
         return tower_obbs
