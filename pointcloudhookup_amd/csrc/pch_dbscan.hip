@@ -615,14 +615,17 @@ __global__ __launch_bounds__(CS_THREADS) void db_chunksort_k(
 // right behind with ovf as its gate, sorts it.  NaN/inf and one-cell chunks keep their rows in place, as db_chunksort_k does.
 // TABLE (the run has at most DB_TABLE_MAX_CHUNKS chunks): the sorted cell list that the scan works on IS the chunk's
 // part of the cell table, so it is staged - st.ncell[c], and at [lo, lo + ncell) the full keys in ascending order and
-// every cell's first sorted position - and no key is written per row: 16 bytes written per row instead of 24, one
-// scattered store instead of two.  db_chunkcells_k and db_celltab_k (below) turn the staged lists into the table.
+// every cell's first sorted position and smallest row (tmin: one more LDS atomic per row in sweep 1; it becomes cell_min,
+// exact for a dense cell, corrected by db_core_k for a sparse one) - and no key is written per row: 16 bytes written per
+// row instead of 24, one scattered store instead of two.  db_chunkcells_k and db_celltab_k (below) turn the staged lists
+// into the table.
 // Every chunk writes st.ncell[c] on every run (the workspace is not cleared): 0 for a chunk handed to db_chunksort_k.
 // !TABLE: a full key per sorted row (keys_out), the table is read off those by db_heads_k / db_cells_k.
 struct DbStage {
     uint32_t* ncell;        // [nchunks] cells of chunk c; 0: the chunk overflowed, its keys come from db_chunksort_k
     uint64_t* key;          // [n] at lo + j: key of the chunk's j-th cell, ascending
     uint32_t* start;        // [n] at lo + j: first sorted row of that cell (an index into pts)
+    uint32_t* minrow;       // [n] at lo + j: smallest original row of that cell (db_celltab_k: cell_min)
 };
 constexpr int CT_SLOTS = 4096;                  // table slots (key + count: 32 KiB)
 constexpr int CT_BITS  = 12;                    // log2(CT_SLOTS)
@@ -639,6 +642,7 @@ __global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
     float4* __restrict__ pts, uint64_t* __restrict__ keys_out, DbStage st, uint32_t* __restrict__ status) {
     __shared__ uint32_t tkey[CT_SLOTS];
     __shared__ uint32_t tcnt[CT_SLOTS];         // sweep 1: rows per cell; sweep 2: the cell's next position
+    __shared__ uint32_t tmin[TABLE ? CT_SLOTS : 1];     // sweep 1: the cell's smallest row of the chunk
     __shared__ uint32_t skey[CT_CELLS];         // the chunk's cell keys, sorted
     __shared__ uint32_t wsum[CS_WAVES];
     __shared__ uint32_t flags[5];               // [0] NaN/inf, [1] point outside the grid, [2] cells, [3] too many
@@ -648,7 +652,10 @@ __global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
     const int64_t lo = c * g.chunk_size;
     const int cn = (int)((n - lo) < g.chunk_size ? (n - lo) : g.chunk_size);
     const Row3* __restrict__ rows = reinterpret_cast<const Row3*>(xyz) + lo;
-    for (int j = tid; j < CT_SLOTS; j += CS_THREADS) { tkey[j] = CT_EMPTY; tcnt[j] = 0u; }
+    for (int j = tid; j < CT_SLOTS; j += CS_THREADS) {
+        tkey[j] = CT_EMPTY; tcnt[j] = 0u;
+        if constexpr (TABLE) tmin[j] = 0xFFFFFFFFu;
+    }
     if (tid < 5) flags[tid] = 0u;
     __syncthreads();
     // ---- sweep 1: checks, cell counts.  A row inserts only while flags[3] is clear, and at most one new key per
@@ -669,7 +676,11 @@ __global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
                 for (int p = 0; p < CT_SLOTS; ++p, h = (h + 1u) & (CT_SLOTS - 1)) {
                     const uint32_t old = atomicCAS(&tkey[h], CT_EMPTY, k);
                     if (old == CT_EMPTY && atomicAdd(&flags[2], 1u) >= (uint32_t)CT_CELLS) flags[3] = 1u;
-                    if (old == CT_EMPTY || old == k) { atomicAdd(&tcnt[h], 1u); break; }
+                    if (old == CT_EMPTY || old == k) {
+                        atomicAdd(&tcnt[h], 1u);
+                        if constexpr (TABLE) atomicMin(&tmin[h], (uint32_t)(i0 + u * CS_THREADS + tid));
+                        break;
+                    }
                 }
             }
         }
@@ -693,7 +704,7 @@ __global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
             // its key: cell 0 of a NaN/inf chunk, else the table's only key
             if (isbad) { if (tid == 0) st.key[lo] = hi; }
             else for (int j = tid; j < CT_SLOTS; j += CS_THREADS) if (tkey[j] != CT_EMPTY) st.key[lo] = hi | tkey[j];
-            if (tid == 0) st.start[lo] = (uint32_t)lo;
+            if (tid == 0) { st.start[lo] = (uint32_t)lo; st.minrow[lo] = (uint32_t)lo; }
         }
         cs_rows_in_place(g, rows, cn, lo, hi, isbad, pts, TABLE ? nullptr : keys_out);
         return;
@@ -750,6 +761,7 @@ __global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
                 if constexpr (TABLE) {                  // ncell <= cn: the chunk's own part of the staging arrays
                     st.key[lo + 4 * tid + u] = hi | skey[4 * tid + u];
                     st.start[lo + 4 * tid + u] = (uint32_t)(lo + run);
+                    st.minrow[lo + 4 * tid + u] = (uint32_t)lo + tmin[slot[u]];
                 }
             }
             run += cnt[u];
@@ -937,11 +949,13 @@ __global__ __launch_bounds__(CC_THREADS) void db_chunkcells_k(
 __global__ __launch_bounds__(DB_THREADS) void db_celltab_k(
     const uint32_t* __restrict__ route, DbStage st, const uint32_t* __restrict__ ovf,
     const uint32_t* __restrict__ chunk_cells, int64_t n, int64_t chunk_size, uint32_t* __restrict__ cid,
-    uint32_t* __restrict__ cell_start, uint64_t* __restrict__ cell_key, uint32_t* __restrict__ cell_acc,
-    uint64_t* __restrict__ keys_out) {
+    uint32_t* __restrict__ cell_start, uint64_t* __restrict__ cell_key, int* __restrict__ cell_min,
+    uint32_t* __restrict__ bits, uint64_t* __restrict__ keys_out) {
     const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * DC_ITEMS;
-    if (base >= n) return;
     const bool fill = *route != 0u;                     // uniform over the grid
+    // the row bitmap db_chunkunion_k sets bits in starts empty: ceil(n/32) words, this grid has a thread per eight rows
+    if (!fill && base / DC_ITEMS < (n + 31) / 32) bits[base / DC_ITEMS] = 0u;
+    if (base >= n) return;
     // the chunk of row `base`, and the last of its staged cells that starts at or before it.  lo <= base < end, and
     // the chunk's first cell starts at lo
     int64_t c = (uint32_t)base / (uint32_t)chunk_size;  // n < 2^31
@@ -979,9 +993,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_celltab_k(
         } else if (head) {
             cell_start[cc[u]] = (uint32_t)i;
             cell_key[cc[u]] = st.key[lo + j];
-            uint4* a4 = reinterpret_cast<uint4*>(cell_acc + 8 * (int64_t)cc[u]);   // neutral start of db_cellstats_k
-            a4[0] = make_uint4(0u, 0u, 0u, 0u);
-            a4[1] = make_uint4(0u, 0u, 0u, 0u);
+            cell_min[cc[u]] = (int)st.minrow[lo + j];   // of all its rows: db_core_k corrects it for a sparse cell
         }
     }
     if (fill) return;
@@ -1120,6 +1132,66 @@ __device__ __forceinline__ int db_query_sweep(const DbGrid& g, const float4* __r
     return count;
 }
 
+// ---- a cell's summary, written by the wave of db_core_k that owns the cell (the staged route only; every other route
+// sweeps the rows for it, db_cellstats_k): cell_box, a box that CONTAINS the cell's core points, and cell_min, their
+// smallest original row.  Every reader of cell_box uses it to reject ("box distance > eps^2: skip", the strip's x
+// range) and tests real points otherwise, so any containing box gives the same links and labels.
+// no core point: the values db_cell_decode yields for an empty accumulator
+__device__ __forceinline__ void db_summary_none(float* __restrict__ cell_box, int* __restrict__ cell_min, int c) {
+    const int l = lane_id();
+    if (l < 6) cell_box[6 * (int64_t)c + l] = l < 3 ? INFINITY : -INFINITY;
+    if (l == 0) cell_min[c] = INT_BIG;
+}
+// Dense cell (all rows core): the cell's own bounds, origin + index * s per axis.  A row of cell i lies in
+// [origin + (i - 2^-21) s, origin + (i + 1 + 2^-21) s] (the rounding of db_cell_coords' product, see DbGrid); the bounds
+// are taken DB_BOX_MARGIN = 2^-16 cells further out, which also covers the roundings of this float64 expression (below
+// 2^-21 cells, or below one float32 step of coordinates that large), and are rounded outward to float32.  cell_min
+// stays what db_celltab_k staged: the smallest row of the cell.
+constexpr double DB_BOX_MARGIN = 1.0 / 65536.0;
+__device__ __forceinline__ void db_summary_dense(const DbGrid& g, uint64_t key, float* __restrict__ cell_box, int c) {
+    const int l = lane_id();
+    if (l >= 6) return;
+    const int a = l % 3;
+    const bool up = l >= 3;
+    const uint64_t i = a == 0 ? key & ((1ull << g.bx) - 1)
+                     : a == 1 ? (key >> g.bx) & ((1ull << g.by) - 1) : (key >> (g.bx + g.by)) & ((1ull << g.bz) - 1);
+    const double o = a == 0 ? (double)g.ox : a == 1 ? (double)g.oy : (double)g.oz;
+    const double edge = o + ((double)i + (up ? 1.0 + DB_BOX_MARGIN : -DB_BOX_MARGIN)) * g.cell;
+    float f = (float)edge;
+    if (up ? (double)f < edge : (double)f > edge) f = nextafterf(f, up ? INFINITY : -INFINITY);
+    cell_box[6 * (int64_t)c + l] = f;
+}
+// Sparse cell: the exact values, folded over the rounds of 64 of its rows that the wave holds as queries anyway.
+// Seven words of LDS per wave, so that nothing is carried in registers through the sweeps: the coordinates as ordered
+// keys (f32_ordered), min xyz | max xyz | smallest row
+__device__ __forceinline__ void db_summary_start(uint32_t* sm) {
+    const int l = lane_id();
+    if (l < 7) sm[l] = l < 3 ? 0xFFFFFFFFu : (l < 6 ? 0u : (uint32_t)INT_BIG);
+    __builtin_amdgcn_wave_barrier();
+}
+// one row per lane: p.w is its original row.  LDS atomics of the core lanes, no wave reductions: seven of those side by
+// side cost db_core_k<false> six to eight VGPRs and a wave of occupancy
+__device__ __forceinline__ void db_summary_fold(uint32_t* sm, bool is_core, const float4& p) {
+    if (!is_core) return;
+    const float v[3] = {p.x, p.y, p.z};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const uint32_t key = f32_ordered(v[k]);
+        atomicMin(&sm[k], key);
+        atomicMax(&sm[3 + k], key);
+    }
+    atomicMin(&sm[6], __float_as_uint(p.w));
+}
+// no core row: +inf / -inf and INT_BIG, as db_summary_none
+__device__ __forceinline__ void db_summary_put(const uint32_t* sm, float* __restrict__ cell_box,
+                                               int* __restrict__ cell_min, int c) {
+    __builtin_amdgcn_wave_barrier();
+    const int l = lane_id();
+    if (l >= 7) return;
+    const uint32_t v = sm[l];
+    if (l == 6) cell_min[c] = (int)v;
+    else cell_box[6 * (int64_t)c + l] = sm[6] == (uint32_t)INT_BIG ? (l < 3 ? INFINITY : -INFINITY) : f32_unordered(v);
+}
 // one wave per cell.  Dense cell: all core.  Sparse cell: n-body tile loop - every lane owns one
 // query point of the cell, candidate tiles (64 points of the sorted neighbour runs) are staged
 // once in LDS and broadcast to all queries; the wave leaves as soon as every query has reached
@@ -1135,7 +1207,9 @@ __global__ __launch_bounds__(DB_THREADS) void db_core_k(DbGrid g, const float4* 
                                                         const int2* __restrict__ rowtab,
                                                         uint8_t* __restrict__ core_s,
                                                         uint32_t* __restrict__ cell_ncore,
+                                                        float* __restrict__ cell_box, int* __restrict__ cell_min,
                                                         unsigned long long* __restrict__ stats) {
+    const bool summary = cell_box != nullptr;              // the staged route: this wave writes the cell's summary
     unsigned long long n_useful = 0, n_slots = 0, n_tiles = 0;
     auto tally = [&]() {
         if (COUNT && lane_id() == 0) {
@@ -1146,6 +1220,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_core_k(DbGrid g, const float4* 
     __shared__ RowSet rows[DB_WAVES];
     __shared__ DbPair tiles[DB_WAVES][32];
     __shared__ uint32_t seg_a[DB_WAVES][DB_SEGS], seg_b[DB_WAVES][DB_SEGS];
+    __shared__ uint32_t sums[DB_WAVES][8];                 // db_summary_fold
     const int c = blockIdx.x * DB_WAVES + wave_id();
     if (c >= m) return;
     const int l = lane_id();
@@ -1156,12 +1231,14 @@ __global__ __launch_bounds__(DB_THREADS) void db_core_k(DbGrid g, const float4* 
         if (g.chunk_bad[sh < 64 ? (cell_key[c] >> sh) : 0]) {            // points of NaN/inf chunks
             for (uint32_t i = s + l; i < e; i += 64) core_s[i] = 0;
             if (l == 0) cell_ncore[c] = 0;
+            if (summary) db_summary_none(cell_box, cell_min, c);
             return;
         }
     }
     if (cnt >= g.min_samples) {
         for (uint32_t i = s + l; i < e; i += 64) core_s[i] = 1;
         if (l == 0) cell_ncore[c] = (uint32_t)cnt;
+        if (summary) db_summary_dense(g, cell_key[c], cell_box, c);
         return;
     }
     RowSet* rs = &rows[wave_id()];
@@ -1173,6 +1250,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_core_k(DbGrid g, const float4* 
     if (tot < (long long)g.min_samples) {
         for (uint32_t i = s + l; i < e; i += 64) core_s[i] = 0;
         if (l == 0) cell_ncore[c] = 0;
+        if (summary) db_summary_none(cell_box, cell_min, c);
         return;
     }
     // candidate segments in nearest-first order: the 27-cell neighbourhood first (x-1..x+1 of the
@@ -1200,8 +1278,11 @@ __global__ __launch_bounds__(DB_THREADS) void db_core_k(DbGrid g, const float4* 
         __builtin_amdgcn_wave_barrier();
     }
     uint32_t ncore = 0;
+    uint32_t* sum = sums[wave_id()];
+    if (summary) db_summary_start(sum);
     const bool long_sweep = tot >= DB_LONG_TOT;            // wave-uniform
     if (cnt < DB_FEW_QUERIES) {
+        unsigned long long cores = 0;                      // bit q - s: query q is core
         // a handful of queries (cluster fringe): lanes sweep the candidates of one query at a
         // time and leave at min_samples - usually within the first tile of a dense neighbour.  The two sweeps are
         // db_query_sweep's from (0, sa[0]), written out: through that function db_core took 0.126 ms on the bench tile
@@ -1244,8 +1325,14 @@ __global__ __launch_bounds__(DB_THREADS) void db_core_k(DbGrid g, const float4* 
             const bool is_core = count >= g.min_samples;
             if (l == 0) core_s[q] = is_core ? 1 : 0;
             ncore += is_core;
+            cores |= (unsigned long long)is_core << (q - s);
         }
         if (l == 0) cell_ncore[c] = ncore;
+        if (summary) {                                     // the cell's rows once more, one per lane
+            const bool is_core = (cores >> l) & 1ull;
+            db_summary_fold(sum, is_core, pts[is_core ? s + l : s]);
+            db_summary_put(sum, cell_box, cell_min, c);
+        }
         tally();
         return;
     }
@@ -1295,8 +1382,13 @@ __global__ __launch_bounds__(DB_THREADS) void db_core_k(DbGrid g, const float4* 
         const bool is_core = valid && count >= g.min_samples;
         if (valid) core_s[q0 + l] = is_core ? 1 : 0;
         ncore += (uint32_t)__popcll(__ballot(is_core));
+        if (summary) {
+            Q.w = pts[valid ? q0 + l : s].w;               // the original row, not kept through the sweeps
+            db_summary_fold(sum, is_core, Q);
+        }
     }
     if (l == 0) cell_ncore[c] = ncore;
+    if (summary) db_summary_put(sum, cell_box, cell_min, c);
     tally();
 }
 
@@ -1927,8 +2019,8 @@ __global__ __launch_bounds__(CU_THREADS) void db_chunkunion_k(DbGrid g, const fl
                                                               const uint64_t* __restrict__ cell_key, int m,
                                                               const uint8_t* __restrict__ core_s,
                                                               const uint32_t* __restrict__ cell_ncore,
-                                                              const uint32_t* __restrict__ acc,
-                                                              float* __restrict__ cell_box,
+                                                              const float* __restrict__ cell_box,
+                                                              const int* __restrict__ cell_min,
                                                               int* __restrict__ root,
                                                               int* __restrict__ comp_min,
                                                               uint32_t* __restrict__ flag, int64_t n) {
@@ -1946,7 +2038,7 @@ __global__ __launch_bounds__(CU_THREADS) void db_chunkunion_k(DbGrid g, const fl
     nc = nc > m - first ? m - first : nc;
     const DbForest f = {start, ncore, box, parent};
 
-    // db_cellfin_k: the cell's words, its decoded accumulators (cell_box also for db_border_k and later queries)
+    // db_cellfin_k: the cell's words, its summary as db_celltab_k and db_core_k left it
     if (tid < nc) {
         const int64_t c = first + tid;
         const int sh = g.bx + g.by + g.bz;                 // <= 31 on this route
@@ -1954,10 +2046,9 @@ __global__ __launch_bounds__(CU_THREADS) void db_chunkunion_k(DbGrid g, const fl
         start[tid] = cell_start[c];
         if (tid == nc - 1) start[nc] = cell_start[c + 1];
         ncore[tid] = cell_ncore[c];
-        float b[6];
-        cmin[tid] = db_cell_decode(acc, c, b);
+        cmin[tid] = cell_min[c];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) { box[6 * tid + k] = b[k]; cell_box[6 * c + k] = b[k]; }
+        for (int k = 0; k < 6; ++k) box[6 * tid + k] = cell_box[6 * c + k];
         parent[tid] = tid;
     }
     __syncthreads();
@@ -2554,16 +2645,17 @@ struct DbWs {
     unsigned long long* core_stats;   // [4] tallies of db_core_k<true> (pch_dbscan_set_pair_counting)
     uint32_t* scan1_b;                // zeroed words of the single-pass scan of the cluster ranks
     uint32_t* bits;         // bitmap over the rows: db_cellstats_k clears it, db_mark_k sets the clusters' first core rows
+                            // (the staged route: db_celltab_k and db_chunkunion_k)
     // Views that db_plan carves into the arrays above:
     uint32_t* wrank;        // bits' array from the next multiple of 64 words on: db_labels' scan of the bitmap's word
                             // counts.  Both are kept for pch_dbscan_first_core_rows_i32; the array has no other use
     uint8_t*  face_todo;    // root as bytes: db_union_pairs_k writes the face pairs it leaves to db_union_face_k.  root
                             // itself is first written by db_compmin_k, behind both
     DbStage   stage;        // the chunk route's staged cell lists (db_cellscatter_k<true>) in arrays that only the global
-                            // sort uses: ncell = v1, key = k0, start = v0
+                            // sort uses: ncell = v1, key = k0, start = v0; and minrow = head, the compressed route's
     uint32_t* cell_route;   // meta->pad[0]: db_chunkcells_k says that a chunk overflowed, so the table comes from keys.
                             // One copy from meta->status up to here brings the host status, ncells and this word
-    unsigned long long* cs_stamps = nullptr;     // cell_box (first written by db_cellfin_k), PCH_CS_STAMPS builds only
+    unsigned long long* cs_stamps = nullptr;     // cell_box (first written by db_core_k), PCH_CS_STAMPS builds only
     // One 16-byte aligned fill zeroes status / ncells / nclusters, scan1_b and the first-cell word of every chunk
     // (db_cells_k writes it at a chunk's first cell; the zeros make a chunk without a cell an empty range)
     void*  clear_from() const { return &meta->box_key[4]; }
@@ -2612,7 +2704,7 @@ static void db_plan(Arena& a, int64_t n, DbWs& w) {
     w.flag2 = a.take<uint32_t>(nn + 8);
     w.wrank = w.bits ? w.bits + ((ceil_div(nn, 32) + 63) & ~int64_t(63)) : nullptr;
     w.face_todo = reinterpret_cast<uint8_t*>(w.root);
-    w.stage = {w.v1, w.k0, w.v0};
+    w.stage = {w.v1, w.k0, w.v0, w.head};
     w.cell_route = w.meta ? &w.meta->pad[0] : nullptr;
 #ifdef PCH_CS_STAMPS
     w.cs_stamps = reinterpret_cast<unsigned long long*>(w.cell_box);
@@ -2893,7 +2985,7 @@ static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const ui
         // table or the keys that db_chunksort_k did not (then the table is read off the keys below, as ever)
         PCH_TRY(peek_enqueue(&w.meta->status, peek_bytes, s));
         PCH_LAUNCH("db_celltab", db_celltab_k, dim3((unsigned)ntile), dim3(DB_THREADS), 0, s, w.cell_route, w.stage,
-                   w.chunk_ovf, w.chunk_cells, n, r.chunk_size, w.cid, w.cell_start, w.cell_key, w.cell_acc, w.k1);
+                   w.chunk_ovf, w.chunk_cells, n, r.chunk_size, w.cid, w.cell_start, w.cell_key, w.cell_min, w.bits, w.k1);
         PCH_TRY(peek_wait(&back.status, peek_bytes));
     }
     if (back.pad[0] != 0u) {
@@ -2915,19 +3007,24 @@ static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const ui
     if (c.rowtab)
         PCH_LAUNCH("db_rowtab", db_rowtab_k, dim3((unsigned)ceil_div(m, 2 * DB_WAVES)), dim3(DB_THREADS), 0, s, g,
                    w.cell_key, m, w.rowtab);
+    // the staged route: db_core_k writes every cell's summary (db_celltab_k staged cell_min and cleared w.bits); any
+    // other route sweeps the rows for it
+    float* const sum_box = c.chunk_union ? w.cell_box : nullptr;
+    int* const sum_min = c.chunk_union ? w.cell_min : nullptr;
     if (count_pairs) {
         PCH_HIP_TRY(hipMemsetAsync(w.core_stats, 0, 4 * sizeof(unsigned long long), s));
         PCH_LAUNCH("db_core_counting", db_core_k<true>, dim3(gc), dim3(DB_THREADS), 0, s, DB_GRID_ARGS(c), w.core_s,
-                   w.cell_ncore, w.core_stats);
+                   w.cell_ncore, sum_box, sum_min, w.core_stats);
     } else {
         PCH_LAUNCH("db_core", db_core_k<false>, dim3(gc), dim3(DB_THREADS), 0, s, DB_GRID_ARGS(c), w.core_s,
-                   w.cell_ncore, nullptr);
+                   w.cell_ncore, sum_box, sum_min, nullptr);
     }
-    PCH_LAUNCH("db_cellstats", db_cellstats_k, dim3((unsigned)ceil_div(n, (int64_t)DB_WAVES * 64 * DB_CS_ROUNDS)),
-               dim3(DB_THREADS), 0, s, w.pts, w.cid, w.core_s, n, w.cell_acc, w.bits, ceil_div(n, 32));
-    if (!c.chunk_union)
+    if (!c.chunk_union) {
+        PCH_LAUNCH("db_cellstats", db_cellstats_k, dim3((unsigned)ceil_div(n, (int64_t)DB_WAVES * 64 * DB_CS_ROUNDS)),
+                   dim3(DB_THREADS), 0, s, w.pts, w.cid, w.core_s, n, w.cell_acc, w.bits, ceil_div(n, 32));
         PCH_LAUNCH("db_cellfin", db_cellfin_k, dim3((unsigned)ceil_div(m, DB_THREADS)), dim3(DB_THREADS), 0, s,
                    w.cell_acc, m, w.cell_box, w.cell_min, w.parent, w.comp_min);
+    }
     return PCH_OK;
 }
 
@@ -2935,9 +3032,9 @@ static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const ui
 static int db_union(const DbRun& r, const DbCells& c) {
     const DbWs& w = r.w; const hipStream_t s = r.s; const int m = c.m;
     const unsigned gc = (unsigned)ceil_div(m, DB_WAVES);
-    if (c.chunk_union) {                                 // every chunk on its own, in LDS; parent and cell_min stay unused
+    if (c.chunk_union) {                                 // every chunk on its own, in LDS; parent stays unused
         PCH_LAUNCH("db_chunkunion", db_chunkunion_k, dim3((unsigned)r.nchunks), dim3(CU_THREADS), 0, s, c.g, c.pts,
-                   c.cell_start, c.cell_key, m, c.core_s, c.cell_ncore, w.cell_acc, w.cell_box, w.root, w.comp_min,
+                   c.cell_start, c.cell_key, m, c.core_s, c.cell_ncore, c.cell_box, w.cell_min, w.root, w.comp_min,
                    w.bits, r.n);
         return PCH_OK;
     }
