@@ -890,10 +890,10 @@ __global__ __launch_bounds__(DB_THREADS) void db_cells_k(const uint64_t* __restr
 }
 // ---- the cell table from the lists that db_cellscatter_k<true> staged: no key per row is written or read ----------
 // db_chunkcells_k (one workgroup) scans the chunks' cell counts into chunk_cells, which makes every staged cell's
-// global index chunk_cells[c] + j, and says in *route whether a chunk overflowed.  db_celltab_k then runs over the rows in
-// db_cells_k's shape.  *route clear: it writes what db_cells_k writes, finding a row's cell in its chunk's staged starts.
-// *route set (some chunk went through db_chunksort_k, which writes keys): it writes the keys of all OTHER chunks' rows
-// instead, and the host, which reads the word in the wait it makes anyway, launches db_heads_k / db_cells_k on them.
+// global index chunk_cells[c] + j, and says in *route whether a chunk overflowed.  db_celltab_k (behind the neighbour
+// rows, which it also finds) then runs over the chunks' lists.  *route clear: it writes the table.  *route set (some
+// chunk went through db_chunksort_k, which writes keys): it writes the keys of all OTHER chunks' rows instead, and
+// the host, which reads the word in the wait it makes anyway, launches db_heads_k / db_cells_k on them.
 constexpr int64_t DB_TABLE_MAX_CHUNKS = 16384;  // beyond: db_cellscatter_k<false>, the table is read off the keys
 constexpr int CC_THREADS = 1024;
 constexpr int CC_ITEMS = (int)(DB_TABLE_MAX_CHUNKS / CC_THREADS);     // consecutive chunks per thread
@@ -943,68 +943,6 @@ __global__ __launch_bounds__(CC_THREADS) void db_chunkcells_k(
             cell_start[total] = (uint32_t)n;            // total <= n
             *ncells = total;
         }
-    }
-}
-
-__global__ __launch_bounds__(DB_THREADS) void db_celltab_k(
-    const uint32_t* __restrict__ route, DbStage st, const uint32_t* __restrict__ ovf,
-    const uint32_t* __restrict__ chunk_cells, int64_t n, int64_t chunk_size, uint32_t* __restrict__ cid,
-    uint32_t* __restrict__ cell_start, uint64_t* __restrict__ cell_key, int* __restrict__ cell_min,
-    uint32_t* __restrict__ bits, uint64_t* __restrict__ keys_out) {
-    const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * DC_ITEMS;
-    const bool fill = *route != 0u;                     // uniform over the grid
-    // the row bitmap db_chunkunion_k sets bits in starts empty: ceil(n/32) words, this grid has a thread per eight rows
-    if (!fill && base / DC_ITEMS < (n + 31) / 32) bits[base / DC_ITEMS] = 0u;
-    if (base >= n) return;
-    // the chunk of row `base`, and the last of its staged cells that starts at or before it.  lo <= base < end, and
-    // the chunk's first cell starts at lo
-    int64_t c = (uint32_t)base / (uint32_t)chunk_size;  // n < 2^31
-    int64_t lo = c * chunk_size, end = lo + chunk_size < n ? lo + chunk_size : n;
-    uint32_t nc = ct_staged_cells(st.ncell, c, end - lo), j = 0;
-    for (uint32_t a = 1, b = nc; a < b;) {              // j = the largest index in [0, nc) with start <= base
-        const uint32_t mid = a + (b - a) / 2;
-        if (st.start[lo + mid] <= (uint32_t)base) { j = mid; a = mid + 1; } else b = mid;
-    }
-    int64_t next = j + 1 < nc ? (int64_t)st.start[lo + j + 1] : end;      // first row of the cell behind j
-    uint32_t cell0 = chunk_cells[c];
-    bool skip = fill && ovf[c] != 0u;                   // (fill) db_chunksort_k wrote this chunk's keys
-    uint32_t cc[DC_ITEMS];
-#pragma unroll
-    for (int u = 0; u < DC_ITEMS; ++u) {
-        const int64_t i = base + u;
-        cc[u] = 0u;
-        if (i >= n) continue;
-        bool head = i == base && nc != 0u && (int64_t)st.start[lo + j] == i;
-        if (i == end) {                                 // the next chunk: chunk_size may be anything from 1 up
-            ++c; lo = end; end = lo + chunk_size < n ? lo + chunk_size : n;
-            nc = ct_staged_cells(st.ncell, c, end - lo); j = 0;
-            next = 1 < nc ? (int64_t)st.start[lo + 1] : end;
-            cell0 = chunk_cells[c];
-            skip = fill && ovf[c] != 0u;
-            head = nc != 0u;
-        } else if (i == next) {                         // the next cell of this chunk (next < end here: j + 1 < nc)
-            ++j;
-            next = j + 1 < nc ? (int64_t)st.start[lo + j + 1] : end;
-            head = true;
-        }
-        cc[u] = cell0 + j;
-        if (fill) {
-            if (!skip) keys_out[i] = st.key[lo + j];
-        } else if (head) {
-            cell_start[cc[u]] = (uint32_t)i;
-            cell_key[cc[u]] = st.key[lo + j];
-            cell_min[cc[u]] = (int)st.minrow[lo + j];   // of all its rows: db_core_k corrects it for a sparse cell
-        }
-    }
-    if (fill) return;
-    if (base + DC_ITEMS <= n) {
-        uint4* o = reinterpret_cast<uint4*>(cid + base);
-        o[0] = make_uint4(cc[0], cc[1], cc[2], cc[3]);
-        o[1] = make_uint4(cc[4], cc[5], cc[6], cc[7]);
-    } else {
-#pragma unroll
-        for (int u = 0; u < DC_ITEMS; ++u)
-            if (base + u < n) cid[base + u] = cc[u];
     }
 }
 
@@ -1095,6 +1033,64 @@ __global__ __launch_bounds__(DB_THREADS) void db_rowtab_k(DbGrid g, const uint64
     const int l = lane_id() & 31;
     if (c >= m || l >= DB_ROWS) return;
     rowtab[(int64_t)c * DB_ROWS + l] = db_row_run(g, cell_key, cell_key[c], l);
+}
+
+// ---- the chunk route's cell table per CELL: one workgroup per chunk (the host does not know the cell count yet) over
+// the chunk's staged list [lo, lo + ncell).
+// *route clear: cell_start, cell_key and cell_min of the chunk's cells, the chunk's words of the row bitmap cleared
+// (two chunks may share a word: both store 0), and the cells' neighbour rows, db_rowtab_k's 25 searches per cell, over
+// an LDS copy of the chunk's keys - no word per row: the staged route's labels need no cid (db_filelabel_k).
+// *route set (fill mode): a chunk that did not overflow writes the keys of its own rows, a wave
+// per cell; an overflowed one returns at once.
+__global__ __launch_bounds__(CS_THREADS) void db_celltab_k(
+    const uint32_t* __restrict__ route, DbStage st, const uint32_t* __restrict__ ovf, DbGrid g, int64_t n,
+    uint32_t* __restrict__ cell_start, uint64_t* __restrict__ cell_key, int* __restrict__ cell_min,
+    uint32_t* __restrict__ bits, int2* __restrict__ rowtab, int64_t rowtab_cells, uint64_t* __restrict__ keys_out) {
+    __shared__ uint32_t key[CT_CELLS];
+    const int tid = threadIdx.x, l = lane_id();
+    const int64_t c = blockIdx.x, lo = c * g.chunk_size;
+    const int64_t end = lo + g.chunk_size < n ? lo + g.chunk_size : n;
+    const bool fill = *route != 0u;                        // uniform over the grid
+    if (fill && ovf[c] != 0u) return;                      // db_chunksort_k wrote this chunk's keys
+    int nc = (int)ct_staged_cells(st.ncell, c, end - lo);
+    nc = nc > CT_CELLS ? CT_CELLS : nc;                    // what db_cellscatter_k stages never exceeds it
+    if (fill) {
+        for (int j = wave_id(); j < nc; j += CS_WAVES) {
+            int64_t a = st.start[lo + j], b = j + 1 < nc ? (int64_t)st.start[lo + j + 1] : end;
+            a = a < lo ? lo : a;
+            b = b > end ? end : b;
+            const uint64_t k = st.key[lo + j];
+            for (int64_t i = a + l; i < b; i += 64) keys_out[i] = k;
+        }
+        return;
+    }
+    const int64_t cell0 = g.chunk_cells[c];
+    if (cell0 + nc > n) return;                            // cannot happen (a cell per row at most): never write outside
+    for (int64_t wd = (lo >> 5) + tid; wd <= ((end - 1) >> 5); wd += CS_THREADS) bits[wd] = 0u;
+    if (tid < nc) {
+        const uint64_t k = st.key[lo + tid];
+        cell_start[cell0 + tid] = st.start[lo + tid];
+        cell_key[cell0 + tid] = k;
+        cell_min[cell0 + tid] = (int)st.minrow[lo + tid];  // of all its rows: db_core_k corrects it for a sparse cell
+        const int sh = g.bx + g.by + g.bz;                 // <= 31 on this route
+        key[tid] = (uint32_t)k & ((1u << sh) - 1u);
+    }
+    if (!rowtab) return;
+    __syncthreads();
+    for (int t = tid; t < 32 * nc; t += CS_THREADS) {      // db_row_run on the chunk's own keys
+        const int j = t >> 5, row = t & 31;
+        if (row >= DB_ROWS || cell0 + j >= rowtab_cells) continue;
+        int2 v;
+        v.x = 0; v.y = 0;
+        DbRowAt at;
+        if (db_row_at(g, key[j], row, at)) {
+            v = db_run_in(key, nc, (uint32_t)db_pack(g, 0, (uint64_t)at.nz, (uint64_t)at.ny, (uint64_t)at.xlo),
+                          (uint32_t)db_pack(g, 0, (uint64_t)at.nz, (uint64_t)at.ny, (uint64_t)at.xhi));
+            v.x += (int)cell0;
+            v.y += (int)cell0;
+        }
+        rowtab[(cell0 + j) * DB_ROWS + row] = v;
+    }
 }
 
 // ---- core points ---------------------------------------------------------------------
@@ -2160,6 +2156,29 @@ __device__ __forceinline__ void db_box_flush(uint32_t* __restrict__ acc, int cur
     }
     if (cur >= 0 && l < 6 && v) atomicMax(&acc[8 * (int64_t)cur + l], v);
 }
+// one row per lane joins the box of its cluster `mine` (-1: none).  The wave carries the per-lane running box m[] of
+// ONE cluster, `cur` (wave-uniform), and hands it over whenever a lane brings another
+__device__ __forceinline__ void db_box_round(uint32_t* __restrict__ acc, int& cur, uint32_t (&m)[6], int mine, float x,
+                                             float y, float z) {
+    const uint32_t k[3] = {f32_ordered(x), f32_ordered(y), f32_ordered(z)};
+    unsigned long long todo = __ballot(mine >= 0);
+    while (todo) {
+        const int L = __builtin_amdgcn_readlane(mine, (int)__builtin_ctzll(todo));
+        const bool in = mine == L;
+        todo &= ~__ballot(in);
+        if (L != cur) {                                    // another cluster: hand the carried box over
+            db_box_flush(acc, cur, m);
+            cur = L;
+        }
+        if (in) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                m[a] = ~k[a] > m[a] ? ~k[a] : m[a];
+                m[3 + a] = k[a] > m[3 + a] ? k[a] : m[3 + a];
+            }
+        }
+    }
+}
 
 // labels of core points (original order), label of every cell, optional core mask.
 // A wave walks DB_LAB_ROUNDS consecutive groups of 64 sorted points.  The points are sorted by cell, so a wave
@@ -2246,26 +2265,151 @@ __global__ __launch_bounds__(DB_THREADS) void db_label_k(const float4* __restric
 #pragma unroll
     for (int u = 0; u < R; ++u) {
         const int mine = (is_core[u] && lab[u] != INT_BIG && lab[u] >= 0 && lab[u] < box_cap) ? lab[u] : -1;
-        const uint32_t k[3] = {f32_ordered(p[u].x), f32_ordered(p[u].y), f32_ordered(p[u].z)};
-        unsigned long long todo = __ballot(mine >= 0);
-        while (todo) {
-            const int L = __builtin_amdgcn_readlane(mine, (int)__builtin_ctzll(todo));
-            const bool in = mine == L;
-            todo &= ~__ballot(in);
-            if (L != cur) {                                // another cluster: hand the carried box over
-                db_box_flush(box_acc, cur, m);
-                cur = L;
+        db_box_round(box_acc, cur, m, mine, p[u].x, p[u].y, p[u].z);
+    }
+    db_box_flush(box_acc, cur, m);
+}
+
+// ---- the staged route's labels (DbCells::chunk_union): every row has ONE owner.  The rows of a dense cell (every row
+// core, so every row carries the cell's label) belong to db_filelabel_k, which never looks at the sorted rows: a row's
+// cell is a function of its coordinates, a chunk holds at most CT_CELLS cells, so a workgroup takes a tile of
+// consecutive INPUT rows of one chunk, keeps that chunk's cell keys and the labels of its dense cells in LDS and
+// finds every row's cell there - 12 bytes read and 4 (+1) written per row, both coalesced, no cid column, no
+// scattered store.  The rows of every other cell - a few per cent - belong to db_border_k<true>, which visits those
+// cells anyway.  The cells' labels, which db_label_k leaves as a side effect, are made per cell in front of both, in
+// db_prelabel_k's launch.
+__global__ void db_prelabel_cells_k(const uint32_t* __restrict__ total, int32_t* __restrict__ out_nclusters,
+                                    uint32_t* __restrict__ box_acc, int64_t box_words,
+                                    const int* __restrict__ root, const int* __restrict__ comp_min,
+                                    const uint32_t* __restrict__ bits, const uint32_t* __restrict__ rank, int m,
+                                    int* __restrict__ cell_label) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *out_nclusters = (int32_t)*total;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (box_acc && i < box_words) box_acc[i] = 0u;
+    if (i >= m) return;
+    const int rt = root[i];
+    int lab = INT_BIG;                                     // no core point: the cell attracts nothing
+    if (rt >= 0) {                                         // db_label_k's chain: the cluster's smallest core row, ranked
+        const uint32_t row = (uint32_t)comp_min[rt];
+        lab = (int)(rank[row >> 5] + (uint32_t)__popc(bits[row >> 5] & ((1u << (row & 31u)) - 1u)));
+    }
+    cell_label[i] = lab;
+}
+
+constexpr int DB_FL_NONE = -0x7fffffff - 1;                // db_filelabel_k: not a dense cell, the row is db_border_k's
+constexpr int FL_SLOTS = 2 * CT_CELLS;                     // ... its table of the chunk's cells, never more than half full
+__device__ __forceinline__ uint32_t fl_hash(uint32_t k) { return (k * 0x9E3779B1u) >> 21; }
+static_assert(FL_SLOTS == 1 << 11, "fl_hash yields 11 bits");
+
+__global__ __launch_bounds__(DB_THREADS) void db_filelabel_k(const float* __restrict__ xyz, int64_t n, DbGrid g,
+                                                             const uint32_t* __restrict__ cell_start,
+                                                             const uint64_t* __restrict__ cell_key, int m,
+                                                             const uint32_t* __restrict__ cell_ncore,
+                                                             const int* __restrict__ cell_label,
+                                                             int32_t* __restrict__ labels,
+                                                             uint8_t* __restrict__ core_out, int bpc, int64_t nchunks,
+                                                             uint32_t* __restrict__ box_acc, int32_t box_cap) {
+    __shared__ uint2 tab[FL_SLOTS];                        // open addressing: (the cell's key in its chunk, a dense cell's
+                                                           // label or DB_FL_NONE for any other cell)
+    const int tid = threadIdx.x;
+    // the blocks of one chunk share blockIdx % 8, as db_label_k's do
+    const int64_t slot = blockIdx.x >> 3;
+    const int64_t c = (slot / bpc) * 8 + (blockIdx.x & 7);
+    const int64_t within = (slot % bpc) * DB_LAB_TILE;
+    if (c >= nchunks || within >= g.chunk_size) return;    // workgroup-uniform, as every return in front of the barrier
+    const int64_t t0 = c * g.chunk_size + within;
+    int64_t t1 = (c + 1) * g.chunk_size < n ? (c + 1) * g.chunk_size : n;
+    if (t1 > t0 + DB_LAB_TILE) t1 = t0 + DB_LAB_TILE;
+    if (t0 >= t1) return;
+    // the tile's rows are on their way while the chunk's table is put together
+    constexpr int R = DB_LAB_ROUNDS;
+    const Row3* __restrict__ rows = reinterpret_cast<const Row3*>(xyz);
+    Row3 q[R];
+    uint32_t k[R];
+    int lab[R];
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+        const int64_t i = t0 + u * DB_THREADS + tid;
+        q[u] = rows[i < t1 ? i : t0];
+    }
+    if (g.chunk_bad[c]) {                                  // a NaN/inf chunk is noise as a whole
+        for (int64_t i = t0 + tid; i < t1; i += DB_THREADS) {
+            labels[i] = -1;
+            if (core_out) core_out[i] = 0;
+        }
+        return;
+    }
+    // a chunk_cells that is not what db_chunkcells_k writes must neither leave LDS nor the table (db_chunkunion_k)
+    int first = (int)g.chunk_cells[c], nc = (int)g.chunk_cells[c + 1] - first;
+    first = first < 0 ? 0 : (first > m ? m : first);
+    nc = nc < 0 ? 0 : (nc > CT_CELLS ? CT_CELLS : nc);
+    nc = nc > m - first ? m - first : nc;
+    const int sh = g.bx + g.by + g.bz;                     // <= 31 on this route
+    for (int j = tid; j < FL_SLOTS; j += DB_THREADS) tab[j].x = CT_EMPTY;
+    __syncthreads();
+    for (int j = tid; j < nc; j += DB_THREADS) {           // keys are distinct and nc <= FL_SLOTS / 2: a free slot is found
+        const int64_t A = first + j;
+        const uint32_t key = (uint32_t)cell_key[A] & ((1u << sh) - 1u);
+        const int label = cell_ncore[A] == cell_start[A + 1] - cell_start[A] ? cell_label[A] : DB_FL_NONE;
+        uint32_t h = fl_hash(key);
+        for (int p = 0; p < FL_SLOTS; ++p, h = (h + 1u) & (FL_SLOTS - 1))
+            if (atomicCAS(&tab[h].x, CT_EMPTY, key) == CT_EMPTY) { tab[h].y = (uint32_t)label; break; }
+    }
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+        bool ok;
+        k[u] = cs_cell_key(g, q[u].x, q[u].y, q[u].z, ok);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+        const int64_t i = t0 + u * DB_THREADS + tid;
+        lab[u] = DB_FL_NONE;                               // (a key the table does not hold: nobody's row, not written)
+        if (i < t1) {
+            uint32_t h = fl_hash(k[u]);
+            for (int p = 0; p < FL_SLOTS; ++p, h = (h + 1u) & (FL_SLOTS - 1)) {
+                const uint2 e = tab[h];
+                if (e.x == k[u]) { lab[u] = (int)e.y; break; }
+                if (e.x == CT_EMPTY) break;
             }
+        }
+        if (lab[u] != DB_FL_NONE) {
+            labels[i] = lab[u];
+            if (core_out) core_out[i] = 1;
+        }
+    }
+    if (!box_acc) return;
+    // In file order the clusters of a chunk take turns from row to row, so a box carried from round to round
+    // (db_box_round) would be handed over at every turn: all rounds' labels are known here, so the wave makes one pass
+    // over its rounds per cluster its rows hold, and one hand-over each
+    unsigned long long todo[R];
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+        if (!(lab[u] != DB_FL_NONE && lab[u] != INT_BIG && lab[u] >= 0 && lab[u] < box_cap)) lab[u] = -1;
+        todo[u] = __ballot(lab[u] >= 0);
+    }
+    for (;;) {
+        int L = -1;                                        // wave-uniform: the next cluster
+#pragma unroll
+        for (int u = 0; u < R; ++u)
+            if (L < 0 && todo[u]) L = __builtin_amdgcn_readlane(lab[u], (int)__builtin_ctzll(todo[u]));
+        if (L < 0) break;
+        uint32_t mm[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const bool in = lab[u] == L;
+            todo[u] &= ~__ballot(in);
             if (in) {
+                const uint32_t kk[3] = {f32_ordered(q[u].x), f32_ordered(q[u].y), f32_ordered(q[u].z)};
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {
-                    m[a] = ~k[a] > m[a] ? ~k[a] : m[a];
-                    m[3 + a] = k[a] > m[3 + a] ? k[a] : m[3 + a];
+                    mm[a] = ~kk[a] > mm[a] ? ~kk[a] : mm[a];
+                    mm[3 + a] = kk[a] > mm[3 + a] ? kk[a] : mm[3 + a];
                 }
             }
         }
+        db_box_flush(box_acc, L, mm);
     }
-    db_box_flush(box_acc, cur, m);
 }
 
 // ---- the border rule: smallest cluster id among the core points within eps, else none (db_border_k, dq_assign_k) ----
@@ -2352,7 +2496,13 @@ __device__ __forceinline__ int db_border_label(const DbGrid& g, const float4 qp,
     }
 }
 
-// border points: smallest cluster id among the core points within eps
+// border points: smallest cluster id among the core points within eps.
+// OWN (the staged route's labels, see db_filelabel_k): nobody has written the rows of a cell that is not dense, so the
+// wave writes every one of them, once - a core row's label (the cell's) and the core flags in front of the early
+// exits, a row that is not core either -1 where the cell has no core cell around or what the border rule says - and
+// folds the cell's core box, which db_core_k left exact for such a cell, into its cluster's box.  A NaN/inf chunk's
+// rows are db_filelabel_k's.
+template <bool OWN>
 __global__ __launch_bounds__(DB_THREADS) void db_border_k(DbGrid g, const float4* __restrict__ pts,
                                                           const uint32_t* __restrict__ cell_start,
                                                           const uint64_t* __restrict__ cell_key, int m,
@@ -2362,27 +2512,49 @@ __global__ __launch_bounds__(DB_THREADS) void db_border_k(DbGrid g, const float4
                                                           const float* __restrict__ cell_box,
                                                           const int* __restrict__ cell_label,
                                                           int32_t* __restrict__ labels,
-                                                          uint32_t* __restrict__ box_acc, int32_t box_cap) {
+                                                          uint32_t* __restrict__ box_acc, int32_t box_cap,
+                                                          uint8_t* __restrict__ core_out) {
     __shared__ RowSet rows[DB_WAVES];
     const int A = blockIdx.x * DB_WAVES + wave_id();
     if (A >= m) return;
     const uint32_t as = cell_start[A], ae = cell_start[A + 1];
-    if (cell_ncore[A] == (ae - as)) return;                // no border candidates here
+    const uint32_t ncoreA = cell_ncore[A];
+    if (ncoreA == (ae - as)) return;                       // no border candidates here
     const int l = lane_id();
+    if constexpr (OWN) {
+        const int sh = g.bx + g.by + g.bz;
+        if (g.chunk_bad[sh < 64 ? (cell_key[A] >> sh) : 0]) return;
+        const int labA = cell_label[A];
+        for (uint32_t q = as + l; q < ae; q += 64) {
+            const bool is_core = core_s[q] != 0;
+            const uint32_t o = __float_as_uint(pts[q].w);
+            if (is_core) labels[o] = labA;
+            if (core_out) core_out[o] = is_core ? 1 : 0;
+        }
+        if (box_acc && ncoreA != 0 && labA != INT_BIG && labA >= 0 && labA < box_cap && l < 6) {
+            const uint32_t k = f32_ordered(cell_box[6 * (int64_t)A + l]);
+            atomicMax(&box_acc[8 * (int64_t)labA + l], l < 3 ? ~k : k);
+        }
+    }
     RowSet* rs = &rows[wave_id()];
     db_rows(g, cell_key, cell_key[A], rs, rowtab, A);
     // quick reject: no core cell anywhere around
     int any = 0;
     if (l < DB_ROWS)
         for (int B = rs->ca[l]; B < rs->cb[l]; ++B) any |= (cell_ncore[B] != 0);
-    if (!__ballot(any != 0)) return;
+    if (!__ballot(any != 0)) {
+        if constexpr (OWN)                                 // (ncoreA is 0 here: the cell is in its own neighbourhood)
+            for (uint32_t q = as + l; q < ae; q += 64)
+                if (!core_s[q]) labels[__float_as_uint(pts[q].w)] = -1;
+        return;
+    }
     DbCoreCells cc;
     db_gather_core_cells(cc, rs, true, cell_start, cell_ncore, cell_box, cell_label);
     for (uint32_t q = as; q < ae; ++q) {
         if (core_s[q]) continue;
         const float4 qp = pts[q];
         const int best = db_border_label(g, qp, cc, pts, cell_start, core_s);
-        if (l == 0 && best != INT_BIG) labels[__float_as_uint(qp.w)] = best;
+        if (l == 0 && (OWN || best != INT_BIG)) labels[__float_as_uint(qp.w)] = best != INT_BIG ? best : -1;
         if (box_acc && best != INT_BIG && best >= 0 && best < box_cap && l < 6) {     // a border point joins its box
             const float v = l % 3 == 0 ? qp.x : (l % 3 == 1 ? qp.y : qp.z);
             const uint32_t k = f32_ordered(v);
@@ -2982,10 +3154,11 @@ static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const ui
     back.pad[0] = 1u;
     if (staged) {
         // db_chunkcells_k left ncells and the route word; db_celltab_k reads the word itself and writes either the
-        // table or the keys that db_chunksort_k did not (then the table is read off the keys below, as ever)
+        // table (and the row table) or the keys that db_chunksort_k did not (then the table is read off the keys
+        // below, as ever)
         PCH_TRY(peek_enqueue(&w.meta->status, peek_bytes, s));
-        PCH_LAUNCH("db_celltab", db_celltab_k, dim3((unsigned)ntile), dim3(DB_THREADS), 0, s, w.cell_route, w.stage,
-                   w.chunk_ovf, w.chunk_cells, n, r.chunk_size, w.cid, w.cell_start, w.cell_key, w.cell_min, w.bits, w.k1);
+        PCH_LAUNCH("db_celltab", db_celltab_k, dim3((unsigned)r.nchunks), dim3(CS_THREADS), 0, s, w.cell_route, w.stage,
+                   w.chunk_ovf, g, n, w.cell_start, w.cell_key, w.cell_min, w.bits, w.rowtab, w.rowtab_cells, w.k1);
         PCH_TRY(peek_wait(&back.status, peek_bytes));
     }
     if (back.pad[0] != 0u) {
@@ -3004,7 +3177,7 @@ static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const ui
     const unsigned gc = (unsigned)ceil_div(m, DB_WAVES);
     c = {g, w.pts, w.cell_start, w.cell_key, m, m <= w.rowtab_cells ? w.rowtab : nullptr, w.core_s, w.cell_ncore,
          w.cell_box, staged && back.pad[0] == 0u};
-    if (c.rowtab)
+    if (c.rowtab && !c.chunk_union)                      // (the staged route: db_celltab_k wrote the rows)
         PCH_LAUNCH("db_rowtab", db_rowtab_k, dim3((unsigned)ceil_div(m, 2 * DB_WAVES)), dim3(DB_THREADS), 0, s, g,
                    w.cell_key, m, w.rowtab);
     // the staged route: db_core_k writes every cell's summary (db_celltab_k staged cell_min and cleared w.bits); any
@@ -3067,17 +3240,30 @@ static int db_labels(const DbRun& r, const DbCells& c, int32_t* k_host, DbBoxOut
     else PCH_TRY(scan_exclusive_popc_u32(w.bits, w.wrank, nw, w.scan_ws, &w.meta->nclusters, s));
     uint32_t* box_acc = (boxes && boxes->acc && boxes->cap > 0) ? boxes->acc : nullptr;
     const int32_t box_cap = box_acc ? boxes->cap : 0;
-    PCH_LAUNCH("db_prelabel", db_prelabel_k, dim3((unsigned)(box_acc ? ceil_div(8 * (int64_t)box_cap, 256) : 1)),
-               dim3(256), 0, s, &w.meta->nclusters, r.out_nclusters, box_acc, 8 * (int64_t)box_cap);
+    const int64_t box_words = box_acc ? 8 * (int64_t)box_cap : 0;
+    if (c.chunk_union)                                   // ... and every cell's label, which both owners of the rows read
+        PCH_LAUNCH("db_prelabel", db_prelabel_cells_k, dim3((unsigned)std::max<int64_t>(ceil_div(std::max<int64_t>(
+                   box_words, m), 256), 1)), dim3(256), 0, s, &w.meta->nclusters, r.out_nclusters, box_acc, box_words,
+                   w.root, w.comp_min, w.bits, w.wrank, m, w.cell_label);
+    else
+        PCH_LAUNCH("db_prelabel", db_prelabel_k, dim3((unsigned)std::max<int64_t>(ceil_div(box_words, 256), 1)),
+                   dim3(256), 0, s, &w.meta->nclusters, r.out_nclusters, box_acc, box_words);
     if (k_host) PCH_TRY(peek_enqueue(r.out_nclusters, sizeof(int32_t), s));    // read while the labels are written
     // many chunks: the blocks of one chunk share an XCD (see db_label_k); otherwise blocks in sorted order
-    const int bpc = nchunks >= 16 ? (int)ceil_div(r.chunk_size, DB_LAB_TILE) : 0;
+    const int bpc = (nchunks >= 16 || c.chunk_union) ? (int)ceil_div(r.chunk_size, DB_LAB_TILE) : 0;
     const unsigned gl = bpc > 0 ? (unsigned)(8 * ceil_div(nchunks, 8) * bpc) : (unsigned)ceil_div(n, DB_LAB_TILE);
-    PCH_LAUNCH("db_label", db_label_k, dim3(gl), dim3(DB_THREADS), 0, s, w.pts, w.cid, w.core_s, w.root, w.comp_min,
-               w.bits, w.wrank, n, w.cell_start, w.cell_label, r.labels, r.core, r.chunk_size, bpc, nchunks, box_acc,
-               box_cap);
-    PCH_LAUNCH("db_border", db_border_k, dim3((unsigned)ceil_div(m, DB_WAVES)), dim3(DB_THREADS), 0, s,
-               DB_CELL_ARGS(c), w.cell_label, r.labels, box_acc, box_cap);
+    if (c.chunk_union) {                                 // one owner per row: dense cells in file order, the rest per cell
+        PCH_LAUNCH("db_label", db_filelabel_k, dim3(gl), dim3(DB_THREADS), 0, s, r.xyz, n, c.g, c.cell_start, c.cell_key,
+                   m, c.cell_ncore, w.cell_label, r.labels, r.core, bpc, nchunks, box_acc, box_cap);
+        PCH_LAUNCH("db_border", db_border_k<true>, dim3((unsigned)ceil_div(m, DB_WAVES)), dim3(DB_THREADS), 0, s,
+                   DB_CELL_ARGS(c), w.cell_label, r.labels, box_acc, box_cap, r.core);
+    } else {
+        PCH_LAUNCH("db_label", db_label_k, dim3(gl), dim3(DB_THREADS), 0, s, w.pts, w.cid, w.core_s, w.root, w.comp_min,
+                   w.bits, w.wrank, n, w.cell_start, w.cell_label, r.labels, r.core, r.chunk_size, bpc, nchunks, box_acc,
+                   box_cap);
+        PCH_LAUNCH("db_border", db_border_k<false>, dim3((unsigned)ceil_div(m, DB_WAVES)), dim3(DB_THREADS), 0, s,
+                   DB_CELL_ARGS(c), w.cell_label, r.labels, box_acc, box_cap, nullptr);
+    }
     if (box_acc) boxes->done = true;
     if (k_host) {
         PCH_TRY(peek_wait(k_host, sizeof(int32_t)));
@@ -3220,8 +3406,8 @@ extern "C" int pch_dbscan_relabel_i32(const int32_t* map, int32_t nmap, int64_t 
                w.pts, w.core_s, n, map, nmap, labels);
     PCH_LAUNCH("db_remap_cells", db_remap_cells_k, dim3((unsigned)ceil_div(c.m, DB_THREADS)), dim3(DB_THREADS), 0, s,
                w.cell_label, w.cell_ncore, c.m, map, nmap);
-    PCH_LAUNCH("db_border", db_border_k, dim3((unsigned)ceil_div(c.m, DB_WAVES)), dim3(DB_THREADS), 0, s,
-               DB_CELL_ARGS(c), w.cell_label, labels, nullptr, 0);
+    PCH_LAUNCH("db_border", db_border_k<false>, dim3((unsigned)ceil_div(c.m, DB_WAVES)), dim3(DB_THREADS), 0, s,
+               DB_CELL_ARGS(c), w.cell_label, labels, nullptr, 0, nullptr);
     return PCH_OK;
 }
 

@@ -67,7 +67,8 @@ names = {"ms_summary_k": "mean_summary", "ms_walk_k": "mean_walk", "ms_level2_k"
          "sl_hist_k": "seg_hist", "sl_scatter_k": "seg_scatter", "sl_offsets_k": "seg_offsets",
          "vx_finish_k": "voxel_finish", "vx_scatter_k": "voxel_scatter", "vx_scatter_lds_k": "voxel_scatter",
          "vx_tilehist_k": "voxel_tilehist", "vx_minmax_k": "voxel_minmax", "vx_split_k": "voxel_split",
-         "vx_binscan_k": "voxel_binscan", "db_chunkunion_k": "db_chunkunion"}
+         "vx_binscan_k": "voxel_binscan", "db_chunkunion_k": "db_chunkunion", "db_filelabel_k": "db_label",
+         "db_prelabel_cells_k": "db_prelabel", "db_border_k<true>": "db_border", "db_border_k<false>": "db_border"}
 sys.path.insert(0, here)
 from stamp import csrc_sha            # noqa: E402
 traffic = {"points": int(points), "kind": kind, "frame": frame, "source": tag, "csrc_sha": csrc_sha(),
