@@ -271,6 +271,55 @@ int pch_filter_plane_f32(const float* raw, int64_t n, const float* centroid3_dev
                          int32_t keep_mode, double offset_or_threshold, float* out_points, int32_t* out_index,
                          int64_t* out_count, float* out_aabb, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ stage B, opt-in: one RANSAC plane per xy tile
+ * The third ground rule, for rolling terrain (a corridor that crosses ridges and valleys): the rule above run once per
+ * tile of an xy grid.  Replaces: test/main_ground.py:77-115 (remove_ground_tiled_ransac, "for complex terrain").
+ * Frame and arithmetic as above: P = fl32(raw - centroid), then float64 on (double)P in exactly the written
+ * association, no FMA, IEEE division.
+ *   1 grid: PchPlaneGrid, given by the caller; tile > 0 and finite, nx, ny >= 1, nx * ny <= 65536 (else PCH_ERR_ARG).
+ *     fx = floor((x - x0) / tile), fy = floor((y - y0) / tile); the row is in the grid iff 0 <= fx < nx and
+ *     0 <= fy < ny (NaN and inf fail the comparisons); then t = fy * nx + fx, otherwise the row has no tile (t = -1).
+ *   2 members: list_t = the rows of tile t in ascending row order, n_t its length.
+ *   3 hypotheses: ONE table draws [nhyp,3] int64 with entries >= 0 for all tiles, 1 <= nhyp <= 4096 and
+ *     nx * ny * nhyp <= 2^22 (else PCH_ERR_ARG).  The triple of (t, h) is list_t[draws[h][k] mod n_t], k = 0, 1, 2;
+ *     validity and a, b, c as for pch_plane_fit_f32 (a repeated row is degenerate, then the slope gate, then
+ *     finiteness).  A tile with n_t < min_tile_rows (>= 1) has no valid hypothesis (the reference skips tiles under 10
+ *     rows); a negative draw invalidates its hypothesis.
+ *   4 counts[t][h] = the rows OF TILE t with |r| <= residual_threshold; 0 for an invalid hypothesis.
+ *   5 best per tile: the valid hypothesis with the most inliers, the smallest h on a tie; none valid: best = -1.
+ *   6 filter, order preserving over the whole cloud in FILE order (the reference emits tile by tile; file order is kept
+ *     because the sequential centroid and the 50 000-row DBSCAN chunks depend on it): a row uses its tile's plane when
+ *     that tile has one, otherwise the fallback record (a tile without a plane, a row without a tile); fallback_dev is
+ *     a PchPlaneBest on the device as pch_plane_fit_f32 writes it and may be NULL.  A row with no plane at all is not
+ *     kept, in either keep mode.
+ * pch_plane_tiles_fit_f32: out_best_dev [ntiles] device records (ntiles = nx * ny); optional outputs out_tile_rows
+ *   [ntiles] int64 (n_t), out_planes [ntiles,nhyp,4] float64 and out_counts [ntiles,nhyp] int64 (NULL: the tables live
+ *   in the workspace).  n == 0 succeeds with every tile at best = -1.  Asynchronous, no host read: the rows are grouped
+ *   by a stable radix sort of (tile, row) on the bits in use, the inlier count takes every tile in passes of at most
+ *   1024 grouped rows that never straddle two tiles, and every launch is sized from n and ntiles alone (surplus
+ *   workgroups return).  Workspace: 24 bytes per row for the sort's two key / row buffers, its digit tables, and the
+ *   two tables above.
+ * pch_filter_plane_tiles_f32: keep modes, outputs, the box of the finite kept rows and the negative count word after
+ *   a bounded wait that ran out are those of pch_filter_plane_f32; best_dev [ntiles] is what the fit wrote.
+ *   Asynchronous. */
+typedef struct PchPlaneGrid {
+    double  x0, y0, tile;     /* origin and tile edge in the centred frame */
+    int32_t nx, ny;           /* tiles along x and y; tile t = fy * nx + fx */
+} PchPlaneGrid;
+size_t pch_plane_tiles_fit_ws_bytes(int64_t n, int32_t ntiles, int32_t nhyp);
+int pch_plane_tiles_fit_f32(const float* raw, int64_t n, const float* centroid3_dev, const PchPlaneGrid* grid_host,
+                            const int64_t* draws_dev /*[nhyp,3]*/, int32_t nhyp, int32_t min_tile_rows,
+                            double residual_threshold, double cos2_max_slope,
+                            PchPlaneBest* out_best_dev /*[ntiles]*/, int64_t* out_tile_rows /*[ntiles], may be NULL*/,
+                            double* out_planes /*[ntiles,nhyp,4], may be NULL*/,
+                            int64_t* out_counts /*[ntiles,nhyp], may be NULL*/, void* ws, size_t ws_bytes,
+                            void* stream);
+size_t pch_filter_plane_tiles_ws_bytes(int64_t n, int32_t ntiles);
+int pch_filter_plane_tiles_f32(const float* raw, int64_t n, const float* centroid3_dev, const PchPlaneGrid* grid_host,
+                               const PchPlaneBest* best_dev /*[ntiles]*/, const PchPlaneBest* fallback_dev /*may be NULL*/,
+                               int32_t keep_mode, double offset_or_threshold, float* out_points, int32_t* out_index,
+                               int64_t* out_count, float* out_aabb, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ stage C
  * sklearn.cluster.DBSCAN(eps, min_samples, algorithm='ball_tree').fit(chunk).labels_ for
  * every consecutive chunk_size-row chunk, with the reference's label offsetting.

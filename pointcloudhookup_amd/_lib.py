@@ -58,6 +58,12 @@ _SIGS = {
     "pch_plane_fit_f32": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pch_filter_plane_ws_bytes": (_sz, [_i64]),
     "pch_filter_plane_f32": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pch_plane_tiles_fit_ws_bytes": (_sz, [_i64, _i32, _i32]),
+    "pch_plane_tiles_fit_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _vp,
+                                          _sz, _vp]),
+    "pch_filter_plane_tiles_ws_bytes": (_sz, [_i64, _i32]),
+    "pch_filter_plane_tiles_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _sz,
+                                             _vp]),
     "pch_dbscan_set_sort_mode": (None, [C.c_int]),
     "pch_first_nonfinite_row_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
     "pch_dbscan_relabel_i32": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _sz, _vp]),
@@ -119,6 +125,11 @@ class PlaneBestC(C.Structure):
     """PchPlaneBest (include/pch_hip.h)."""
     _fields_ = [("a", C.c_double), ("b", C.c_double), ("c", C.c_double), ("count", C.c_int64),
                 ("best", C.c_int32), ("nvalid", C.c_int32)]
+
+
+class PlaneGridC(C.Structure):
+    """PchPlaneGrid (include/pch_hip.h)."""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("tile", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32)]
 
 
 _lib = None

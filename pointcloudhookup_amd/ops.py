@@ -10,6 +10,7 @@ One function per reference library call:
   percentile_f32    <- np.percentile(z, 25)                  utils/tower_extraction.py:83
   ground_filter     <- centring + percentile filter          utils/tower_extraction.py:63-64,82-89
   ground_filter_plane <- RANSAC ground plane (opt-in)      test/main_ground.py:8-32
+  ground_filter_plane_tiles <- the same per xy tile (opt-in) test/main_ground.py:77-115
   dbscan            <- chunked sklearn DBSCAN + label offset utils/tower_extraction.py:96-117
   segment_by_label  <- per-label boolean masks               utils/tower_extraction.py:125,131-134
   crop_boxes        <- per-tower box masks over the cloud    test/kuangxuan.py:60-79, ui/extract.py:345-420
@@ -511,6 +512,268 @@ def ground_filter_plane(raw, hypotheses=256, seed=0, residual_threshold=0.1, max
                          used_fallback, first, host[64:88].view(np.float32))
     out.update(plane=np.array([rec.a, rec.b, rec.c], dtype=np.float64), inliers=int(rec.count),
                nvalid=int(rec.nvalid), best=int(rec.best))
+    return out
+
+
+# ------------------------------------------------------------- stage B, opt-in: one RANSAC plane per xy tile
+PLANE_MAX_TILES = 65536
+PLANE_MAX_TILE_TABLE = 1 << 22          # tiles x hypotheses
+_BEST_FIELDS = [("a", "<f8"), ("b", "<f8"), ("c", "<f8"), ("count", "<i8"), ("best", "<i4"), ("nvalid", "<i4")]
+
+
+def plane_tile_grid(raw, centroid, tile_size):
+    """The xy grid of the per-tile plane rule over the finite x and y of fl32(raw - centroid): dict(x0, y0, tile, nx,
+    ny) with x0 = (double)fl32(min_x - cx), nx = floor((max - x0) / tile) + 1, likewise y (PchPlaneGrid,
+    include/pch_hip.h).  The bounds come from a torch reduction; one small host read.  ValueError beyond 65 536
+    tiles, naming the smallest tile_size that fits."""
+    import math
+    import numpy as np
+    raw = _need_cuda(raw, torch.float32, "raw").reshape(-1, 3)
+    tile = float(tile_size)
+    if not (tile > 0.0 and math.isfinite(tile)):
+        raise ValueError(f"tile_size must be positive and finite, got {tile_size!r}")
+    cen = _centroid_dev(centroid, raw.device)
+    inf = torch.tensor(float("inf"), dtype=torch.float32, device=raw.device)
+    fin = torch.isfinite(raw[:, :2])
+    lo = torch.where(fin, raw[:, :2], inf).amin(dim=0) if raw.shape[0] else inf.expand(2)
+    hi = torch.where(fin, raw[:, :2], -inf).amax(dim=0) if raw.shape[0] else (-inf).expand(2)
+    host = torch.cat([lo, hi, cen]).cpu().numpy()
+    return _plane_grid_of(host[0:2], host[2:4], host[4:6], tile)
+
+
+def _plane_grid_of(lo, hi, cen, tile):
+    """the grid from the float32 bounds of the finite raw x, y (inf / -inf without any) and the float32 centroid"""
+    import math
+    import numpy as np
+    out, ext = dict(tile=float(tile)), [0.0, 0.0]
+    for k, name in enumerate(("x", "y")):
+        if not lo[k] <= hi[k]:                          # no finite coordinate: one tile at the origin
+            out[name + "0"], out["n" + name] = 0.0, 1
+            continue
+        with np.errstate(over="ignore"):
+            a, b = float(np.float32(lo[k]) - np.float32(cen[k])), float(np.float32(hi[k]) - np.float32(cen[k]))
+        if not (math.isfinite(a) and math.isfinite(b)):
+            raise ValueError("the centred bounds of the cloud are not finite")
+        out[name + "0"], out["n" + name], ext[k] = a, int(math.floor((b - a) / tile)) + 1, b - a
+    if out["nx"] * out["ny"] > PLANE_MAX_TILES:
+        fits = lambda s: (math.floor(ext[0] / s) + 1) * (math.floor(ext[1] / s) + 1) <= PLANE_MAX_TILES
+        lo_s, hi_s = tile, max(ext) + 1.0                              # hi_s: one tile, fits
+        for _ in range(100):
+            mid = 0.5 * (lo_s + hi_s)
+            lo_s, hi_s = (lo_s, mid) if fits(mid) else (mid, hi_s)
+        raise ValueError(f"tile_size {tile:g} gives {out['nx']} x {out['ny']} tiles, more than {PLANE_MAX_TILES}; "
+                         f"the smallest tile_size that fits is {hi_s:.6g}")
+    return out
+
+
+def plane_tile_draws(H=64, seed=0):
+    """The draw table of H hypotheses, shared by all tiles: host int64 [H,3] in [0, 2^62); the triple of (tile t,
+    hypothesis h) is list_t[draws[h][k] mod n_t].  The first H of a longer table with the same seed."""
+    import numpy as np
+    H = int(H)
+    if not 1 <= H <= PLANE_MAX_HYPOTHESES:
+        raise ValueError(f"between 1 and {PLANE_MAX_HYPOTHESES} hypotheses, got {H}")
+    return np.random.Generator(np.random.PCG64(int(seed))).integers(0, 2 ** 62, size=(H, 3), dtype=np.int64)
+
+
+def _plane_grid_c(grid):
+    g = _lib.PlaneGridC(float(grid["x0"]), float(grid["y0"]), float(grid["tile"]), int(grid["nx"]), int(grid["ny"]))
+    ntiles = g.nx * g.ny
+    if g.nx < 1 or g.ny < 1 or ntiles > PLANE_MAX_TILES:
+        raise ValueError(f"the grid must have between 1 and {PLANE_MAX_TILES} tiles, got {g.nx} x {g.ny}")
+    return g, ntiles
+
+
+def _plane_draws_dev(draws, ntiles, dev):
+    import numpy as np
+    if isinstance(draws, torch.Tensor) and draws.is_cuda:
+        draws = _need_cuda(draws, torch.int64, "draws").reshape(-1, 3)
+    else:
+        host = np.ascontiguousarray(np.asarray(draws, dtype=np.int64)).reshape(-1, 3)
+        if host.size and host.min() < 0:
+            raise ValueError("draws: every entry must be >= 0")
+        draws = torch.from_numpy(host).to(dev)
+    H = draws.shape[0]
+    if not 1 <= H <= PLANE_MAX_HYPOTHESES:
+        raise ValueError(f"between 1 and {PLANE_MAX_HYPOTHESES} hypotheses, got {H}")
+    if ntiles * H > PLANE_MAX_TILE_TABLE:
+        raise ValueError(f"{ntiles} tiles x {H} hypotheses exceed {PLANE_MAX_TILE_TABLE} table entries")
+    return draws
+
+
+def _plane_tiles_fit_launch(raw, cen_dev, grid_c, ntiles, draws_dev, min_tile_rows, residual_threshold, max_slope_deg,
+                            best, tile_rows, planes=None, counts=None):
+    """pch_plane_tiles_fit_f32, enqueued; best: uint8 [ntiles * 40], tile_rows: int64 [ntiles] (device)"""
+    import ctypes as C
+    import math
+    L = _lib.lib()
+    n, H = raw.shape[0], draws_dev.shape[0]
+    cos2 = math.cos(math.radians(float(max_slope_deg))) ** 2
+    ws = _workspace(L.pch_plane_tiles_fit_ws_bytes(n, ntiles, H), raw.device)
+    _lib.check(L.pch_plane_tiles_fit_f32(_ptr(raw), n, _ptr(cen_dev), C.cast(C.pointer(grid_c), C.c_void_p), _ptr(draws_dev),
+                                         H, int(min_tile_rows), float(residual_threshold), cos2, _ptr(best),
+                                         _ptr(tile_rows), _ptr(planes), _ptr(counts), _ptr(ws), ws.numel(), _stream()))
+
+
+def _plane_tiles_table(best_bytes, rows):
+    """the per-tile host table from the record bytes (numpy uint8 [ntiles * 40]) and the row counts"""
+    import numpy as np
+    rec = best_bytes.view(np.dtype(_BEST_FIELDS))
+    return dict(best=rec["best"].copy(), planes=np.stack([rec["a"], rec["b"], rec["c"]], axis=1),
+                inliers=rec["count"].copy(), rows=rows.copy(), nvalid=rec["nvalid"].copy())
+
+
+def plane_tiles_fit(raw, centroid, grid, draws, min_tile_rows=64, residual_threshold=0.1, max_slope_deg=45.0,
+                    want_tables=False):
+    """One RANSAC plane per tile of ``grid`` (plane_tile_grid, or any dict(x0, y0, tile, nx, ny)) over the draw table
+    ``draws`` (plane_tile_draws); the rule is stated in include/pch_hip.h.  Returns host arrays over the tiles
+    t = fy * nx + fx: best int32 (-1: no plane), planes float64 [ntiles,3] (zeros without one), inliers int64, rows
+    int64 (the tile's population), nvalid int32, plus grid; with ``want_tables`` also planes_table float64
+    [ntiles,H,4] and counts_table int64 [ntiles,H].  Synchronises once."""
+    import numpy as np
+    if int(min_tile_rows) < 1:
+        raise ValueError("min_tile_rows must be at least 1")
+    raw = _need_cuda(raw, torch.float32, "raw").reshape(-1, 3)
+    dev = raw.device
+    grid_c, ntiles = _plane_grid_c(grid)
+    with torch.cuda.device(dev):
+        draws_dev = _plane_draws_dev(draws, ntiles, dev)
+        H = draws_dev.shape[0]
+        best = torch.empty((ntiles * 40,), dtype=torch.uint8, device=dev)
+        rows = torch.empty((ntiles,), dtype=torch.int64, device=dev)
+        planes = torch.empty((ntiles, H, 4), dtype=torch.float64, device=dev) if want_tables else None
+        counts = torch.empty((ntiles, H), dtype=torch.int64, device=dev) if want_tables else None
+        _plane_tiles_fit_launch(raw, _centroid_dev(centroid, dev), grid_c, ntiles, draws_dev, min_tile_rows,
+                                residual_threshold, max_slope_deg, best, rows, planes, counts)
+        parts = [best, rows.view(torch.uint8)]
+        if want_tables:
+            parts += [planes.view(torch.uint8).reshape(-1), counts.view(torch.uint8).reshape(-1)]
+        host = torch.cat(parts).cpu().numpy()
+    out = _plane_tiles_table(host[:40 * ntiles], host[40 * ntiles:48 * ntiles].view(np.int64))
+    out["grid"] = dict(x0=grid_c.x0, y0=grid_c.y0, tile=grid_c.tile, nx=grid_c.nx, ny=grid_c.ny)
+    if want_tables:
+        at = 48 * ntiles
+        out["planes_table"] = host[at:at + 32 * ntiles * H].view(np.float64).reshape(ntiles, H, 4).copy()
+        out["counts_table"] = host[at + 32 * ntiles * H:].view(np.int64).reshape(ntiles, H).copy()
+    return out
+
+
+def _plane_record_dev(plane, dev):
+    """a PchPlaneBest on the device from (a, b, c), a plane_fit result or None (no plane: best = -1)"""
+    import numpy as np
+    if isinstance(plane, dict):
+        plane = plane["plane"]
+    rec = _lib.PlaneBestC(0.0, 0.0, 0.0, 0, -1, 0)
+    if plane is not None:
+        a, b, c = (float(v) for v in plane)
+        rec = _lib.PlaneBestC(a, b, c, 0, 0, 1)
+    return torch.from_numpy(np.frombuffer(bytes(rec), dtype=np.uint8).copy()).to(dev)
+
+
+def _filter_plane_tiles_launch(raw, cen_dev, grid_c, ntiles, best_ptr, fallback_ptr, keep, value, out_points,
+                               out_index, cnt_ptr, aabb_ptr):
+    import ctypes as C
+    L = _lib.lib()
+    n = raw.shape[0]
+    ws = _workspace(L.pch_filter_plane_tiles_ws_bytes(n, ntiles), raw.device)
+    _lib.check(L.pch_filter_plane_tiles_f32(_ptr(raw), n, _ptr(cen_dev), C.cast(C.pointer(grid_c), C.c_void_p), best_ptr,
+                                            fallback_ptr, _PLANE_KEEP[keep], float(value), _ptr(out_points),
+                                            _ptr(out_index), cnt_ptr, aabb_ptr, _ptr(ws), ws.numel(), _stream()))
+
+
+def filter_plane_tiles(raw, centroid, grid, fit_or_table, fallback=None, keep="above", offset=3.0,
+                       residual_threshold=0.1, want_index=True):
+    """points = fl32(raw - centroid), every row kept by its residual to the plane of ITS tile, in file order:
+    fit_or_table is what plane_tiles_fit returned (or any dict with best [ntiles] and planes [ntiles,3]); a row whose
+    tile has no plane, or that lies outside the grid, uses ``fallback`` - (a, b, c), a plane_fit result, or None - and
+    a row with no plane at all is dropped.  keep / offset / residual_threshold as in filter_plane.  Returns the dict
+    of filter_gt.  Synchronises."""
+    import numpy as np
+    value = _plane_keep_value(keep, offset, residual_threshold)
+    raw = _need_cuda(raw, torch.float32, "raw").reshape(-1, 3)
+    n, dev = raw.shape[0], raw.device
+    grid_c, ntiles = _plane_grid_c(grid)
+    rec = np.zeros((ntiles,), dtype=np.dtype(_BEST_FIELDS))
+    tb = np.asarray(fit_or_table["best"]).reshape(-1)
+    tp = np.asarray(fit_or_table["planes"], dtype=np.float64).reshape(-1, 3)
+    if tb.shape[0] != ntiles or tp.shape[0] != ntiles:
+        raise ValueError(f"the table must have one entry per tile ({ntiles}), got {tb.shape[0]}")
+    rec["a"], rec["b"], rec["c"], rec["best"] = tp[:, 0], tp[:, 1], tp[:, 2], tb
+    with torch.cuda.device(dev):
+        best = torch.from_numpy(rec.view(np.uint8)).to(dev)
+        fb = None if fallback is None else _plane_record_dev(fallback, dev)
+        out_points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        out_index = torch.empty((n,), dtype=torch.int32, device=dev) if want_index else None
+        cnt = torch.zeros((1,), dtype=torch.int64, device=dev)
+        aabb = torch.zeros((6,), dtype=torch.float32, device=dev)
+        _filter_plane_tiles_launch(raw, _centroid_dev(centroid, dev), grid_c, ntiles, _ptr(best), _ptr(fb), keep, value,
+                                   out_points, out_index, _ptr(cnt), _ptr(aabb))
+        m = _lib.check_count(cnt.item(), "filter_plane_tiles")
+    return dict(points=out_points[:m], index=None if out_index is None else out_index[:m], count=m,
+                aabb=aabb.cpu().numpy())
+
+
+def ground_filter_plane_tiles(raw, tile_size=20.0, hypotheses=64, seed=0, min_tile_rows=64, fallback_hypotheses=64,
+                              residual_threshold=0.1, max_slope_deg=45.0, offset=3.0, fallback_offset=1.0,
+                              min_keep=1000, keep="above", want_index=True):
+    """Stage B with one plane per xy tile, for rolling terrain (test/main_ground.py:77-115; tile_size 20 is the
+    reference's own call, :142): centroid (mean_seq_f32), the grid (plane_tile_grid), a global plane_fit over
+    plane_hypothesis_rows(n, fallback_hypotheses, seed) as the fallback, plane_tiles_fit over plane_tile_draws(
+    hypotheses, seed), filter_plane_tiles, and in "above" mode the reference's fallback offset as in
+    ground_filter_plane.  Returns the dict of ground_filter plus tiles (grid and the per-tile table of
+    plane_tiles_fit) and fallback_plane (float64 [3] | None); base = float32(c) of the fallback plane, NaN without
+    one.  ValueError when neither a tile nor the fallback has a plane.  The grid is a host structure, so the centroid
+    and the bounds are read once (a few words); fits and filter then chain on the device with one host read, a
+    second after a fallback offset."""
+    import numpy as np
+    value = _plane_keep_value(keep, offset, residual_threshold)
+    L = _lib.lib()
+    raw = _need_cuda(raw, torch.float32, "raw").reshape(-1, 3)
+    n, dev = raw.shape[0], raw.device
+    if n == 0:
+        raise ValueError("no valid ground plane: the cloud is empty")
+    if int(min_tile_rows) < 1:
+        raise ValueError("min_tile_rows must be at least 1")
+    with torch.cuda.device(dev):
+        # one block for the host: [0:40] fallback record, [48:56] count, [64:88] aabb, [96:108] centroid
+        scal = torch.zeros((112,), dtype=torch.uint8, device=dev)
+        base = scal.data_ptr()
+        cen = scal[96:108].view(torch.float32)
+        ws = _workspace(L.pch_mean_seq_f32_ws_bytes(n), dev)
+        _lib.check(L.pch_mean_seq_f32(_ptr(raw), n, _ptr(cen), _ptr(ws), ws.numel(), _stream()))
+        grid = plane_tile_grid(raw, cen, tile_size)
+        grid_c, ntiles = _plane_grid_c(grid)
+        draws_dev = _plane_draws_dev(plane_tile_draws(hypotheses, seed), ntiles, dev)
+        rows_dev = _plane_rows_dev(plane_hypothesis_rows(n, fallback_hypotheses, seed), n, dev)
+        out_points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        out_index = torch.empty((n,), dtype=torch.int32, device=dev) if want_index else None
+        best = torch.empty((ntiles * 40,), dtype=torch.uint8, device=dev)
+        tile_rows = torch.empty((ntiles,), dtype=torch.int64, device=dev)
+        _plane_fit_launch(raw, cen, rows_dev, residual_threshold, max_slope_deg, base)
+        _plane_tiles_fit_launch(raw, cen, grid_c, ntiles, draws_dev, min_tile_rows, residual_threshold, max_slope_deg,
+                                best, tile_rows)
+
+        def sweep(v):
+            _filter_plane_tiles_launch(raw, cen, grid_c, ntiles, _ptr(best), base, keep, v, out_points, out_index,
+                                       base + 48, base + 64)
+            host = torch.cat([scal, best, tile_rows.view(torch.uint8)]).cpu().numpy()
+            return host, _lib.check_count(host[48:56].view("<i8")[0], "ground_filter_plane_tiles")
+
+        host, nf = sweep(value)
+        rec = _plane_best(host[:40])
+        tiles = _plane_tiles_table(host[112:112 + 40 * ntiles], host[112 + 40 * ntiles:].view(np.int64))
+        tiles["grid"] = grid
+        if rec.best < 0 and not (tiles["best"] >= 0).any():
+            raise ValueError(f"no valid ground plane in any of {ntiles} tiles nor among {rows_dev.shape[0]} global "
+                             f"hypotheses (degenerate triples, or none within {max_slope_deg} degrees of level)")
+        first, used_fallback = nf, False
+        if keep == "above" and nf < int(min_keep):
+            used_fallback, value = True, fallback_offset
+            host, nf = sweep(value)
+    out = _ground_result(out_points, out_index, nf, host[96:108].view(np.float32),
+                         np.float32(rec.c) if rec.best >= 0 else np.float32(np.nan), value, used_fallback, first,
+                         host[64:88].view(np.float32))
+    out.update(tiles=tiles, fallback_plane=None if rec.best < 0 else np.array([rec.a, rec.b, rec.c], dtype=np.float64))
     return out
 
 

@@ -27,12 +27,14 @@ def cluster_points(raw, eps=8.0, min_points=80, chunk_size=REF_CHUNK, pct=25.0, 
     ``ground`` selects the ground rule of stage B: "percentile" (the reference's, the default: one fused library
     call) or "plane" (opt-in, for sloped terrain: ops.ground_filter_plane, then ops.dbscan and ops.segment_by_label;
     ``plane`` is a dict of keyword arguments for it - hypotheses, seed, residual_threshold, max_slope_deg, keep, ...
-    - whose offset / fallback_offset / min_keep / want_index default to this call's).
+    - whose offset / fallback_offset / min_keep / want_index default to this call's) or "plane_tiles" (opt-in, for
+    rolling terrain: the same plane per xy tile, ops.ground_filter_plane_tiles; ``plane`` then carries its keyword
+    arguments - tile_size, hypotheses, seed, min_tile_rows, fallback_hypotheses, ...).
     """
-    if ground == "plane":
+    if ground in ("plane", "plane_tiles"):
         kw = dict(offset=offset, fallback_offset=fallback_offset, min_keep=min_keep, want_index=want_index)
         kw.update(plane or {})
-        gf = ops.ground_filter_plane(raw, **kw)
+        gf = (ops.ground_filter_plane if ground == "plane" else ops.ground_filter_plane_tiles)(raw, **kw)
         points = gf["points"]
         if gf["count"]:
             labels, _, k = ops.dbscan(points, eps, min_points, chunk_size, aabb=gf["aabb"])
@@ -44,7 +46,7 @@ def cluster_points(raw, eps=8.0, min_points=80, chunk_size=REF_CHUNK, pct=25.0, 
             out.update(perm=perm, offsets=offsets, stats=stats)
         return out
     if ground != "percentile":
-        raise ValueError(f"ground must be 'percentile' or 'plane', got {ground!r}")
+        raise ValueError(f"ground must be 'percentile', 'plane' or 'plane_tiles', got {ground!r}")
     gf, labels, k, perm, offsets, stats = ops.tower_clusters(
         raw, eps, min_points, chunk_size, pct, offset, fallback_offset, min_keep,
         want_index=want_index, segment=segment)

@@ -24,7 +24,10 @@ facets differently on the reduced input, so a box can differ in the centimetres;
 ``GROUND_MODE`` ("percentile" | "plane", env PCH_GROUND_MODE): "percentile" is the reference's height filter;
 "plane" removes the ground by one RANSAC plane instead (ops.ground_filter_plane, the remedy of the reference's own
 test/main_ground.py:8-32) - for sloped terrain, where one global percentile keeps the ground uphill and cuts the
-towers downhill.  It logs one extra line with the plane.
+towers downhill.  It logs one extra line with the plane.  "plane_tiles" fits that plane once per xy tile of
+``GROUND_TILE`` metres (env PCH_GROUND_TILE, default 20.0; ops.ground_filter_plane_tiles, the reference's
+remove_ground_tiled_ransac, test/main_ground.py:77-115) - for rolling terrain, which no single plane fits.  It logs one
+extra line with the tile size, the tiles with a plane of their own out of the occupied ones, and the fallback plane.
 """
 from __future__ import annotations
 
@@ -40,6 +43,7 @@ DEVICE = os.environ.get("PCH_DEVICE", "cuda:0")
 CHUNK_FAILURE = os.environ.get("PCH_CHUNK_FAILURE", "reference")
 OBB_MODE = os.environ.get("PCH_OBB_MODE", "exact")
 GROUND_MODE = os.environ.get("PCH_GROUND_MODE", "percentile")
+GROUND_TILE = float(os.environ.get("PCH_GROUND_TILE", "20.0"))
 PRESTART_BYTES = 100 << 20                             # LAS files from here on get worker processes early
 CHUNK_SIZE = 50000                                     # utils/tower_extraction.py:96
 
@@ -127,11 +131,14 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
         if GROUND_MODE == "plane":
             gf = ops.ground_filter_plane(raw, want_index=False)
             clock.mark("centroid + plane fit + plane filter")
+        elif GROUND_MODE == "plane_tiles":
+            gf = ops.ground_filter_plane_tiles(raw, tile_size=GROUND_TILE, want_index=False)
+            clock.mark("centroid + plane fit per tile + plane filter")
         elif GROUND_MODE == "percentile":
             gf = ops.ground_filter(raw, 25.0, 3.0, 1.0, 1000, want_index=False)
             clock.mark("centroid + percentile filter")
         else:
-            raise ValueError("GROUND_MODE must be 'percentile' or 'plane'")
+            raise ValueError("GROUND_MODE must be 'percentile', 'plane' or 'plane_tiles'")
         header_info["centroid"] = gf["centroid"]
         if gf["used_fallback"]:
             log(f"✅ 高度过滤完成，保留点数: {gf['count_at_offset']}")
@@ -141,6 +148,8 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
         if GROUND_MODE == "plane":
             a, b, c = gf["plane"]
             log(f"📐 地面平面: z = {a:.6f}·x + {b:.6f}·y + {c:.3f}（内点 {gf['inliers']}/{raw.shape[0]}）")
+        if GROUND_MODE == "plane_tiles":
+            log(ground_tiles_line(gf))
     except Exception as e:
         log(f"⚠️ 高度过滤失败: {str(e)}")
         return tower_obbs
@@ -241,6 +250,15 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
     progress(100)
     log("✅ 杆塔提取完成")
     return tower_obbs
+
+
+def ground_tiles_line(gf):
+    """the extra log line of GROUND_MODE "plane_tiles" for a result of ops.ground_filter_plane_tiles"""
+    tiles = gf["tiles"]
+    own, occupied = int((tiles["best"] >= 0).sum()), int((tiles["rows"] > 0).sum())
+    fb = gf["fallback_plane"]
+    fb_text = "无" if fb is None else f"z = {fb[0]:.6f}·x + {fb[1]:.6f}·y + {fb[2]:.3f}"
+    return f"📐 分块地面平面: 分块 {tiles['grid']['tile']:g} m，独立平面 {own}/{occupied} 块，回退平面: {fb_text}"
 
 
 _UNBOUND_MSG = ("local variable 'clustering' referenced before assignment" if sys.version_info < (3, 11)
