@@ -27,9 +27,7 @@ struct SelState {
     uint32_t pad;
 };
 
-__device__ __forceinline__ uint32_t sel_key(float v) {
-    return (v != v) ? 0xFFFFFFFFu : f32_ordered(v);
-}
+// (sel_key, the order-preserving key of a value, lives in pch_mean.h: the summary pass brackets with it too)
 
 // adds 1 to h[bin] for every active lane; lanes of a wave that share a bin are merged into one
 // LDS atomic (z values of a flat corridor fall into a handful of bins)
@@ -384,6 +382,61 @@ __global__ __launch_bounds__(256) void sel_bracket_k(const float* __restrict__ b
     }
 }
 
+// The same BrState from what the centroid summary left (MsBracket, pch_mean.h) instead of a sweep over a z column:
+// per 1024-row block one record (keys below L, NaN values, values inside the bracket) and those values at the front
+// of the block's segment.  A workgroup takes SEL_CBLKS blocks, one record per thread; the counts are known before a
+// value is read, so the output offsets come from a scan and ONE reservation per workgroup (382 at 100 M rows; see
+// sel_bracket_k for the price of reserving more often) and the values go straight from the segments to `cand` -
+// item k of the workgroup finds its block by a search over the scanned counts, so every lane copies and consecutive
+// lanes write consecutive words.  An invalid bracket raises `overflow`: the device check behind (sel_bracket_fix_k)
+// then fails as it does for a full buffer or a rank outside the bracket, and the select reads the rows.
+constexpr int SEL_CBLKS = 256;
+__global__ __launch_bounds__(SEL_CBLKS) void sel_collect_k(const MsBracket* __restrict__ brk,
+                                                           const MsBrRec* __restrict__ brec, int64_t nblk,
+                                                           const float* __restrict__ zseg, BrState* __restrict__ br,
+                                                           float* __restrict__ cand, uint32_t cap) {
+    __shared__ uint32_t first[SEL_CBLKS];                  // values of the workgroup in front of block t
+    __shared__ uint32_t wtot[SEL_CBLKS / 64];
+    __shared__ uint32_t gbase;
+    if ((brk->valid[0] & brk->valid[1]) == 0u) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) br->overflow = 1u;
+        return;
+    }
+    const int64_t b0 = (int64_t)blockIdx.x * SEL_CBLKS;
+    const int64_t b = b0 + threadIdx.x;
+    MsBrRec r = {0u, 0u};
+    if (b < nblk) r = brec[b];
+    const uint32_t c = r.count_less & 0xFFFFu;
+    const uint32_t incl = wave_scan_incl(c);
+    if (lane_id() == 63) wtot[wave_id()] = incl;
+    unsigned long long less = wave_reduce_add((unsigned long long)(r.count_less >> 16));
+    unsigned long long nans = wave_reduce_add((unsigned long long)r.nan);
+    if (lane_id() == 0) {
+        if (less) atomicAdd(&br->less, less);
+        if (nans) atomicAdd(&br->nan, nans);
+    }
+    __syncthreads();
+    uint32_t before = incl - c, T = 0;
+    for (int w = 0; w < SEL_CBLKS / 64; ++w) { before += w < wave_id() ? wtot[w] : 0u; T += wtot[w]; }
+    first[threadIdx.x] = before;
+    if (threadIdx.x == 0) gbase = T ? atomicAdd(&br->count, T) : 0u;
+    __syncthreads();
+    if (T == 0) return;                                    // workgroup-uniform
+    const uint32_t g0 = gbase;
+    if (g0 + T > cap || g0 + T < g0) {                     // (the sum of all counts is below 2^31: n is)
+        if (threadIdx.x == 0) br->overflow = 1u;
+        return;                                            // the candidates will not be used
+    }
+#pragma unroll 4
+    for (uint32_t k = threadIdx.x; k < T; k += SEL_CBLKS) {
+        int t = 0;                                         // largest block with first[t] <= k
+#pragma unroll
+        for (int step = SEL_CBLKS / 2; step > 0; step >>= 1)
+            if (first[t + step] <= k) t += step;
+        cand[g0 + k] = zseg[(b0 + t) * 1024 + (k - first[t])];
+    }
+}
+
 // decides whether the candidates hold both order statistics and prepares the state of whichever select runs next
 __global__ void sel_bracket_fix_k(BrState* __restrict__ br, SelRun* __restrict__ run, unsigned long long k0, int same) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -429,7 +482,10 @@ struct SelWs {
     uint32_t* also_zero;   // optional: words sel_init clears for the caller (see sel_init_k)
     int64_t   also_words;
 };
-static void sel_plan(Arena& a, SelWs& w, int64_t n = 0) {
+// from_summary: the bracket comes from the centroid summary's samples (sel_collect_k; the fused filter, from 131 072
+// rows on).  One sample per 1024 rows makes a wider bracket than sixteen in 1024 (bracket_ranks): a tenth of the column
+// at 4 M rows and the 25th percentile, a third at 400 000 - hence the larger buffers.
+static void sel_plan(Arena& a, SelWs& w, int64_t n = 0, bool from_summary = false) {
     w.scal = a.take<float>(4);
     w.run = a.take<SelRun>(3);
     w.hist = a.take<uint32_t>(9 * SEL_BINS);
@@ -439,7 +495,11 @@ static void sel_plan(Arena& a, SelWs& w, int64_t n = 0) {
         w.br = a.take<BrState>(1);
         w.ns = SEL_GROUP * (n / SEL_EVERY);
         w.sample = a.take<float>(w.ns);
-        w.cap = (uint32_t)(n / 16) + 1024u;
+        w.cap = (uint32_t)(n / (from_summary ? 4 : 16)) + 1024u;
+        w.cand = a.take<float>(w.cap);
+    } else if (from_summary && n > 0) {
+        w.br = a.take<BrState>(1);
+        w.cap = (uint32_t)(n / 2) + 1024u;
         w.cand = a.take<float>(w.cap);
     }
 }
@@ -482,17 +542,20 @@ static bool select_is_bracketed(const SelWs& w, int64_t n, int64_t stride) {
     return w.sample && stride == 1 && n >= SEL_BRACKET_MIN;
 }
 struct SelBracket { int64_t r_lo, r_hi; };
-static SelBracket select_bracket_ranks(const SelWs& w, int64_t n, const PctIndex& pi) {
-    // bracket from the sample: ranks around k0 * ns / n, six sigma for ns/16 independent draws + 0.2 %
-    const int64_t ns = w.ns;
+// bracket from a sample of ns values drawn in runs of `group` consecutive ones: ranks around k0 * ns / n, six sigma
+// of the binomial rank error for ns / group independent draws + 0.2 % + 16
+static SelBracket bracket_ranks(int64_t ns, int group, int64_t n, const PctIndex& pi) {
     const double p = (double)pi.k0 / (double)(n > 1 ? n - 1 : 1);
-    const double sigma = sqrt(p * (1.0 - p) * (double)ns * 16.0);
+    const double sigma = sqrt(p * (1.0 - p) * (double)ns * (double)group);
     const int64_t margin = (int64_t)(6.0 * sigma) + ns / 500 + 16;
     const int64_t mid = (int64_t)(p * (double)(ns - 1));
     SelBracket r;
     r.r_lo = mid - margin < 0 ? 0 : mid - margin;
     r.r_hi = mid + margin > ns - 1 ? ns - 1 : mid + margin;
     return r;
+}
+static SelBracket select_bracket_ranks(const SelWs& w, int64_t n, const PctIndex& pi) {
+    return bracket_ranks(w.ns, SEL_GROUP, n, pi);
 }
 // First half of the bracketed select: the sample and the two order statistics of it that bracket the ranks.  It
 // needs the VALUES only (src / src_stride: the column itself, or the z of the (n,3) rows it will be copied from), so the
@@ -558,6 +621,21 @@ static int select_passes(const float* base, int64_t n, int64_t stride, double q_
     // way, the kernels pick their source from br->ok
     const SelGate src = {&w.br->ok, w.cand, &w.br->count};
     return select_rounds(base, n, stride, !pi.same, fin, hfin, s, src, n);
+}
+// The same second half when the centroid summary bracketed the column (MsBracket, pch_mean.h; the caller has run
+// sel_init_k): gather what it left, check it, and select - from the candidates, or if the check fails from the z of the
+// (n,3) rows themselves (three passes over 12 B per row: exact and rare).
+static int select_from_summary(const float* raw, int64_t n, double q_percent, const MsCand& mc, const float* zseg,
+                               SelWs& w, hipStream_t s) {
+    const PctIndex pi = pct_index(n, q_percent);
+    SelRun* fin = w.run + 2;
+    const int64_t nblk = ceil_div(n, 1024);
+    PCH_LAUNCH("sel_collect", sel_collect_k, dim3((unsigned)ceil_div(nblk, SEL_CBLKS)), dim3(SEL_CBLKS), 0, s,
+               (const MsBracket*)mc.bracket, (const MsBrRec*)mc.brec, nblk, zseg, w.br, w.cand, w.cap);
+    PCH_LAUNCH("sel_bracket_fix", sel_bracket_fix_k, dim3(1), dim3(64), 0, s, w.br, fin, (unsigned long long)pi.k0,
+               pi.same);
+    const SelGate src = {&w.br->ok, w.cand, &w.br->count};
+    return select_rounds(raw + 2, n, 3, !pi.same, fin, w.hist + 6 * SEL_BINS, s, src, n);
 }
 // ... and the final interpolation, which is where `sub` (the centroid) enters
 static int select_lerp(int64_t n, const float* sub, double q_percent, float add1, float add2, SelWs& w,
@@ -967,7 +1045,7 @@ __global__ void gf_finalize_k(const GfState* __restrict__ st, const float* __res
 
 struct GfWs {
     float*    centroid;
-    float*    zcol;              // copy of the z column (written by the centroid pass)
+    float*    zcol;              // copy of the z column (written by the centroid pass), or the blocks' segments (MsBracket)
     MsWs      ms;
     SelWs     sel;
     GfState*  st;
@@ -975,12 +1053,19 @@ struct GfWs {
     size_t    clear_bytes;       // st .. end of status: zeroed before the sweeps
     MsCand    cand;              // candidate rows emitted by the summary pass (see gf_cand_k)
 };
+// The percentile's bracket from the summary (MsBracket) instead of a z column: on wherever the summary emits candidate
+// slots.  PCH_GF_NO_BRACKET turns it off (the z column, sel_sample_k and sel_bracket_k as before);
+// PCH_GF_BRACKET_INVALID keeps it on and fails its device check, so that the select reads the rows.
+static bool gf_brackets(int64_t n) {
+    static const bool off = getenv("PCH_GF_NO_BRACKET") != nullptr;                // tuning toggle
+    return !off && ms_makes_cand(n);
+}
 static void gf_plan(Arena& a, int64_t n, GfWs& w) {
     const int64_t nb = ceil_div(n > 0 ? n : 1, GF_TILE);
     w.centroid = a.take<float>(4);
     ms_plan(a, n, w.ms);
-    w.zcol = a.take<float>(n > 0 ? n : 1);
-    sel_plan(a, w.sel, n);
+    w.zcol = a.take<float>(n > 0 ? n : 1);                 // with the bracket: the blocks' segments (MsBracket)
+    sel_plan(a, w.sel, n, gf_brackets(n));
     const size_t st_off = a.off;
     w.st = a.take<GfState>(1);
     w.status = a.take<uint64_t>(2 * nb);
@@ -992,6 +1077,10 @@ static void gf_plan(Arena& a, int64_t n, GfWs& w) {
     w.cand.slots = a.take<float>(nblk * 4 * MS_CAND_SLOT); // 8 KB per 1024-row block: four planes (MsCand)
     w.cand.pct = 0.0;
     w.cand.add = 0.0f;
+    w.cand.bracket = a.take<MsBracket>(1);
+    w.cand.brec = a.take<MsBrRec>(nblk);
+    w.cand.r_lo = w.cand.r_hi = 0;
+    w.cand.force_invalid = 0;
 }
 
 }  // namespace pch
@@ -1181,16 +1270,35 @@ int pch::ground_filter_run(const float* raw, int64_t n, double pct, float offset
     // front of the interpolation.  With the sample half out of the way both strands end within a few us of each
     // other (measured: the other assignment, select on `s` and walk on the side stream, loses 45 us to the hops).
     // Without a side stream the select follows the walk on `s` and takes its own sample.
-    const bool sample_early = ss.ok && select_is_bracketed(w.sel, n, 1);
-    if (sample_early) {
+    // (That is the route with a z column: clouds below 131 072 rows, or PCH_GF_NO_BRACKET.)
+    // From 131 072 rows on the summary brackets the percentile itself (MsBracket, pch_mean.h): no sample strand, no z
+    // column; behind the summary the side stream gathers the blocks' values (sel_collect_k) instead of sweeping a column.
+    const bool bracket = gf_brackets(n);
+    if (bracket) {
+        static const bool invalid = getenv("PCH_GF_BRACKET_INVALID") != nullptr;   // tuning toggle
+        const int64_t nblk = ceil_div(n, GF_CBLK);
+        const SelBracket r = bracket_ranks(ceil_div(nblk, ms_bracket_stride(nblk)), 1, n, pct_index(n, pct));
+        w.cand.r_lo = r.r_lo;
+        w.cand.r_hi = r.r_hi;
+        w.cand.force_invalid = invalid ? 1 : 0;
+    } else {
+        w.cand.bracket = nullptr;
+    }
+    const bool sample_early = !bracket && ss.ok && select_is_bracketed(w.sel, n, 1);
+    if (sample_early || (bracket && ss.ok)) {
         PCH_HIP_TRY(hipEventRecord(ss.ev_start, s));            // everything the caller queued before this call
         PCH_HIP_TRY(hipStreamWaitEvent(ss.s, ss.ev_start, 0));   // (the rows; the previous user of the workspace)
-        PCH_TRY(select_sample_passes(raw + 2, 3, n, pct, w.sel, ss.s));
     }
+    if (sample_early) PCH_TRY(select_sample_passes(raw + 2, 3, n, pct, w.sel, ss.s));
+    if (bracket)
+        PCH_LAUNCH("sel_init", sel_init_k, dim3((unsigned)ceil_div(9 * SEL_BINS, 256)), dim3(256), 0, ss.ok ? ss.s : s,
+                   w.sel.hist, 9 * SEL_BINS, w.sel.run, 3, 0ull, 0ull, 0ull, w.sel.br, w.sel.also_zero, w.sel.also_words);
     PCH_TRY(mean_seq_launch(raw, n, w.centroid, w.ms, w.zcol, s, ss.ok ? ss.ev_fork : nullptr, nullptr, MS_DIVIDE_BY_N,
                             MS_PHASE_BOTH, &w.cand, &cand_made));
+    PCH_REQUIRE(!bracket || cand_made, "bracket route without candidate slots");
     if (ss.ok) PCH_HIP_TRY(hipStreamWaitEvent(ss.s, ss.ev_fork, 0));
-    PCH_TRY(select_passes(w.zcol, n, 1, pct, w.sel, ss.ok ? ss.s : s, sample_early));
+    if (bracket) PCH_TRY(select_from_summary(raw, n, pct, w.cand, w.zcol, w.sel, ss.ok ? ss.s : s));
+    else PCH_TRY(select_passes(w.zcol, n, 1, pct, w.sel, ss.ok ? ss.s : s, sample_early));
     if (ss.ok) {
         PCH_HIP_TRY(hipEventRecord(ss.ev_join, ss.s));
         PCH_HIP_TRY(hipStreamWaitEvent(s, ss.ev_join, 0));
@@ -1198,6 +1306,7 @@ int pch::ground_filter_run(const float* raw, int64_t n, double pct, float offset
     PCH_TRY(select_lerp(n, w.centroid + 2, pct, offset, fallback_offset, w.sel, s));
     const dim3 grid((unsigned)nb), blk(GF_THREADS);
     const float* tcand = cand_made ? (const float*)w.cand.tcand : (const float*)nullptr;
+    const float* zcol = bracket ? (const float*)nullptr : (const float*)w.zcol;   // no column: the sweep reads the rows' z
     // Sweep A (first threshold) from the candidate slots when the device-side guard allows it (gf_cand_ok), else over
     // the tile - one of the two kernels returns at once; same tiles, same tickets, same look-back words.  Then the
     // results are published ONCE ALREADY (gf_finalize; and queued for the host if the caller asked): they are final
@@ -1209,7 +1318,7 @@ int pch::ground_filter_run(const float* raw, int64_t n, double pct, float offset
         PCH_LAUNCH("gf_cand", gf_cand_k<0>, cgrid, blk, 0, s, (const float*)w.cand.slots, (const uint32_t*)w.cand.counts,
                    tcand, nblk, (const float*)w.centroid, (const float*)w.sel.scal, w.st, w.status, (long long)min_keep,
                    out_points, out_index);
-    PCH_LAUNCH("gf_compact", gf_compact_k<0>, grid, blk, 0, s, raw, (const float*)w.zcol, n,
+    PCH_LAUNCH("gf_compact", gf_compact_k<0>, grid, blk, 0, s, raw, zcol, n,
                (const float*)w.centroid, (const float*)w.sel.scal, w.st, w.status, (long long)min_keep, out_points,
                out_index, tcand);
     if (early) {
@@ -1221,7 +1330,7 @@ int pch::ground_filter_run(const float* raw, int64_t n, double pct, float offset
         PCH_LAUNCH("gf_cand_fb", gf_cand_k<1>, cgrid, blk, 0, s, (const float*)w.cand.slots,
                    (const uint32_t*)w.cand.counts, tcand, nblk, (const float*)w.centroid, (const float*)w.sel.scal, w.st,
                    w.status + nb, (long long)min_keep, out_points, out_index);
-    PCH_LAUNCH("gf_compact_fb", gf_compact_k<1>, grid, blk, 0, s, raw, (const float*)w.zcol, n,
+    PCH_LAUNCH("gf_compact_fb", gf_compact_k<1>, grid, blk, 0, s, raw, zcol, n,
                (const float*)w.centroid, (const float*)w.sel.scal, w.st, w.status + nb, (long long)min_keep, out_points,
                out_index, tcand);
     PCH_LAUNCH("gf_finalize", gf_finalize_k, dim3(1), dim3(64), 0, s, (const GfState*)w.st,

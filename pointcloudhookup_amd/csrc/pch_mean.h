@@ -18,6 +18,28 @@ struct MsPred;
 //   counts [nb]       rows used in every slot
 //   tcand  [2]        [0] the threshold that was used (device; written before the summary runs), [1] overflow word
 constexpr int MS_CAND_SLOT = 512;
+// The percentile's bracket, taken from the same samples in front of the summary (ms_prefix_k, ms_zbracket): two exact
+// order statistics of every `stride`-th sampled z as sel_key keys L <= H.  With it the summary keeps, per block, the
+// z values whose key lies in [L, H] packed at the front of the block's own 1024-float segment of the z buffer
+// (zcol[1024 * blk ...]: as large as the block, so it cannot overflow; order inside a block is not kept) and one
+// MsBrRec - instead of the z column.  sel_collect_k (pch_filter.hip) gathers them; whether they hold the wanted
+// order statistics is checked on the device there, so the keys only decide how much is read.
+struct MsBracket {
+    uint32_t L, H;               // as used: 0 / 0xFFFFFFFF at an open end
+    uint32_t lo_is_min, hi_is_max;
+    uint32_t valid[2];           // one word per end (two workgroups write them): a NaN sample or none clears it
+    uint32_t pad[2];
+};
+struct MsBrRec { uint32_t count_less, nan; };       // count | less << 16 (both <= 1024), NaN values of the block
+constexpr int MS_BR_PER = 16;                       // samples a thread of ms_zbracket holds in registers
+__host__ __device__ inline int64_t ms_bracket_stride(int64_t ns) {      // every stride-th sample: at most 16 384 of them
+    const int64_t s = (ns + 1024 * MS_BR_PER - 1) / (1024 * MS_BR_PER);
+    return s < 1 ? 1 : s;
+}
+// order-preserving key of the select (NaN sorts last, as in numpy's partition)
+__device__ __forceinline__ uint32_t sel_key(float v) {
+    return (v != v) ? 0xFFFFFFFFu : f32_ordered(v);
+}
 struct MsCand {
     float*    slots;
     uint32_t* counts;
@@ -25,6 +47,11 @@ struct MsCand {
     float*    zsample;           // [nb] one sampled z per block (scratch of the estimate)
     double    pct;               // the percentile the filter will ask for
     float     add;               // tcand = (estimated percentile of z) + add
+    // bracket emission (optional: bracket == nullptr keeps the z column)
+    MsBracket* bracket;
+    MsBrRec*   brec;             // [nb], every record rewritten by every call
+    int64_t    r_lo, r_hi;       // ranks of L and H among the ceil(nb / ms_bracket_stride(nb)) samples used
+    int        force_invalid;    // tuning toggle: valid = 0, whatever the sample holds
 };
 struct MsWs {
     MsPred*    pred;             // [3][nb2] estimated running sum in front of every level-2 row (candidate windows)
@@ -44,7 +71,9 @@ void ms_plan(Arena& a, int64_t n, MsWs& w);
 constexpr int64_t MS_DIVIDE_BY_N = -1, MS_NO_DIVIDE = -2;
 constexpr int MS_PHASE_BOTH = 0, MS_PHASE_TABLES = 1, MS_PHASE_WALK = 2;
 // cand (optional): emit the candidate rows described above; *cand_made says whether they were (needs the sampled
-// estimate, i.e. an array of at least two 65 536-row groups and prediction enabled)
+// estimate, i.e. an array of at least two 65 536-row groups and prediction enabled): ms_makes_cand(n) tells beforehand.
+// With cand->bracket the z values inside the bracket go to the fronts of zcol's segments and the column is NOT written.
+bool ms_makes_cand(int64_t n);
 int mean_seq_launch(const float* xyz, int64_t n, float* out, MsWs& w, float* zcol, hipStream_t s,
                     hipEvent_t ev_zcol = nullptr, const float* sum_in = nullptr, int64_t divide_n = MS_DIVIDE_BY_N,
                     int phase = MS_PHASE_BOTH, const MsCand* cand = nullptr, bool* cand_made = nullptr);

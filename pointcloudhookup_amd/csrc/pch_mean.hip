@@ -8,7 +8,8 @@
 // on m - unless a_i/u has fraction exactly 1/2 (a "tie", resolved towards the even mantissa).
 //
 //   ms_summary_k : one wave per 1024-point block (read ONCE, staged in LDS; the z column is also
-//                  copied out for the percentile passes).  Per column and for the 24 useful
+//                  copied out for the percentile passes - or, given the percentile's bracket, only
+//                  the block's z values inside it: MsBracket, pch_mean.h).  Per column and for the 24 useful
 //                  candidate binades E = emax+1 .. emax+24 (E <= emax: an element as large as
 //                  the sum; E > emax+24: every increment is 0) it stores the signed increment
 //                  sum S_E, one bound A0 >= sum |a/ulp(2^(emax+1))| (so that
@@ -151,40 +152,46 @@ __global__ __launch_bounds__(64) void ms_sample_k(const float* __restrict__ xyz,
     }
 }
 
+// LDS of the single-workgroup selects of ms_prefix_k (1024 threads): a 2048-bin histogram and the pick from it
+struct MsPick { uint32_t hist[2048]; uint32_t wsum[16]; uint32_t bin, below, total; };
+// most samples share a handful of bins (flat ground): lanes that hold the leader's bin add ONCE for all of them
+__device__ __forceinline__ void ms_pick_add(MsPick* P, bool in, uint32_t bin) {
+    const unsigned long long act = __ballot(in);
+    if (!act) return;
+    const int lead = (int)__builtin_ctzll(act);
+    const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)bin, lead);
+    const unsigned long long same = __ballot(in && bin == b0);
+    if (lane_id() == lead) atomicAdd(&P->hist[b0], (uint32_t)__popcll(same));
+    if (in && bin != b0) atomicAdd(&P->hist[bin], 1u);
+}
+// bin that holds `rank` and the count below it: every thread owns two bins, block-wide exclusive scan
+__device__ __forceinline__ void ms_pick_scan(MsPick* P, uint32_t rank) {
+    const int l = lane_id(), w = wave_id();
+    __syncthreads();
+    const uint32_t h0 = P->hist[2 * threadIdx.x], h1 = P->hist[2 * threadIdx.x + 1];
+    const uint32_t incl = wave_scan_incl(h0 + h1);
+    if (l == 63) P->wsum[w] = incl;
+    __syncthreads();
+    uint32_t before = incl - (h0 + h1);
+    for (int k = 0; k < w; ++k) before += P->wsum[k];
+    if (rank >= before && rank < before + h0) { P->bin = 2 * threadIdx.x; P->below = before; }
+    else if (rank >= before + h0 && rank < before + h0 + h1) { P->bin = 2 * threadIdx.x + 1; P->below = before + h0; }
+    __syncthreads();
+}
+
 // exclusive prefix of the row sums per column (one 1024-thread workgroup per column: a block scan per 1024 rows),
 // starting from the incoming running sum
 // Block 3 (when launched): a deliberately LOW estimate of the height filter's raw-z threshold from the sampled z values
 // (one per block): the lower edge of the 2^-11-wide key bin that holds the sample's pct-quantile, found by two LDS
 // histogram passes over the order-preserving keys, plus `add`.  Only an estimate: what it is used for is checked
 // against the exact threshold later (gf_cand_k).
-__device__ void ms_zestimate(const float* __restrict__ zs, int64_t ns, double pct, float add, float* __restrict__ tcand) {
-    __shared__ uint32_t hist[2048];
-    __shared__ uint32_t wsum[16];
-    __shared__ uint32_t pick_bin, pick_below, total_sh;
-    const int l = lane_id(), w = wave_id();
-    // most samples share a handful of bins (flat ground): lanes that hold the leader's bin add ONCE for all of them
-    auto add_bin = [&](bool in, uint32_t bin) {
-        const unsigned long long act = __ballot(in);
-        if (!act) return;
-        const int lead = (int)__builtin_ctzll(act);
-        const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)bin, lead);
-        const unsigned long long same = __ballot(in && bin == b0);
-        if (l == lead) atomicAdd(&hist[b0], (uint32_t)__popcll(same));
-        if (in && bin != b0) atomicAdd(&hist[bin], 1u);
-    };
-    // bin that holds `rank` and the count below it: every thread owns two bins, block-wide exclusive scan
-    auto scan_pick = [&](uint32_t rank) {
-        __syncthreads();
-        const uint32_t h0 = hist[2 * threadIdx.x], h1 = hist[2 * threadIdx.x + 1];
-        const uint32_t incl = wave_scan_incl(h0 + h1);
-        if (l == 63) wsum[w] = incl;
-        __syncthreads();
-        uint32_t before = incl - (h0 + h1);
-        for (int k = 0; k < w; ++k) before += wsum[k];
-        if (rank >= before && rank < before + h0) { pick_bin = 2 * threadIdx.x; pick_below = before; }
-        else if (rank >= before + h0 && rank < before + h0 + h1) { pick_bin = 2 * threadIdx.x + 1; pick_below = before + h0; }
-        __syncthreads();
-    };
+__device__ void ms_zestimate(const float* __restrict__ zs, int64_t ns, double pct, float add, float* __restrict__ tcand,
+                             MsPick* P) {
+    uint32_t* hist = P->hist;
+    uint32_t &pick_bin = P->bin, &pick_below = P->below, &total_sh = P->total;
+    const int l = lane_id();
+    auto add_bin = [&](bool in, uint32_t bin) { ms_pick_add(P, in, bin); };
+    auto scan_pick = [&](uint32_t rank) { ms_pick_scan(P, rank); };
     for (int j = threadIdx.x; j < 2048; j += 1024) hist[j] = 0;
     if (threadIdx.x == 0) { total_sh = 0; pick_bin = 2047; pick_below = 0; }
     __syncthreads();
@@ -234,12 +241,59 @@ __device__ void ms_zestimate(const float* __restrict__ zs, int64_t ns, double pc
     }
 }
 
+// Blocks 4 and 5 (when launched): the two ends of the percentile's bracket (MsBracket, pch_mean.h) - the exact order
+// statistic `rank` of every stride-th sample, as a key.  The samples (at most MS_BR_PER per thread) are loaded once
+// and stay in registers for three histogram passes over 11 + 11 + 10 key bits: the full key, because a bin edge of
+// two passes is 8 mm wide at z ~ 80 and everything inside it would become a candidate.  end 0 writes L, end 1 H.
+struct MsBrArgs { MsBracket* out; int64_t stride; uint32_t rank[2]; int open[2]; int force_invalid; };
+__device__ void ms_zbracket(const float* __restrict__ zs, int64_t ns, const MsBrArgs& A, int end, MsPick* P) {
+    const int64_t ne = (ns + A.stride - 1) / A.stride;       // <= 1024 * MS_BR_PER (ms_bracket_stride)
+    uint32_t k[MS_BR_PER];
+    bool anynan = false;
+#pragma unroll
+    for (int u = 0; u < MS_BR_PER; ++u) {
+        const int64_t i = (int64_t)u * 1024 + threadIdx.x;
+        const float z = i < ne ? zs[i * A.stride] : 0.0f;
+        anynan |= z != z;
+        k[u] = f32_ordered(z);
+    }
+    if (threadIdx.x == 0) P->total = 0u;
+    uint32_t rank = A.rank[end], prefix = 0;
+#pragma unroll 1
+    for (int pass = 0; pass < 3; ++pass) {
+        const int shift = pass == 0 ? 21 : (pass == 1 ? 10 : 0), up = pass == 0 ? 32 : (pass == 1 ? 21 : 10);
+        const uint32_t bins = pass == 2 ? 1023u : 2047u;
+        __syncthreads();                                     // the pick of the pass before has been read
+        for (int j = threadIdx.x; j < 2048; j += 1024) P->hist[j] = 0;
+        if (threadIdx.x == 0) { P->bin = bins; P->below = 0; }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < MS_BR_PER; ++u) {
+            const bool in = (int64_t)u * 1024 + threadIdx.x < ne && (pass == 0 || (k[u] >> up) == prefix);
+            ms_pick_add(P, in, (k[u] >> shift) & bins);
+        }
+        if (pass == 0 && __ballot(anynan) && lane_id() == 0) atomicOr(&P->total, 1u);
+        ms_pick_scan(P, rank);
+        prefix = (prefix << (pass == 2 ? 10 : 11)) | P->bin;
+        rank -= P->below;
+    }
+    if (threadIdx.x == 0) {
+        const bool valid = ne > 0 && P->total == 0u && !A.force_invalid;
+        if (end == 0) { A.out->L = A.open[0] ? 0u : prefix; A.out->lo_is_min = (uint32_t)A.open[0]; }
+        else { A.out->H = A.open[1] ? 0xFFFFFFFFu : prefix; A.out->hi_is_max = (uint32_t)A.open[1]; }
+        A.out->valid[end] = valid ? 1u : 0u;
+    }
+}
+
 __global__ __launch_bounds__(1024) void ms_prefix_k(MsPred* __restrict__ pred, int64_t nb2,
                                                     const float* __restrict__ sum_in, const float* __restrict__ zs,
-                                                    int64_t ns, double pct, float add, float* __restrict__ tcand) {
+                                                    int64_t ns, double pct, float add, float* __restrict__ tcand,
+                                                    MsBrArgs br) {
     __shared__ double wsum[16];
     __shared__ double carry_sh;
-    if (blockIdx.x == 3) { ms_zestimate(zs, ns, pct, add, tcand); return; }
+    __shared__ MsPick pick;
+    if (blockIdx.x == 3) { ms_zestimate(zs, ns, pct, add, tcand, &pick); return; }
+    if (blockIdx.x >= 4) { ms_zbracket(zs, ns, br, (int)blockIdx.x - 4, &pick); return; }
     const int c = blockIdx.x;
     const int l = lane_id(), w = wave_id();
     if (threadIdx.x == 0) carry_sh = sum_in ? (double)sum_in[c] : 0.0;
@@ -272,7 +326,9 @@ __global__ __launch_bounds__(64 * MS_WAVES) void ms_summary_k(const float* __res
                                                              float* __restrict__ zcol,
                                                              const MsPred* __restrict__ pred, int64_t nb2,
                                                              float* __restrict__ cslots, uint32_t* __restrict__ ccounts,
-                                                             const float* __restrict__ tcand) {
+                                                             const float* __restrict__ tcand,
+                                                             const MsBracket* __restrict__ brk,
+                                                             MsBrRec* __restrict__ brec, float* __restrict__ zseg) {
     __shared__ __attribute__((aligned(16))) float lds[MS_WAVES][MSB * 3];
     __shared__ MsRec stage[MS_WAVES];                    // a record is assembled here, stored as whole lines
     const int64_t blk = (int64_t)blockIdx.x * MS_WAVES + wave_id();
@@ -293,7 +349,7 @@ __global__ __launch_bounds__(64 * MS_WAVES) void ms_summary_k(const float* __res
     __builtin_amdgcn_wave_barrier();
     // the block's z values, once: for the z column copy and for the candidate test below
     float zr[MS_PER];
-    if (zcol || cslots) {
+    if (zcol || cslots || brk) {
 #pragma unroll
         for (int i = 0; i < MS_PER; ++i) zr[i] = tile[3 * (i * 64 + l) + 2];
     }
@@ -302,6 +358,45 @@ __global__ __launch_bounds__(64 * MS_WAVES) void ms_summary_k(const float* __res
         for (int i = 0; i < MS_PER; ++i) {
             const int p = i * 64 + l;
             if (p < cnt) zcol[p0 + p] = zr[i];
+        }
+    }
+    if (brk) {
+        // the percentile's bracket (MsBracket, pch_mean.h) instead of the column: count the keys below L and the NaN
+        // values, and pack the z values whose key lies in [L, H] at the front of the block's own segment.  A lane marks
+        // its elements in a 16-bit mask; one wave scan of the lane counts gives it its first position, and it then
+        // stores its elements one set bit at a time (read back from the tile: registers cannot be indexed by the bit).
+        // Where the bracket is narrow a block holds a few dozen such values (two or three rounds), where it lies
+        // wholly inside, all 1024: the segment is as large as the block.  The record is written for every block by
+        // every call; an invalid bracket is an empty one here (sel_collect_k then fails the device check).
+        const bool valid = (brk->valid[0] & brk->valid[1]) != 0u;
+        const uint32_t L = valid ? brk->L : 1u, H = valid ? brk->H : 0u;
+        uint32_t tally = 0, mask = 0;                          // tally: keys < L | NaN values << 16 (16 each at most)
+#pragma unroll
+        for (int i = 0; i < MS_PER; ++i) {
+            const bool in = i * 64 + l < cnt;
+            const uint32_t k = sel_key(zr[i]);
+            tally += (in && k < L ? 1u : 0u) + (in && zr[i] != zr[i] ? 0x10000u : 0u);
+            mask |= (in && k >= L && k <= H) ? (1u << i) : 0u;
+        }
+        tally = ms_wave_all(tally, [](uint32_t a, uint32_t b) { return a + b; });      // <= 1024 in either half
+        uint32_t total = 0;
+        if (__ballot(mask != 0u)) {                            // wave-uniform
+            const uint32_t mine = (uint32_t)__popc(mask);
+            const uint32_t incl = wave_scan_incl(mine);
+            total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            float* __restrict__ seg = zseg + p0;
+            uint32_t pos = incl - mine;
+            while (mask) {
+                const int i = __ffs((int)mask) - 1;
+                mask &= mask - 1u;
+                seg[pos++] = tile[3 * (i * 64 + l) + 2];
+            }
+        }
+        if (l == 0) {
+            MsBrRec r;
+            r.count_less = total | ((tally & 0xFFFFu) << 16);
+            r.nan = tally >> 16;
+            brec[blk] = r;
         }
     }
     if (cslots) {
@@ -1155,6 +1250,17 @@ void ms_plan(Arena& a, int64_t n, MsWs& w) {
     w.rows2 = a.take<long long>(3 * nb2 * MS_ROW2);
 }
 
+// candidate prediction (see ms_sample_k): only when the running sum the rows continue is known now - the whole sum
+// (phase both), not for tables built ahead of their walk - and the array spans several rows
+static bool ms_predicts(int64_t n, int phase) {
+    static const bool no_predict = getenv("PCH_MEAN_NO_PREDICT") != nullptr;      // tuning toggle
+    return !no_predict && phase == MS_PHASE_BOTH && ceil_div(ceil_div(n, MSB), 64) >= 2;
+}
+bool ms_makes_cand(int64_t n) {
+    static const bool no_cand = getenv("PCH_GF_NO_CAND") != nullptr;              // tuning toggle
+    return n > 0 && !no_cand && ms_predicts(n, MS_PHASE_BOTH);
+}
+
 int mean_seq_launch(const float* xyz, int64_t n, float* out, MsWs& w, float* zcol, hipStream_t s,
                     hipEvent_t ev_zcol, const float* sum_in, int64_t divide_n, int phase, const MsCand* cand,
                     bool* cand_made) {
@@ -1162,25 +1268,40 @@ int mean_seq_launch(const float* xyz, int64_t n, float* out, MsWs& w, float* zco
     const int64_t nb = n > 0 ? ceil_div(n, MSB) : 0;
     const int64_t nb2 = ceil_div(nb, 64);
     if (n > 0 && phase != MS_PHASE_WALK) {
-        // candidate prediction (see ms_sample_k): only when the running sum the rows continue is known now -
-        // the whole sum (phase both), not for tables built ahead of their walk - and the array spans several rows
-        static const bool no_predict = getenv("PCH_MEAN_NO_PREDICT") != nullptr;      // tuning toggle
         const MsPred* pred = nullptr;
-        if (!no_predict && phase == MS_PHASE_BOTH && nb2 >= 2) {
-            static const bool no_cand = getenv("PCH_GF_NO_CAND") != nullptr;              // tuning toggle
-            const bool mk = cand && !no_cand;
+        bool bracket = false;
+        if (ms_predicts(n, phase)) {
+            const bool mk = cand && ms_makes_cand(n);
+            bracket = mk && cand->bracket;
+            MsBrArgs ba;
+            memset(&ba, 0, sizeof(ba));
+            if (bracket) {
+                ba.out = cand->bracket;
+                ba.stride = ms_bracket_stride(nb);
+                const int64_t ne = ceil_div(nb, ba.stride);
+                ba.rank[0] = (uint32_t)cand->r_lo; ba.rank[1] = (uint32_t)cand->r_hi;
+                ba.open[0] = cand->r_lo == 0; ba.open[1] = cand->r_hi == ne - 1;
+                ba.force_invalid = cand->force_invalid;
+            }
             PCH_LAUNCH("mean_sample", ms_sample_k, dim3((unsigned)nb2), dim3(64), 0, s, xyz, n, nb, nb2, w.pred,
                        mk ? cand->zsample : (float*)nullptr);
-            PCH_LAUNCH("mean_prefix", ms_prefix_k, dim3(mk ? 4 : 3), dim3(1024), 0, s, w.pred, nb2, sum_in,
+            PCH_LAUNCH("mean_prefix", ms_prefix_k, dim3(mk ? (bracket ? 6 : 4) : 3), dim3(1024), 0, s, w.pred, nb2, sum_in,
                        mk ? (const float*)cand->zsample : (const float*)nullptr, nb, mk ? cand->pct : 0.0,
-                       mk ? cand->add : 0.0f, mk ? cand->tcand : (float*)nullptr);
+                       mk ? cand->add : 0.0f, mk ? cand->tcand : (float*)nullptr, ba);
             pred = w.pred;
             if (mk && cand_made) *cand_made = true;
         }
         const bool emit = cand && cand_made && *cand_made;
+        // with the bracket the buffer `zcol` holds the blocks' segments (MsBracket) and the column is not written
         PCH_LAUNCH("mean_summary", ms_summary_k, dim3((unsigned)ceil_div(nb, MS_WAVES)), dim3(64 * MS_WAVES),
-                   0, s, xyz, n, nb, w.rec, zcol, pred, nb2, emit ? cand->slots : (float*)nullptr,
-                   emit ? cand->counts : (uint32_t*)nullptr, emit ? (const float*)cand->tcand : (const float*)nullptr);
+                   0, s, xyz, n, nb, w.rec, bracket ? (float*)nullptr : zcol, pred, nb2,
+                   emit ? cand->slots : (float*)nullptr, emit ? cand->counts : (uint32_t*)nullptr,
+                   emit ? (const float*)cand->tcand : (const float*)nullptr,
+                   bracket ? (const MsBracket*)cand->bracket : (const MsBracket*)nullptr,
+                   bracket ? cand->brec : (MsBrRec*)nullptr, bracket ? zcol : (float*)nullptr);
+        // (with the bracket too: what waits for the event is then a short gather, sel_collect_k.  Recorded behind
+        // level 2 instead, that kernel ran alone - 27 us for 49 - but the walk had the gather and the three histogram
+        // passes beside it for longer: 226 us for 192, a loss of 12 on the critical path)
         if (ev_zcol) PCH_HIP_TRY(hipEventRecord(ev_zcol, s));
         PCH_LAUNCH("mean_level2", ms_level2_k, dim3((unsigned)(3 * nb2)), dim3(256), 0, s,
                    (const MsRec*)w.rec, nb, nb2, w.hdr2, w.rows2);

@@ -102,7 +102,12 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
         from .. import las as _las
         from .. import ops, pipeline, stages
         clock = stages.Clock("extract_towers")
-        if os.path.getsize(input_las_path) >= PRESTART_BYTES:
+        if resident_entry is not None and resident_entry.records is not None:
+            # (a background writer may not have created the file yet: its size follows from the records)
+            in_bytes = int(resident_entry.records.shape[0]) * _las.RECORD_LEN[resident_entry.header.point_format]
+        else:
+            in_bytes = os.path.getsize(input_las_path)
+        if in_bytes >= PRESTART_BYTES:
             from .. import obb as _obb
             _obb.prestart()                # the box workers import scipy while the file is being read
         dev = torch.device(DEVICE)
