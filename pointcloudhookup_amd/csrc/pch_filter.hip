@@ -3,7 +3,7 @@
 // Reference: utils/tower_extraction.py:62-64 (centroid, centring), :82-89 (percentile filter).
 #include "pch_prims.h"
 #include "pch_mean.h"
-#include "pch_lookback.h"
+#include "pch_compact.h"
 
 namespace pch {
 
@@ -693,7 +693,6 @@ static SideStream& side_stream() {
 constexpr int GF_THREADS = 256;
 constexpr int GF_ROUNDS  = 64;
 constexpr int GF_TILE    = GF_THREADS * GF_ROUNDS;   // 16 384 points per workgroup: few enough tiles for the look-back
-constexpr int GF_SLOTS   = 64;
 
 struct GfState {
     uint32_t total[2];                     // kept with threshold A (offset) / B (fallback)
@@ -701,7 +700,7 @@ struct GfState {
     uint32_t failed;                       // a look-back wait ran out of its budget (pch_lookback.h): count -> -1
     uint32_t ticket[2];                    // next logical tile of either sweep (order of arrival, see gf_compact_k)
     uint32_t pad2[2];
-    uint32_t slots[2][GF_SLOTS][6];        // per sweep: ~min xyz (complemented) / max xyz as ordered uint32,
+    uint32_t slots[2][OC_SLOTS][6];        // per sweep: ~min xyz (complemented) / max xyz as ordered uint32,
                                            // all folded with atomicMax so that 0 is the neutral start
 };
 
@@ -725,12 +724,8 @@ __device__ __forceinline__ bool gf_cand_ok(const float* __restrict__ tcand, cons
 }
 
 // ---- what the two sweeps share (gf_compact_k over the z column, gf_cand_k over the candidate slots): the tile order,
-// the tile's output offset, what becomes of a survivor, and the fold of the tile's bounding box
-// The look-back waits for every tile in front of this one, so the tile order must be an
-// order in which workgroups START: HIP promises nothing about blockIdx dispatch order, and a
-// resident workgroup spinning on a tile that was never scheduled would hang the GPU.  The logical
-// tile is therefore a ticket drawn on arrival (as rocPRIM's look-back scan does): every tile with
-// a smaller ticket belongs to a workgroup that is already running.
+// the tile's output offset and what becomes of a survivor (its store and the fold of the tile's bounding box are those
+// of pch_compact.h).  The logical tile is a ticket drawn on arrival, for the reason given at oc_take_tile.
 // false: this sweep does not run (the fallback sweep without use_b).  The caller's next barrier publishes *tile_sh.
 template <int WHICH>
 __device__ __forceinline__ bool gf_take_tile(GfState* __restrict__ st, uint32_t* tile_sh) {
@@ -755,49 +750,6 @@ __device__ __forceinline__ void gf_tile_prefix(GfState* __restrict__ st, uint64_
             st->total[WHICH] = e + T;                        // whether the fallback threshold applies
             if (WHICH == 0) st->use_b = ((long long)(e + T) < min_keep) ? 1u : 0u;
         }
-    }
-}
-// first output row of wave w: the tile's prefix plus the survivors of the waves in front
-__device__ __forceinline__ uint32_t gf_wave_offset(uint32_t excl, const uint32_t (&wtot)[GF_THREADS / 64], int w) {
-    uint32_t woff = excl;
-    for (int w2 = 0; w2 < w; ++w2) woff += wtot[w2];
-    return woff;
-}
-// survivor (x, y, z) = input row `row` becomes output row o, centred; lo / hi collect the box (lo holds ~ordered(min))
-__device__ __forceinline__ void gf_emit(float x, float y, float z, const float (&c)[3], int64_t o, int64_t row,
-                                        float* __restrict__ out_points, int32_t* __restrict__ out_index,
-                                        uint32_t (&lo)[3], uint32_t (&hi)[3]) {
-    const float v[3] = {x - c[0], y - c[1], z - c[2]};       // points = raw_points - centroid (float32)
-    out_points[3 * o + 0] = v[0];
-    out_points[3 * o + 1] = v[1];
-    out_points[3 * o + 2] = v[2];
-    if (out_index) out_index[o] = (int32_t)row;
-    if (fabsf(v[0]) < INFINITY && fabsf(v[1]) < INFINITY && fabsf(v[2]) < INFINITY) {   // NaN/inf rows
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const uint32_t kk = f32_ordered(v[a]);
-            lo[a] = ~kk > lo[a] ? ~kk : lo[a];
-            hi[a] = kk > hi[a] ? kk : hi[a];
-        }
-    }
-}
-// the tile's box: over the wave, over the waves, into one of the sweep's slot sets
-template <int WHICH>
-__device__ __forceinline__ void gf_fold_box(GfState* __restrict__ st, int64_t tile, uint32_t (&lo)[3], uint32_t (&hi)[3],
-                                            uint32_t (&box)[GF_THREADS / 64][6]) {
-    const int w = wave_id();
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = wave_reduce_max(lo[a]);
-        hi[a] = wave_reduce_max(hi[a]);
-        if (lane_id() == 0) { box[w][a] = lo[a]; box[w][3 + a] = hi[a]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int a = threadIdx.x;
-        uint32_t v = box[0][a];
-        for (int w2 = 1; w2 < GF_THREADS / 64; ++w2) v = box[w2][a] > v ? box[w2][a] : v;
-        if (v) atomicMax(&st->slots[WHICH][tile % GF_SLOTS][a], v);
     }
 }
 
@@ -851,7 +803,7 @@ __global__ __launch_bounds__(GF_THREADS) void gf_compact_k(
     // consecutive lanes write consecutive output rows (a pass over the 64 rounds with the ~10 % surviving
     // lanes active would leave most lanes idle and scatter the writes)
     struct Row3 { float x, y, z; };
-    const uint32_t woff = gf_wave_offset(excl_sh, wtot, w);
+    const uint32_t woff = oc_wave_offset(excl_sh, wtot, w);
     uint32_t lo[3] = {0u, 0u, 0u}, hi[3] = {0u, 0u, 0u};
     const uint32_t nw = wtot[w];
 #pragma unroll 2
@@ -875,9 +827,9 @@ __global__ __launch_bounds__(GF_THREADS) void gf_compact_k(
         }
         const int64_t i = seg + r * 64 + bit;
         const Row3 q = reinterpret_cast<const Row3*>(raw)[i];
-        gf_emit(q.x, q.y, q.z, cen, (int64_t)woff + j, i, out_points, out_index, lo, hi);
+        oc_emit(q.x, q.y, q.z, cen, (int64_t)woff + j, i, out_points, out_index, lo, hi);
     }
-    gf_fold_box<WHICH>(st, tile, lo, hi, box);
+    oc_fold_box(st->slots[WHICH], tile, lo, hi, box);
 }
 
 // The same sweep from the candidate slots (MsCand, pch_mean.h: four planes per 1024-row block): a workgroup takes 64
@@ -975,7 +927,7 @@ __global__ __launch_bounds__(GF_THREADS, 6) void gf_cand_k(     // six waves per
             const unsigned long long m = ms[k];
             if ((m >> l) & 1ull) {
                 const float4 c4 = q[k];
-                gf_emit(c4.x, c4.y, c4.z, cen, (int64_t)woff + cum[w][kb * NR + r] + (uint32_t)__popcll(m & lt),
+                oc_emit(c4.x, c4.y, c4.z, cen, (int64_t)woff + cum[w][kb * NR + r] + (uint32_t)__popcll(m & lt),
                         (b0 + kb) * GF_CBLK + (int64_t)__float_as_uint(c4.w), out_points, out_index, lo, hi);
             }
         }
@@ -994,7 +946,7 @@ __global__ __launch_bounds__(GF_THREADS, 6) void gf_cand_k(     // six waves per
     }
     __syncthreads();
     if (T == 0) return;                                    // workgroup-uniform
-    const uint32_t woff = gf_wave_offset(excl_sh, wtot, w);
+    const uint32_t woff = oc_wave_offset(excl_sh, wtot, w);
     if (maxnc != 0) {
         emit_half(0, 0, q0, ms0, woff);
         {
@@ -1015,7 +967,7 @@ __global__ __launch_bounds__(GF_THREADS, 6) void gf_cand_k(     // six waves per
             }
         }
     }
-    gf_fold_box<WHICH>(st, tile, lo, hi, box);
+    oc_fold_box(st->slots[WHICH], tile, lo, hi, box);
 }
 
 // publishes the scalars, the count and the bounding box of the sweep that counts
@@ -1035,12 +987,7 @@ __global__ void gf_finalize_k(const GfState* __restrict__ st, const float* __res
         out_scalars[7] = 0.0f;
         *out_count = st->failed ? (int64_t)-1 : (int64_t)st->total[use_b];
     }
-    if (threadIdx.x < 6 && out_aabb) {
-        const int a = threadIdx.x;
-        uint32_t v = 0;
-        for (int k = 0; k < GF_SLOTS; ++k) { const uint32_t u = st->slots[use_b][k][a]; v = u > v ? u : v; }
-        out_aabb[a] = v == 0u ? 0.0f : f32_unordered(a < 3 ? ~v : v);
-    }
+    if (threadIdx.x < 6 && out_aabb) out_aabb[threadIdx.x] = oc_box_word(st->slots[use_b], threadIdx.x);
 }
 
 struct GfWs {

@@ -10,8 +10,7 @@
 //   filter: keep r > offset ("above"), or keep !(|r| <= residual_threshold) ("off_plane", ~inlier_mask_)
 // No refit on the inliers (sklearn's inlier_mask_ is the best trial's mask too).
 // The opt-in third rule, the same plane once per xy tile (test/main_ground.py:77-115), follows in the second half.
-#include "pch_common.h"
-#include "pch_lookback.h"
+#include "pch_compact.h"
 #include "pch_prims.h"
 
 namespace pch {
@@ -165,17 +164,16 @@ __global__ __launch_bounds__(PL_THREADS) void pl_best_k(const PlPlane* __restric
     *best = pl_best_record(planes, counts, key, nv);
 }
 
-// ---- step 5: order-preserving compaction in one sweep, the skeleton of crop_aabb_k (pch_view.hip): tiles by ticket,
-// the tile's offset from the look-back, the count word with the sign-bit failure mark; what is emitted and how the
-// box is folded follows gf_emit / gf_fold_box (pch_filter.hip)
+// ---- step 5: the register-resident ordered compaction of pch_compact.h on float32 rows, with the box of the finite
+// kept rows; what this file adds is the centring, where a row's plane comes from (Src) and the residual predicate
 constexpr int PF_ROUNDS = 8;
 constexpr int PF_TILE   = PL_THREADS * PF_ROUNDS;       // 2048 rows per workgroup
-constexpr int PF_SLOTS  = 64;
 
 struct PfState {
     uint32_t ticket, pad[3];
-    uint32_t slots[PF_SLOTS][6];                        // ~ordered(min xyz) / ordered(max xyz), folded with atomicMax
+    uint32_t slots[OC_SLOTS][6];                        // ~ordered(min xyz) / ordered(max xyz), folded with atomicMax
 };
+typedef OcWs<PfState, PF_TILE> PfWs;
 
 // the tile of a centred row, the one arithmetic of the per-tile rule (grouping and filter): -1 outside the grid;
 // NaN and inf fail the comparisons
@@ -216,20 +214,15 @@ __global__ __launch_bounds__(PL_THREADS) void pl_filter_k(const float* __restric
                                                           uint64_t* __restrict__ status, float* __restrict__ out_points,
                                                           int32_t* __restrict__ out_index,
                                                           int64_t* __restrict__ out_count) {
-    __shared__ uint32_t wtot[PL_THREADS / 64];
-    __shared__ uint32_t tile_sh, excl_sh;
-    __shared__ uint32_t box[PL_THREADS / 64][6];
+    __shared__ uint32_t box[OC_WAVES][6];
     if (src.none()) return;                             // no plane: nothing is kept, the count word stays 0
-    if (threadIdx.x == 0) tile_sh = atomicAdd(&st->ticket, 1u);
-    __syncthreads();
-    const int64_t tile = tile_sh;
+    const int64_t tile = oc_take_tile(&st->ticket);
     const float cen[3] = {centroid[0], centroid[1], centroid[2]};
-    const int w = wave_id(), l = lane_id();
-    const int64_t seg = tile * PF_TILE + (int64_t)w * (64 * PF_ROUNDS);
+    const int l = lane_id();
+    const int64_t seg = tile * PF_TILE + (int64_t)wave_id() * (64 * PF_ROUNDS);
     const PlRow3* __restrict__ r3 = reinterpret_cast<const PlRow3*>(raw);
     PlRow3 q[PF_ROUNDS];
     unsigned long long m[PF_ROUNDS];
-    uint32_t run = 0;
 #pragma unroll
     for (int r = 0; r < PF_ROUNDS; ++r) {
         const int64_t i = seg + r * 64 + l;
@@ -238,79 +231,26 @@ __global__ __launch_bounds__(PL_THREADS) void pl_filter_k(const float* __restric
 #pragma unroll
     for (int r = 0; r < PF_ROUNDS; ++r) {
         const int64_t i = seg + r * 64 + l;
-        q[r].x -= cen[0];                               // points = raw_points - centroid (float32)
-        q[r].y -= cen[1];
-        q[r].z -= cen[2];
+        // points = raw_points - centroid (float32), as oc_emit stores them
+        const double x = (double)(q[r].x - cen[0]), y = (double)(q[r].y - cen[1]), z = (double)(q[r].z - cen[2]);
         double pa = 0.0, pb = 0.0, pc = 0.0;
-        const bool has = src.plane((double)q[r].x, (double)q[r].y, pa, pb, pc);
-        const double res = (double)q[r].z - ((pa * (double)q[r].x + pb * (double)q[r].y) + pc);
+        const bool has = src.plane(x, y, pa, pb, pc);
+        const double res = z - ((pa * x + pb * y) + pc);
         const bool keep = i < n && has && (keep_mode == 0 ? res > val : !(fabs(res) <= val));
         m[r] = __ballot(keep);
-        run += (uint32_t)__popcll(m[r]);
     }
-    if (l == 0) wtot[w] = run;
-    __syncthreads();
-    const uint32_t T = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    if (w == 0) {
-        const uint32_t e0 = gf_lookback(status, tile, T);
-        const bool lb_failed = e0 == GF_LB_FAILED;
-        const uint32_t e = lb_failed ? 0u : e0;              // prefix 0 keeps the writes below inside the output
-        if (l == 0) {
-            excl_sh = e;
-            // out_count starts at 0: the last tile adds the total, a tile whose wait ran out sets the sign bit
-            unsigned long long* oc = reinterpret_cast<unsigned long long*>(out_count);
-            if (lb_failed) atomicOr(oc, 1ull << 63);
-            else if (tile == (int64_t)gridDim.x - 1) atomicAdd(oc, (unsigned long long)e + T);
-        }
-    }
-    __syncthreads();
-    if (T == 0) return;
-    uint32_t woff = excl_sh;
-    for (int w2 = 0; w2 < w; ++w2) woff += wtot[w2];
-    const uint64_t lt = lanemask_lt();
+    const uint32_t woff = oc_place(m, status, tile, out_count);
+    if (woff == OC_NONE) return;
     uint32_t lo[3] = {0u, 0u, 0u}, hi[3] = {0u, 0u, 0u};
-#pragma unroll
-    for (int r = 0; r < PF_ROUNDS; ++r) {
-        if ((m[r] >> l) & 1ull) {
-            const int64_t o = (int64_t)woff + (uint32_t)__popcll(m[r] & lt);
-            const float v[3] = {q[r].x, q[r].y, q[r].z};
-            out_points[3 * o + 0] = v[0];
-            out_points[3 * o + 1] = v[1];
-            out_points[3 * o + 2] = v[2];
-            if (out_index) out_index[o] = (int32_t)(seg + r * 64 + l);
-            if (fabsf(v[0]) < INFINITY && fabsf(v[1]) < INFINITY && fabsf(v[2]) < INFINITY) {   // NaN/inf rows
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    const uint32_t kk = f32_ordered(v[a]);
-                    lo[a] = ~kk > lo[a] ? ~kk : lo[a];
-                    hi[a] = kk > hi[a] ? kk : hi[a];
-                }
-            }
-        }
-        woff += (uint32_t)__popcll(m[r]);
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = wave_reduce_max(lo[a]);
-        hi[a] = wave_reduce_max(hi[a]);
-        if (l == 0) { box[w][a] = lo[a]; box[w][3 + a] = hi[a]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int a = threadIdx.x;
-        uint32_t v = box[0][a];
-        for (int w2 = 1; w2 < PL_THREADS / 64; ++w2) v = box[w2][a] > v ? box[w2][a] : v;
-        if (v) atomicMax(&st->slots[tile % PF_SLOTS][a], v);
-    }
+    oc_visit(m, woff, [&](int r, int64_t o) {
+        oc_emit(q[r].x, q[r].y, q[r].z, cen, o, seg + r * 64 + l, out_points, out_index, lo, hi);
+    });
+    oc_fold_box(st->slots, tile, lo, hi, box);
 }
 
 // the bounding box of the finite kept rows; zeros when there are none (as gf_finalize_k reports it)
 __global__ void pl_box_k(const PfState* __restrict__ st, float* __restrict__ out_aabb) {
-    const int a = threadIdx.x;
-    if (a >= 6) return;
-    uint32_t v = 0u;
-    for (int k = 0; k < PF_SLOTS; ++k) { const uint32_t u = st->slots[k][a]; v = u > v ? u : v; }
-    out_aabb[a] = v == 0u ? 0.0f : f32_unordered(a < 3 ? ~v : v);
+    if (threadIdx.x < 6) out_aabb[threadIdx.x] = oc_box_word(st->slots, threadIdx.x);
 }
 
 // ==================================================================================================================
@@ -522,11 +462,27 @@ extern "C" int pch_plane_fit_f32(const float* raw, int64_t n, const float* centr
 }
 
 extern "C" size_t pch_filter_plane_ws_bytes(int64_t n) {
-    if (n < 0) return 0;
-    Arena a;
-    a.take<PfState>(1);
-    a.take<uint64_t>(ceil_div(n > 0 ? n : 1, PF_TILE));
-    return a.off;
+    return n < 0 ? 0 : PfWs::bytes(n);
+}
+
+// both filters behind their own argument checks; fn: the entry point, for the error text
+template <class Src>
+static int pl_filter_run(const char* fn, const char* launch, const float* raw, int64_t n, const float* centroid3_dev,
+                         const Src& src, int32_t keep_mode, double offset_or_threshold, float* out_points,
+                         int32_t* out_index, int64_t* out_count, float* out_aabb, void* ws, size_t ws_bytes,
+                         hipStream_t s) {
+    PCH_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(int64_t), s));
+    if (out_aabb) PCH_HIP_TRY(hipMemsetAsync(out_aabb, 0, 6 * sizeof(float), s));
+    if (n == 0) return PCH_OK;
+    if (!(raw && centroid3_dev && src.best && out_points && ws)) { set_error("%s: null buffer", fn); return PCH_ERR_ARG; }
+    Arena a(ws, ws_bytes);
+    const PfWs w(a, n);
+    if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
+    PCH_HIP_TRY(hipMemsetAsync(ws, 0, a.off, s));
+    PCH_LAUNCH(launch, pl_filter_k<Src>, dim3((unsigned)w.nt), dim3(PL_THREADS), 0, s, raw, n, centroid3_dev, src,
+               (int)keep_mode, offset_or_threshold, w.st, w.status, out_points, out_index, out_count);
+    if (out_aabb) PCH_LAUNCH("pl_box", pl_box_k, dim3(1), dim3(64), 0, s, (const PfState*)w.st, out_aabb);
+    return PCH_OK;
 }
 
 extern "C" int pch_filter_plane_f32(const float* raw, int64_t n, const float* centroid3_dev,
@@ -534,22 +490,10 @@ extern "C" int pch_filter_plane_f32(const float* raw, int64_t n, const float* ce
                                     float* out_points, int32_t* out_index, int64_t* out_count, float* out_aabb,
                                     void* ws, size_t ws_bytes, void* stream) {
     PCH_DEVICE_GUARD(out_count);
-    hipStream_t s = (hipStream_t)stream;
     PCH_REQUIRE(n >= 0 && n < (int64_t(1) << 31) && out_count && (keep_mode == 0 || keep_mode == 1), "bad argument");
-    PCH_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(int64_t), s));
-    if (out_aabb) PCH_HIP_TRY(hipMemsetAsync(out_aabb, 0, 6 * sizeof(float), s));
-    if (n == 0) return PCH_OK;
-    PCH_REQUIRE(raw && centroid3_dev && best_dev && out_points && ws, "null buffer");
-    Arena a(ws, ws_bytes);
-    PfState* st = a.take<PfState>(1);
-    const int64_t nt = ceil_div(n, PF_TILE);
-    uint64_t* status = a.take<uint64_t>(nt);
-    if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
-    PCH_HIP_TRY(hipMemsetAsync(ws, 0, a.off, s));
-    PCH_LAUNCH("pl_filter", pl_filter_k<PfOnePlane>, dim3((unsigned)nt), dim3(PL_THREADS), 0, s, raw, n, centroid3_dev,
-               PfOnePlane{best_dev}, (int)keep_mode, offset_or_threshold, st, status, out_points, out_index, out_count);
-    if (out_aabb) PCH_LAUNCH("pl_box", pl_box_k, dim3(1), dim3(64), 0, s, (const PfState*)st, out_aabb);
-    return PCH_OK;
+    return pl_filter_run(__func__, "pl_filter", raw, n, centroid3_dev, PfOnePlane{best_dev}, keep_mode,
+                         offset_or_threshold, out_points, out_index, out_count, out_aabb, ws, ws_bytes,
+                         (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ the per-tile rule
@@ -651,22 +595,9 @@ extern "C" int pch_filter_plane_tiles_f32(const float* raw, int64_t n, const flo
                                           int64_t* out_count, float* out_aabb, void* ws, size_t ws_bytes,
                                           void* stream) {
     PCH_DEVICE_GUARD(out_count);
-    hipStream_t s = (hipStream_t)stream;
     PCH_REQUIRE(n >= 0 && n < (int64_t(1) << 31) && out_count && (keep_mode == 0 || keep_mode == 1), "bad argument");
     PCH_REQUIRE(plt_grid_ok(grid_host), "bad grid: tile > 0 and finite, nx, ny >= 1, nx * ny <= 65536");
-    PCH_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(int64_t), s));
-    if (out_aabb) PCH_HIP_TRY(hipMemsetAsync(out_aabb, 0, 6 * sizeof(float), s));
-    if (n == 0) return PCH_OK;
-    PCH_REQUIRE(raw && centroid3_dev && best_dev && out_points && ws, "null buffer");
-    Arena a(ws, ws_bytes);
-    PfState* st = a.take<PfState>(1);
-    const int64_t nt = ceil_div(n, PF_TILE);
-    uint64_t* status = a.take<uint64_t>(nt);
-    if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
-    PCH_HIP_TRY(hipMemsetAsync(ws, 0, a.off, s));
-    PCH_LAUNCH("plt_filter", pl_filter_k<PfTilePlanes>, dim3((unsigned)nt), dim3(PL_THREADS), 0, s, raw, n,
-               centroid3_dev, PfTilePlanes{best_dev, fallback_dev, *grid_host}, (int)keep_mode, offset_or_threshold, st,
-               status, out_points, out_index, out_count);
-    if (out_aabb) PCH_LAUNCH("pl_box", pl_box_k, dim3(1), dim3(64), 0, s, (const PfState*)st, out_aabb);
-    return PCH_OK;
+    return pl_filter_run(__func__, "plt_filter", raw, n, centroid3_dev, PfTilePlanes{best_dev, fallback_dev, *grid_host},
+                         keep_mode, offset_or_threshold, out_points, out_index, out_count, out_aabb, ws, ws_bytes,
+                         (hipStream_t)stream);
 }

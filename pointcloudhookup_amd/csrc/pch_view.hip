@@ -3,38 +3,32 @@
 //   crop     : points[(x>=x0)&(x<=x1)&(y>=y0)&(y<=y1)&(z>=z0)&(z<=z1)]     test/kuangxuan.py:69-79
 //   decimate : points[np.random.choice(len(points), k, replace=False)]      pyGUI_towers_test.py:174-177,
 //                                                                           ui/vtk_widget.py:115-118
-#include "pch_common.h"
-#include "pch_lookback.h"
+#include "pch_compact.h"
 
 namespace pch {
 
-constexpr int CR_THREADS = 256;
+constexpr int CR_THREADS = OC_THREADS;
 constexpr int CR_ROUNDS  = 8;
 constexpr int CR_TILE    = CR_THREADS * CR_ROUNDS;          // 2048 rows per workgroup
 
 struct CropBox { double lo[3], hi[3]; };
 struct Row64 { double x, y, z; };
 
-struct CropState { uint32_t ticket, total, pad[2]; };
+struct CropState { uint32_t ticket, pad[3]; };
+typedef OcWs<CropState, CR_TILE> CropWs;
 
-// order-preserving compaction in one sweep: tiles are taken by ticket (order of arrival), the output
-// offset of a tile comes from a decoupled look-back over the tiles in front of it
+// the register-resident ordered compaction of pch_compact.h on float64 rows: the row type, the predicate, the store
 __global__ __launch_bounds__(CR_THREADS) void crop_aabb_k(const double* __restrict__ xyz, int64_t n, CropBox box,
                                                           CropState* __restrict__ st, uint64_t* __restrict__ status,
                                                           double* __restrict__ out_points,
                                                           int64_t* __restrict__ out_index,
                                                           int64_t* __restrict__ out_count) {
-    __shared__ uint32_t wtot[CR_THREADS / 64];
-    __shared__ uint32_t tile_sh, excl_sh;
-    if (threadIdx.x == 0) tile_sh = atomicAdd(&st->ticket, 1u);
-    __syncthreads();
-    const int64_t tile = tile_sh;
-    const int w = wave_id(), l = lane_id();
-    const int64_t seg = tile * CR_TILE + (int64_t)w * (64 * CR_ROUNDS);
+    const int64_t tile = oc_take_tile(&st->ticket);
+    const int l = lane_id();
+    const int64_t seg = tile * CR_TILE + (int64_t)wave_id() * (64 * CR_ROUNDS);
     const Row64* __restrict__ rows = reinterpret_cast<const Row64*>(xyz);
     Row64 q[CR_ROUNDS];
     unsigned long long m[CR_ROUNDS];
-    uint32_t run = 0;
 #pragma unroll
     for (int r = 0; r < CR_ROUNDS; ++r) {
         const int64_t i = seg + r * 64 + l;
@@ -46,39 +40,13 @@ __global__ __launch_bounds__(CR_THREADS) void crop_aabb_k(const double* __restri
         const bool keep = i < n && q[r].x >= box.lo[0] && q[r].x <= box.hi[0] && q[r].y >= box.lo[1] &&
                           q[r].y <= box.hi[1] && q[r].z >= box.lo[2] && q[r].z <= box.hi[2];
         m[r] = __ballot(keep);
-        run += (uint32_t)__popcll(m[r]);
     }
-    if (l == 0) wtot[w] = run;
-    __syncthreads();
-    const uint32_t T = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    if (w == 0) {
-        const uint32_t e0 = gf_lookback(status, tile, T);
-        const bool lb_failed = e0 == GF_LB_FAILED;
-        const uint32_t e = lb_failed ? 0u : e0;              // prefix 0 keeps the writes below inside the output
-        if (l == 0) {
-            excl_sh = e;
-            // out_count starts at 0: the last tile adds the total (< 2^62), a tile whose wait ran out of its budget
-            // sets the sign bit - idempotent, so the word reads negative iff some tile failed, however many did
-            // (every tile behind a poisoned one fails too) and in whatever order the two happen
-            unsigned long long* oc = reinterpret_cast<unsigned long long*>(out_count);
-            if (lb_failed) atomicOr(oc, 1ull << 63);
-            else if (tile == (int64_t)gridDim.x - 1) atomicAdd(oc, (unsigned long long)e + T);
-        }
-    }
-    __syncthreads();
-    if (T == 0) return;
-    uint32_t woff = excl_sh;
-    for (int w2 = 0; w2 < w; ++w2) woff += wtot[w2];
-    const uint64_t lt = lanemask_lt();
-#pragma unroll
-    for (int r = 0; r < CR_ROUNDS; ++r) {
-        if ((m[r] >> l) & 1ull) {
-            const int64_t o = (int64_t)woff + (uint32_t)__popcll(m[r] & lt);
-            reinterpret_cast<Row64*>(out_points)[o] = q[r];
-            if (out_index) out_index[o] = seg + r * 64 + l;
-        }
-        woff += (uint32_t)__popcll(m[r]);
-    }
+    const uint32_t woff = oc_place(m, status, tile, out_count);
+    if (woff == OC_NONE) return;
+    oc_visit(m, woff, [&](int r, int64_t o) {
+        reinterpret_cast<Row64*>(out_points)[o] = q[r];
+        if (out_index) out_index[o] = seg + r * 64 + l;
+    });
 }
 
 // ---- seeded sampling without replacement: a keyed bijection of [0, 2^b) (four Feistel rounds) walked
@@ -119,11 +87,7 @@ __global__ void decimate_k(const double* __restrict__ xyz, int64_t n, int64_t k,
 using namespace pch;
 
 extern "C" size_t pch_crop_aabb_ws_bytes(int64_t n) {
-    if (n < 0) return 0;
-    Arena a;
-    a.take<CropState>(1);
-    a.take<uint64_t>(ceil_div(n > 0 ? n : 1, CR_TILE));
-    return a.off;
+    return n < 0 ? 0 : CropWs::bytes(n);
 }
 
 extern "C" int pch_crop_aabb_f64(const double* xyz, int64_t n, const double* min3_host, const double* max3_host,
@@ -138,40 +102,33 @@ extern "C" int pch_crop_aabb_f64(const double* xyz, int64_t n, const double* min
     }
     PCH_REQUIRE(xyz && out_points && ws, "null buffer");
     Arena a(ws, ws_bytes);
-    CropState* st = a.take<CropState>(1);
-    const int64_t nt = ceil_div(n, CR_TILE);
-    uint64_t* status = a.take<uint64_t>(nt);
+    const CropWs w(a, n);
     if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
     PCH_HIP_TRY(hipMemsetAsync(ws, 0, a.off, s));
     PCH_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(int64_t), s));
     CropBox box;
     for (int k = 0; k < 3; ++k) { box.lo[k] = min3_host[k]; box.hi[k] = max3_host[k]; }
-    PCH_LAUNCH("crop_aabb", crop_aabb_k, dim3((unsigned)nt), dim3(CR_THREADS), 0, s, xyz, n, box, st, status,
-               out_points, out_index, out_count);
+    PCH_LAUNCH("crop_aabb", crop_aabb_k, dim3((unsigned)w.nt), dim3(CR_THREADS), 0, s, xyz, n, box, w.st,
+               w.status, out_points, out_index, out_count);
     return PCH_OK;
 }
 
 // ---- self-test of the bounded look-back wait (pch_lookback.h): eight tiles in ticket order, the workgroup that
 // draws ticket 1 leaves WITHOUT publishing - what a lost or never-scheduled tile looks like to the tiles behind
 // it.  Tickets 2..7 must give up after `budget` ticks (the first by its own clock, the rest on its poisoned word),
-// poison their words and mark the count word exactly like crop_aabb_k / vx_finish_k do (sign bit, idempotent;
-// the last ticket would add the total); the grid drains by construction.  Never part of the data path.
+// poison their words and mark the count word through the data path's own oc_count_update (pch_compact.h: sign bit,
+// idempotent; the last ticket would add the total), as vx_finish_k marks its own; the grid drains by construction.
+// Never part of the data path.
 namespace pch {
 __global__ __launch_bounds__(64) void lb_selftest_k(uint64_t* __restrict__ status, uint32_t* __restrict__ state,
                                                     unsigned long long* __restrict__ count,
                                                     unsigned long long budget) {
-    __shared__ uint32_t tile_sh;
-    if (threadIdx.x == 0) tile_sh = atomicAdd(&state[0], 1u);
-    __syncthreads();
-    const int64_t tile = tile_sh;
+    const int64_t tile = oc_take_tile(&state[0]);
     if (tile == 1) return;                               // the tile that never publishes
     const uint32_t e = gf_lookback(status, tile, 1u, false, budget);
     if (threadIdx.x == 0) {
-        if (e == GF_LB_FAILED) { atomicAdd(&state[1], 1u); atomicOr(count, 1ull << 63); }
-        else {
-            atomicAdd(&state[2], 1u);
-            if (tile == (int64_t)gridDim.x - 1) atomicAdd(count, (unsigned long long)e + 1u);
-        }
+        atomicAdd(&state[e == GF_LB_FAILED ? 1 : 2], 1u);
+        oc_count_update(count, e == GF_LB_FAILED, tile == (int64_t)gridDim.x - 1, (unsigned long long)e + 1u);
     }
 }
 }  // namespace pch

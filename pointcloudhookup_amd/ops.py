@@ -295,14 +295,24 @@ def filter_gt(raw, centroid, threshold, want_index=True):
     dev = raw.device
     cen = (C.c_float * 3)(*[float(np.float32(v)) for v in centroid])
     with torch.cuda.device(dev):
-        out_points = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        out_index = torch.empty((n,), dtype=torch.int32, device=dev) if want_index else None
-        cnt = torch.zeros((1,), dtype=torch.int64, device=dev)
-        aabb = torch.zeros((6,), dtype=torch.float32, device=dev)
+        out_points, out_index, cnt, aabb = _filter_outputs(raw, want_index)
         ws = _workspace(L.pch_filter_gt_ws_bytes(n), dev)
         _lib.check(L.pch_filter_gt_f32(_ptr(raw), n, C.cast(cen, C.c_void_p), float(np.float32(threshold)), _ptr(out_points),
                                        _ptr(out_index), _ptr(cnt), _ptr(aabb), _ptr(ws), ws.numel(), _stream()))
-        m = _lib.check_count(cnt.item(), "filter_gt")
+        return _filter_result("filter_gt", out_points, out_index, cnt, aabb)
+
+
+def _filter_outputs(raw, want_index):
+    """the device buffers of filter_gt, filter_plane and filter_plane_tiles: out_points, out_index | None, count, aabb"""
+    n, dev = raw.shape[0], raw.device
+    return (torch.empty((n, 3), dtype=torch.float32, device=dev),
+            torch.empty((n,), dtype=torch.int32, device=dev) if want_index else None,
+            torch.zeros((1,), dtype=torch.int64, device=dev), torch.zeros((6,), dtype=torch.float32, device=dev))
+
+
+def _filter_result(what, out_points, out_index, cnt, aabb):
+    """the dict those three return; reads the count (synchronises)"""
+    m = _lib.check_count(cnt.item(), what)
     return dict(points=out_points[:m], index=None if out_index is None else out_index[:m], count=m,
                 aabb=aabb.cpu().numpy())
 
@@ -346,6 +356,17 @@ PLANE_COUNT_TILE = 1024        # rows per workgroup pass of the inlier count (pl
 _PLANE_KEEP = {"above": 0, "off_plane": 1}
 
 
+def _check_hypotheses(H):
+    if not 1 <= H <= PLANE_MAX_HYPOTHESES:
+        raise ValueError(f"between 1 and {PLANE_MAX_HYPOTHESES} hypotheses, got {H}")
+
+
+def _cos2(max_slope_deg):
+    """the slope gate of a fit as the library takes it"""
+    import math
+    return math.cos(math.radians(float(max_slope_deg))) ** 2
+
+
 def plane_hypothesis_rows(n, H=256, seed=0):
     """The row triples of H plane hypotheses over a cloud of n rows: host int64 [H,3], drawn with replacement (a
     triple with a repeat is simply an invalid hypothesis).  The first H of a longer draw with the same seed."""
@@ -353,8 +374,7 @@ def plane_hypothesis_rows(n, H=256, seed=0):
     n, H = int(n), int(H)
     if n < 1:
         raise ValueError("plane_hypothesis_rows needs a cloud with at least one row")
-    if not 1 <= H <= PLANE_MAX_HYPOTHESES:
-        raise ValueError(f"between 1 and {PLANE_MAX_HYPOTHESES} hypotheses, got {H}")
+    _check_hypotheses(H)
     return np.random.Generator(np.random.PCG64(int(seed))).integers(0, n, size=(H, 3), dtype=np.int64)
 
 
@@ -376,29 +396,39 @@ def _plane_rows_dev(rows, n, dev):
         if n and host.size and (host.min() < 0 or host.max() >= n):
             raise ValueError("rows: every entry must lie in [0, n)")
         rows = torch.from_numpy(host).to(dev)
-    if not 1 <= rows.shape[0] <= PLANE_MAX_HYPOTHESES:
-        raise ValueError(f"between 1 and {PLANE_MAX_HYPOTHESES} hypotheses, got {rows.shape[0]}")
+    _check_hypotheses(rows.shape[0])
     return rows
 
 
 def _plane_fit_launch(raw, cen_dev, rows_dev, residual_threshold, max_slope_deg, best_ptr):
     """pch_plane_fit_f32, enqueued: (planes float64 [H,4], counts int64 [H]) device tensors, the best record at
     best_ptr (device)"""
-    import math
     L = _lib.lib()
     n, H, dev = raw.shape[0], rows_dev.shape[0], raw.device
     planes = torch.empty((H, 4), dtype=torch.float64, device=dev)
     counts = torch.empty((H,), dtype=torch.int64, device=dev)
-    cos2 = math.cos(math.radians(float(max_slope_deg))) ** 2
     ws = _workspace(L.pch_plane_fit_ws_bytes(n, H), dev)
-    _lib.check(L.pch_plane_fit_f32(_ptr(raw), n, _ptr(cen_dev), _ptr(rows_dev), H, float(residual_threshold), cos2,
-                                   _ptr(planes), _ptr(counts), best_ptr, _ptr(ws), ws.numel(), _stream()))
+    _lib.check(L.pch_plane_fit_f32(_ptr(raw), n, _ptr(cen_dev), _ptr(rows_dev), H, float(residual_threshold),
+                                   _cos2(max_slope_deg), _ptr(planes), _ptr(counts), best_ptr, _ptr(ws), ws.numel(),
+                                   _stream()))
     return planes, counts
 
 
 def _plane_best(words):
     """PchPlaneBest from its 40 bytes (numpy uint8)"""
     return _lib.PlaneBestC.from_buffer_copy(words.tobytes())
+
+
+def _plane_record_dev(plane, dev):
+    """a PchPlaneBest on the device from (a, b, c), a plane_fit result or None (no plane: best = -1)"""
+    import numpy as np
+    if isinstance(plane, dict):
+        plane = plane["plane"]
+    rec = _lib.PlaneBestC(0.0, 0.0, 0.0, 0, -1, 0)
+    if plane is not None:
+        a, b, c = (float(v) for v in plane)
+        rec = _lib.PlaneBestC(a, b, c, 0, 0, 1)
+    return torch.from_numpy(np.frombuffer(bytes(rec), dtype=np.uint8).copy()).to(dev)
 
 
 def plane_fit(raw, centroid, rows, residual_threshold=0.1, max_slope_deg=45.0):
@@ -445,26 +475,15 @@ def filter_plane(raw, centroid, plane_or_fit, keep="above", offset=3.0, residual
     !(|r| <= residual_threshold), remove_ground_ransac's own non-ground set.  plane_or_fit: (a, b, c), or what
     plane_fit returned (a fit without a valid hypothesis keeps nothing).  Returns the dict of filter_gt.
     Synchronises."""
-    import numpy as np
     value = _plane_keep_value(keep, offset, residual_threshold)
     raw = _need_cuda(raw, torch.float32, "raw").reshape(-1, 3)
-    n, dev = raw.shape[0], raw.device
-    plane = plane_or_fit["plane"] if isinstance(plane_or_fit, dict) else plane_or_fit
-    rec = _lib.PlaneBestC(0.0, 0.0, 0.0, 0, -1, 0)
-    if plane is not None:
-        a, b, c = (float(v) for v in plane)
-        rec = _lib.PlaneBestC(a, b, c, 0, 0, 1)
+    dev = raw.device
     with torch.cuda.device(dev):
-        best = torch.from_numpy(np.frombuffer(bytes(rec), dtype=np.uint8).copy()).to(dev)
-        out_points = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        out_index = torch.empty((n,), dtype=torch.int32, device=dev) if want_index else None
-        cnt = torch.zeros((1,), dtype=torch.int64, device=dev)
-        aabb = torch.zeros((6,), dtype=torch.float32, device=dev)
+        best = _plane_record_dev(plane_or_fit, dev)
+        out_points, out_index, cnt, aabb = _filter_outputs(raw, want_index)
         _filter_plane_launch(raw, _centroid_dev(centroid, dev), _ptr(best), keep, value, out_points, out_index,
                              _ptr(cnt), _ptr(aabb))
-        m = _lib.check_count(cnt.item(), "filter_plane")
-    return dict(points=out_points[:m], index=None if out_index is None else out_index[:m], count=m,
-                aabb=aabb.cpu().numpy())
+        return _filter_result("filter_plane", out_points, out_index, cnt, aabb)
 
 
 def ground_filter_plane(raw, hypotheses=256, seed=0, residual_threshold=0.1, max_slope_deg=45.0, offset=3.0,
@@ -477,42 +496,64 @@ def ground_filter_plane(raw, hypotheses=256, seed=0, residual_threshold=0.1, max
     device; one host read, a second after a fallback."""
     import numpy as np
     value = _plane_keep_value(keep, offset, residual_threshold)
-    L = _lib.lib()
     raw = _need_cuda(raw, torch.float32, "raw").reshape(-1, 3)
     n, dev = raw.shape[0], raw.device
     if n == 0:
         raise ValueError("no valid ground plane: the cloud is empty")
     with torch.cuda.device(dev):
         rows_dev = _plane_rows_dev(plane_hypothesis_rows(n, hypotheses, seed) if rows is None else rows, n, dev)
-        out_points = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        out_index = torch.empty((n,), dtype=torch.int32, device=dev) if want_index else None
-        # one block for the host: [0:40] best record, [48:56] count, [64:88] aabb, [96:108] centroid
-        scal = torch.zeros((112,), dtype=torch.uint8, device=dev)
-        base = scal.data_ptr()
-        cen = scal[96:108].view(torch.float32)
-        ws = _workspace(L.pch_mean_seq_f32_ws_bytes(n), dev)
-        _lib.check(L.pch_mean_seq_f32(_ptr(raw), n, _ptr(cen), _ptr(ws), ws.numel(), _stream()))
-        _plane_fit_launch(raw, cen, rows_dev, residual_threshold, max_slope_deg, base)
 
-        def sweep(v):
-            _filter_plane_launch(raw, cen, base, keep, v, out_points, out_index, base + 48, base + 64)
-            host = scal.cpu().numpy()
-            return host, _lib.check_count(host[48:56].view("<i8")[0], "ground_filter_plane")
+        def check(rec, _):
+            if rec.best < 0:
+                raise ValueError(f"no valid ground plane among {rows_dev.shape[0]} hypotheses (degenerate triples, or "
+                                 f"none within {max_slope_deg} degrees of level)")
 
-        host, nf = sweep(value)
-        rec = _plane_best(host[:40])
-        if rec.best < 0:
-            raise ValueError(f"no valid ground plane among {rows_dev.shape[0]} hypotheses (degenerate triples, or "
-                             f"none within {max_slope_deg} degrees of level)")
-        first, used_fallback = nf, False
-        if keep == "above" and nf < int(min_keep):
-            used_fallback, value = True, fallback_offset
-            host, nf = sweep(value)
-    out = _ground_result(out_points, out_index, nf, host[96:108].view(np.float32), np.float32(rec.c), value,
-                         used_fallback, first, host[64:88].view(np.float32))
+        def fits(cen, record_ptr):
+            _plane_fit_launch(raw, cen, rows_dev, residual_threshold, max_slope_deg, record_ptr)
+            return (lambda *a: _filter_plane_launch(raw, cen, record_ptr, keep, *a)), [], check
+
+        out, rec, _ = _plane_stage_b(raw, "ground_filter_plane", keep, value, fallback_offset, min_keep, want_index,
+                                     fits)
     out.update(plane=np.array([rec.a, rec.b, rec.c], dtype=np.float64), inliers=int(rec.count),
                nvalid=int(rec.nvalid), best=int(rec.best))
     return out
+
+
+def _plane_stage_b(raw, what, keep, value, fallback_offset, min_keep, want_index, fits):
+    """What ground_filter_plane and ground_filter_plane_tiles share: one block for the host - [0:40] the record of the
+    global fit, [48:56] count, [64:88] aabb, [96:108] centroid - the centroid launch, then ``fits(cen, record_ptr)``,
+    which enqueues the rule's fits and returns (launch, extra, check): launch(v, out_points, out_index, cnt_ptr,
+    aabb_ptr) enqueues the filter at the value v, ``extra`` are uint8 device tensors that ride along with the block's
+    host read, check(rec, extra_host) raises when there is no plane at all.  Sweep, read once, check, and in "above"
+    mode the fallback offset with a second read.  Returns (the dict of ground_filter, rec, what check returned)."""
+    import numpy as np
+    L = _lib.lib()
+    n, dev = raw.shape[0], raw.device
+    scal = torch.zeros((112,), dtype=torch.uint8, device=dev)
+    base = scal.data_ptr()
+    cen = scal[96:108].view(torch.float32)
+    ws = _workspace(L.pch_mean_seq_f32_ws_bytes(n), dev)
+    _lib.check(L.pch_mean_seq_f32(_ptr(raw), n, _ptr(cen), _ptr(ws), ws.numel(), _stream()))
+    launch, extra, check = fits(cen, base)
+    out_points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    out_index = torch.empty((n,), dtype=torch.int32, device=dev) if want_index else None
+
+    def sweep(v):
+        launch(v, out_points, out_index, base + 48, base + 64)
+        host = (torch.cat([scal] + extra) if extra else scal).cpu().numpy()
+        return host, _lib.check_count(host[48:56].view("<i8")[0], what)
+
+    host, nf = sweep(value)
+    rec = _plane_best(host[:40])
+    info = check(rec, host[112:])
+    first, used_fallback = nf, False
+    if keep == "above" and nf < int(min_keep):
+        used_fallback, value = True, fallback_offset
+        host, nf = sweep(value)
+    out = _ground_result(out_points, out_index, nf, host[96:108].view(np.float32),
+                         np.float32(rec.c) if rec.best >= 0 else np.float32(np.nan), value, used_fallback, first,
+                         host[64:88].view(np.float32))
+    return out, rec, info
 
 
 # ------------------------------------------------------------- stage B, opt-in: one RANSAC plane per xy tile
@@ -571,8 +612,7 @@ def plane_tile_draws(H=64, seed=0):
     hypothesis h) is list_t[draws[h][k] mod n_t].  The first H of a longer table with the same seed."""
     import numpy as np
     H = int(H)
-    if not 1 <= H <= PLANE_MAX_HYPOTHESES:
-        raise ValueError(f"between 1 and {PLANE_MAX_HYPOTHESES} hypotheses, got {H}")
+    _check_hypotheses(H)
     return np.random.Generator(np.random.PCG64(int(seed))).integers(0, 2 ** 62, size=(H, 3), dtype=np.int64)
 
 
@@ -594,8 +634,7 @@ def _plane_draws_dev(draws, ntiles, dev):
             raise ValueError("draws: every entry must be >= 0")
         draws = torch.from_numpy(host).to(dev)
     H = draws.shape[0]
-    if not 1 <= H <= PLANE_MAX_HYPOTHESES:
-        raise ValueError(f"between 1 and {PLANE_MAX_HYPOTHESES} hypotheses, got {H}")
+    _check_hypotheses(H)
     if ntiles * H > PLANE_MAX_TILE_TABLE:
         raise ValueError(f"{ntiles} tiles x {H} hypotheses exceed {PLANE_MAX_TILE_TABLE} table entries")
     return draws
@@ -605,14 +644,13 @@ def _plane_tiles_fit_launch(raw, cen_dev, grid_c, ntiles, draws_dev, min_tile_ro
                             best, tile_rows, planes=None, counts=None):
     """pch_plane_tiles_fit_f32, enqueued; best: uint8 [ntiles * 40], tile_rows: int64 [ntiles] (device)"""
     import ctypes as C
-    import math
     L = _lib.lib()
     n, H = raw.shape[0], draws_dev.shape[0]
-    cos2 = math.cos(math.radians(float(max_slope_deg))) ** 2
     ws = _workspace(L.pch_plane_tiles_fit_ws_bytes(n, ntiles, H), raw.device)
     _lib.check(L.pch_plane_tiles_fit_f32(_ptr(raw), n, _ptr(cen_dev), C.cast(C.pointer(grid_c), C.c_void_p), _ptr(draws_dev),
-                                         H, int(min_tile_rows), float(residual_threshold), cos2, _ptr(best),
-                                         _ptr(tile_rows), _ptr(planes), _ptr(counts), _ptr(ws), ws.numel(), _stream()))
+                                         H, int(min_tile_rows), float(residual_threshold), _cos2(max_slope_deg),
+                                         _ptr(best), _ptr(tile_rows), _ptr(planes), _ptr(counts), _ptr(ws), ws.numel(),
+                                         _stream()))
 
 
 def _plane_tiles_table(best_bytes, rows):
@@ -658,18 +696,6 @@ def plane_tiles_fit(raw, centroid, grid, draws, min_tile_rows=64, residual_thres
     return out
 
 
-def _plane_record_dev(plane, dev):
-    """a PchPlaneBest on the device from (a, b, c), a plane_fit result or None (no plane: best = -1)"""
-    import numpy as np
-    if isinstance(plane, dict):
-        plane = plane["plane"]
-    rec = _lib.PlaneBestC(0.0, 0.0, 0.0, 0, -1, 0)
-    if plane is not None:
-        a, b, c = (float(v) for v in plane)
-        rec = _lib.PlaneBestC(a, b, c, 0, 0, 1)
-    return torch.from_numpy(np.frombuffer(bytes(rec), dtype=np.uint8).copy()).to(dev)
-
-
 def _filter_plane_tiles_launch(raw, cen_dev, grid_c, ntiles, best_ptr, fallback_ptr, keep, value, out_points,
                                out_index, cnt_ptr, aabb_ptr):
     import ctypes as C
@@ -691,7 +717,7 @@ def filter_plane_tiles(raw, centroid, grid, fit_or_table, fallback=None, keep="a
     import numpy as np
     value = _plane_keep_value(keep, offset, residual_threshold)
     raw = _need_cuda(raw, torch.float32, "raw").reshape(-1, 3)
-    n, dev = raw.shape[0], raw.device
+    dev = raw.device
     grid_c, ntiles = _plane_grid_c(grid)
     rec = np.zeros((ntiles,), dtype=np.dtype(_BEST_FIELDS))
     tb = np.asarray(fit_or_table["best"]).reshape(-1)
@@ -702,15 +728,10 @@ def filter_plane_tiles(raw, centroid, grid, fit_or_table, fallback=None, keep="a
     with torch.cuda.device(dev):
         best = torch.from_numpy(rec.view(np.uint8)).to(dev)
         fb = None if fallback is None else _plane_record_dev(fallback, dev)
-        out_points = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        out_index = torch.empty((n,), dtype=torch.int32, device=dev) if want_index else None
-        cnt = torch.zeros((1,), dtype=torch.int64, device=dev)
-        aabb = torch.zeros((6,), dtype=torch.float32, device=dev)
+        out_points, out_index, cnt, aabb = _filter_outputs(raw, want_index)
         _filter_plane_tiles_launch(raw, _centroid_dev(centroid, dev), grid_c, ntiles, _ptr(best), _ptr(fb), keep, value,
                                    out_points, out_index, _ptr(cnt), _ptr(aabb))
-        m = _lib.check_count(cnt.item(), "filter_plane_tiles")
-    return dict(points=out_points[:m], index=None if out_index is None else out_index[:m], count=m,
-                aabb=aabb.cpu().numpy())
+        return _filter_result("filter_plane_tiles", out_points, out_index, cnt, aabb)
 
 
 def ground_filter_plane_tiles(raw, tile_size=20.0, hypotheses=64, seed=0, min_tile_rows=64, fallback_hypotheses=64,
@@ -727,7 +748,6 @@ def ground_filter_plane_tiles(raw, tile_size=20.0, hypotheses=64, seed=0, min_ti
     second after a fallback offset."""
     import numpy as np
     value = _plane_keep_value(keep, offset, residual_threshold)
-    L = _lib.lib()
     raw = _need_cuda(raw, torch.float32, "raw").reshape(-1, 3)
     n, dev = raw.shape[0], raw.device
     if n == 0:
@@ -735,44 +755,30 @@ def ground_filter_plane_tiles(raw, tile_size=20.0, hypotheses=64, seed=0, min_ti
     if int(min_tile_rows) < 1:
         raise ValueError("min_tile_rows must be at least 1")
     with torch.cuda.device(dev):
-        # one block for the host: [0:40] fallback record, [48:56] count, [64:88] aabb, [96:108] centroid
-        scal = torch.zeros((112,), dtype=torch.uint8, device=dev)
-        base = scal.data_ptr()
-        cen = scal[96:108].view(torch.float32)
-        ws = _workspace(L.pch_mean_seq_f32_ws_bytes(n), dev)
-        _lib.check(L.pch_mean_seq_f32(_ptr(raw), n, _ptr(cen), _ptr(ws), ws.numel(), _stream()))
-        grid = plane_tile_grid(raw, cen, tile_size)
-        grid_c, ntiles = _plane_grid_c(grid)
-        draws_dev = _plane_draws_dev(plane_tile_draws(hypotheses, seed), ntiles, dev)
-        rows_dev = _plane_rows_dev(plane_hypothesis_rows(n, fallback_hypotheses, seed), n, dev)
-        out_points = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        out_index = torch.empty((n,), dtype=torch.int32, device=dev) if want_index else None
-        best = torch.empty((ntiles * 40,), dtype=torch.uint8, device=dev)
-        tile_rows = torch.empty((ntiles,), dtype=torch.int64, device=dev)
-        _plane_fit_launch(raw, cen, rows_dev, residual_threshold, max_slope_deg, base)
-        _plane_tiles_fit_launch(raw, cen, grid_c, ntiles, draws_dev, min_tile_rows, residual_threshold, max_slope_deg,
-                                best, tile_rows)
+        def fits(cen, record_ptr):
+            grid = plane_tile_grid(raw, cen, tile_size)
+            grid_c, ntiles = _plane_grid_c(grid)
+            draws_dev = _plane_draws_dev(plane_tile_draws(hypotheses, seed), ntiles, dev)
+            rows_dev = _plane_rows_dev(plane_hypothesis_rows(n, fallback_hypotheses, seed), n, dev)
+            best = torch.empty((ntiles * 40,), dtype=torch.uint8, device=dev)
+            tile_rows = torch.empty((ntiles,), dtype=torch.int64, device=dev)
+            _plane_fit_launch(raw, cen, rows_dev, residual_threshold, max_slope_deg, record_ptr)
+            _plane_tiles_fit_launch(raw, cen, grid_c, ntiles, draws_dev, min_tile_rows, residual_threshold,
+                                    max_slope_deg, best, tile_rows)
 
-        def sweep(v):
-            _filter_plane_tiles_launch(raw, cen, grid_c, ntiles, _ptr(best), base, keep, v, out_points, out_index,
-                                       base + 48, base + 64)
-            host = torch.cat([scal, best, tile_rows.view(torch.uint8)]).cpu().numpy()
-            return host, _lib.check_count(host[48:56].view("<i8")[0], "ground_filter_plane_tiles")
+            def check(rec, extra_host):
+                tiles = _plane_tiles_table(extra_host[:40 * ntiles], extra_host[40 * ntiles:].view(np.int64))
+                tiles["grid"] = grid
+                if rec.best < 0 and not (tiles["best"] >= 0).any():
+                    raise ValueError(f"no valid ground plane in any of {ntiles} tiles nor among {rows_dev.shape[0]} global"
+                                     f" hypotheses (degenerate triples, or none within {max_slope_deg} degrees of level)")
+                return tiles
 
-        host, nf = sweep(value)
-        rec = _plane_best(host[:40])
-        tiles = _plane_tiles_table(host[112:112 + 40 * ntiles], host[112 + 40 * ntiles:].view(np.int64))
-        tiles["grid"] = grid
-        if rec.best < 0 and not (tiles["best"] >= 0).any():
-            raise ValueError(f"no valid ground plane in any of {ntiles} tiles nor among {rows_dev.shape[0]} global "
-                             f"hypotheses (degenerate triples, or none within {max_slope_deg} degrees of level)")
-        first, used_fallback = nf, False
-        if keep == "above" and nf < int(min_keep):
-            used_fallback, value = True, fallback_offset
-            host, nf = sweep(value)
-    out = _ground_result(out_points, out_index, nf, host[96:108].view(np.float32),
-                         np.float32(rec.c) if rec.best >= 0 else np.float32(np.nan), value, used_fallback, first,
-                         host[64:88].view(np.float32))
+            return (lambda *a: _filter_plane_tiles_launch(raw, cen, grid_c, ntiles, _ptr(best), record_ptr, keep, *a),
+                    [best, tile_rows.view(torch.uint8)], check)
+
+        out, rec, tiles = _plane_stage_b(raw, "ground_filter_plane_tiles", keep, value, fallback_offset, min_keep,
+                                         want_index, fits)
     out.update(tiles=tiles, fallback_plane=None if rec.best < 0 else np.array([rec.a, rec.b, rec.c], dtype=np.float64))
     return out
 

@@ -96,6 +96,32 @@ def filtered(P, mask):
     return dict(points=pts, index=np.flatnonzero(mask).astype(np.int32), count=int(mask.sum()), aabb=aabb)
 
 
+PATCHY_TILE, PATCHY_SEG = 2048, 512      # rows a workgroup / a wave of the compacting sweeps takes (PF_TILE, CR_TILE)
+
+
+def patchy_cloud():
+    """(raw float32 [n,3], mask bool [n]), n = 5 tiles + 300 rows, for the sweeps that compact a tile of four wave
+    segments (ops.crop_aabb, filter_plane, filter_plane_tiles): x, y random, z = 10 in a kept row and 0 otherwise, the
+    kept set chosen per segment - tile 0 keeps everything, tile 1 nothing, tile 2 its last row alone, tile 3 every
+    7th row of wave 2's segment alone, tile 4 nothing, the partial tile 5 the cloud's last row alone"""
+    kinds = ["all"] * 4 + ["none"] * 4 + ["none", "none", "none", "last"] + ["none", "none", "every7", "none"] + \
+            ["none"] * 4 + ["last"]
+    n = 5 * PATCHY_TILE + 300
+    mask = np.zeros((n,), dtype=bool)
+    for s, kind in enumerate(kinds):
+        seg = mask[PATCHY_SEG * s:PATCHY_SEG * (s + 1)]          # a view; the last one has 300 rows
+        if kind == "all":
+            seg[:] = True
+        elif kind == "last":
+            seg[-1] = True
+        elif kind == "every7":
+            seg[::7] = True
+    raw = np.empty((n, 3), dtype=np.float32)
+    raw[:, :2] = np.random.Generator(np.random.PCG64(7)).uniform(0.0, 100.0, size=(n, 2))
+    raw[:, 2] = np.where(mask, 10.0, 0.0)
+    return raw, mask
+
+
 def ground(raw, rows, thr=0.1, max_slope_deg=45.0, offset=3.0, fallback_offset=1.0, min_keep=1000, keep="above"):
     """steps 1-6 on a float32 cloud: what ops.ground_filter_plane returns (ValueError without a valid plane)"""
     centroid = np.mean(raw, axis=0)

@@ -161,6 +161,33 @@ def test_filter_empty_and_all_kept(cuda):
         ops.filter_plane(x, centroid, plane, keep="below")
 
 
+@pytest.mark.parametrize("route", ["crop_aabb", "filter_plane", "filter_plane_tiles"])
+def test_patchy_tiles(cuda, route):
+    """empty tiles between live ones, a wave segment kept alone, a tile whose only kept row is its last (the facts are
+    asserted on the mask in test_plane_host.py): every sweep on the shared compaction, bit for bit against numpy"""
+    raw, mask = pc.patchy_cloud()
+    zero, plane = np.zeros(3, dtype=np.float32), (0.0, 0.0, 0.0)
+    want = pc.filtered(raw, mask)
+    if route == "crop_aabb":
+        x = _dev(raw.astype(np.float64), cuda)
+        pts, idx = ops.crop_aabb(x, (-1e9, -1e9, 5.0), (1e9, 1e9, 15.0), want_index=True)
+        assert idx.dtype == torch.int64
+        np.testing.assert_array_equal(idx.cpu().numpy(), np.flatnonzero(mask))
+        for got in (pts, ops.crop_aabb(x, (-1e9, -1e9, 5.0), (1e9, 1e9, 15.0))):
+            np.testing.assert_array_equal(got.cpu().numpy().view(np.uint64), raw.astype(np.float64)[mask].view(np.uint64))
+        return
+    if route == "filter_plane":
+        call = functools.partial(ops.filter_plane, _dev(raw, cuda), zero, plane, keep="above", offset=3.0)
+    else:
+        call = functools.partial(ops.filter_plane_tiles, _dev(raw, cuda), zero, dict(x0=0.0, y0=0.0, tile=200.0, nx=1, ny=1),
+                                 dict(best=[0], planes=[plane]), keep="above", offset=3.0)
+    _same_filter(call(), want)
+    nox = call(want_index=False)
+    assert nox["index"] is None and nox["count"] == want["count"]
+    np.testing.assert_array_equal(nox["points"].cpu().numpy().view(np.uint32), want["points"].view(np.uint32))
+    np.testing.assert_array_equal(np.asarray(nox["aabb"], dtype=np.float32).view(np.uint32), want["aabb"].view(np.uint32))
+
+
 def _same_ground(got, want):
     _same_filter(got, want)
     np.testing.assert_array_equal(got["centroid"].view(np.uint32), want["centroid"].view(np.uint32))

@@ -24,6 +24,20 @@ def _ground(seed):
     return pc.ground(raw, pc.hypothesis_rows(N, H, seed))
 
 
+def test_patchy_cloud_has_the_tiles_it_is_for():
+    """the cloud of test_gpu_plane.py::test_patchy_tiles: a tile that keeps nothing between tiles that keep something,
+    a wave segment kept alone inside a tile, a tile whose only kept row is its last, the cloud's last row kept"""
+    _, mask = pc.patchy_cloud()
+    n, T, S = len(mask), pc.PATCHY_TILE, pc.PATCHY_SEG
+    assert n == 5 * T + 300
+    tiles = [mask[T * t:T * (t + 1)] for t in range(6)]
+    assert tiles[0].all() and not tiles[1].any() and not tiles[4].any()
+    assert np.flatnonzero(tiles[2]).tolist() == [T - 1]
+    assert tiles[3][2 * S:3 * S].any() and not tiles[3][:2 * S].any() and not tiles[3][3 * S:].any()
+    assert len(tiles[5]) == 300 and np.flatnonzero(tiles[5]).tolist() == [299] and mask[n - 1]
+    assert 0 < mask.sum() < n
+
+
 def test_plane_rule_stays_on_the_truth_where_the_percentile_rule_floods():
     """15 % grade: the plane rule's kept set differs from the generator truth in at most 0.1 % of the truth rows,
     the percentile rule's in more than 100 % of them (measured: 0 and 26 768 of 19 690)"""
