@@ -450,6 +450,45 @@ int pch_segment_by_label(const int32_t* labels, const float* xyz, int64_t n,
                          int32_t nclusters, int32_t* out_perm, int64_t* out_offsets,
                          float* out_stats, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ between C and D0, opt-in: merge of cluster pieces
+ * Stage C fits once per file-order chunk, so a tower whose kept rows straddle a chunk boundary comes out as two or
+ * more clusters, of which the 30 m centre de-dup (utils/tower_extraction.py:153-162) keeps the first piece only.  These
+ * calls restate the remedy of the reference's own test/tttt.py:93-175 ("聚类后处理：合并相邻簇"): clusters whose
+ * centres lie within merge_threshold (6.0 there) of each other, directly or through a chain of others, become one.
+ *
+ * The rule.  P: the kept, centred float32 rows [n,3]; labels in [-1, K); cluster k owns the rows with labels == k in
+ * ascending row order, i.e. perm[offsets[k]:offsets[k+1]] as pch_segment_by_label writes them.
+ *   1 centre: c_k = np.mean(P[labels == k], axis=0) (tttt.py:113): per column a sequential float32 running sum over the
+ *     cluster's rows in that order, divided by float32(n_k) with a correctly rounded float32 division - the arithmetic
+ *     of pch_mean_seq_f32.  A cluster without rows has centre NaN; non-finite rows propagate as in numpy.
+ *   2 reach: clusters i, j are linked iff ((dx*dx + dy*dy) + dz*dz) <= r*r in float64 on (double)c_i - (double)c_j,
+ *     accumulated in x, y, z order without FMA, r = merge_threshold: the predicate of sklearn's
+ *     KDTree.query_radius (reduced distance against r*r).  A NaN centre is linked to nothing.
+ *   3 components of that graph: the new id of a cluster is the rank of its component, components ordered by their
+ *     smallest old id.  So map[0] == 0, map[k] <= max(map[:k]) + 1, and clusters that merge with nothing keep their
+ *     relative order.  nmerged = number of components, empty clusters included as singletons.
+ *   4 relabel: labels[i] = map[labels[i]] for labels[i] in [0, K), everything else becomes -1.
+ * Two deliberate deviations from the script, neither of which changes the partition: it numbers the merged clusters
+ * from max(label) + 1 and then iterates a Python set of those numbers (an order that wraps at the set's table size, so
+ * which piece the later de-dup sees first depends on CPython internals); here they are numbered from 0 and iterated
+ * ascending.
+ *
+ * pch_cluster_centers_f32: step 1.  xyz [*,3] float32; perm int32 and offsets [nclusters+1] int64 as written by
+ * pch_segment_by_label (perm entries are trusted to be rows of xyz); out_centers [nclusters,3] float32; out_sizes
+ * [nclusters] int64 (may be NULL).  One wave per cluster, so the time is linear in the LARGEST cluster (a cluster of
+ * millions of rows - a global fit - is summed serially).  Enqueues and returns; no workspace, no host read.
+ *
+ * pch_cluster_merge_f32: steps 2-4.  centers [nclusters,3] float32; labels [n] int32 in/out (may be NULL: map only);
+ * out_map [nclusters] int32; out_nmerged [1] int32 (device).  All pairs are tested, so nclusters > 65536 is
+ * PCH_ERR_RANGE; merge_threshold not finite or < 0: PCH_ERR_ARG; nclusters == 0: success, nmerged = 0 (and every
+ * label -1); ws_bytes below pch_cluster_merge_ws_bytes(nclusters): PCH_ERR_WORKSPACE.  Nothing in it waits on
+ * another workgroup.  Enqueues and returns; no host read. */
+int pch_cluster_centers_f32(const float* xyz, const int32_t* perm, const int64_t* offsets, int32_t nclusters,
+                            float* out_centers, int64_t* out_sizes, void* stream);
+size_t pch_cluster_merge_ws_bytes(int32_t nclusters);
+int pch_cluster_merge_f32(const float* centers, int32_t nclusters, double merge_threshold, int32_t* labels, int64_t n,
+                          int32_t* out_map, int32_t* out_nmerged, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ stage D1, fast mode
  * The reference boxes every cluster with trimesh (utils/tower_extraction.py:137-139:
  * trimesh.PointCloud(cluster_points).bounding_box_oriented): qhull's 3-D hull of the whole cluster, then a

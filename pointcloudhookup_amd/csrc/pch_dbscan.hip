@@ -15,6 +15,7 @@
 // index; a border point takes the smallest id among its core neighbours.
 #include <assert.h>
 #include "pch_prims.h"
+#include "pch_unionfind.h"
 
 namespace pch {
 
@@ -1613,36 +1614,7 @@ __device__ __forceinline__ bool db_cells_connected(const DbGrid& g, const float4
     return false;
 }
 
-// ---- union-find over cells (hook larger root under smaller; lock free) ------------------
-// Invariant: parent[x] <= x, only roots (parent[x] == x) are ever hooked, and only by a CAS, so
-// every value ever stored in parent[x] is an ancestor of x.  Loads bypass the (incoherent) L1;
-// path compression is a PLAIN store of an ancestor - racing writers all write ancestors, and a
-// stale read merely costs an extra hop or a failed CAS, whose return value is the truth.
-__device__ __forceinline__ int uf_load(int* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int uf_find(int* __restrict__ parent, int x) {
-    int p = uf_load(&parent[x]);
-    while (p != x) {
-        const int gp = uf_load(&parent[p]);
-        if (gp != p) __hip_atomic_store(&parent[x], gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-// a, b: any members (ideally already roots) of the two sets
-__device__ __forceinline__ void uf_union(int* __restrict__ parent, int a, int b) {
-    for (;;) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }   // a > b: hook a under b
-        const int old = atomicCAS(&parent[a], a, b);
-        if (old == a) return;
-        a = old;                                          // somebody hooked a first: follow it
-    }
-}
+// ---- union-find over cells: uf_load / uf_find / uf_union of pch_unionfind.h (hook larger root under smaller; lock free)
 
 // face neighbour dir (0: +x, 1: +y, 2: +z) of the cell `key`: the key it has if it exists and, for +y / +z, the row
 // that holds it ((dy,dz) = (1,0) / (0,1): rows 1 and 3 of DB_ROW_DY/DZ); +x is the next cell in sorted order

@@ -13,6 +13,7 @@ One function per reference library call:
   ground_filter_plane_tiles <- the same per xy tile (opt-in) test/main_ground.py:77-115
   dbscan            <- chunked sklearn DBSCAN + label offset utils/tower_extraction.py:96-117
   segment_by_label  <- per-label boolean masks               utils/tower_extraction.py:125,131-134
+  merge_clusters    <- merge of neighbouring clusters (opt-in) test/tttt.py:93-175
   crop_boxes        <- per-tower box masks over the cloud    test/kuangxuan.py:60-79, ui/extract.py:345-420
 """
 from __future__ import annotations
@@ -1038,6 +1039,56 @@ def segment_by_label(labels, xyz, nclusters):
         _lib.check(L.pch_segment_by_label(_ptr(labels), _ptr(xyz), n, K, _ptr(perm), _ptr(offsets),
                                           _ptr(stats), _ptr(ws), ws.numel(), _stream()))
     return perm, offsets, stats[:K]
+
+
+# ------------------------------------------------------------- between C and D0, opt-in: merge of cluster pieces
+def cluster_centers(xyz, perm, offsets, nclusters):
+    """(centers float32 [K,3], sizes int64 [K]), both on the device: per cluster of the grouped rows (perm / offsets of
+    ``segment_by_label``) numpy's ``np.mean(P[labels == k], axis=0)`` bit for bit - a sequential float32 sum in row
+    order, one float32 division (pch_cluster_centers_f32).  A cluster without rows has centre NaN.  One wave per
+    cluster: the time is linear in the largest cluster.  Asynchronous."""
+    L = _lib.lib()
+    xyz = _need_cuda(xyz, torch.float32, "xyz").reshape(-1, 3)
+    perm = _need_cuda(perm, torch.int32, "perm")
+    offsets = _need_cuda(offsets, torch.int64, "offsets")
+    K = int(nclusters)
+    if K < 0 or offsets.numel() != K + 1:
+        raise ValueError("offsets must hold nclusters + 1 entries")
+    dev = offsets.device
+    with torch.cuda.device(dev):
+        centers = torch.empty((K, 3), dtype=torch.float32, device=dev)
+        sizes = torch.empty((K,), dtype=torch.int64, device=dev)
+        _lib.check(L.pch_cluster_centers_f32(_ptr(xyz), _ptr(perm), _ptr(offsets), K, _ptr(centers), _ptr(sizes),
+                                             _stream()))
+    return centers, sizes
+
+
+def merge_clusters(xyz, labels, perm, offsets, nclusters, merge_threshold=6.0):
+    """Merges the clusters whose centres lie within ``merge_threshold`` of each other, directly or through a chain of
+    others - the pieces a chunk boundary of ``dbscan`` cut a tower into (the reference's own remedy, test/tttt.py:93-175;
+    the rule is in include/pch_hip.h).  labels / perm / offsets: a fit and its ``segment_by_label`` grouping.
+
+    Returns dict: labels (a new int32 tensor, the input is left untouched), nclusters (after the merge), perm / offsets /
+    stats (``segment_by_label`` of the new labels), map int32 [K] (old id -> new id), centers float32 [K,3] (of the OLD
+    clusters), nclusters_before.  One host read (the new cluster count)."""
+    L = _lib.lib()
+    xyz = _need_cuda(xyz, torch.float32, "xyz").reshape(-1, 3)
+    labels = _need_cuda(labels, torch.int32, "labels")
+    K = int(nclusters)
+    centers, _ = cluster_centers(xyz, perm, offsets, K)
+    dev = labels.device
+    n = labels.shape[0]
+    with torch.cuda.device(dev):
+        merged = labels.clone()
+        cmap = torch.empty((K,), dtype=torch.int32, device=dev)
+        cnt = torch.empty((1,), dtype=torch.int32, device=dev)
+        ws = _workspace(L.pch_cluster_merge_ws_bytes(K), dev)
+        _lib.check(L.pch_cluster_merge_f32(_ptr(centers), K, float(merge_threshold), _ptr(merged), n, _ptr(cmap),
+                                           _ptr(cnt), _ptr(ws), ws.numel(), _stream()))
+        k2 = int(cnt.item())
+    perm2, offsets2, stats2 = segment_by_label(merged, xyz, k2)
+    return dict(labels=merged, nclusters=k2, perm=perm2, offsets=offsets2, stats=stats2, map=cmap, centers=centers,
+                nclusters_before=K)
 
 
 # ---------------------------------------------------------------------------- stage D1, fast mode

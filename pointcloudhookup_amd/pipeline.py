@@ -18,7 +18,7 @@ REF_CHUNK = 50000          # utils/tower_extraction.py:96
 
 def cluster_points(raw, eps=8.0, min_points=80, chunk_size=REF_CHUNK, pct=25.0, offset=3.0,
                    fallback_offset=1.0, min_keep=1000, want_index=False, segment=True, ground="percentile",
-                   plane=None):
+                   plane=None, merge_threshold=None):
     """Stages B + C + D0 on a float32 [N,3] device tensor.
 
     Returns dict: ground (ops.ground_filter result), labels int32 [N_f] (device), nclusters,
@@ -30,7 +30,31 @@ def cluster_points(raw, eps=8.0, min_points=80, chunk_size=REF_CHUNK, pct=25.0, 
     - whose offset / fallback_offset / min_keep / want_index default to this call's) or "plane_tiles" (opt-in, for
     rolling terrain: the same plane per xy tile, ops.ground_filter_plane_tiles; ``plane`` then carries its keyword
     arguments - tile_size, hypotheses, seed, min_tile_rows, fallback_hypotheses, ...).
+
+    ``merge_threshold`` (opt-in, metres; None = off, the reference's behaviour): after the grouping, clusters whose
+    centres lie within it of each other become one (ops.merge_clusters - the pieces a chunk boundary cut a tower into;
+    the reference's test/tttt.py uses 6.0).  labels / nclusters / perm / offsets / stats are then the merged ones and
+    ``merge`` holds map, centers and nclusters_before; with ``segment=False`` the grouping is made internally and only
+    the labels are returned.
     """
+    out = _cluster_points(raw, eps, min_points, chunk_size, pct, offset, fallback_offset, min_keep, want_index,
+                          segment or merge_threshold is not None, ground, plane)
+    if merge_threshold is None:
+        return out
+    m = ops.merge_clusters(out["ground"]["points"], out["labels"], out["perm"], out["offsets"], out["nclusters"],
+                           merge_threshold)
+    out.update(labels=m["labels"], nclusters=m["nclusters"],
+               merge=dict(map=m["map"], centers=m["centers"], nclusters_before=m["nclusters_before"]))
+    if segment:
+        out.update(perm=m["perm"], offsets=m["offsets"], stats=m["stats"])
+    else:
+        for key in ("perm", "offsets", "stats"):
+            del out[key]
+    return out
+
+
+def _cluster_points(raw, eps, min_points, chunk_size, pct, offset, fallback_offset, min_keep, want_index, segment,
+                    ground, plane):
     if ground in ("plane", "plane_tiles"):
         kw = dict(offset=offset, fallback_offset=fallback_offset, min_keep=min_keep, want_index=want_index)
         kw.update(plane or {})

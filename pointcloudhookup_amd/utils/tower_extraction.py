@@ -28,6 +28,12 @@ towers downhill.  It logs one extra line with the plane.  "plane_tiles" fits tha
 ``GROUND_TILE`` metres (env PCH_GROUND_TILE, default 20.0; ops.ground_filter_plane_tiles, the reference's
 remove_ground_tiled_ransac, test/main_ground.py:77-115) - for rolling terrain, which no single plane fits.  It logs one
 extra line with the tile size, the tiles with a plane of their own out of the occupied ones, and the fallback plane.
+``MERGE_THRESHOLD`` (metres, env PCH_MERGE_THRESHOLD; unset or 0 = off, the reference's behaviour): the clustering runs
+once per 50 000-row chunk, so a tower whose rows straddle a chunk boundary comes out in pieces and the centre de-dup
+keeps the first piece only.  When set, clusters whose centres lie within it of each other are merged between the
+per-chunk replay and the detection (ops.merge_clusters, the remedy of the reference's own test/tttt.py:93-175, which
+uses 6.0); it logs that script's two lines ("=== 合并相邻簇 ===", "✅ 合并后簇数量: C") and the candidate count and
+the towers are those of the merged clusters.  No progress milestone is added.
 """
 from __future__ import annotations
 
@@ -44,6 +50,17 @@ CHUNK_FAILURE = os.environ.get("PCH_CHUNK_FAILURE", "reference")
 OBB_MODE = os.environ.get("PCH_OBB_MODE", "exact")
 GROUND_MODE = os.environ.get("PCH_GROUND_MODE", "percentile")
 GROUND_TILE = float(os.environ.get("PCH_GROUND_TILE", "20.0"))
+
+
+def merge_threshold_from_env(value):
+    """MERGE_THRESHOLD of an environment value: None (off) when unset, empty or 0, else the distance in metres"""
+    if value is None or not value.strip():
+        return None
+    r = float(value)
+    return r if r != 0.0 else None
+
+
+MERGE_THRESHOLD = merge_threshold_from_env(os.environ.get("PCH_MERGE_THRESHOLD"))
 PRESTART_BYTES = 100 << 20                             # LAS files from here on get worker processes early
 CHUNK_SIZE = 50000                                     # utils/tower_extraction.py:96
 
@@ -187,6 +204,16 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
                 raise UnboundLocalError(_UNBOUND_MSG)
             continue
         progress(20 + int(50 * (i + 1) / n_chunks))
+
+    # ---- opt-in: merge of the pieces the chunk boundaries cut (test/tttt.py:93-175)
+    if MERGE_THRESHOLD:
+        log("\n=== 合并相邻簇 ===")
+        if "labels" in clusters:
+            merged = ops.merge_clusters(filtered, clusters["labels"], clusters["perm"], clusters["offsets"],
+                                        clusters["nclusters"], MERGE_THRESHOLD)
+            clusters.update({key: merged[key] for key in ("labels", "nclusters", "perm", "offsets", "stats")})
+            clock.mark("merge of neighbouring clusters")
+        log(f"✅ 合并后簇数量: {int(clusters['nclusters'])}")
 
     # ---- tower detection + de-dup (reference :125-218)
     k = int(clusters["nclusters"])
