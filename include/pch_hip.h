@@ -518,7 +518,55 @@ int pch_obb_min_boxes_f64(const double* verts, const int64_t* vert_offsets, cons
                           const int64_t* tri_offsets, int32_t nhulls, int32_t sorted_extents,
                           int32_t nthreads, double* out_to_origin, double* out_extents, int32_t* out_status);
 
-/* HOST function: the search alone, for the exact mode.  The caller (pointcloudhookup_amd/obb.py) lets qhull
+/* ------------------------------------------------------------------ stage D1, upright mode (opt-in)
+ * A transmission tower stands upright: the box its height, width and north angle presume has z as one axis and the
+ * smallest rectangle around the footprint as the other two.  That box is minima and maxima only, so it is order-free
+ * and can be stated in numpy and checked bit for bit (tests/upright_cases.py); it needs no hull and no host copy of the
+ * clustered points.
+ *
+ * The rule.  Constants: PCH_UPRIGHT_COARSE = 128, PCH_UPRIGHT_FINE = 32, T = 4096 = 128 * 32.
+ * Angle table: cs[j] = (cos th_j, sin th_j) with th_j = j * (pi/2) / T as float64, computed with numpy on the host and
+ * passed in as a device array [T,2]; the kernels never evaluate a sine or a cosine, so device libm cannot enter the
+ * result.
+ * Input: P, the kept, centred float32 rows; cluster k owns perm[offsets[k]:offsets[k+1]] as written by
+ * pch_segment_by_label.  For every cluster:
+ *   1 status = 1 (no box) if the cluster has no rows or any coordinate of any of its rows is not finite; then
+ *     j = j0 = -1 and the six bounds are NaN.  Otherwise status = 0.
+ *   2 rectangle at table index j: x, y as float64 of the float32 coordinates, (c, s) = cs[j]; u = x*c + y*s and
+ *     v = y*c - x*s (two products and one add or subtract each, no FMA); umin, umax, vmin, vmax are the minima and
+ *     maxima over the cluster's rows; area(j) = (umax - umin) * (vmax - vmin) in float64, from the bounds of the WHOLE
+ *     cluster.
+ *   3 level 0: j0 is the index among {a * 32 : a = 0..127} with the smallest area; ties go to the smallest index.
+ *   4 level 1: the candidates are {(j0 + d) mod T : d = -31..31} (63 of them, d = 0 among them; wrapping past 0 or T is
+ *     the same rectangle with u and v exchanged); j is the candidate with the smallest area, ties go to the smallest
+ *     table index.
+ *   5 zmin, zmax are the extremes of the float32 z values, stored as float64.
+ *   6 the record PchUprightBox (72 bytes), the four rectangle bounds taken at j.
+ * Bounds are compared by value (-0.0 equals +0.0).
+ * Quality: a set inside a du x dv rectangle has, at an angle delta away, widths at most du cos d + dv sin d and
+ * dv cos d + du sin d; some coarse angle lies within h = pi/512 of the optimum and level 1 can only improve on level 0,
+ * so the found area is at most A_opt * (1 + h (r + 1/r) + h^2) for a footprint of aspect r.
+ *
+ * pch_upright_boxes_f32: xyz [*,3] float32; perm [n_rows_cap] int32; offsets [nclusters+1] int64 (device); n_rows_cap
+ * is the number of perm entries, an upper bound of offsets[nclusters], used only to size grids and the workspace
+ * (offsets beyond it are clamped to it); cs_table_dev [4096,2] float64 (device); out_boxes [nclusters].  Enqueues and
+ * returns: no host read, no float atomics, nothing that waits on another workgroup.  A cluster is spread over up to
+ * min(1024, 16384 / nclusters) workgroups, so with very many clusters the time is linear in the largest one.
+ * nclusters == 0: success, no work; negative counts or NULL pointers: PCH_ERR_ARG; ws_bytes below
+ * pch_upright_boxes_ws_bytes(nclusters, n_rows_cap): PCH_ERR_WORKSPACE; a host pointer as the table: PCH_ERR_ARG. */
+#define PCH_UPRIGHT_COARSE 128
+#define PCH_UPRIGHT_FINE   32
+typedef struct PchUprightBox {
+    int32_t status, j, j0, reserved;
+    int64_t n;
+    double  umin, umax, vmin, vmax, zmin, zmax;
+} PchUprightBox;
+size_t pch_upright_boxes_ws_bytes(int32_t nclusters, int64_t n_rows_cap);
+int pch_upright_boxes_f32(const float* xyz, const int32_t* perm, const int64_t* offsets, int32_t nclusters,
+                          int64_t n_rows_cap, const double* cs_table_dev, PchUprightBox* out_boxes, void* ws,
+                          size_t ws_bytes, void* stream);
+
+/* HOST function: the search alone, for the exact mode. The caller (pointcloudhookup_amd/obb.py) lets qhull
  * build the hull of the FULL cluster and derives the candidate directions exactly as trimesh does; this call
  * evaluates the box volume of every candidate and names the winner, which the caller then evaluates once
  * more with the reference's own arithmetic - so the result is the python loop's, at 1/50 of its cost.

@@ -91,6 +91,8 @@ _SIGS = {
     "pch_selftest_lookback_timeout": (C.c_int, [C.c_int, _vp, _sz, _vp]),
     "pch_obb_shell_ws_bytes": (_sz, [_i32]),
     "pch_obb_shell_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _sz, _vp]),
+    "pch_upright_boxes_ws_bytes": (_sz, [_i32, _i64]),
+    "pch_upright_boxes_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _sz, _vp]),
     "pch_obb_search_f64": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "pch_obb_min_boxes_f64": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "pch_tower_clusters_ws_bytes": (_sz, [_i64, _i64, _i32]),
@@ -128,6 +130,13 @@ class PlaneBestC(C.Structure):
     """PchPlaneBest (include/pch_hip.h)."""
     _fields_ = [("a", C.c_double), ("b", C.c_double), ("c", C.c_double), ("count", C.c_int64),
                 ("best", C.c_int32), ("nvalid", C.c_int32)]
+
+
+class UprightBoxC(C.Structure):
+    """PchUprightBox (include/pch_hip.h)."""
+    _fields_ = [("status", C.c_int32), ("j", C.c_int32), ("j0", C.c_int32), ("reserved", C.c_int32),
+                ("n", C.c_int64), ("umin", C.c_double), ("umax", C.c_double), ("vmin", C.c_double),
+                ("vmax", C.c_double), ("zmin", C.c_double), ("zmax", C.c_double)]
 
 
 class PlaneGridC(C.Structure):

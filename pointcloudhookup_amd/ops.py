@@ -14,6 +14,7 @@ One function per reference library call:
   dbscan            <- chunked sklearn DBSCAN + label offset utils/tower_extraction.py:96-117
   segment_by_label  <- per-label boolean masks               utils/tower_extraction.py:125,131-134
   merge_clusters    <- merge of neighbouring clusters (opt-in) test/tttt.py:93-175
+  upright_boxes     <- upright box per cluster (opt-in)      test/008.py:302-331 (axis-aligned there)
   crop_boxes        <- per-tower box masks over the cloud    test/kuangxuan.py:60-79, ui/extract.py:345-420
 """
 from __future__ import annotations
@@ -1111,6 +1112,60 @@ def obb_shell(xyz, perm, offsets, nclusters):
             _lib.check(L.pch_obb_shell_f32(_ptr(xyz), _ptr(perm), _ptr(offsets), K, ng, _ptr(keep), _ptr(ws),
                                            ws.numel(), _stream()))
     return keep
+
+
+# ---------------------------------------------------------------------------- stage D1, upright mode (opt-in)
+UPRIGHT_T = 4096
+UPRIGHT_RECORD = [("status", "<i4"), ("j", "<i4"), ("j0", "<i4"), ("reserved", "<i4"), ("n", "<i8"),
+                  ("umin", "<f8"), ("umax", "<f8"), ("vmin", "<f8"), ("vmax", "<f8"), ("zmin", "<f8"), ("zmax", "<f8")]
+_upright_tables = {}
+_upright_lock = threading.Lock()
+
+
+def upright_angle_table_host():
+    """float64 [4096,2]: (cos, sin) of j * (pi/2) / 4096, by numpy - the table of the rule in include/pch_hip.h"""
+    import numpy as np
+    theta = np.arange(UPRIGHT_T, dtype=np.float64) * (np.pi / 2) / UPRIGHT_T
+    return np.stack([np.cos(theta), np.sin(theta)], axis=1)
+
+
+def upright_angle_table(device):
+    """The angle table of the upright boxes as a float64 [4096,2] tensor on ``device``: built with numpy once per
+    device and kept (the kernels evaluate no sine or cosine of their own)."""
+    device = torch.device(device)
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    with _upright_lock:
+        table = _upright_tables.get(key)
+        if table is None:
+            table = _upright_tables[key] = torch.from_numpy(upright_angle_table_host()).to(torch.device("cuda", key))
+    return table
+
+
+def upright_boxes(xyz, perm, offsets, nclusters, to_host=False):
+    """Per cluster of the grouped rows (perm / offsets of ``segment_by_label``) the upright box of the rule in
+    include/pch_hip.h: z as one axis, the smallest footprint rectangle among 4096 table angles as the other two
+    (pch_upright_boxes_f32).  Returns the PchUprightBox records as a uint8 [K,72] device tensor (asynchronous), or with
+    ``to_host`` after one copy as a structured numpy array of dtype ``UPRIGHT_RECORD``."""
+    import numpy as np
+    L = _lib.lib()
+    xyz = _need_cuda(xyz, torch.float32, "xyz").reshape(-1, 3)
+    perm = _need_cuda(perm, torch.int32, "perm")
+    offsets = _need_cuda(offsets, torch.int64, "offsets")
+    K = int(nclusters)
+    if K < 0 or offsets.numel() != K + 1:
+        raise ValueError("offsets must hold nclusters + 1 entries")
+    dev = offsets.device
+    with torch.cuda.device(dev):
+        records = torch.empty((K, 72), dtype=torch.uint8, device=dev)
+        if K:
+            table = upright_angle_table(dev)
+            cap = perm.numel()
+            ws = _workspace(L.pch_upright_boxes_ws_bytes(K, cap), dev)
+            _lib.check(L.pch_upright_boxes_f32(_ptr(xyz), _ptr(perm), _ptr(offsets), K, cap, _ptr(table),
+                                               _ptr(records), _ptr(ws), ws.numel(), _stream()))
+    if not to_host:
+        return records
+    return records.cpu().numpy().reshape(-1).view(np.dtype(UPRIGHT_RECORD))
 
 
 def obb_min_boxes(verts, vert_offsets, tris, tri_offsets, sorted_extents=False, nthreads=0):

@@ -169,6 +169,35 @@ def _accept(boxes, centroid, aspect_ratio_threshold, min_height, max_width, min_
     return events
 
 
+def upright_boxes_from_records(records):
+    """The boxes ``_accept`` takes, from the PchUprightBox records of ``ops.upright_boxes(..., to_host=True)`` in label
+    order, in pure numpy float64: ((extents, transform), None) per cluster, or (None, ValueError) for a status-1 record
+    (no row, or a coordinate that is not finite).  extents = [rect_long, rect_short, height] as a float64 array (a zero
+    width then gives inf and a warning in the accept rule, not an exception); the rotation's columns are the long
+    rectangle axis, the short one and (0, 0, 1); transform = [R | centre] (include/pch_hip.h)."""
+    cs = ops.upright_angle_table_host()
+    boxes = []
+    for rec in records:
+        if int(rec["status"]) != 0:
+            boxes.append((None, ValueError("no upright box: the cluster has no rows or a coordinate that is not finite")))
+            continue
+        c, s = cs[int(rec["j"])]
+        umin, umax, vmin, vmax = (np.float64(rec[f]) for f in ("umin", "umax", "vmin", "vmax"))
+        zmin, zmax = np.float64(rec["zmin"]), np.float64(rec["zmax"])
+        du, dv, dz = umax - umin, vmax - vmin, zmax - zmin
+        mu, mv, mz = 0.5 * (umin + umax), 0.5 * (vmin + vmax), 0.5 * (zmin + zmax)
+        transform = np.eye(4)
+        transform[:3, 3] = (mu * c - mv * s, mu * s + mv * c, mz)
+        if dv > du:
+            transform[:3, 0], transform[:3, 1] = (-s, c, 0.0), (-c, -s, 0.0)
+            extents = np.array([dv, du, dz], dtype=np.float64)
+        else:
+            transform[:3, 0], transform[:3, 1] = (c, s, 0.0), (-s, c, 0.0)
+            extents = np.array([du, dv, dz], dtype=np.float64)
+        boxes.append(((extents, transform), None))
+    return boxes
+
+
 class TowerTableJob:
     """Stage D1-D3 of one tile in flight (``tower_table_async``): the clustered points are on their way to (or in)
     a shared host buffer, the boxes are being computed by the worker pool.  ``result()`` waits and returns the tower
@@ -294,12 +323,15 @@ def tower_table(clusters, aspect_ratio_threshold=0.8, min_height=15.0, max_width
     called for every accepted tower in order (the drop-in writes the tower LAS there).
     ``obb_mode``: "exact" (qhull on every full cluster, in the worker pool of obb.py: the clustered points go
     to a shared, registered host buffer in one copy and the workers map it) or "fast" (obb.boxes_fast: device
-    pre-filter + native candidate search; only the accepted towers' points are copied to the host).
+    pre-filter + native candidate search; only the accepted towers' points are copied to the host) or "upright"
+    (opt-in: ops.upright_boxes - z as one axis, the smallest footprint rectangle among 4096 table angles as the other
+    two, the rule of include/pch_hip.h, all on the device; ``extent_order`` does not apply: the extents are always
+    [rect_long, rect_short, height]; only the accepted towers' points are copied to the host, no worker is started).
     ``timings``: optional dict that receives the wall-clock split of the exact mode in ms.
     ``prepare(accepted)``: called once with all accepted towers (points filled in) before the replay starts - the
     drop-in starts writing the per-tower files there."""
-    if obb_mode not in ("exact", "fast"):
-        raise ValueError("obb_mode must be 'exact' or 'fast'")
+    if obb_mode not in ("exact", "fast", "upright"):
+        raise ValueError("obb_mode must be 'exact', 'fast' or 'upright'")
     gf = clusters["ground"]
     k = int(clusters["nclusters"])
     towers = []
@@ -315,7 +347,14 @@ def tower_table(clusters, aspect_ratio_threshold=0.8, min_height=15.0, max_width
     else:
         offsets = clusters["offsets"].cpu().numpy()
         perm, pts = clusters["perm"], gf["points"]
-        boxes = _obb.boxes_fast(pts, perm, clusters["offsets"], k, extent_order)
+        if obb_mode == "fast":
+            boxes = _obb.boxes_fast(pts, perm, clusters["offsets"], k, extent_order)
+        else:
+            if offsets[0] < 0:
+                from . import _lib
+                _lib.check_count(int(offsets[0]), "segment_by_label")
+            # two launches per level on the device, then K records of 72 bytes to the host: no hull, no worker pool
+            boxes = upright_boxes_from_records(ops.upright_boxes(pts, perm, clusters["offsets"], k, to_host=True))
         events = _accept(boxes, centroid, *params)
         accepted = [ev[1] for ev in events if ev[0] == "tower"]
         if accepted:

@@ -17,10 +17,14 @@ in tests/golden/refrun_nonfinite.npz: it logs the failure of that chunk and then
 ``finally: del chunk, clustering, chunk_labels`` (reference :120-122) raises UnboundLocalError out
 of extract_towers, because ``clustering`` was never bound.  "noise" is the behaviour its
 ``except`` clause evidently intended: the chunk stays unlabelled and the run continues.
-``OBB_MODE`` ("exact" | "fast", env PCH_OBB_MODE): "exact" hands every full cluster to qhull on the host
+``OBB_MODE`` ("exact" | "fast" | "upright", env PCH_OBB_MODE): "exact" hands every full cluster to qhull on the host
 (what trimesh does); "fast" filters the clusters on the device down to the points that can be hull vertices
 and searches the box natively (pointcloudhookup_amd/obb.py:boxes_fast) - same procedure, but qhull may merge
 facets differently on the reduced input, so a box can differ in the centimetres; see DESIGN.md section 11.
+"upright" (opt-in, not the reference's box) fits on the device the box a standing tower presumes: z as one axis, the
+smallest rectangle around the footprint as the other two (ops.upright_boxes), so the height is
+the z extent whichever way the tower is turned; ``OBB_EXTENT_ORDER`` does not apply to it, no worker process is
+started, and only the accepted towers' points come to the host.
 ``GROUND_MODE`` ("percentile" | "plane", env PCH_GROUND_MODE): "percentile" is the reference's height filter;
 "plane" removes the ground by one RANSAC plane instead (ops.ground_filter_plane, the remedy of the reference's own
 test/main_ground.py:8-32) - for sloped terrain, where one global percentile keeps the ground uphill and cuts the
@@ -124,7 +128,7 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
             in_bytes = int(resident_entry.records.shape[0]) * _las.RECORD_LEN[resident_entry.header.point_format]
         else:
             in_bytes = os.path.getsize(input_las_path)
-        if in_bytes >= PRESTART_BYTES:
+        if in_bytes >= PRESTART_BYTES and OBB_MODE != "upright":       # (the upright boxes need no worker)
             from .. import obb as _obb
             _obb.prestart()                # the box workers import scipy while the file is being read
         dev = torch.device(DEVICE)
