@@ -292,17 +292,16 @@ struct BrState {
 };
 
 // four consecutive values per thread (SEL_GROUP is a multiple of 4, SEL_EVERY of 16: both sides 16-byte aligned when
-// the column is); stride 3 reads the z of (n,3) rows (base = rows + 2)
-__global__ void sel_sample_k(const float* __restrict__ base, int64_t stride, int64_t ns, float* __restrict__ sample) {
+// the column is)
+__global__ void sel_sample_k(const float* __restrict__ base, int64_t ns, float* __restrict__ sample) {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i >= ns) return;
     const int64_t src = (i / SEL_GROUP) * SEL_EVERY + (i % SEL_GROUP);
     float4 q;
-    if (stride == 1 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0) {
+    if ((reinterpret_cast<uintptr_t>(base) & 15u) == 0) {
         q = *reinterpret_cast<const float4*>(base + src);
     } else {
-        q.x = base[src * stride]; q.y = base[(src + 1) * stride];
-        q.z = base[(src + 2) * stride]; q.w = base[(src + 3) * stride];
+        q.x = base[src]; q.y = base[src + 1]; q.z = base[src + 2]; q.w = base[src + 3];
     }
     *reinterpret_cast<float4*>(sample + i) = q;
 }
@@ -482,10 +481,8 @@ struct SelWs {
     uint32_t* also_zero;   // optional: words sel_init clears for the caller (see sel_init_k)
     int64_t   also_words;
 };
-// from_summary: the bracket comes from the centroid summary's samples (sel_collect_k; the fused filter, from 131 072
-// rows on).  One sample per 1024 rows makes a wider bracket than sixteen in 1024 (bracket_ranks): a tenth of the column
-// at 4 M rows and the 25th percentile, a third at 400 000 - hence the larger buffers.
-static void sel_plan(Arena& a, SelWs& w, int64_t n = 0, bool from_summary = false) {
+// a select over a plain column of n values: with its own sample bracket from SEL_BRACKET_MIN values on
+static void sel_plan(Arena& a, SelWs& w, int64_t n = 0) {
     w.scal = a.take<float>(4);
     w.run = a.take<SelRun>(3);
     w.hist = a.take<uint32_t>(9 * SEL_BINS);
@@ -495,13 +492,20 @@ static void sel_plan(Arena& a, SelWs& w, int64_t n = 0, bool from_summary = fals
         w.br = a.take<BrState>(1);
         w.ns = SEL_GROUP * (n / SEL_EVERY);
         w.sample = a.take<float>(w.ns);
-        w.cap = (uint32_t)(n / (from_summary ? 4 : 16)) + 1024u;
-        w.cand = a.take<float>(w.cap);
-    } else if (from_summary && n > 0) {
-        w.br = a.take<BrState>(1);
-        w.cap = (uint32_t)(n / 2) + 1024u;
+        w.cap = (uint32_t)(n / 16) + 1024u;
         w.cand = a.take<float>(w.cap);
     }
+}
+// The fused filter's select where the centroid summary brackets the percentile (sel_collect_k): no sample, and larger
+// candidate buffers - one sample per 1024 rows makes a wider bracket than sixteen in 1024 (bracket_ranks): a tenth of
+// the column at 4 M rows and the 25th percentile, a third at 400 000.  Hence n/2 below 4 M rows and n/4 above; the
+// 2 M values in between keep the plan monotone in n (a grow-only workspace is sized by it).
+static void sel_plan_from_summary(Arena& a, SelWs& w, int64_t n) {
+    sel_plan(a, w);
+    const int64_t half = n / 2, quarter = n / 4, flat = SEL_BRACKET_MIN / 2;
+    w.br = a.take<BrState>(1);
+    w.cap = (uint32_t)(half < flat ? half : (quarter > flat ? quarter : flat)) + 1024u;
+    w.cand = a.take<float>(w.cap);
 }
 
 // host side of np.percentile's index arithmetic (float32 under NEP 50)
@@ -537,10 +541,6 @@ static int select_rounds(const float* base, int64_t n, int64_t stride, bool with
     return PCH_OK;
 }
 
-// Bracketed select (columns of >= SEL_BRACKET_MIN values with a sample buffer planned): is it?
-static bool select_is_bracketed(const SelWs& w, int64_t n, int64_t stride) {
-    return w.sample && stride == 1 && n >= SEL_BRACKET_MIN;
-}
 struct SelBracket { int64_t r_lo, r_hi; };
 // bracket from a sample of ns values drawn in runs of `group` consecutive ones: ranks around k0 * ns / n, six sigma
 // of the binomial rank error for ns / group independent draws + 0.2 % + 16
@@ -557,11 +557,9 @@ static SelBracket bracket_ranks(int64_t ns, int group, int64_t n, const PctIndex
 static SelBracket select_bracket_ranks(const SelWs& w, int64_t n, const PctIndex& pi) {
     return bracket_ranks(w.ns, SEL_GROUP, n, pi);
 }
-// First half of the bracketed select: the sample and the two order statistics of it that bracket the ranks.  It
-// needs the VALUES only (src / src_stride: the column itself, or the z of the (n,3) rows it will be copied from), so the
-// fused filter runs it beside the centroid summary, before the column exists.
-static int select_sample_passes(const float* src, int64_t src_stride, int64_t n, double q_percent, SelWs& w,
-                                hipStream_t s) {
+// First half of the bracketed select of a plain column (>= SEL_BRACKET_MIN values, sample buffer planned): the sample
+// and the two order statistics of it that bracket the ranks.
+static int select_sample_passes(const float* base, int64_t n, double q_percent, SelWs& w, hipStream_t s) {
     const PctIndex pi = pct_index(n, q_percent);
     const SelGate always = {nullptr, nullptr, nullptr};
     const SelBracket br = select_bracket_ranks(w, n, pi);
@@ -569,8 +567,7 @@ static int select_sample_passes(const float* src, int64_t src_stride, int64_t n,
     PCH_LAUNCH("sel_init", sel_init_k, dim3((unsigned)ceil_div(9 * SEL_BINS, 256)), dim3(256), 0, s, w.hist,
                9 * SEL_BINS, w.run, 3, (unsigned long long)br.r_lo, (unsigned long long)br.r_hi, 0ull, w.br,
                w.also_zero, w.also_words);
-    PCH_LAUNCH("sel_sample", sel_sample_k, dim3((unsigned)ceil_div(ns, 1024)), dim3(256), 0, s, src, src_stride, ns,
-               w.sample);
+    PCH_LAUNCH("sel_sample", sel_sample_k, dim3((unsigned)ceil_div(ns, 1024)), dim3(256), 0, s, base, ns, w.sample);
     int64_t gs = ceil_div(ns, SEL_TILE);                   // both ends of the bracket in the same three sweeps
     if (gs > 2048) gs = 2048;
     if (gs < 1) gs = 1;
@@ -582,20 +579,18 @@ static int select_sample_passes(const float* src, int64_t src_stride, int64_t n,
 }
 
 // the histogram / next passes (need only the raw values) ...
-// sample_done: select_sample_passes already ran for this column (and is ordered in front of `s`)
-static int select_passes(const float* base, int64_t n, int64_t stride, double q_percent, SelWs& w,
-                         hipStream_t s, bool sample_done = false) {
+static int select_passes(const float* base, int64_t n, int64_t stride, double q_percent, SelWs& w, hipStream_t s) {
     const PctIndex pi = pct_index(n, q_percent);
     const SelGate always = {nullptr, nullptr, nullptr};
     SelRun* fin = w.run + 2;
     uint32_t* hfin = w.hist + 6 * SEL_BINS;
-    if (!select_is_bracketed(w, n, stride)) {
+    if (!w.sample || stride != 1) {                          // (a sample is planned from SEL_BRACKET_MIN values on)
         PCH_LAUNCH("sel_init", sel_init_k, dim3((unsigned)ceil_div(9 * SEL_BINS, 256)), dim3(256), 0, s, w.hist,
                    9 * SEL_BINS, w.run, 3, 0ull, 0ull, (unsigned long long)pi.k0, (BrState*)nullptr, w.also_zero,
                    w.also_words);
         return select_rounds(base, n, stride, !pi.same, fin, hfin, s, always, n);
     }
-    if (!sample_done) PCH_TRY(select_sample_passes(base, 1, n, q_percent, w, s));
+    PCH_TRY(select_sample_passes(base, n, q_percent, w, s));
     const SelBracket br = select_bracket_ranks(w, n, pi);
     const int64_t ns = w.ns;
     // one resident round of workgroups: 32 KB of LDS each, five per CU (a 2048-workgroup grid ran as 1280 + 768:
@@ -622,16 +617,16 @@ static int select_passes(const float* base, int64_t n, int64_t stride, double q_
     const SelGate src = {&w.br->ok, w.cand, &w.br->count};
     return select_rounds(base, n, stride, !pi.same, fin, hfin, s, src, n);
 }
-// The same second half when the centroid summary bracketed the column (MsBracket, pch_mean.h; the caller has run
+// The second half when the centroid summary bracketed the z of the rows (MsBracket, pch_mean.h; the caller has run
 // sel_init_k): gather what it left, check it, and select - from the candidates, or if the check fails from the z of the
 // (n,3) rows themselves (three passes over 12 B per row: exact and rare).
-static int select_from_summary(const float* raw, int64_t n, double q_percent, const MsCand& mc, const float* zseg,
-                               SelWs& w, hipStream_t s) {
+static int select_from_summary(const float* raw, int64_t n, double q_percent, const MsCand& mc, SelWs& w,
+                               hipStream_t s) {
     const PctIndex pi = pct_index(n, q_percent);
     SelRun* fin = w.run + 2;
     const int64_t nblk = ceil_div(n, 1024);
     PCH_LAUNCH("sel_collect", sel_collect_k, dim3((unsigned)ceil_div(nblk, SEL_CBLKS)), dim3(SEL_CBLKS), 0, s,
-               (const MsBracket*)mc.bracket, (const MsBrRec*)mc.brec, nblk, zseg, w.br, w.cand, w.cap);
+               (const MsBracket*)mc.bracket, (const MsBrRec*)mc.brec, nblk, (const float*)mc.zseg, w.br, w.cand, w.cap);
     PCH_LAUNCH("sel_bracket_fix", sel_bracket_fix_k, dim3(1), dim3(64), 0, s, w.br, fin, (unsigned long long)pi.k0,
                pi.same);
     const SelGate src = {&w.br->ok, w.cand, &w.br->count};
@@ -651,8 +646,8 @@ static int select_percentile(const float* base, int64_t n, int64_t stride, const
     return select_lerp(n, sub, q_percent, 0.0f, 0.0f, w, s);
 }
 
-// per-thread side stream + events: the select passes only need the raw z values, so they run
-// beside the centroid passes (the sample half beside the summary, the sweep beside the 3-wave walk)
+// per-thread side stream + events: the fused filter's select only needs the raw z values (and what the summary left),
+// so it runs beside the centroid's level 2 and 3-wave walk
 struct SideStream { hipStream_t s; hipEvent_t ev_fork, ev_join, ev_start; bool ok; };
 struct SideStreams {                                    // one per device this thread has used; gone with the thread
     SideStream ss[PCH_MAX_DEVICES];
@@ -681,7 +676,7 @@ static SideStream& side_stream() {
 }
 
 // =====================================================================================
-// B2/B3: keep = (z - cz) > thr, order preserving, in ONE sweep over the z column: every
+// B2/B3: keep = (z - cz) > thr, order preserving, in ONE sweep over the z of the rows: every
 // workgroup counts its tile, publishes the count and obtains its output offset by a decoupled
 // look-back over the tiles in front of it (status word = 2-bit flag + 32-bit value, one 64-bit
 // relaxed atomic), then writes the centred survivors and folds their bounding box into one of
@@ -723,7 +718,7 @@ __device__ __forceinline__ bool gf_cand_ok(const float* __restrict__ tcand, cons
     return t <= nextafter(ta, -INFINITY) && t <= nextafter(tb, -INFINITY);
 }
 
-// ---- what the two sweeps share (gf_compact_k over the z column, gf_cand_k over the candidate slots): the tile order,
+// ---- what the two sweeps share (gf_compact_k over the rows, gf_cand_k over the candidate slots): the tile order,
 // the tile's output offset and what becomes of a survivor (its store and the fold of the tile's bounding box are those
 // of pch_compact.h).  The logical tile is a ticket drawn on arrival, for the reason given at oc_take_tile.
 // false: this sweep does not run (the fallback sweep without use_b).  The caller's next barrier publishes *tile_sh.
@@ -755,8 +750,7 @@ __device__ __forceinline__ void gf_tile_prefix(GfState* __restrict__ st, uint64_
 
 template <int WHICH>
 __global__ __launch_bounds__(GF_THREADS) void gf_compact_k(
-    const float* __restrict__ raw, const float* __restrict__ zcol, int64_t n,
-    const float* __restrict__ centroid, const float* __restrict__ scal, GfState* __restrict__ st,
+    const float* __restrict__ raw, int64_t n, const float* __restrict__ centroid, const float* __restrict__ scal, GfState* __restrict__ st,
     uint64_t* __restrict__ status, long long min_keep, float* __restrict__ out_points,
     int32_t* __restrict__ out_index, const float* __restrict__ tcand) {
     if (gf_cand_ok(tcand, centroid, scal)) return;         // gf_cand_k does this sweep from the candidate slots
@@ -773,12 +767,12 @@ __global__ __launch_bounds__(GF_THREADS) void gf_compact_k(
     const float cz = cen[2], thr = scal[1 + WHICH];
     const int w = wave_id(), l = lane_id();
     const int64_t seg = tile * GF_TILE + (int64_t)w * (64 * GF_ROUNDS);
-    // ---- sweep over the z column: survivor masks and the tile's count
+    // ---- sweep over the z of the rows: survivor masks and the tile's count
     uint32_t run = 0;
 #pragma unroll 8
     for (int r = 0; r < GF_ROUNDS; ++r) {
         const int64_t i = seg + r * 64 + l;
-        const float z = i < n ? (zcol ? zcol[i] : raw[3 * i + 2]) : 0.0f;     // no column given: the z of the rows
+        const float z = i < n ? raw[3 * i + 2] : 0.0f;
         const bool keep = i < n && (z - cz) > thr;       // points = raw_points - centroid (float32)
         const unsigned long long m = __ballot(keep);
         if (l == 0) masks[w][r] = m;
@@ -992,27 +986,24 @@ __global__ void gf_finalize_k(const GfState* __restrict__ st, const float* __res
 
 struct GfWs {
     float*    centroid;
-    float*    zcol;              // copy of the z column (written by the centroid pass), or the blocks' segments (MsBracket)
     MsWs      ms;
     SelWs     sel;
     GfState*  st;
     uint64_t* status;            // [2][tiles] look-back words of the two sweeps
     size_t    clear_bytes;       // st .. end of status: zeroed before the sweeps
-    MsCand    cand;              // candidate rows emitted by the summary pass (see gf_cand_k)
+    MsCand    cand;              // candidate rows and the percentile's bracket, emitted by the summary pass
 };
-// The percentile's bracket from the summary (MsBracket) instead of a z column: on wherever the summary emits candidate
-// slots.  PCH_GF_NO_BRACKET turns it off (the z column, sel_sample_k and sel_bracket_k as before);
-// PCH_GF_BRACKET_INVALID keeps it on and fails its device check, so that the select reads the rows.
-static bool gf_brackets(int64_t n) {
-    static const bool off = getenv("PCH_GF_NO_BRACKET") != nullptr;                // tuning toggle
-    return !off && ms_makes_cand(n);
-}
+// The percentile's bracket comes from the summary (MsBracket) wherever it emits candidate slots (ms_makes_cand); a
+// cloud without them has the select read the z of the rows.  PCH_GF_BRACKET_INVALID fails the bracket's device check,
+// so that the select of a large cloud reads the rows too.
 static void gf_plan(Arena& a, int64_t n, GfWs& w) {
     const int64_t nb = ceil_div(n > 0 ? n : 1, GF_TILE);
+    const bool bracket = ms_makes_cand(n);
     w.centroid = a.take<float>(4);
     ms_plan(a, n, w.ms);
-    w.zcol = a.take<float>(n > 0 ? n : 1);                 // with the bracket: the blocks' segments (MsBracket)
-    sel_plan(a, w.sel, n, gf_brackets(n));
+    w.cand.zseg = bracket ? a.take<float>(n) : nullptr;    // one 1024-float segment per block of the summary
+    if (bracket) sel_plan_from_summary(a, w.sel, n);
+    else sel_plan(a, w.sel);
     const size_t st_off = a.off;
     w.st = a.take<GfState>(1);
     w.status = a.take<uint64_t>(2 * nb);
@@ -1024,8 +1015,8 @@ static void gf_plan(Arena& a, int64_t n, GfWs& w) {
     w.cand.slots = a.take<float>(nblk * 4 * MS_CAND_SLOT); // 8 KB per 1024-row block: four planes (MsCand)
     w.cand.pct = 0.0;
     w.cand.add = 0.0f;
-    w.cand.bracket = a.take<MsBracket>(1);
-    w.cand.brec = a.take<MsBrRec>(nblk);
+    w.cand.bracket = bracket ? a.take<MsBracket>(1) : nullptr;
+    w.cand.brec = bracket ? a.take<MsBrRec>(nblk) : nullptr;
     w.cand.r_lo = w.cand.r_hi = 0;
     w.cand.force_invalid = 0;
 }
@@ -1165,8 +1156,7 @@ extern "C" int pch_filter_gt_f32(const float* raw, int64_t n, const float* centr
     const float* scal = f + 4;
     // the sweep reads z straight from the rows (a pass that first copied the z column out - 16 B per point of traffic
     // for a 12 B per point sweep - is gone)
-    PCH_LAUNCH("gf_compact", gf_compact_k<0>, dim3((unsigned)nb), dim3(GF_THREADS), 0, s, raw, (const float*)nullptr, n,
-               centroid, scal, st, status, (long long)0, out_points, out_index, (const float*)nullptr);
+    PCH_LAUNCH("gf_compact", gf_compact_k<0>, dim3((unsigned)nb), dim3(GF_THREADS), 0, s, raw, n, centroid, scal, st, status, (long long)0, out_points, out_index, (const float*)nullptr);
     PCH_LAUNCH("gf_finalize", gf_finalize_k, dim3(1), dim3(64), 0, s, (const GfState*)st, centroid, scal,
                f + 8, out_count, out_aabb);
     PCH_HIP_TRY(hipStreamSynchronize(s));               // `hs` lives on this stack frame
@@ -1212,40 +1202,38 @@ int pch::ground_filter_run(const float* raw, int64_t n, double pct, float offset
     w.sel.also_words = (int64_t)(w.clear_bytes / 4);
     SideStream& ss = side_stream();
     // Two strands.  `s`: summary, level 2, walk - no cross-stream hop inside the chain.  Side stream: at once the
-    // sample half of the percentile (it reads the z of the raw rows, so it does not wait for the z column and
-    // runs beside the summary), then - behind the summary - the percentile's sweep and exact select; joined in
-    // front of the interpolation.  With the sample half out of the way both strands end within a few us of each
-    // other (measured: the other assignment, select on `s` and walk on the side stream, loses 45 us to the hops).
-    // Without a side stream the select follows the walk on `s` and takes its own sample.
-    // (That is the route with a z column: clouds below 131 072 rows, or PCH_GF_NO_BRACKET.)
-    // From 131 072 rows on the summary brackets the percentile itself (MsBracket, pch_mean.h): no sample strand, no z
-    // column; behind the summary the side stream gathers the blocks' values (sel_collect_k) instead of sweeping a column.
-    const bool bracket = gf_brackets(n);
-    if (bracket) {
-        static const bool invalid = getenv("PCH_GF_BRACKET_INVALID") != nullptr;   // tuning toggle
-        const int64_t nblk = ceil_div(n, GF_CBLK);
-        const SelBracket r = bracket_ranks(ceil_div(nblk, ms_bracket_stride(nblk)), 1, n, pct_index(n, pct));
-        w.cand.r_lo = r.r_lo;
-        w.cand.r_hi = r.r_hi;
-        w.cand.force_invalid = invalid ? 1 : 0;
-    } else {
-        w.cand.bracket = nullptr;
-    }
-    const bool sample_early = !bracket && ss.ok && select_is_bracketed(w.sel, n, 1);
-    if (sample_early || (bracket && ss.ok)) {
+    // select's init kernel, then - behind the summary - the exact select; joined in front of the interpolation
+    // (measured: the other assignment, select on `s` and walk on the side stream, loses 45 us to the hops).  Without a
+    // side stream the select follows the walk on `s`.
+    // Where the summary emits candidate slots it brackets the percentile too (MsBracket, pch_mean.h) and the select
+    // gathers the blocks' values (sel_collect_k); a cloud without them has the three passes read the z of the rows.
+    const bool bracket = ms_makes_cand(n);
+    const PctIndex pi = pct_index(n, pct);
+    static const bool invalid = getenv("PCH_GF_BRACKET_INVALID") != nullptr;       // tuning toggle
+    const int64_t nblk = ceil_div(n, GF_CBLK);
+    const SelBracket r = bracket_ranks(ceil_div(nblk, ms_bracket_stride(nblk)), 1, n, pi);   // (used with the bracket)
+    w.cand.r_lo = r.r_lo;
+    w.cand.r_hi = r.r_hi;
+    w.cand.force_invalid = invalid ? 1 : 0;
+    const hipStream_t sel_s = ss.ok ? ss.s : s;
+    if (ss.ok) {
         PCH_HIP_TRY(hipEventRecord(ss.ev_start, s));            // everything the caller queued before this call
         PCH_HIP_TRY(hipStreamWaitEvent(ss.s, ss.ev_start, 0));   // (the rows; the previous user of the workspace)
     }
-    if (sample_early) PCH_TRY(select_sample_passes(raw + 2, 3, n, pct, w.sel, ss.s));
-    if (bracket)
-        PCH_LAUNCH("sel_init", sel_init_k, dim3((unsigned)ceil_div(9 * SEL_BINS, 256)), dim3(256), 0, ss.ok ? ss.s : s,
-                   w.sel.hist, 9 * SEL_BINS, w.sel.run, 3, 0ull, 0ull, 0ull, w.sel.br, w.sel.also_zero, w.sel.also_words);
-    PCH_TRY(mean_seq_launch(raw, n, w.centroid, w.ms, w.zcol, s, ss.ok ? ss.ev_fork : nullptr, nullptr, MS_DIVIDE_BY_N,
+    // (the rank is that of the rows' select; with the bracket sel_bracket_fix_k sets it again)
+    PCH_LAUNCH("sel_init", sel_init_k, dim3((unsigned)ceil_div(9 * SEL_BINS, 256)), dim3(256), 0, sel_s, w.sel.hist,
+               9 * SEL_BINS, w.sel.run, 3, 0ull, 0ull, (unsigned long long)pi.k0, w.sel.br, w.sel.also_zero,
+               w.sel.also_words);
+    PCH_TRY(mean_seq_launch(raw, n, w.centroid, w.ms, nullptr, s, ss.ok ? ss.ev_fork : nullptr, nullptr, MS_DIVIDE_BY_N,
                             MS_PHASE_BOTH, &w.cand, &cand_made));
     PCH_REQUIRE(!bracket || cand_made, "bracket route without candidate slots");
     if (ss.ok) PCH_HIP_TRY(hipStreamWaitEvent(ss.s, ss.ev_fork, 0));
-    if (bracket) PCH_TRY(select_from_summary(raw, n, pct, w.cand, w.zcol, w.sel, ss.ok ? ss.s : s));
-    else PCH_TRY(select_passes(w.zcol, n, 1, pct, w.sel, ss.ok ? ss.s : s, sample_early));
+    if (bracket) {
+        PCH_TRY(select_from_summary(raw, n, pct, w.cand, w.sel, sel_s));
+    } else {
+        const SelGate always = {nullptr, nullptr, nullptr};
+        PCH_TRY(select_rounds(raw + 2, n, 3, !pi.same, w.sel.run + 2, w.sel.hist + 6 * SEL_BINS, sel_s, always, n));
+    }
     if (ss.ok) {
         PCH_HIP_TRY(hipEventRecord(ss.ev_join, ss.s));
         PCH_HIP_TRY(hipStreamWaitEvent(s, ss.ev_join, 0));
@@ -1253,21 +1241,18 @@ int pch::ground_filter_run(const float* raw, int64_t n, double pct, float offset
     PCH_TRY(select_lerp(n, w.centroid + 2, pct, offset, fallback_offset, w.sel, s));
     const dim3 grid((unsigned)nb), blk(GF_THREADS);
     const float* tcand = cand_made ? (const float*)w.cand.tcand : (const float*)nullptr;
-    const float* zcol = bracket ? (const float*)nullptr : (const float*)w.zcol;   // no column: the sweep reads the rows' z
     // Sweep A (first threshold) from the candidate slots when the device-side guard allows it (gf_cand_ok), else over
     // the tile - one of the two kernels returns at once; same tiles, same tickets, same look-back words.  Then the
     // results are published ONCE ALREADY (gf_finalize; and queued for the host if the caller asked): they are final
     // unless the last tile of sweep A raised use_b.  Sweep B (fallback threshold) and the second gf_finalize follow;
     // without use_b they return at once, and the host is by then preparing the next stage.
-    const int64_t nblk = ceil_div(n, GF_CBLK);
     const dim3 cgrid((unsigned)ceil_div(nblk, GF_CT_BLKS));
     if (cand_made)
         PCH_LAUNCH("gf_cand", gf_cand_k<0>, cgrid, blk, 0, s, (const float*)w.cand.slots, (const uint32_t*)w.cand.counts,
                    tcand, nblk, (const float*)w.centroid, (const float*)w.sel.scal, w.st, w.status, (long long)min_keep,
                    out_points, out_index);
-    PCH_LAUNCH("gf_compact", gf_compact_k<0>, grid, blk, 0, s, raw, zcol, n,
-               (const float*)w.centroid, (const float*)w.sel.scal, w.st, w.status, (long long)min_keep, out_points,
-               out_index, tcand);
+    PCH_LAUNCH("gf_compact", gf_compact_k<0>, grid, blk, 0, s, raw, n, (const float*)w.centroid,
+               (const float*)w.sel.scal, w.st, w.status, (long long)min_keep, out_points, out_index, tcand);
     if (early) {
         PCH_LAUNCH("gf_finalize", gf_finalize_k, dim3(1), dim3(64), 0, s, (const GfState*)w.st,
                    (const float*)w.centroid, (const float*)w.sel.scal, out_scalars, out_count, out_aabb);
@@ -1277,9 +1262,8 @@ int pch::ground_filter_run(const float* raw, int64_t n, double pct, float offset
         PCH_LAUNCH("gf_cand_fb", gf_cand_k<1>, cgrid, blk, 0, s, (const float*)w.cand.slots,
                    (const uint32_t*)w.cand.counts, tcand, nblk, (const float*)w.centroid, (const float*)w.sel.scal, w.st,
                    w.status + nb, (long long)min_keep, out_points, out_index);
-    PCH_LAUNCH("gf_compact_fb", gf_compact_k<1>, grid, blk, 0, s, raw, zcol, n,
-               (const float*)w.centroid, (const float*)w.sel.scal, w.st, w.status + nb, (long long)min_keep, out_points,
-               out_index, tcand);
+    PCH_LAUNCH("gf_compact_fb", gf_compact_k<1>, grid, blk, 0, s, raw, n, (const float*)w.centroid,
+               (const float*)w.sel.scal, w.st, w.status + nb, (long long)min_keep, out_points, out_index, tcand);
     PCH_LAUNCH("gf_finalize", gf_finalize_k, dim3(1), dim3(64), 0, s, (const GfState*)w.st,
                (const float*)w.centroid, (const float*)w.sel.scal, out_scalars, out_count, out_aabb);
     return PCH_OK;

@@ -20,10 +20,10 @@ struct MsPred;
 constexpr int MS_CAND_SLOT = 512;
 // The percentile's bracket, taken from the same samples in front of the summary (ms_prefix_k, ms_zbracket): two exact
 // order statistics of every `stride`-th sampled z as sel_key keys L <= H.  With it the summary keeps, per block, the
-// z values whose key lies in [L, H] packed at the front of the block's own 1024-float segment of the z buffer
-// (zcol[1024 * blk ...]: as large as the block, so it cannot overflow; order inside a block is not kept) and one
-// MsBrRec - instead of the z column.  sel_collect_k (pch_filter.hip) gathers them; whether they hold the wanted
-// order statistics is checked on the device there, so the keys only decide how much is read.
+// z values whose key lies in [L, H] packed at the front of the block's own 1024-float segment of MsCand::zseg
+// (zseg[1024 * blk ...]: as large as the block, so it cannot overflow; order inside a block is not kept) and one
+// MsBrRec.  sel_collect_k (pch_filter.hip) gathers them; whether they hold the wanted order statistics is checked on
+// the device there, so the keys only decide how much is read.
 struct MsBracket {
     uint32_t L, H;               // as used: 0 / 0xFFFFFFFF at an open end
     uint32_t lo_is_min, hi_is_max;
@@ -47,9 +47,10 @@ struct MsCand {
     float*    zsample;           // [nb] one sampled z per block (scratch of the estimate)
     double    pct;               // the percentile the filter will ask for
     float     add;               // tcand = (estimated percentile of z) + add
-    // bracket emission (optional: bracket == nullptr keeps the z column)
+    // bracket emission (optional: bracket == nullptr emits none)
     MsBracket* bracket;
     MsBrRec*   brec;             // [nb], every record rewritten by every call
+    float*     zseg;             // [n] the blocks' segments: what lies behind a block's front is stale and never read
     int64_t    r_lo, r_hi;       // ranks of L and H among the ceil(nb / ms_bracket_stride(nb)) samples used
     int        force_invalid;    // tuning toggle: valid = 0, whatever the sample holds
 };
@@ -63,7 +64,7 @@ struct MsWs {
 void ms_plan(Arena& a, int64_t n, MsWs& w);
 // centroid[3] = np.mean(xyz, axis=0) (float32).  zcol (optional, n floats) receives a copy of
 // the z column, written by the same pass that reads the tile.
-// ev_zcol (optional) is recorded on `s` right after the pass that writes zcol.
+// ev_summary (optional) is recorded on `s` right behind the summary, the pass that writes zcol and the candidates.
 // sum_in (optional, device float[3]): running sum to continue instead of +0.0; divide_n: MS_DIVIDE_BY_N (the
 // mean of these n rows), MS_NO_DIVIDE (out = the running sum after the rows) or the row count to divide by.
 // phase: both kernels groups (default), only the tables (summary + level 2: they do not depend on sum_in), or only
@@ -71,11 +72,12 @@ void ms_plan(Arena& a, int64_t n, MsWs& w);
 constexpr int64_t MS_DIVIDE_BY_N = -1, MS_NO_DIVIDE = -2;
 constexpr int MS_PHASE_BOTH = 0, MS_PHASE_TABLES = 1, MS_PHASE_WALK = 2;
 // cand (optional): emit the candidate rows described above; *cand_made says whether they were (needs the sampled
-// estimate, i.e. an array of at least two 65 536-row groups and prediction enabled): ms_makes_cand(n) tells beforehand.
-// With cand->bracket the z values inside the bracket go to the fronts of zcol's segments and the column is NOT written.
+// estimate, i.e. more than 65 536 rows - a second group of 64 blocks - and prediction enabled): ms_makes_cand(n) tells
+// beforehand.
+// With cand->bracket the z values inside the bracket go to the fronts of cand->zseg's segments.
 bool ms_makes_cand(int64_t n);
 int mean_seq_launch(const float* xyz, int64_t n, float* out, MsWs& w, float* zcol, hipStream_t s,
-                    hipEvent_t ev_zcol = nullptr, const float* sum_in = nullptr, int64_t divide_n = MS_DIVIDE_BY_N,
+                    hipEvent_t ev_summary = nullptr, const float* sum_in = nullptr, int64_t divide_n = MS_DIVIDE_BY_N,
                     int phase = MS_PHASE_BOTH, const MsCand* cand = nullptr, bool* cand_made = nullptr);
 
 }  // namespace pch

@@ -7,9 +7,9 @@
 // i.e. the sum is INTEGER addition of per-element increments d_i = rne(a_i/u) that do not depend
 // on m - unless a_i/u has fraction exactly 1/2 (a "tie", resolved towards the even mantissa).
 //
-//   ms_summary_k : one wave per 1024-point block (read ONCE, staged in LDS; the z column is also
-//                  copied out for the percentile passes - or, given the percentile's bracket, only
-//                  the block's z values inside it: MsBracket, pch_mean.h).  Per column and for the 24 useful
+//   ms_summary_k : one wave per 1024-point block (read ONCE, staged in LDS; on request the z column
+//                  is also copied out (the tiled path) and, given the percentile's bracket, the block's
+//                  z values inside it are kept: MsBracket, pch_mean.h).  Per column and for the 24 useful
 //                  candidate binades E = emax+1 .. emax+24 (E <= emax: an element as large as
 //                  the sum; E > emax+24: every increment is 0) it stores the signed increment
 //                  sum S_E, one bound A0 >= sum |a/ulp(2^(emax+1))| (so that
@@ -1262,7 +1262,7 @@ bool ms_makes_cand(int64_t n) {
 }
 
 int mean_seq_launch(const float* xyz, int64_t n, float* out, MsWs& w, float* zcol, hipStream_t s,
-                    hipEvent_t ev_zcol, const float* sum_in, int64_t divide_n, int phase, const MsCand* cand,
+                    hipEvent_t ev_summary, const float* sum_in, int64_t divide_n, int phase, const MsCand* cand,
                     bool* cand_made) {
     if (cand_made) *cand_made = false;
     const int64_t nb = n > 0 ? ceil_div(n, MSB) : 0;
@@ -1292,17 +1292,16 @@ int mean_seq_launch(const float* xyz, int64_t n, float* out, MsWs& w, float* zco
             if (mk && cand_made) *cand_made = true;
         }
         const bool emit = cand && cand_made && *cand_made;
-        // with the bracket the buffer `zcol` holds the blocks' segments (MsBracket) and the column is not written
         PCH_LAUNCH("mean_summary", ms_summary_k, dim3((unsigned)ceil_div(nb, MS_WAVES)), dim3(64 * MS_WAVES),
-                   0, s, xyz, n, nb, w.rec, bracket ? (float*)nullptr : zcol, pred, nb2,
+                   0, s, xyz, n, nb, w.rec, zcol, pred, nb2,
                    emit ? cand->slots : (float*)nullptr, emit ? cand->counts : (uint32_t*)nullptr,
                    emit ? (const float*)cand->tcand : (const float*)nullptr,
                    bracket ? (const MsBracket*)cand->bracket : (const MsBracket*)nullptr,
-                   bracket ? cand->brec : (MsBrRec*)nullptr, bracket ? zcol : (float*)nullptr);
+                   bracket ? cand->brec : (MsBrRec*)nullptr, bracket ? cand->zseg : (float*)nullptr);
         // (with the bracket too: what waits for the event is then a short gather, sel_collect_k.  Recorded behind
         // level 2 instead, that kernel ran alone - 27 us for 49 - but the walk had the gather and the three histogram
         // passes beside it for longer: 226 us for 192, a loss of 12 on the critical path)
-        if (ev_zcol) PCH_HIP_TRY(hipEventRecord(ev_zcol, s));
+        if (ev_summary) PCH_HIP_TRY(hipEventRecord(ev_summary, s));
         PCH_LAUNCH("mean_level2", ms_level2_k, dim3((unsigned)(3 * nb2)), dim3(256), 0, s,
                    (const MsRec*)w.rec, nb, nb2, w.hdr2, w.rows2);
     }

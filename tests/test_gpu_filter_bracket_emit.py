@@ -1,16 +1,17 @@
 """Height filter, percentile bracket from the centroid summary (MsBracket, pch_mean.h; sel_collect_k, pch_filter.hip).
 
-From 131 072 rows on the summary pass keeps, per 1024-row block, the z values inside a bracket of the wanted
-percentile at the front of the block's segment plus one small record, instead of writing the z column.  Whether the
-bracket holds the wanted order statistics is checked on the device; if not, the select reads the z of the rows.
+Above 65 536 rows (where the summary has a sampled estimate: ms_predicts, pch_mean.hip) the summary pass keeps, per
+1024-row block, the z values inside a bracket of the wanted percentile at the front of the block's segment plus one
+small record.  Whether the bracket holds the wanted order statistics is checked on the device; if not, the select reads
+the z of the rows.  A smaller cloud has no bracket: its select reads the z of the rows at once.
 
-Every case runs ops.ground_filter on three routes and holds each against oracle.ground_filter bit for bit:
+Every case runs ops.ground_filter on two routes and holds each against oracle.ground_filter bit for bit:
   bracket   the default
   rows      PCH_GF_BRACKET_INVALID: the bracket's device check fails, the three select passes read the rows (stride 3)
-  column    PCH_GF_NO_BRACKET: the route is off - z column, sample and bracket sweep as before
-and the three must equal each other.  A route is a property of the process (the toggles are read once), so each route
+and the two must equal each other.  A route is a property of the process (the toggle is read once), so each route
 is one child process that runs all cases one after the other ON ONE WORKSPACE (ops keeps a grow-only buffer): stale
-per-block records and stale segment fronts of the call before are always there to be tripped over.
+per-block records and stale segment fronts of the call before are always there to be tripped over - also by the small
+clouds, which lay the workspace out without segments and records.
 """
 import json
 import os
@@ -21,11 +22,14 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-ROUTES = {"bracket": {}, "rows": {"PCH_GF_BRACKET_INVALID": "1"}, "column": {"PCH_GF_NO_BRACKET": "1"}}
+ROUTES = {"bracket": {}, "rows": {"PCH_GF_BRACKET_INVALID": "1"}}
 
 CASES = ["flat", "pct0", "pct25", "pct50", "pct100", "constant", "two_inside", "two_last_of_lower", "two_first_of_upper",
          "quantised", "ascending", "cliff", "nan_rows", "nan_block", "inf_rows", "nan_inf_mixed",
-         "n131072", "n131073", "n1048575", "n1048577", "reuse_1m_a", "reuse_200k", "reuse_1m_b"]
+         # around one 1024-row summary block, one 16 384-row sweep tile and the largest cloud without a bracket (65 536)
+         "n1", "n2", "n1023", "n1025", "n16384", "n16385", "n65536", "n65537",
+         "n131072", "n131073", "n1048575", "n1048577",
+         "reuse_1m_a", "reuse_small", "reuse_200k", "reuse_1m_b"]
 
 CHILD = r'''
 import hashlib, json, sys, numpy as np, torch
@@ -92,6 +96,8 @@ def build(case):
         pts, _ = flat(int(case[1:]), 17)
     elif case == "reuse_1m_a":
         pts, _ = flat(1_000_000, 18)
+    elif case == "reuse_small":
+        pts, _ = flat(40_000, 21)                     # no bracket: the rows' select on a workspace full of segments
     elif case == "reuse_200k":
         pts, _ = flat(200_000, 19)
     elif case == "reuse_1m_b":
@@ -137,33 +143,34 @@ def run(case):
 
 for c in sys.argv[2].split(","):
     run(c)
-# which kernels does this route launch?  (one more small call, profiled: the calls above ran without the events)
+# which kernels does this route launch?  (two more small calls, profiled: the calls above ran without the events)
 ops.set_profiling(True)
-raw, _ = build("n131072")
-ops.ground_filter(torch.from_numpy(raw).cuda())
-print("kernels", json.dumps(sorted({k for k, _, _ in ops.get_profile()})), flush=True)
+for case in ("n131072", "n4096"):
+    raw, _ = build(case)
+    ops.ground_filter(torch.from_numpy(raw).cuda())
+    print("kernels", json.dumps({case: sorted({k for k, _, _ in ops.get_profile()})}), flush=True)
 '''
 
 
 @pytest.fixture(scope="module")
 def routes(cuda):
-    """{route: ({case: record}, kernel names, exit status, end of stderr)}.  One child after the other; a child that
-    does not end cleanly is the last one started."""
+    """{route: ({case: record}, {profiled case: kernel names}, exit status, end of stderr)}.  One child after the other; a
+    child that does not end cleanly is the last one started."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    drop = ("PCH_GF_BRACKET_INVALID", "PCH_GF_NO_BRACKET", "PCH_GF_NO_CAND", "PCH_MEAN_NO_PREDICT")
+    drop = ("PCH_GF_BRACKET_INVALID", "PCH_GF_NO_CAND", "PCH_MEAN_NO_PREDICT")
     out = {name: ({}, None, None, "not started: a route before it did not end cleanly") for name in ROUTES}
-    for name in ("column", "bracket", "rows"):
+    for name in ("bracket", "rows"):
         env = {k: v for k, v in os.environ.items() if k not in drop}
         env.update(ROUTES[name])
         p = subprocess.run([sys.executable, "-c", CHILD, root, ",".join(CASES)], env=env, capture_output=True,
                            text=True, timeout=300)
-        recs, kernels = {}, None
+        recs, kernels = {}, {}
         for ln in p.stdout.splitlines():
             if ln.startswith("case "):
                 r = json.loads(ln[5:])
                 recs[r["case"]] = r
             elif ln.startswith("kernels "):
-                kernels = json.loads(ln[8:])
+                kernels.update(json.loads(ln[8:]))
         out[name] = (recs, kernels, p.returncode, p.stderr[-2000:])
         if p.returncode != 0:
             break
@@ -181,11 +188,12 @@ def test_ground_filter_equals_the_oracle_on_every_bracket_route(routes, case):
 
 
 def test_the_toggles_choose_the_routes(routes):
-    """The bracket routes gather from the summary and never copy or sweep a z column; the route that is off does what
-    it did before."""
+    """Both routes gather from the summary and never sample or sweep a z column; a cloud too small for the summary's
+    estimate runs the three histogram passes over the rows and gathers nothing."""
     for name, (_, kernels, rc, err) in routes.items():
-        assert rc == 0 and kernels is not None, f"route {name}: exit {rc}\n{err}"
-    for name in ("bracket", "rows"):
-        k = routes[name][1]
+        assert rc == 0 and set(kernels) == {"n131072", "n4096"}, f"route {name}: exit {rc}\n{err}"
+        k = kernels["n131072"]
         assert "sel_collect" in k and "sel_bracket" not in k and "sel_sample" not in k, (name, k)
-    assert "sel_collect" not in routes["column"][1]
+        k = kernels["n4096"]
+        assert {"sel_hist0", "sel_hist1", "sel_hist2"} <= set(k), (name, k)
+        assert not {"sel_collect", "sel_sample", "sel_bracket"} & set(k), (name, k)
