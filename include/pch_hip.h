@@ -230,6 +230,42 @@ int pch_ground_filter_f32(const float* raw, int64_t n, double pct, float offset,
                           int64_t* out_count, float* out_aabb,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ stage B, opt-in: the LAS-integer frame
+ * The reference casts world coordinates to float32 BEFORE it centres them (utils/tower_extraction.py:62-64): at
+ * projected-CRS scale that is a 0.25 m grid in y.  This frame centres on the int32 LAS records first (the remedy of
+ * the reference's own test/pipei.py:68-79, restated on the integers) and applies the reference's height rule to the
+ * result.  XYZ [n,3] int32 (device), scale3_host [3] float64 (host; `offset` of the LAS header does not enter):
+ *   1 centroid: S_j = sum_i XYZ[i,j] in int64 (exact: |S| < 2^62); C_j = floor(S_j / n) (Python's //, not C
+ *     truncation).  World centroid, for the caller: (double)C_j * scale_j + offset_j, a multiply, then an add.
+ *   2 rows: p[i,j] = (float)((double)((int64)XYZ[i,j] - C_j) * scale_j) - an exact difference, one float64 multiply,
+ *     one rounding to float32, no FMA.
+ *   3 threshold: base = np.percentile(p[:,2], pct) under numpy's float32 'linear' rule (the arithmetic of
+ *     pch_percentile_f32); threshold = base + offset; keep p_z > threshold (strict), order preserving; if fewer than
+ *     min_keep rows are kept, keep p_z > base + fallback_offset instead.  p_z is non-decreasing in Z, so the two order
+ *     statistics are taken on the integers (an exact radix select on Z - min Z, digits cut from the range of Z).
+ *   4 outputs: out_points [n,3] float32 capacity, the first count rows = the kept p rows in file order; out_index [n]
+ *     int32 (may be NULL): their rows; out_frame_dev: the DEVICE record below - aabb is the box of the finite kept
+ *     rows (zeros if none), count_at_offset the rows kept at `offset`, count those of the threshold that stands;
+ *     count reads negative after a bounded wait that ran out (above).
+ * Asynchronous: enqueues and returns, no host read; three to six sweeps over the 12-byte rows (sums and range of Z,
+ * one histogram pass per 12 bits of that range, the compaction, its repeat for the fallback), every launch sized from
+ * n alone, no float copy of the cloud.  n <= 0, n >= 2^31, a scale that is not finite or <= 0, pct outside [0, 100]
+ * or NaN: PCH_ERR_ARG; ws_bytes below pch_ground_filter_las_ws_bytes(n): PCH_ERR_WORKSPACE.  The size query is host
+ * arithmetic and gives 0 for n < 0. */
+typedef struct PchLasFrame {
+    int64_t  centroid[3];     /* C, in LAS counts */
+    int64_t  count;           /* kept rows; negative: PCH_ERR_TIMEOUT */
+    int64_t  count_at_offset; /* kept at base + offset */
+    float    base, threshold;
+    float    aabb[6];         /* min xyz, max xyz of the finite kept rows */
+    uint32_t used_fallback;   /* 1: threshold = base + fallback_offset */
+    uint32_t reserved;
+} PchLasFrame;                /* 80 bytes */
+size_t pch_ground_filter_las_ws_bytes(int64_t n);
+int pch_ground_filter_las_i32(const int32_t* XYZ, int64_t n, const double* scale3_host, double pct, float offset,
+                              float fallback_offset, int64_t min_keep, float* out_points, int32_t* out_index,
+                              PchLasFrame* out_frame_dev, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ stage B, opt-in: one RANSAC ground plane
  * The second ground rule, for sloped terrain: a plane z = a x + b y + c fitted by RANSAC on z ~ (x, y) instead of one
  * global percentile.  Replaces: test/main_ground.py:8-32 (remove_ground_ransac; RANSACRegressor with

@@ -54,6 +54,8 @@ _SIGS = {
     "pch_ground_filter_ws_bytes": (_sz, [_i64]),
     "pch_ground_filter_f32": (C.c_int, [_vp, _i64, _f64, _f32, _f32, _i64, _vp, _vp, _vp, _vp, _vp,
                                         _vp, _sz, _vp]),
+    "pch_ground_filter_las_ws_bytes": (_sz, [_i64]),
+    "pch_ground_filter_las_i32": (C.c_int, [_vp, _i64, _vp, _f64, _f32, _f32, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pch_plane_fit_ws_bytes": (_sz, [_i64, _i32]),
     "pch_plane_fit_f32": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pch_filter_plane_ws_bytes": (_sz, [_i64]),
@@ -130,6 +132,13 @@ class PlaneBestC(C.Structure):
     """PchPlaneBest (include/pch_hip.h)."""
     _fields_ = [("a", C.c_double), ("b", C.c_double), ("c", C.c_double), ("count", C.c_int64),
                 ("best", C.c_int32), ("nvalid", C.c_int32)]
+
+
+class LasFrameC(C.Structure):
+    """PchLasFrame (include/pch_hip.h)."""
+    _fields_ = [("centroid", C.c_int64 * 3), ("count", C.c_int64), ("count_at_offset", C.c_int64),
+                ("base", C.c_float), ("threshold", C.c_float), ("aabb", C.c_float * 6),
+                ("used_fallback", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class UprightBoxC(C.Structure):

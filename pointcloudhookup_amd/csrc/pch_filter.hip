@@ -4,6 +4,7 @@
 #include "pch_prims.h"
 #include "pch_mean.h"
 #include "pch_compact.h"
+#include "pch_select.h"
 
 namespace pch {
 
@@ -262,9 +263,7 @@ __global__ __launch_bounds__(256) void sel_lerp_k(const SelRun* __restrict__ run
     const float a = sel_key_to_float(st.v0key) - c;
     float b = a;
     if (!same_index && st.need_next) b = sel_key_to_float(run->next_min) - c;
-    const float diff = b - a;
-    float r = a + diff * gamma;
-    if (gamma >= 0.5f) r = b - diff * (1.0f - gamma);
+    float r = sel_lerp_f32(a, b, gamma);
     if (run->nan_count) r = __uint_as_float(0x7FC00000u);
     scal[0] = r;
     scal[1] = r + add1;
@@ -508,24 +507,7 @@ static void sel_plan_from_summary(Arena& a, SelWs& w, int64_t n) {
     w.cand = a.take<float>(w.cap);
 }
 
-// host side of np.percentile's index arithmetic (float32 under NEP 50)
-struct PctIndex { int64_t k0; int same; float gamma; };
-static PctIndex pct_index(int64_t n, double q_percent) {
-    PctIndex r;
-    const float q = (float)q_percent / 100.0f;          // np.true_divide(q, float32(100))
-    const float vi = (float)(n - 1) * q;                // (n - 1) * quantiles -> float32
-    float prev = floorf(vi);
-    r.gamma = vi - prev;
-    r.same = 0;
-    if (vi >= (float)(n - 1)) { prev = (float)(n - 1); r.same = 1; }   // indexes -> -1 (last)
-    if (vi < 0.0f) { prev = 0.0f; r.same = 1; }
-    int64_t k0 = (int64_t)prev;
-    if (k0 > n - 1) k0 = n - 1;                          // float32(n-1) may round up
-    if (k0 < 0) k0 = 0;
-    if (k0 == n - 1) r.same = 1;
-    r.k0 = k0;
-    return r;
-}
+// (np.percentile's index arithmetic, pct_index, lives in pch_select.h: the LAS-integer frame selects with it too)
 
 // three histogram passes (+ the "next key" pass) on one SelRun; run and histograms are prepared by the caller
 static int select_rounds(const float* base, int64_t n, int64_t stride, bool with_next, SelRun* run, uint32_t* hist,

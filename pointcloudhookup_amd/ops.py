@@ -352,6 +352,52 @@ def ground_filter(raw, pct=25.0, offset=3.0, fallback_offset=1.0, min_keep=1000,
                           host[6:7].view("<u4")[0], host[8:14])
 
 
+# ------------------------------------------------------------- stage B, opt-in: the LAS-integer frame
+FRAME_TILE = 2048              # rows per workgroup of the frame's filter sweep (fr_filter_k): the sizes tests straddle
+
+
+def frame_scales(scales):
+    """the three LAS scales of the "las" frame as float64; ValueError unless every one is finite and > 0"""
+    import numpy as np
+    sc = np.asarray(scales, dtype=np.float64).reshape(-1)
+    if sc.shape != (3,) or not np.all(np.isfinite(sc)) or not np.all(sc > 0.0):
+        raise ValueError(f"the LAS scales must be three finite numbers > 0, got {scales!r}")
+    return sc
+
+
+def ground_filter_las(XYZ, scales, offsets, pct=25.0, offset=3.0, fallback_offset=1.0, min_keep=1000, want_index=True):
+    """Stage B in the LAS-integer frame (opt-in; include/pch_hip.h, pch_ground_filter_las_i32) on the int32 [n,3] LAS
+    records themselves: the centroid is the exact integer one, C = floor(sum / n), every row is centred on the integers
+    and rounded to float32 once, p = float32(float64(XYZ - C) * scale), and the reference's percentile rule runs on p.
+    No float64 or float32 copy of the cloud is made.  Returns the dict of ground_filter, where ``centroid`` is the
+    float64 world centroid C * scale + offset (points.astype(float64) + centroid are world coordinates), plus
+    ``centroid_int`` (int64 [3]) and ``frame`` = "las".  Synchronises (reads the record)."""
+    import ctypes as C
+    import numpy as np
+    sc = frame_scales(scales)
+    of = np.asarray(offsets, dtype=np.float64).reshape(3)
+    L = _lib.lib()
+    XYZ = _need_cuda(XYZ, torch.int32, "XYZ").reshape(-1, 3)
+    n = XYZ.shape[0]
+    dev = XYZ.device
+    sc_c = _double3(sc)
+    with torch.cuda.device(dev):
+        out_points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        out_index = torch.empty((n,), dtype=torch.int32, device=dev) if want_index else None
+        rec = torch.zeros((C.sizeof(_lib.LasFrameC),), dtype=torch.uint8, device=dev)
+        ws = _workspace(L.pch_ground_filter_las_ws_bytes(n), dev)
+        _lib.check(L.pch_ground_filter_las_i32(_ptr(XYZ), n, C.cast(sc_c, C.c_void_p), float(pct), float(offset),
+                                               float(fallback_offset), int(min_keep), _ptr(out_points),
+                                               _ptr(out_index), _ptr(rec), _ptr(ws), ws.numel(), _stream()))
+        f = _lib.LasFrameC.from_buffer_copy(rec.cpu().numpy().tobytes())     # one D2H copy, synchronises the stream
+    nf = _lib.check_count(f.count, "ground_filter_las")
+    cint = np.array(list(f.centroid), dtype=np.int64)
+    out = _ground_result(out_points, out_index, nf, (0.0, 0.0, 0.0), f.base, f.threshold, f.used_fallback != 0,
+                         f.count_at_offset, list(f.aabb))
+    out.update(centroid=cint.astype(np.float64) * sc + of, centroid_int=cint, frame="las")
+    return out
+
+
 # ------------------------------------------------------------- stage B, opt-in: one RANSAC ground plane
 PLANE_MAX_HYPOTHESES = 4096
 PLANE_COUNT_TILE = 1024        # rows per workgroup pass of the inlier count (pl_count_k): the sizes tests straddle

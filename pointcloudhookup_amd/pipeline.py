@@ -39,8 +39,11 @@ def cluster_points(raw, eps=8.0, min_points=80, chunk_size=REF_CHUNK, pct=25.0, 
     """
     out = _cluster_points(raw, eps, min_points, chunk_size, pct, offset, fallback_offset, min_keep, want_index,
                           segment or merge_threshold is not None, ground, plane)
-    if merge_threshold is None:
-        return out
+    return out if merge_threshold is None else _merged(out, merge_threshold, segment)
+
+
+def _merged(out, merge_threshold, segment):
+    """the opt-in merge behind the grouping, for cluster_points and cluster_points_las"""
     m = ops.merge_clusters(out["ground"]["points"], out["labels"], out["perm"], out["offsets"], out["nclusters"],
                            merge_threshold)
     out.update(labels=m["labels"], nclusters=m["nclusters"],
@@ -78,6 +81,44 @@ def _cluster_points(raw, eps, min_points, chunk_size, pct, offset, fallback_offs
     if segment:
         out.update(perm=perm, offsets=offsets, stats=stats)
     return out
+
+
+FRAMES = ("reference", "las")
+_PLANE_GROUNDS = ("plane", "plane_tiles")
+
+
+def check_frame(frame, ground="percentile"):
+    """ValueError for an unknown frame, and for the "las" frame with a plane ground rule: those rules compute their own
+    float32 centroid in the reference's frame.  Touches no device."""
+    if frame not in FRAMES:
+        raise ValueError(f"frame must be 'reference' or 'las', got {frame!r}")
+    if frame == "las" and ground in _PLANE_GROUNDS:
+        raise ValueError(f"frame 'las' is defined for the percentile ground rule only, not for ground={ground!r}: "
+                         "the plane rules centre the cloud themselves, in the reference's float32 frame")
+    return frame
+
+
+def cluster_points_las(XYZ, scales, offsets, eps=8.0, min_points=80, chunk_size=REF_CHUNK, pct=25.0, offset=3.0,
+                       fallback_offset=1.0, min_keep=1000, want_index=False, segment=True, merge_threshold=None,
+                       ground="percentile"):
+    """Stages B + C + D0 in the LAS-integer frame (opt-in) on the int32 [N,3] LAS records of a device tensor:
+    ops.ground_filter_las, then ops.dbscan with its box, ops.segment_by_label and the optional merge.  Returns the dict
+    of ``cluster_points`` - ``tower_table`` and ``tower_table_async`` take it unchanged; ground["centroid"] is the
+    float64 world centroid.  ``ground`` exists to say no: a plane rule raises ValueError before any device call."""
+    check_frame("las", ground)
+    if ground != "percentile":
+        raise ValueError(f"ground must be 'percentile' in the 'las' frame, got {ground!r}")
+    gf = ops.ground_filter_las(XYZ, scales, offsets, pct, offset, fallback_offset, min_keep, want_index=want_index)
+    points = gf["points"]
+    if gf["count"]:
+        labels, _, k = ops.dbscan(points, eps, min_points, chunk_size, aabb=gf["aabb"])
+    else:
+        labels, k = torch.empty((0,), dtype=torch.int32, device=points.device), 0
+    out = dict(ground=gf, labels=labels, nclusters=k)
+    if segment or merge_threshold is not None:
+        perm, offsets_, stats = ops.segment_by_label(labels, points, k)
+        out.update(perm=perm, offsets=offsets_, stats=stats)
+    return out if merge_threshold is None else _merged(out, merge_threshold, segment)
 
 
 def label_full_cloud(sampled_raw, full_raw, eps=8.0, min_points=80, chunk_size=0, pct=25.0, offset=3.0,

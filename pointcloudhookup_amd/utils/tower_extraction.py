@@ -38,6 +38,13 @@ keeps the first piece only.  When set, clusters whose centres lie within it of e
 per-chunk replay and the detection (ops.merge_clusters, the remedy of the reference's own test/tttt.py:93-175, which
 uses 6.0); it logs that script's two lines ("=== 合并相邻簇 ===", "✅ 合并后簇数量: C") and the candidate count and
 the towers are those of the merged clusters.  No progress milestone is added.
+``FRAME`` ("reference" | "las", env PCH_FRAME): "reference" casts the world coordinates to float32 and then centres
+them, as the reference does - at projected-CRS scale a 0.25 m grid in y.  "las" (opt-in) hands the int32 LAS records
+straight to ops.ground_filter_las: exact integer centroid, rows centred on the integers and rounded to float32 once
+(DESIGN.md section 10e), for a file read and for resident records alike; the per-tower LAS files are
+points.astype(float64) + the float64 world centroid.  It logs one extra line with the integer centroid and its world
+coordinates.  It is defined for ``GROUND_MODE`` "percentile"; with a plane mode, or an unknown value, the run ends as
+a logged failure of the filter step before anything touches the device.
 """
 from __future__ import annotations
 
@@ -54,6 +61,7 @@ CHUNK_FAILURE = os.environ.get("PCH_CHUNK_FAILURE", "reference")
 OBB_MODE = os.environ.get("PCH_OBB_MODE", "exact")
 GROUND_MODE = os.environ.get("PCH_GROUND_MODE", "percentile")
 GROUND_TILE = float(os.environ.get("PCH_GROUND_TILE", "20.0"))
+FRAME = os.environ.get("PCH_FRAME", "reference")
 
 
 def merge_threshold_from_env(value):
@@ -122,6 +130,13 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
         import torch
         from .. import las as _las
         from .. import ops, pipeline, stages
+        try:
+            pipeline.check_frame(FRAME, GROUND_MODE)
+        except ValueError as e:            # a failure of the filter step, found before anything touches the device
+            log("🔍 执行高度过滤...")
+            progress(10)
+            log(f"⚠️ 高度过滤失败: {str(e)}")
+            return tower_obbs
         clock = stages.Clock("extract_towers")
         if resident_entry is not None and resident_entry.records is not None:
             # (a background writer may not have created the file yet: its size follows from the records)
@@ -138,9 +153,12 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
         else:
             hdr, XYZ = _las.read_device(input_las_path, dev)           # records decoded on the GPU
             clock.mark("read LAS -> device int32 (file, H2D, decode)")
-        raw = ops.cast_f32(ops.las_scale(XYZ, hdr.scales, hdr.offsets))
+        if FRAME == "las":
+            raw = XYZ                      # the filter centres the LAS integers themselves: no float copy of the cloud
+        else:
+            raw = ops.cast_f32(ops.las_scale(XYZ, hdr.scales, hdr.offsets))
+            clock.mark("int32 -> float64 -> float32")
         del XYZ
-        clock.mark("int32 -> float64 -> float32")
         header_info = {"scales": hdr.scales, "offsets": hdr.offsets,
                        "point_format": hdr.point_format, "version": hdr.version}
         log(f"✅ 点云读取完成，总点数: {raw.shape[0]}")
@@ -154,7 +172,10 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
         progress(10)
         if raw.shape[0] == 0:
             raise IndexError("index -1 is out of bounds for axis 0 with size 0")
-        if GROUND_MODE == "plane":
+        if FRAME == "las" and GROUND_MODE == "percentile":
+            gf = ops.ground_filter_las(raw, hdr.scales, hdr.offsets, 25.0, 3.0, 1.0, 1000, want_index=False)
+            clock.mark("integer centroid + percentile filter (LAS frame)")
+        elif GROUND_MODE == "plane":
             gf = ops.ground_filter_plane(raw, want_index=False)
             clock.mark("centroid + plane fit + plane filter")
         elif GROUND_MODE == "plane_tiles":
@@ -171,6 +192,8 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
             log("⚠️ 过滤后点数太少，尝试降低过滤阈值")
         else:
             log(f"✅ 高度过滤完成，保留点数: {gf['count']}")
+        if FRAME == "las":
+            log(frame_line(gf))
         if GROUND_MODE == "plane":
             a, b, c = gf["plane"]
             log(f"📐 地面平面: z = {a:.6f}·x + {b:.6f}·y + {c:.3f}（内点 {gf['inliers']}/{raw.shape[0]}）")
@@ -286,6 +309,13 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
     progress(100)
     log("✅ 杆塔提取完成")
     return tower_obbs
+
+
+def frame_line(gf):
+    """the extra log line of FRAME "las" for a result of ops.ground_filter_las"""
+    ci, cw = gf["centroid_int"], gf["centroid"]
+    return (f"📐 LAS整数坐标系: 整数质心 ({int(ci[0])}, {int(ci[1])}, {int(ci[2])})，"
+            f"世界坐标 ({cw[0]:.3f}, {cw[1]:.3f}, {cw[2]:.3f})")
 
 
 def ground_tiles_line(gf):
