@@ -451,6 +451,29 @@ int pch_dbscan_assign_f32(const float* query, int64_t nq, const float* sub3_host
                           int64_t n, int32_t* out_labels, void* qws, size_t qws_bytes,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* The k-distance of points against that same last fit: for every query the squared distance to its k-th nearest row of
+ * the fit, exactly - the sorted k-distance plot is the instrument DBSCAN's authors give for choosing eps, and
+ * pch_dbscan_f32 itself stops counting neighbours at min_samples.  For query i:
+ *   q = fl32(query[i] - sub3) per component (sub3_host == NULL: no subtraction), c = query_chunk[i];
+ *   d2(q, p) = (dx*dx + dy*dy) + dz*dz in float64 on the float64 images of the float32 coordinates, accumulated in x,
+ *       y, z order without FMA - the library's predicate, sklearn's euclidean_rdist;
+ *   R = { d2(q, p) : p a row of the fit in chunk c, core or not, d2 <= eps*eps } as a multiset (the fit's own eps*eps);
+ *   out_count[i] = |R|; out_d2[i] = the k-th smallest element of R (1-based, equal values counted separately) if
+ *       |R| >= k, else +inf.
+ * A query holding NaN or +-inf, a chunk index outside [0, nchunks) and a chunk that held NaN/inf give count 0 and +inf.
+ * Applied to the fit's own rows (query_chunk[i] = i / chunk_size) the row itself is in R with d2 = 0, so
+ * core[i] == (out_count[i] >= min_samples), and with k = min_samples also core[i] == (out_d2[i] <= eps*eps).
+ * The answer is truncated at the fit's eps (the grid reaches two cells): for k-distances up to 16 m fit at eps = 16 with
+ * any min_samples; one fit then serves every k.  Answers do not depend on labels: before or after a relabel alike.
+ * query [nq,3] float32, query_chunk [nq] int32 or NULL (single-chunk fits only), out_d2 [nq] float64, out_count [nq]
+ * int32 or NULL - all device; sub3_host 3 floats on the host or NULL.  k < 1: PCH_ERR_ARG.
+ * n, ws, ws_bytes, qws (>= pch_dbscan_kdist_ws_bytes(nq) bytes) and every other status: as for pch_dbscan_assign_f32.
+ * Enqueues its work and returns; no host reads; the fit is only read, so the call may be repeated. */
+size_t pch_dbscan_kdist_ws_bytes(int64_t nq);
+int pch_dbscan_kdist_f32(const float* query, int64_t nq, const float* sub3_host, const int32_t* query_chunk,
+                         int32_t k, int64_t n, double* out_d2, int32_t* out_count, void* qws, size_t qws_bytes,
+                         void* ws, size_t ws_bytes, void* stream);
+
 /* One representative per LATTICE cell of up to two strips of a tile: the smallest row among the core points of the
  * cell whose x lies in the strip.  The lattice is shared by all ranks (cell = floor(coordinate / side) per axis, side =
  * eps / sqrt(3) * (1 - 2^-16), anchored at the origin of the common frame), so the two tiles on either side of an edge

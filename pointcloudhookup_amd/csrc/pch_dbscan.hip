@@ -54,7 +54,7 @@ __device__ __forceinline__ uint64_t db_pack(const DbGrid& g, uint64_t chunk, uin
     return ((((chunk << g.bz) | cz) << g.by | cy) << g.bx) | cx;
 }
 
-__device__ __forceinline__ bool db_within(const float4& q, const float4& p, double eps2) {
+__device__ __forceinline__ double db_d2(const float4& q, const float4& p) {
     // euclidean_rdist: tmp = x1[j] - x2[j]; d += tmp * tmp   (float64, j = 0,1,2)
     const double dx = (double)q.x - (double)p.x;
     const double dy = (double)q.y - (double)p.y;
@@ -62,7 +62,10 @@ __device__ __forceinline__ bool db_within(const float4& q, const float4& p, doub
     double d = dx * dx;
     d += dy * dy;
     d += dz * dz;
-    return d <= eps2;
+    return d;
+}
+__device__ __forceinline__ bool db_within(const float4& q, const float4& p, double eps2) {
+    return db_d2(q, p) <= eps2;
 }
 
 // Same predicate, cheaper: the float32 value d32 of the squared distance carries a relative error
@@ -2586,23 +2589,27 @@ __global__ __launch_bounds__(DB_THREADS) void dq_keys_k(DbQuery Q, DbGrid g, uin
     vals[i] = (uint32_t)i | (ok ? 0u : DQ_OUT);
 }
 
-// Pieces of the sorted queries: a piece starts where the key changes and at every multiple of DQ_PIECE, so it lies
-// inside one cell and holds at most DQ_PIECE queries (64: one query per lane; measured against 256 and 1024).  dq_heads_k writes the start flags (scanned in place),
+// Pieces of the sorted queries: a piece starts where the key changes and at every multiple of PIECE, so it lies
+// inside one cell and holds at most PIECE queries (dq_assign_k: DQ_PIECE = 64, one query per lane; measured against 256
+// and 1024.  dq_kdist_k: DK_PIECE).  dq_heads_k writes the start flags (scanned in place),
 // dq_pieces_k the first query of every piece and, behind the last one, nq.
+template <int PIECE>
 __device__ __forceinline__ bool dq_head(const uint64_t* __restrict__ keys, int64_t i) {
-    return i % DQ_PIECE == 0 || keys[i] != keys[i - 1];
+    return i % PIECE == 0 || keys[i] != keys[i - 1];
 }
+template <int PIECE>
 __global__ __launch_bounds__(DB_THREADS) void dq_heads_k(const uint64_t* __restrict__ keys, int64_t nq,
                                                          uint32_t* __restrict__ flag) {
     const int64_t i = (int64_t)blockIdx.x * DB_THREADS + threadIdx.x;
-    if (i < nq) flag[i] = dq_head(keys, i) ? 1u : 0u;
+    if (i < nq) flag[i] = dq_head<PIECE>(keys, i) ? 1u : 0u;
 }
+template <int PIECE>
 __global__ __launch_bounds__(DB_THREADS) void dq_pieces_k(const uint64_t* __restrict__ keys, int64_t nq,
                                                           const uint32_t* __restrict__ excl,
                                                           uint32_t* __restrict__ piece_start) {
     const int64_t i = (int64_t)blockIdx.x * DB_THREADS + threadIdx.x;
     if (i >= nq) return;
-    const bool h = dq_head(keys, i);
+    const bool h = dq_head<PIECE>(keys, i);
     if (h) piece_start[excl[i]] = (uint32_t)i;
     if (i == nq - 1) piece_start[excl[i] + (h ? 1u : 0u)] = (uint32_t)nq;
 }
@@ -2663,6 +2670,201 @@ __global__ __launch_bounds__(DB_THREADS) void dq_assign_k(DbQuery Q, DbGrid g, c
                 if (l == j && best != INT_BIG) res = best;
             }
             if (have) out[v & ~DQ_OUT] = res;
+        }
+    }
+}
+
+// ---- the k-th neighbour distance of every query among the rows of the fit (pch_dbscan_kdist_f32): the k-distance
+// plot that sets eps.  Queries are binned, sorted and cut into pieces as for dq_assign_k (of DK_PIECE queries), one
+// wave per piece.  The 25 neighbour rows of the piece's cell are 25 runs of consecutive rows of the sorted copy,
+// [cell_start[ca], cell_start[cb]); the wave numbers their rows 0 .. T-1 across the runs (seg_off: first number of a
+// run, seg_a: its first row), so a sweep keeps 64 lanes busy whatever the runs' lengths.  Per query:
+//   * one sweep forms d2 of every candidate in float64 (db_d2, db_within's sum); the float32 value of db_within2 only
+//     skips candidates that are surely outside (d32 >= eps2_hi).  Those with d2 <= eps2 are counted, the first DK_CAP
+//     bit patterns are kept in LDS, and the histogram of their top byte is taken;
+//   * an exact MSB-first radix select on the 64-bit pattern of d2 (non-negative doubles order as unsigned integers; d2
+//     is a sum of squares, never -0.0), a byte per pass: the wave scans the 256 bins, four per lane, picks the bin that
+//     holds rank k, and tallies the next byte of the keys that share the prefix so far - from the LDS copy when all
+//     in-range keys fitted, else by sweeping the candidates again (the neighbourhood of a tower core: thousands).
+// Nothing here leaves the wave: no global atomics, no waiting on another workgroup.
+constexpr int DK_CAP = 1024;                 // in-range keys a wave keeps in LDS (8 KiB of the workgroup's 37 KiB)
+constexpr int DK_PIECE = 8;                  // queries per piece: a query costs up to eight sweeps of its neighbourhood, so
+                                             // short pieces, many waves (DESIGN.md section 5a has the figures)
+constexpr int DK_AHEAD = 4;                  // 64-candidate groups whose loads are in flight together (as DB_AHEAD)
+struct DkWave {
+    uint64_t buf[DK_CAP];
+    uint32_t hist[256];
+    uint32_t seg_off[DB_ROWS + 1], seg_a[DB_ROWS];
+};
+// LDS written by some lanes is read by others of the same wave: the wave's DS operations execute in order, the fence
+// and the barrier keep the compiler from reordering them
+__device__ __forceinline__ void dk_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+// hist[d] += 1 for every lane of the ballot m; the lanes of a group mostly share the leading bytes, and 64 adds to one
+// word would serialise
+__device__ __forceinline__ void dk_tally(uint32_t* hist, bool on, uint32_t d, uint64_t m) {
+    if (m == 0) return;                                    // wave-uniform
+    const int first = __ffsll((unsigned long long)m) - 1;
+    const uint32_t d0 = (uint32_t)__shfl((int)d, first, 64);
+    if (__ballot(on && d != d0) == 0) {
+        if (lane_id() == first) atomicAdd(&hist[d0], (uint32_t)__popcll(m));
+    } else if (on) {
+        atomicAdd(&hist[d], 1u);
+    }
+}
+// f(in, key) for every group of 64 candidates, called by all lanes: in = the lane holds a candidate with d2 <= eps2,
+// key = the bit pattern of its d2
+template <typename F>
+__device__ __forceinline__ void dk_sweep(const DbGrid& g, const float4* __restrict__ pts, const DkWave& W, uint32_t T,
+                                         const float4& q, F&& f) {
+    const int l = lane_id();
+    int r = 0;
+    for (uint32_t t0 = 0; t0 < T; t0 += 64u * DK_AHEAD) {  // wave-uniform
+        float4 P[DK_AHEAD];
+#pragma unroll
+        for (int u = 0; u < DK_AHEAD; ++u) {
+            const uint32_t t = t0 + 64u * u + l;
+            P[u].x = P[u].y = P[u].z = P[u].w = 0.0f;
+            if (t < T) {
+                while (t >= W.seg_off[r + 1]) ++r;         // t < T = seg_off[DB_ROWS]: r stays below DB_ROWS
+                P[u] = pts[W.seg_a[r] + (t - W.seg_off[r])];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < DK_AHEAD; ++u) {
+            if (t0 + 64u * u >= T) break;                  // wave-uniform
+            bool in = false;
+            uint64_t key = 0;
+            if (t0 + 64u * u + l < T) {
+                const float4 p = P[u];
+                const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
+                float d = dx * dx;
+                d = __builtin_fmaf(dy, dy, d);
+                d = __builtin_fmaf(dz, dz, d);
+                if (!(d >= g.eps2_hi)) {                   // (db_within2's band: d32 >= eps2_hi implies d64 > eps2)
+                    const double d2 = db_d2(q, p);
+                    in = d2 <= g.eps2;
+                    key = (uint64_t)__double_as_longlong(d2);
+                }
+            }
+            f(in, key);
+        }
+    }
+}
+// the k-th smallest d2 <= eps2 among the T candidates of the wave's piece, +inf if there are fewer; count: how many
+__device__ __forceinline__ double dk_select(const DbGrid& g, const float4* __restrict__ pts, DkWave& W, uint32_t T,
+                                            const float4& q, int32_t k, int& count_out) {
+    const int l = lane_id();
+#pragma unroll
+    for (int u = 0; u < 4; ++u) W.hist[l + 64 * u] = 0u;
+    dk_sync();
+    uint32_t count = 0;
+    dk_sweep(g, pts, W, T, q, [&](bool in, uint64_t key) {
+        const uint64_t m = __ballot(in);
+        if (in) {
+            const uint32_t pos = count + (uint32_t)__popcll(m & lanemask_lt());
+            if (pos < (uint32_t)DK_CAP) W.buf[pos] = key;
+        }
+        dk_tally(W.hist, in, (uint32_t)(key >> 56), m);
+        count += (uint32_t)__popcll(m);
+    });
+    count_out = (int)count;
+    if (count < (uint32_t)k) return __longlong_as_double(0x7FF0000000000000ll);
+    const bool kept = count <= (uint32_t)DK_CAP;
+    uint64_t prefix = 0;
+    uint32_t kk = (uint32_t)k;                              // rank among the keys that share the prefix, 1-based
+    for (int shift = 56;; shift -= 8) {
+        dk_sync();
+        uint32_t h[4], sum = 0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { h[u] = W.hist[4 * l + u]; sum += h[u]; }
+        const uint32_t incl = wave_scan_incl(sum);
+        uint32_t e = incl - sum, digit = 0, knew = 0;
+        const bool mine = e < kk && kk <= incl;            // one lane: the bins hold kk keys at least
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (mine && e < kk && kk <= e + h[u]) { digit = 4u * l + u; knew = kk - e; }
+            e += h[u];
+        }
+        const int src = __ffsll((unsigned long long)__ballot(mine)) - 1;
+        digit = (uint32_t)__shfl((int)digit, src, 64);
+        kk = (uint32_t)__shfl((int)knew, src, 64);
+        prefix |= (uint64_t)digit << shift;
+        if (shift == 0) break;
+        dk_sync();                                         // every lane has read its bins
+#pragma unroll
+        for (int u = 0; u < 4; ++u) W.hist[l + 64 * u] = 0u;
+        dk_sync();
+        const int ns = shift - 8;
+        auto tally = [&](bool in, uint64_t key) {
+            const bool on = in && (key >> shift) == (prefix >> shift);
+            dk_tally(W.hist, on, (uint32_t)(key >> ns) & 255u, __ballot(on));
+        };
+        if (kept) {
+            for (uint32_t i0 = 0; i0 < count; i0 += 64) {
+                const bool in = i0 + l < count;
+                tally(in, in ? W.buf[i0 + l] : 0ull);
+            }
+        } else {
+            dk_sweep(g, pts, W, T, q, tally);
+        }
+    }
+    return __longlong_as_double((long long)prefix);
+}
+
+__global__ __launch_bounds__(DB_THREADS) void dq_kdist_k(DbQuery Q, DbGrid g, const float4* __restrict__ pts,
+                                                         const uint32_t* __restrict__ cell_start,
+                                                         const uint64_t* __restrict__ cell_key,
+                                                         const uint64_t* __restrict__ keys,
+                                                         const uint32_t* __restrict__ vals,
+                                                         const uint32_t* __restrict__ piece_start,
+                                                         const uint32_t* __restrict__ npieces, int32_t k,
+                                                         double* __restrict__ out_d2, int32_t* __restrict__ out_count) {
+    __shared__ DkWave waves[DB_WAVES];
+    const int l = lane_id();
+    DkWave& W = waves[wave_id()];
+    const uint32_t np = *npieces;
+    for (uint32_t p = blockIdx.x * DB_WAVES + wave_id(); p < np; p += gridDim.x * DB_WAVES) {   // wave-uniform
+        const uint32_t ps = piece_start[p], pe = piece_start[p + 1];
+        const uint64_t key = keys[ps];
+        uint32_t a = 0, len = 0;
+        if (l < DB_ROWS) {
+            const int2 v = db_row_run(g, cell_key, key, l);
+            a = cell_start[v.x];
+            len = cell_start[v.y] - a;
+        }
+        const uint32_t incl = wave_scan_incl(len);
+        const uint32_t T = (uint32_t)__shfl((int)incl, 63, 64);
+        dk_sync();                                         // the piece before this one has read its runs
+        if (l < DB_ROWS) { W.seg_a[l] = a; W.seg_off[l + 1] = incl; }
+        if (l == 0) W.seg_off[0] = 0u;
+        dk_sync();
+        for (uint32_t q0 = ps; q0 < pe; q0 += 64) {
+            const bool have = q0 + l < pe;
+            const uint32_t v = have ? vals[q0 + l] : DQ_OUT;
+            float4 mine;
+            mine.x = mine.y = mine.z = mine.w = 0.0f;
+            if (have && T != 0u && !(v & DQ_OUT)) mine = dq_point(Q, (int64_t)v);
+            double res = __longlong_as_double(0x7FF0000000000000ll);
+            int res_count = 0;
+            const int cnt = (int)(pe - q0 < 64u ? pe - q0 : 64u);
+            for (int j = 0; j < cnt && T != 0u; ++j) {
+                if ((uint32_t)__builtin_amdgcn_readlane((int)v, j) & DQ_OUT) continue;          // wave-uniform
+                float4 qp;
+                qp.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.x), j));
+                qp.y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.y), j));
+                qp.z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.z), j));
+                qp.w = 0.0f;
+                int c;
+                const double d = dk_select(g, pts, W, T, qp, k, c);
+                if (l == j) { res = d; res_count = c; }
+            }
+            if (have) {
+                out_d2[v & ~DQ_OUT] = res;
+                if (out_count) out_count[v & ~DQ_OUT] = res_count;
+            }
         }
     }
 }
@@ -3406,6 +3608,61 @@ extern "C" size_t pch_dbscan_assign_ws_bytes(int64_t nq) {
     return a.off;
 }
 
+// What pch_dbscan_assign_f32 and pch_dbscan_kdist_f32 share: the checks of a query call against the fit `entry`
+// continues (nq != 0, `out` its output), then the queries binned into the fit's cells, sorted and cut into pieces.
+struct DqPieces { DbQuery Q; const uint64_t* ks; const uint32_t* vs; const uint32_t *piece_start, *npieces; };
+static int dq_pieces(const char* entry, const float* query, int64_t nq, const float* sub3_host,
+                     const int32_t* query_chunk, int64_t n, const void* out, void* qws, size_t qws_bytes, void* ws,
+                     size_t ws_bytes, hipStream_t s, bool kdist, DbWs& w, DqPieces& P) {
+    PCH_TRY(db_continue(entry, n, ws, ws_bytes, w));
+    if (!(query && out && qws)) { set_error("%s: null buffer", entry); return PCH_ERR_ARG; }
+    if (g_last.compressed) {
+        set_error("%s: the fit took the compressed-coordinate path, which keeps no map from a coordinate to a cell",
+                  entry);
+        return PCH_ERR_RANGE;
+    }
+    if (!(query_chunk || g_last.nchunks == 1)) {
+        set_error("%s: query_chunk is null but the fit has several chunks", entry);
+        return PCH_ERR_ARG;
+    }
+    {
+        const char* a0 = static_cast<const char*>(qws);
+        const char* b0 = static_cast<const char*>(ws);
+        if (a0 < b0 + ws_bytes && b0 < a0 + qws_bytes) {
+            set_error("%s: the query workspace overlaps the fit's workspace", entry);
+            return PCH_ERR_ARG;
+        }
+    }
+    Arena qa(qws, qws_bytes);                     // (disjoint from the fit's workspace: the fit stays remembered)
+    DqWs qw;
+    dq_plan(qa, nq, qw);
+    if (qa.overflow) { set_error("query workspace too small: need %zu bytes", qa.off); return PCH_ERR_WORKSPACE; }
+    const DbCells& c = g_last.c;
+    P.Q = {query, nq, sub3_host ? sub3_host[0] : 0.0f, sub3_host ? sub3_host[1] : 0.0f,
+           sub3_host ? sub3_host[2] : 0.0f, query_chunk, g_last.nchunks};
+    const unsigned gq = (unsigned)ceil_div(nq, DB_THREADS);
+    const int nbits = c.g.bx + c.g.by + c.g.bz + bits_for((uint64_t)g_last.nchunks);     // <= 64: not compressed
+    PCH_LAUNCH("dq_keys", dq_keys_k, dim3(gq), dim3(DB_THREADS), 0, s, P.Q, c.g, qw.k0, qw.v0);
+    PCH_TRY(radix_sort_pairs(qw.k0, qw.v0, qw.k1, qw.v1, nq, nbits, qw.radix_ws, s));
+    const bool in1 = radix_sort_result_buffer(nbits) == 1;
+    P.ks = in1 ? qw.k1 : qw.k0;
+    P.vs = in1 ? qw.v1 : qw.v0;
+    if (kdist) PCH_LAUNCH("dq_heads", dq_heads_k<DK_PIECE>, dim3(gq), dim3(DB_THREADS), 0, s, P.ks, nq, qw.flag);
+    else PCH_LAUNCH("dq_heads", dq_heads_k<DQ_PIECE>, dim3(gq), dim3(DB_THREADS), 0, s, P.ks, nq, qw.flag);
+    PCH_TRY(scan_exclusive_u32(qw.flag, qw.flag, nq, qw.scan_ws, qw.npieces, s));
+    if (kdist)
+        PCH_LAUNCH("dq_pieces", dq_pieces_k<DK_PIECE>, dim3(gq), dim3(DB_THREADS), 0, s, P.ks, nq, qw.flag, qw.piece_start);
+    else
+        PCH_LAUNCH("dq_pieces", dq_pieces_k<DQ_PIECE>, dim3(gq), dim3(DB_THREADS), 0, s, P.ks, nq, qw.flag, qw.piece_start);
+    P.piece_start = qw.piece_start;
+    P.npieces = qw.npieces;
+    return PCH_OK;
+}
+// pieces <= cells with queries + nq / PIECE; the host does not read the count: the waves stride over it
+static unsigned dq_piece_blocks(int64_t nq) {
+    return (unsigned)std::min(ceil_div(nq, (int64_t)DB_WAVES * 8), int64_t(16384));
+}
+
 extern "C" int pch_dbscan_assign_f32(const float* query, int64_t nq, const float* sub3_host, const int32_t* query_chunk,
                                      int64_t n, int32_t* out_labels, void* qws, size_t qws_bytes, void* ws,
                                      size_t ws_bytes, void* stream) {
@@ -3415,41 +3672,33 @@ extern "C" int pch_dbscan_assign_f32(const float* query, int64_t nq, const float
     PCH_REQUIRE(n >= 0, "bad argument");
     if (nq == 0) return PCH_OK;
     DbWs w;
-    PCH_TRY(db_continue(__func__, n, ws, ws_bytes, w));
-    PCH_REQUIRE(query && out_labels && qws, "null buffer");
-    if (g_last.compressed) {
-        set_error("%s: the fit took the compressed-coordinate path, which keeps no map from a coordinate to a cell",
-                  __func__);
-        return PCH_ERR_RANGE;
-    }
-    PCH_REQUIRE(query_chunk || g_last.nchunks == 1, "query_chunk is null but the fit has several chunks");
-    {
-        const char* a0 = static_cast<const char*>(qws);
-        const char* b0 = static_cast<const char*>(ws);
-        PCH_REQUIRE(!(a0 < b0 + ws_bytes && b0 < a0 + qws_bytes), "the query workspace overlaps the fit's workspace");
-    }
-    Arena qa(qws, qws_bytes);                     // (disjoint from the fit's workspace: the fit stays remembered)
-    DqWs qw;
-    dq_plan(qa, nq, qw);
-    if (qa.overflow) { set_error("query workspace too small: need %zu bytes", qa.off); return PCH_ERR_WORKSPACE; }
+    DqPieces P;
+    PCH_TRY(dq_pieces(__func__, query, nq, sub3_host, query_chunk, n, out_labels, qws, qws_bytes, ws, ws_bytes, s, false, w,
+                      P));
     const DbCells& c = g_last.c;
-    const DbQuery Q = {query, nq, sub3_host ? sub3_host[0] : 0.0f, sub3_host ? sub3_host[1] : 0.0f,
-                       sub3_host ? sub3_host[2] : 0.0f, query_chunk, g_last.nchunks};
-    const unsigned gq = (unsigned)ceil_div(nq, DB_THREADS);
-    const int nbits = c.g.bx + c.g.by + c.g.bz + bits_for((uint64_t)g_last.nchunks);     // <= 64: not compressed
-    PCH_LAUNCH("dq_keys", dq_keys_k, dim3(gq), dim3(DB_THREADS), 0, s, Q, c.g, qw.k0, qw.v0);
-    PCH_TRY(radix_sort_pairs(qw.k0, qw.v0, qw.k1, qw.v1, nq, nbits, qw.radix_ws, s));
-    const bool in1 = radix_sort_result_buffer(nbits) == 1;
-    const uint64_t* ks = in1 ? qw.k1 : qw.k0;
-    const uint32_t* vs = in1 ? qw.v1 : qw.v0;
-    PCH_LAUNCH("dq_heads", dq_heads_k, dim3(gq), dim3(DB_THREADS), 0, s, ks, nq, qw.flag);
-    PCH_TRY(scan_exclusive_u32(qw.flag, qw.flag, nq, qw.scan_ws, qw.npieces, s));
-    PCH_LAUNCH("dq_pieces", dq_pieces_k, dim3(gq), dim3(DB_THREADS), 0, s, ks, nq, qw.flag, qw.piece_start);
-    // pieces <= cells with queries + nq / DQ_PIECE; the host does not read the count: the waves stride over it
-    const unsigned ga = (unsigned)std::min(ceil_div(nq, (int64_t)DB_WAVES * 8), int64_t(16384));
-    PCH_LAUNCH("dq_assign", dq_assign_k, dim3(ga), dim3(DB_THREADS), 0, s, Q, c.g, c.pts, c.cell_start, c.cell_key,
-               c.core_s, c.cell_ncore, c.cell_box, (const int*)w.cell_label, ks, vs, qw.piece_start, qw.npieces,
-               out_labels);
+    PCH_LAUNCH("dq_assign", dq_assign_k, dim3(dq_piece_blocks(nq)), dim3(DB_THREADS), 0, s, P.Q, c.g, c.pts,
+               c.cell_start, c.cell_key, c.core_s, c.cell_ncore, c.cell_box, (const int*)w.cell_label, P.ks, P.vs,
+               P.piece_start, P.npieces, out_labels);
+    return PCH_OK;
+}
+
+extern "C" size_t pch_dbscan_kdist_ws_bytes(int64_t nq) { return pch_dbscan_assign_ws_bytes(nq); }
+
+extern "C" int pch_dbscan_kdist_f32(const float* query, int64_t nq, const float* sub3_host, const int32_t* query_chunk,
+                                    int32_t k, int64_t n, double* out_d2, int32_t* out_count, void* qws,
+                                    size_t qws_bytes, void* ws, size_t ws_bytes, void* stream) {
+    PCH_DEVICE_GUARD(out_d2 ? (const void*)out_d2 : (const void*)ws);
+    hipStream_t s = (hipStream_t)stream;
+    PCH_REQUIRE(k >= 1, "k must be >= 1");
+    PCH_REQUIRE(nq >= 0 && nq < (int64_t(1) << 31), "nq out of range [0, 2^31)");
+    PCH_REQUIRE(n >= 0, "bad argument");
+    if (nq == 0) return PCH_OK;
+    DbWs w;
+    DqPieces P;
+    PCH_TRY(dq_pieces(__func__, query, nq, sub3_host, query_chunk, n, out_d2, qws, qws_bytes, ws, ws_bytes, s, true, w, P));
+    const DbCells& c = g_last.c;
+    PCH_LAUNCH("dq_kdist", dq_kdist_k, dim3(dq_piece_blocks(nq)), dim3(DB_THREADS), 0, s, P.Q, c.g, c.pts,
+               c.cell_start, c.cell_key, P.ks, P.vs, P.piece_start, P.npieces, k, out_d2, out_count);
     return PCH_OK;
 }
 

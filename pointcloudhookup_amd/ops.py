@@ -944,6 +944,47 @@ class DbscanFit:
                                                _ptr(self.workspace), self.workspace.numel(), _stream()))
         return out
 
+    def kdist(self, query, k, sub=None, chunk=None, want_count=False):
+        """Squared distance (float64 [nq], device) from every float32 [nq,3] point to its ``k``-th nearest row of the
+        fit, core or not, exactly: the k-th smallest ``d2 <= eps*eps`` under the library's float64 predicate, ``+inf``
+        where fewer than ``k`` rows lie within the fit's eps (pch_dbscan_kdist_f32).  The answer is truncated at the
+        fit's eps: fit at the largest eps of interest with any min_samples, one fit then serves every ``k``.  ``sub``
+        and ``chunk`` as for ``assign``; ``chunk="own"`` says that the query is the fitted array itself (row i belongs
+        to chunk i // chunk_size; the row itself is then its own first neighbour at 0.0).  ``want_count``: also the
+        int32 [nq] number of rows within eps - on the fit's own rows ``core == (count >= min_samples)``.  Reads the
+        fit only and does not depend on labels.  Asynchronous."""
+        import ctypes as C
+        import numpy as np
+        if int(k) < 1:
+            raise ValueError("k must be at least 1")
+        own = isinstance(chunk, str)
+        if own and chunk != "own":
+            raise ValueError('chunk must be an int32 tensor, None or "own"')
+        query = _need_cuda(query, torch.float32, "query").reshape(-1, 3)
+        nq = query.shape[0]
+        if own:
+            if nq != self.n:
+                raise ValueError('chunk="own" needs the fitted array itself: one query row per fitted row')
+            chunk = None
+        elif chunk is not None:
+            chunk = _need_cuda(chunk, torch.int32, "chunk").reshape(-1)
+            if chunk.numel() != nq:
+                raise ValueError("chunk must name one chunk per query row")
+        with torch.cuda.device(self.device):
+            if own and self.chunk_size:
+                chunk = (torch.arange(nq, dtype=torch.int64, device=self.device) // self.chunk_size).to(torch.int32)
+            d2 = torch.empty((nq,), dtype=torch.float64, device=self.device)
+            count = torch.empty((nq,), dtype=torch.int32, device=self.device) if want_count else None
+            if nq:
+                L = _lib.lib()
+                s3 = None if sub is None else (C.c_float * 3)(*[float(np.float32(v)) for v in sub])
+                qws = torch.empty(int(L.pch_dbscan_kdist_ws_bytes(nq)) + 256, dtype=torch.uint8, device=self.device)
+                _lib.check(L.pch_dbscan_kdist_f32(_ptr(query), nq, None if s3 is None else C.cast(s3, C.c_void_p),
+                                                  _ptr(chunk), int(k), self.n, _ptr(d2), _ptr(count), _ptr(qws),
+                                                  qws.numel(), _ptr(self.workspace), self.workspace.numel(),
+                                                  _stream()))
+        return (d2, count) if want_count else d2
+
 
 def set_pair_counting(enable):
     """Counting variant of the radius-count kernel for the fits this thread makes from now on (measurement only)."""

@@ -159,6 +159,65 @@ def label_full_cloud(sampled_raw, full_raw, eps=8.0, min_points=80, chunk_size=0
     return out
 
 
+def kdistance_knee(y):
+    """The value of an ascending array furthest below the chord from its first to its last element: with
+    ``x_i = i/(m-1)`` and ``yn_i = (y_i - y_0)/(y_{m-1} - y_0)`` it is ``y[argmax(x - yn)]`` (first index on ties).
+    Fewer than 3 values: None; a constant array: that constant.  A hint where the k-distance plot bends, not a rule:
+    look at the quantiles and at ``core_share`` before setting eps by it."""
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    m = len(y)
+    if m < 3:
+        return None
+    if y[-1] == y[0]:
+        return float(y[0])
+    x = np.arange(m, dtype=np.float64) / (m - 1)
+    yn = (y - y[0]) / (y[-1] - y[0])
+    return float(y[int(np.argmax(x - yn))])
+
+
+def kdistance_profile(points, k=80, eps_max=16.0, chunk_size=REF_CHUNK, sample=200_000, seed=0,
+                      quantiles=(5, 25, 50, 75, 90, 95, 99), aabb=None):
+    """The k-distance plot of stage C's input, the instrument DBSCAN's authors give for choosing eps: for a seeded
+    sample of the rows, the exact distance to the k-th nearest row of the same file-order chunk (the row itself is
+    the first), sorted.  ``points``: the kept, centred float32 [N,3] rows of stage B on the device
+    (``cluster_points(...)["ground"]["points"]``).
+
+    One ``ops.DbscanFit(points, eps_max, k, chunk_size)``, ``min(sample, n)`` distinct rows drawn with
+    ``numpy.random.default_rng(seed)`` and sorted ascending, ``fit.kdist`` on them with their chunks; the square root
+    and the sort run on the host.  Distances beyond ``eps_max`` are not measured (``truncated`` counts them): raise
+    ``eps_max`` if too many are.  A row is core at ``(eps, k)`` exactly when its k-distance is <= eps, so the plot
+    read at eps gives the share of core rows (``core_share``).
+
+    Returns dict: k, eps_max, n, rows int64 [m]; kdist float64 metres, ascending, finite answers only; truncated
+    (answers that were +inf); count int32 [m] rows within eps_max of every sampled row; quantiles {q: np.percentile
+    of kdist} or None where there is no finite answer; knee (``kdistance_knee(kdist)``)."""
+    points = points.reshape(-1, 3)
+    n = points.shape[0]
+    fit = ops.DbscanFit(points, float(eps_max), int(k), int(chunk_size), aabb=aabb)
+    rows = np.sort(np.random.default_rng(seed).choice(n, min(int(sample), n), replace=False)).astype(np.int64)
+    idx = torch.from_numpy(rows).to(points.device)
+    chunk = (idx // fit.chunk_size).to(torch.int32) if fit.chunk_size else None
+    d2, count = fit.kdist(points[idx], int(k), chunk=chunk, want_count=True)
+    d2 = d2.cpu().numpy()
+    finite = np.isfinite(d2)
+    kdist = np.sort(np.sqrt(d2[finite]))
+    return dict(k=int(k), eps_max=float(eps_max), n=int(n), rows=rows, kdist=kdist,
+                truncated=int(len(d2) - finite.sum()), count=count.cpu().numpy(),
+                quantiles={q: float(np.percentile(kdist, q)) for q in quantiles} if len(kdist) else None,
+                knee=kdistance_knee(kdist))
+
+
+def core_share(profile, eps):
+    """Share of a profile's sampled rows that are core at ``(eps, profile["k"])``: the rows whose k-distance is <= eps.
+    ``eps`` beyond the profile's ``eps_max`` was not measured: ValueError."""
+    if float(eps) > profile["eps_max"]:
+        raise ValueError(f"eps {eps} lies beyond the profile's eps_max {profile['eps_max']}: profile again at a larger "
+                         f"eps_max")
+    if len(profile["rows"]) == 0:
+        return 0.0
+    return float(np.searchsorted(profile["kdist"], float(eps), side="right")) / len(profile["rows"])
+
+
 def north_angle_deg(rotation):
     """utils/tower_extraction.py:165-177."""
     hx, hy = float(rotation[0, 0]), float(rotation[1, 0])

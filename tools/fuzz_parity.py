@@ -45,6 +45,30 @@ def cloud(n):
     return X.astype(np.float32)
 
 
+def kdist_brute(X, Q, qc, eps, k, cs):
+    """pch_dbscan_kdist_f32 by all pairs: (k-th smallest float64 d2 <= eps*eps among the rows of the query's chunk, or
+    inf; how many there are), d2 accumulated in x, y, z order"""
+    n, r2 = len(X), float(eps) * float(eps)
+    d2 = np.full(len(Q), np.inf)
+    cnt = np.zeros(len(Q), dtype=np.int32)
+    fin = np.isfinite(Q).all(1)
+    for c in range(-(-n // cs)):
+        Xc = X[c * cs:(c + 1) * cs].astype(np.float64)
+        sel = np.flatnonzero((qc == c) & fin)
+        if not len(sel) or not np.isfinite(Xc).all():
+            continue
+        D = np.zeros((len(sel), len(Xc)))
+        for j in range(3):
+            t = Q[sel, j:j + 1].astype(np.float64) - Xc[None, :, j]
+            D += t * t
+        inside = D <= r2
+        cnt[sel] = inside.sum(1)
+        if k <= len(Xc):
+            D[~inside] = np.inf
+            d2[sel] = np.partition(D, k - 1, axis=1)[:, k - 1]
+    return d2, cnt
+
+
 it = 0
 t_say = time.time() + 30
 while time.time() < t_end:
@@ -99,6 +123,29 @@ while time.time() < t_end:
         assert np.array_equal(lab.cpu().numpy(), want), ("dbscan", n, m, eps, ms, chunk, it)
         assert k == (want.max() + 1 if (want >= 0).any() else 0)
         stats["dbscan"] += 1
+        # k-th neighbour distances on a retained fit: own rows, jittered rows and rows far outside, against all pairs;
+        # chunk ids of foreign queries are random, -1 and nchunks (both outside) included
+        cs = chunk if 0 < chunk < m else m
+        nchunks = -(-m // cs)
+        kk = int(rng.choice([1, 2, ms, ms + 1, 50, 300]))
+        own = rng.choice(m, min(m, 600), replace=False)
+        jit = pts[rng.choice(m, 300)] + rng.normal(0, 0.5 * eps, (300, 3)).astype(np.float32)
+        out = (pts[rng.choice(m, 50)].astype(np.float64) + rng.choice([-1.0, 1.0], (50, 3)) * 7.0 * eps).astype(np.float32)
+        Q = np.vstack([pts[own], jit, out])
+        qc = np.concatenate([own // cs, rng.integers(-1, nchunks + 1, 350)]).astype(np.int32)
+        fit = ops.DbscanFit(torch.from_numpy(pts).to(dev), eps, ms, chunk)
+        assert np.array_equal(fit.labels.cpu().numpy(), want), ("fit labels", n, m, eps, ms, chunk, it)
+        try:
+            gd, gc = fit.kdist(torch.from_numpy(Q).to(dev), kk, chunk=torch.from_numpy(qc).to(dev), want_count=True)
+        except PchError as e:                  # no grid to query: compressed coordinates (-4), per-chunk refits (-1)
+            assert e.code in (-1, -4), e
+            stats["kdist_refused"] = stats.get("kdist_refused", 0) + 1
+        else:
+            wd, wc = kdist_brute(pts, Q, qc, eps, kk, cs)
+            assert np.array_equal(gc.cpu().numpy(), wc), ("kdist count", n, m, eps, ms, chunk, kk, it)
+            assert np.array_equal(gd.cpu().numpy().view(np.uint64), wd.view(np.uint64)), ("kdist d2", n, m, eps, kk, it)
+            stats["kdist"] = stats.get("kdist", 0) + 1
+            stats["kdist_finite"] = stats.get("kdist_finite", 0) + int(np.isfinite(wd).sum())
         g2, l2, k2, perm, offs, st = ops.tower_clusters(torch.from_numpy(pts + ref["centroid"]).to(dev), eps, ms,
                                                         chunk if chunk else 50000)
         assert g2["count"] <= m
