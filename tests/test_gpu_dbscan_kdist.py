@@ -236,7 +236,8 @@ def test_a_chunk_holding_nan_answers_nothing(cuda):
 
 # ------------------------------------------------------------------ f. pieces
 def test_pieces_of_one_cell(cuda):
-    """65, 193 and 200 queries inside one cell each (two, four and four pieces of 64) and one query 200 times over;
+    """65, 193 and 200 queries inside one cell each (at least nine, twenty-five and twenty-five pieces of DK_PIECE = 8) and one query
+    200 times over;
     the answers do not depend on the order of the queries"""
     X = _bridge()[0]
     rng = np.random.default_rng(41)

@@ -23,7 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pointcloudhookup_amd import las, ops, pipeline, synth  # noqa: E402
 
 REF_EPS = 8.0
-DK_CAP = 1024                                  # keys a wave of dq_kdist_k keeps in LDS (pch_dbscan.hip)
+DK_CAP = 1024                                  # keys a wave of dq_kdist_k keeps in LDS (pch_dbscan_query.hip)
 
 
 def event_ms(fn):
