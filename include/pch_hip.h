@@ -474,6 +474,42 @@ int pch_dbscan_kdist_f32(const float* query, int64_t nq, const float* sub3_host,
                          int32_t k, int64_t n, double* out_d2, int32_t* out_count, void* qws, size_t qws_bytes,
                          void* ws, size_t ws_bytes, void* stream);
 
+/* What a neighbourhood looks like, against that same last fit: for every query the number of rows of the fit within
+ * `radius` and their first and second moments about the query - the input of the covariance features that tell a
+ * conductor (a line) from vegetation (a blob) and from a tower.  For query i:
+ *   q = fl32(query[i] - sub3) per component (sub3_host == NULL: no subtraction), c = query_chunk[i], exactly as for
+ *       pch_dbscan_kdist_f32;
+ *   d = (double)p - (double)q per component (dx, dy, dz); these differences are exact;
+ *   d2 = (dx*dx + dy*dy) + dz*dz in float64, accumulated in x, y, z order without FMA - the library's predicate;
+ *   R = the rows p of the fit in chunk c, core or not, with d2 <= radius*radius;
+ *   out_count[i] = |R|;
+ *   out_moments[i] = (Σdx, Σdy, Σdz, Σdx², Σdy², Σdz², Σdx·dy, Σdx·dz, Σdy·dz) over R, in float64.
+ * The moments are taken about the query, not the origin, so a covariance formed from them loses nothing at the scale
+ * of projected coordinates.  count is exact.  The order of summation is the library's own: with u = 2^-53 and n = count,
+ * each of the first three moments lies within 2(n+1)·u·n·radius and each of the six second moments within
+ * 2(n+1)·u·n·radius² of the sum taken in any other order.  Membership of R is decided by the float32 guard-band
+ * pre-filter and the float64 test, as everywhere else in stage C.
+ * radius must be finite, > 0 and <= the fit's eps (the grid reaches two cells): anything else is PCH_ERR_ARG.
+ * A query holding NaN or +-inf, a chunk index outside [0, nchunks) and a chunk that held NaN/inf give count 0 and nine
+ * zeros.  Labels play no part: before or after a relabel alike.
+ * query [nq,3] float32, query_chunk [nq] int32 or NULL (single-chunk fits only), out_count [nq] int32, out_moments
+ * [nq,9] float64 - all device; sub3_host 3 floats on the host or NULL.
+ * n, ws, ws_bytes, qws (>= pch_dbscan_shape_ws_bytes(nq) bytes), nq == 0, nq >= 2^31, compressed-coordinate fits
+ * (PCH_ERR_RANGE), refits and all-noise fits (PCH_ERR_ARG): as for pch_dbscan_assign_f32.
+ * Enqueues its work and returns; no host reads; the fit is only read, so the call may be repeated. */
+size_t pch_dbscan_shape_ws_bytes(int64_t nq);
+int pch_dbscan_shape_f32(const float* query, int64_t nq, const float* sub3_host, const int32_t* query_chunk,
+                         double radius, int64_t n, int32_t* out_count, double* out_moments /* [nq,9] */,
+                         void* qws, size_t qws_bytes, void* ws, size_t ws_bytes, void* stream);
+
+/* Covariance eigenvalues from those moments, one query per thread: n = max(count, 1), mu = M[0:3]/n,
+ * C = M2/n - mu mu^T (symmetric, not clamped: rounding may leave a tiny negative eigenvalue), eigen-decomposed by
+ * cyclic Jacobi in float64 (six sweeps over (0,1), (0,2), (1,2)).  out4[i] = (l1, l2, l3, v) with l1 >= l2 >= l3 and
+ * v = |e1.z|, the z component of the unit eigenvector of l1; for the zero matrix (count 0) e1 = (1,0,0) and v = 0.
+ * count [nq] int32, moments [nq,9] float64, out4 [nq,4] float64 - all device.  Needs no fit.  nq == 0 is success. */
+int pch_shape_features_f64(const int32_t* count, const double* moments, int64_t nq, double* out4 /* [nq,4] */,
+                           void* stream);
+
 /* One representative per LATTICE cell of up to two strips of a tile: the smallest row among the core points of the
  * cell whose x lies in the strip.  The lattice is shared by all ranks (cell = floor(coordinate / side) per axis, side =
  * eps / sqrt(3) * (1 - 2^-16), anchored at the origin of the common frame), so the two tiles on either side of an edge

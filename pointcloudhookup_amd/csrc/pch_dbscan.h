@@ -27,6 +27,18 @@ struct DbGrid {
     int     min_samples;
 };
 
+// The band of one radius r: r*r and the float32 pre-filter of db_within2 around it (2^-20 guard band, one float32
+// step further out).  The one place that forms it: DbGrid::eps2* from eps (db_grid), a query's radius (dq_shape_k).
+struct DbBand { double r2; float lo, hi; };
+inline DbBand db_band(double r) {
+    DbBand b;
+    b.r2 = r * r;
+    b.lo = nextafterf((float)(b.r2 * (1.0 - 1.0 / 1048576.0)), -INFINITY);
+    b.hi = nextafterf((float)(b.r2 * (1.0 + 1.0 / 1048576.0)), INFINITY);
+    if (!(b.hi < 3.0e38f)) { b.lo = -1.0f; b.hi = NAN; }    // absurd radius: exact path only
+    return b;
+}
+
 // (dy,dz) rows ordered by distance so that early exits trigger as soon as possible (static: a copy per
 // translation unit)
 static __constant__ int8_t DB_ROW_DY[DB_ROWS] = {0, 1, -1, 0, 0, 1, 1, -1, -1, 2, -2, 0, 0,
@@ -368,8 +380,9 @@ struct DbCells {
 #define DB_CELL_ARGS(c) DB_GRID_ARGS(c), (c).core_s, (c).cell_ncore, (c).cell_box
 
 // the run whose workspace the entries of pch_dbscan_query.hip continue, and its cell table
-// (nchunks and compressed: what pch_dbscan_assign_f32 needs to know about the grid beyond the cell table)
-struct DbLastRun { void* ws; size_t ws_bytes; int64_t n; DbCells c; int64_t nchunks; bool compressed; };
+// (nchunks and compressed: what pch_dbscan_assign_f32 needs to know about the grid beyond the cell table; eps: the
+// largest radius pch_dbscan_shape_f32 may ask for)
+struct DbLastRun { void* ws; size_t ws_bytes; int64_t n; DbCells c; int64_t nchunks; bool compressed; double eps; };
 extern thread_local DbLastRun g_last;
 
 // The entry points that continue the grid the last pch_dbscan_f32 of this thread left in `ws` carve it up again

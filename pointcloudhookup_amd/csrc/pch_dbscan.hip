@@ -1550,7 +1550,7 @@ static DbTuning db_tuning() {
 }
 
 // the retained fit of this thread: one per thread, dropped by ws_touched
-thread_local DbLastRun g_last = {nullptr, 0, 0, {}, 0, false};
+thread_local DbLastRun g_last = {nullptr, 0, 0, {}, 0, false, 0.0};
 
 void ws_touched(const void* base, size_t bytes) {
     if (!g_last.ws) return;
@@ -1629,10 +1629,8 @@ static bool db_grid(const DbRun& r, const float (&box)[6], double eps, int32_t m
     g.ox = box[0]; g.oy = box[1]; g.oz = box[2];
     g.cell = eps / 1.7320508075688772 * (1.0 - 1.0 / 65536.0);
     g.inv_cell = 1.0 / g.cell;
-    g.eps2 = eps * eps;
-    g.eps2_lo = nextafterf((float)(g.eps2 * (1.0 - 1.0 / 1048576.0)), -INFINITY);
-    g.eps2_hi = nextafterf((float)(g.eps2 * (1.0 + 1.0 / 1048576.0)), INFINITY);
-    if (!(g.eps2_hi < 3.0e38f)) { g.eps2_lo = -1.0f; g.eps2_hi = NAN; }    // absurd eps: exact path only
+    const DbBand band = db_band(eps);
+    g.eps2 = band.r2; g.eps2_lo = band.lo; g.eps2_hi = band.hi;
     g.chunk_size = r.chunk_size;
     g.chunk_bad = r.w.chunk_bad;
     g.chunk_cells = r.w.chunk_cells;
@@ -1855,7 +1853,7 @@ int pch::dbscan_run(const float* xyz, int64_t n, double eps, int32_t min_samples
     PCH_TRY(db_cells_core(r, g, cellbits, ks, staged, tune.count_pairs, c));
     PCH_TRY(db_union(r, c));
     PCH_TRY(db_labels(r, c, k_host, boxes));
-    g_last = {ws, ws_bytes, n, c, r.nchunks, overflow};
+    g_last = {ws, ws_bytes, n, c, r.nchunks, overflow, eps};
     return PCH_OK;
 }
 

@@ -1,6 +1,6 @@
 // Stage C, continuations of a retained fit: the calls that carve the workspace of this thread's last pch_dbscan_f32
 // up again (db_continue) and go on with its cell table - relabel, first core rows, pair statistics, strip pairs, and
-// the two that hold new points against the fit: assign and k-th neighbour distances.
+// the three that hold new points against the fit: assign, k-th neighbour distances and neighbourhood moments.
 #include "pch_dbscan.h"
 
 namespace pch {
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(DB_THREADS) void dq_keys_k(DbQuery Q, DbGrid g, uin
 
 // Pieces of the sorted queries: a piece starts where the key changes and at every multiple of PIECE, so it lies
 // inside one cell and holds at most PIECE queries (dq_assign_k: DQ_PIECE = 64, one query per lane; measured against 256
-// and 1024.  dq_kdist_k: DK_PIECE).  dq_heads_k writes the start flags (scanned in place),
+// and 1024.  dq_kdist_k: DK_PIECE, dq_shape_k: DS_PIECE).  dq_heads_k writes the start flags (scanned in place),
 // dq_pieces_k the first query of every piece and, behind the last one, nq.
 template <int PIECE>
 __device__ __forceinline__ bool dq_head(const uint64_t* __restrict__ keys, int64_t i) {
@@ -150,10 +150,11 @@ constexpr int DK_CAP = 1024;                 // in-range keys a wave keeps in LD
 constexpr int DK_PIECE = 8;                  // queries per piece: a query costs up to eight sweeps of its neighbourhood, so
                                              // short pieces, many waves (DESIGN.md section 5a has the figures)
 constexpr int DK_AHEAD = 4;                  // 64-candidate groups whose loads are in flight together (as DB_AHEAD)
+struct DkRuns { uint32_t seg_off[DB_ROWS + 1], seg_a[DB_ROWS]; };     // 204 bytes: all the LDS dq_shape_k's wave has
 struct DkWave {
     uint64_t buf[DK_CAP];
     uint32_t hist[256];
-    uint32_t seg_off[DB_ROWS + 1], seg_a[DB_ROWS];
+    DkRuns runs;
 };
 // LDS written by some lanes is read by others of the same wave: the wave's DS operations execute in order, the fence
 // and the barrier keep the compiler from reordering them
@@ -173,11 +174,32 @@ __device__ __forceinline__ void dk_tally(uint32_t* hist, bool on, uint32_t d, ui
         atomicAdd(&hist[d], 1u);
     }
 }
-// f(in, key) for every group of 64 candidates, called by all lanes: in = the lane holds a candidate with d2 <= eps2,
-// key = the bit pattern of its d2
+// The runs of the piece's cell `key` into W, numbered across: lanes 0..24 find one run each (db_row_run), a wave scan
+// numbers their rows.  Returns T, the number of candidates.
+__device__ __forceinline__ uint32_t dk_runs(const DbGrid& g, const uint32_t* __restrict__ cell_start,
+                                            const uint64_t* __restrict__ cell_key, uint64_t key, DkRuns& W) {
+    const int l = lane_id();
+    uint32_t a = 0, len = 0;
+    if (l < DB_ROWS) {
+        const int2 v = db_row_run(g, cell_key, key, l);
+        a = cell_start[v.x];
+        len = cell_start[v.y] - a;
+    }
+    const uint32_t incl = wave_scan_incl(len);
+    const uint32_t T = (uint32_t)__shfl((int)incl, 63, 64);
+    dk_sync();                                             // the piece before this one has read its runs
+    if (l < DB_ROWS) { W.seg_a[l] = a; W.seg_off[l + 1] = incl; }
+    if (l == 0) W.seg_off[0] = 0u;
+    dk_sync();
+    return T;
+}
+// f(in, key, dx, dy, dz) for every group of 64 candidates, called by all lanes: in = the lane holds a candidate with
+// d2 <= band.r2, key = the bit pattern of its d2, (dx, dy, dz) = candidate - query in float64 (exact: both are float32;
+// zeros where the lane holds no candidate or the float32 value already says outside).  d2 is db_d2's number: the
+// squares of p - q are those of q - p, and the sum runs in its order.
 template <typename F>
-__device__ __forceinline__ void dk_sweep(const DbGrid& g, const float4* __restrict__ pts, const DkWave& W, uint32_t T,
-                                         const float4& q, F&& f) {
+__device__ __forceinline__ void dk_sweep(const DbBand& band, const float4* __restrict__ pts, const DkRuns& W,
+                                         uint32_t T, const float4& q, F&& f) {
     const int l = lane_id();
     int r = 0;
     for (uint32_t t0 = 0; t0 < T; t0 += 64u * DK_AHEAD) {  // wave-uniform
@@ -196,15 +218,21 @@ __device__ __forceinline__ void dk_sweep(const DbGrid& g, const float4* __restri
             if (t0 + 64u * u >= T) break;                  // wave-uniform
             bool in = false;
             uint64_t key = 0;
+            double dx = 0.0, dy = 0.0, dz = 0.0;
             if (t0 + 64u * u + l < T) {
                 const float4 p = P[u];
-                if (!(db_d2f(q, p) >= g.eps2_hi)) {                   // (db_within2's band: d32 >= eps2_hi implies d64 > eps2)
-                    const double d2 = db_d2(q, p);
-                    in = d2 <= g.eps2;
+                if (!(db_d2f(q, p) >= band.hi)) {                     // (db_within2's band: d32 >= hi implies d64 > r2)
+                    dx = (double)p.x - (double)q.x;
+                    dy = (double)p.y - (double)q.y;
+                    dz = (double)p.z - (double)q.z;
+                    double d2 = dx * dx;
+                    d2 += dy * dy;
+                    d2 += dz * dz;
+                    in = d2 <= band.r2;
                     key = (uint64_t)__double_as_longlong(d2);
                 }
             }
-            f(in, key);
+            f(in, key, dx, dy, dz);
         }
     }
 }
@@ -215,8 +243,9 @@ __device__ __forceinline__ double dk_select(const DbGrid& g, const float4* __res
 #pragma unroll
     for (int u = 0; u < 4; ++u) W.hist[l + 64 * u] = 0u;
     dk_sync();
+    const DbBand band = {g.eps2, g.eps2_lo, g.eps2_hi};
     uint32_t count = 0;
-    dk_sweep(g, pts, W, T, q, [&](bool in, uint64_t key) {
+    dk_sweep(band, pts, W.runs, T, q, [&](bool in, uint64_t key, double, double, double) {
         const uint64_t m = __ballot(in);
         if (in) {
             const uint32_t pos = count + (uint32_t)__popcll(m & lanemask_lt());
@@ -253,7 +282,7 @@ __device__ __forceinline__ double dk_select(const DbGrid& g, const float4* __res
         for (int u = 0; u < 4; ++u) W.hist[l + 64 * u] = 0u;
         dk_sync();
         const int ns = shift - 8;
-        auto tally = [&](bool in, uint64_t key) {
+        auto tally = [&](bool in, uint64_t key, double = 0.0, double = 0.0, double = 0.0) {
             const bool on = in && (key >> shift) == (prefix >> shift);
             dk_tally(W.hist, on, (uint32_t)(key >> ns) & 255u, __ballot(on));
         };
@@ -263,7 +292,7 @@ __device__ __forceinline__ double dk_select(const DbGrid& g, const float4* __res
                 tally(in, in ? W.buf[i0 + l] : 0ull);
             }
         } else {
-            dk_sweep(g, pts, W, T, q, tally);
+            dk_sweep(band, pts, W.runs, T, q, tally);
         }
     }
     return __longlong_as_double((long long)prefix);
@@ -283,19 +312,7 @@ __global__ __launch_bounds__(DB_THREADS) void dq_kdist_k(DbQuery Q, DbGrid g, co
     const uint32_t np = *npieces;
     for (uint32_t p = blockIdx.x * DB_WAVES + wave_id(); p < np; p += gridDim.x * DB_WAVES) {   // wave-uniform
         const uint32_t ps = piece_start[p], pe = piece_start[p + 1];
-        const uint64_t key = keys[ps];
-        uint32_t a = 0, len = 0;
-        if (l < DB_ROWS) {
-            const int2 v = db_row_run(g, cell_key, key, l);
-            a = cell_start[v.x];
-            len = cell_start[v.y] - a;
-        }
-        const uint32_t incl = wave_scan_incl(len);
-        const uint32_t T = (uint32_t)__shfl((int)incl, 63, 64);
-        dk_sync();                                         // the piece before this one has read its runs
-        if (l < DB_ROWS) { W.seg_a[l] = a; W.seg_off[l + 1] = incl; }
-        if (l == 0) W.seg_off[0] = 0u;
-        dk_sync();
+        const uint32_t T = dk_runs(g, cell_start, cell_key, keys[ps], W.runs);
         for (uint32_t q0 = ps; q0 < pe; q0 += 64) {
             const bool have = q0 + l < pe;
             const uint32_t v = have ? vals[q0 + l] : DQ_OUT;
@@ -322,6 +339,124 @@ __global__ __launch_bounds__(DB_THREADS) void dq_kdist_k(DbQuery Q, DbGrid g, co
             }
         }
     }
+}
+
+// ---- what a neighbourhood looks like (pch_dbscan_shape_f32): count and the nine first and second moments of the
+// rows of the fit within `band` of every query, taken about the query.  dq_kdist_k's skeleton - pieces of DS_PIECE
+// queries of one cell, one wave per piece, the 25 runs numbered across (dk_runs), the queries handed round by readlane
+// - and its sweep (dk_sweep), once per query: a lane adds the nine terms of its in-range candidates into nine float64
+// registers, the count goes by ballot; nine wave butterflies, then lanes 0..8 store the sums side by side (72 bytes)
+// and lane 0 the count.  A query that has nobody in reach (DQ_OUT, or T == 0) stores zeros the same way.  There is no
+// dense-cell shortcut: a cell that is core as a whole has a count to give but no sums.  LDS: the run tables alone.
+// Nothing leaves the wave.
+#ifndef PCH_DS_PIECE
+#define PCH_DS_PIECE 8                       // tuning builds: make EXTRA=-DPCH_DS_PIECE=16 (DESIGN.md section 5b has the figures)
+#endif
+constexpr int DS_PIECE = PCH_DS_PIECE;       // as DK_PIECE: a crowded cell's queries go to many waves
+__global__ __launch_bounds__(DB_THREADS) void dq_shape_k(DbQuery Q, DbGrid g, DbBand band,
+                                                         const float4* __restrict__ pts,
+                                                         const uint32_t* __restrict__ cell_start,
+                                                         const uint64_t* __restrict__ cell_key,
+                                                         const uint64_t* __restrict__ keys,
+                                                         const uint32_t* __restrict__ vals,
+                                                         const uint32_t* __restrict__ piece_start,
+                                                         const uint32_t* __restrict__ npieces,
+                                                         int32_t* __restrict__ out_count, double* __restrict__ out_m) {
+    __shared__ DkRuns runs[DB_WAVES];
+    const int l = lane_id();
+    DkRuns& W = runs[wave_id()];
+    const uint32_t np = *npieces;
+    for (uint32_t p = blockIdx.x * DB_WAVES + wave_id(); p < np; p += gridDim.x * DB_WAVES) {   // wave-uniform
+        const uint32_t ps = piece_start[p], pe = piece_start[p + 1];
+        const uint32_t T = dk_runs(g, cell_start, cell_key, keys[ps], W);
+        for (uint32_t q0 = ps; q0 < pe; q0 += 64) {
+            const bool have = q0 + l < pe;
+            const uint32_t v = have ? vals[q0 + l] : DQ_OUT;
+            float4 mine;
+            mine.x = mine.y = mine.z = mine.w = 0.0f;
+            if (have && T != 0u && !(v & DQ_OUT)) mine = dq_point(Q, (int64_t)v);
+            const int cnt = (int)(pe - q0 < 64u ? pe - q0 : 64u);
+            for (int j = 0; j < cnt; ++j) {
+                const uint32_t vj = (uint32_t)__builtin_amdgcn_readlane((int)v, j);
+                double s[9];
+#pragma unroll
+                for (int a = 0; a < 9; ++a) s[a] = 0.0;
+                uint32_t count = 0;
+                if (T != 0u && !(vj & DQ_OUT)) {           // wave-uniform
+                    float4 qp;
+                    qp.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.x), j));
+                    qp.y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.y), j));
+                    qp.z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.z), j));
+                    qp.w = 0.0f;
+                    dk_sweep(band, pts, W, T, qp, [&](bool in, uint64_t, double dx, double dy, double dz) {
+                        count += (uint32_t)__popcll(__ballot(in));
+                        if (in) {
+                            s[0] += dx; s[1] += dy; s[2] += dz;
+                            s[3] += dx * dx; s[4] += dy * dy; s[5] += dz * dz;
+                            s[6] += dx * dy; s[7] += dx * dz; s[8] += dy * dz;
+                        }
+                    });
+#pragma unroll
+                    for (int a = 0; a < 9; ++a) s[a] = wave_reduce_add(s[a]);    // every lane holds every sum
+                }
+                double sl = s[0];
+#pragma unroll
+                for (int a = 1; a < 9; ++a) sl = l == a ? s[a] : sl;
+                const int64_t row = (int64_t)(vj & ~DQ_OUT);
+                if (l < 9) out_m[9 * row + l] = sl;
+                if (l == 0) out_count[row] = (int32_t)count;
+            }
+        }
+    }
+}
+
+// ---- eigenvalues of the neighbourhood's covariance from those moments (pch_shape_features_f64), one thread per
+// query: n = max(count, 1), mu = M[0:3]/n, C = M2/n - mu mu^T (symmetric, not clamped), then cyclic Jacobi in float64 -
+// SF_SWEEPS fixed sweeps over (0,1), (0,2), (1,2), every rotation branch-free.  A closed-form trigonometric solve loses
+// the small eigenvalue of a line, Jacobi's rotations do not.  Of the eigenvectors only the z row is carried: what is
+// asked for is |e1.z|.
+constexpr int SF_SWEEPS = 6;
+// one rotation that zeroes the (p, q) entry: app, aqq the diagonal, apq the entry, (arp, arq) the third row's entries
+// in columns p and q, (vp, vq) the z components of eigenvector columns p and q.  apq == 0 (and a ratio beyond the
+// range of float64, whose rotation would move nothing) gives the identity.
+__device__ __forceinline__ void sf_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& vp,
+                                          double& vq) {
+    const bool zero = apq == 0.0;
+    const double theta = (aqq - app) / (2.0 * (zero ? 1.0 : apq));
+    double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    t = zero ? 0.0 : t;
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    app -= t * apq;
+    aqq += t * apq;
+    apq = 0.0;
+    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
+    arp = rp; arq = rq;
+    const double wp = c * vp - s * vq, wq = s * vp + c * vq;
+    vp = wp; vq = wq;
+}
+__global__ __launch_bounds__(DB_THREADS) void sf_features_k(const int32_t* __restrict__ count,
+                                                            const double* __restrict__ M, int64_t nq,
+                                                            double* __restrict__ out4) {
+    const int64_t i = (int64_t)blockIdx.x * DB_THREADS + threadIdx.x;
+    if (i >= nq) return;
+    const int32_t cn = count[i];
+    const double n = (double)(cn > 1 ? cn : 1);
+    const double* m = M + 9 * i;
+    const double mx = m[0] / n, my = m[1] / n, mz = m[2] / n;
+    double a00 = m[3] / n - mx * mx, a11 = m[4] / n - my * my, a22 = m[5] / n - mz * mz;
+    double a01 = m[6] / n - mx * my, a02 = m[7] / n - mx * mz, a12 = m[8] / n - my * mz;
+    double v0 = 0.0, v1 = 0.0, v2 = 1.0;                   // the z row of V = I
+    for (int sweep = 0; sweep < SF_SWEEPS; ++sweep) {
+        sf_rotate(a00, a11, a01, a02, a12, v0, v1);
+        sf_rotate(a00, a22, a02, a01, a12, v0, v2);
+        sf_rotate(a11, a22, a12, a01, a02, v1, v2);
+    }
+    // descending, ties to the lower index: the zero matrix gives e1 = (1, 0, 0), v = 0
+    double l1 = a00, l2 = a11, l3 = a22, e1 = v0;
+    if (l2 > l1) { const double t = l1; l1 = l2; l2 = t; e1 = v1; }
+    if (l3 > l1) { const double t = l1; l1 = l3; l3 = t; e1 = v2; }
+    if (l3 > l2) { const double t = l2; l2 = l3; l3 = t; }
+    out4[4 * i + 0] = l1; out4[4 * i + 1] = l2; out4[4 * i + 2] = l3; out4[4 * i + 3] = fabs(e1);
 }
 
 // ---- relabelling with an external cluster map (cross-tile reconciliation, tiles.py): core points and
@@ -489,7 +624,7 @@ extern "C" size_t pch_dbscan_assign_ws_bytes(int64_t nq) {
     return a.off;
 }
 
-// What pch_dbscan_assign_f32 and pch_dbscan_kdist_f32 share: the checks of a query call against the fit `entry`
+// What pch_dbscan_assign_f32, pch_dbscan_kdist_f32 and pch_dbscan_shape_f32 share: the checks of a query call against the fit `entry`
 // continues (nq != 0, `out` its output), then the queries binned into the fit's cells, sorted and cut into pieces.
 struct DqPieces { DbQuery Q; const uint64_t* ks; const uint32_t* vs; const uint32_t *piece_start, *npieces; };
 template <int PIECE>
@@ -578,5 +713,43 @@ extern "C" int pch_dbscan_kdist_f32(const float* query, int64_t nq, const float*
     const DbCells& c = g_last.c;
     PCH_LAUNCH("dq_kdist", dq_kdist_k, dim3(dq_piece_blocks(nq)), dim3(DB_THREADS), 0, s, P.Q, c.g, c.pts,
                c.cell_start, c.cell_key, P.ks, P.vs, P.piece_start, P.npieces, k, out_d2, out_count);
+    return PCH_OK;
+}
+
+extern "C" size_t pch_dbscan_shape_ws_bytes(int64_t nq) { return pch_dbscan_assign_ws_bytes(nq); }
+
+extern "C" int pch_dbscan_shape_f32(const float* query, int64_t nq, const float* sub3_host, const int32_t* query_chunk,
+                                    double radius, int64_t n, int32_t* out_count, double* out_moments, void* qws,
+                                    size_t qws_bytes, void* ws, size_t ws_bytes, void* stream) {
+    PCH_DEVICE_GUARD(out_moments ? (const void*)out_moments : (const void*)ws);
+    hipStream_t s = (hipStream_t)stream;
+    PCH_REQUIRE(radius > 0.0 && radius <= 1.7e308, "radius must be finite and > 0");     // (NaN fails the first)
+    PCH_REQUIRE(nq >= 0 && nq < (int64_t(1) << 31), "nq out of range [0, 2^31)");
+    PCH_REQUIRE(n >= 0, "bad argument");
+    if (nq == 0) return PCH_OK;
+    PCH_REQUIRE(out_count != nullptr, "null buffer");
+    // the grid reaches two cells, which is the fit's eps: a larger radius would miss rows.  (Another workspace than
+    // the remembered fit's is dq_pieces' error.)
+    if (ws && g_last.ws == ws && !(radius <= g_last.eps)) {
+        set_error("%s: radius %g exceeds the fit's eps %g", __func__, radius, g_last.eps);
+        return PCH_ERR_ARG;
+    }
+    DbWs w;
+    DqPieces P;
+    PCH_TRY(dq_pieces<DS_PIECE>(__func__, query, nq, sub3_host, query_chunk, n, out_moments, qws, qws_bytes, ws, ws_bytes,
+                                s, w, P));
+    const DbCells& c = g_last.c;
+    PCH_LAUNCH("dq_shape", dq_shape_k, dim3(dq_piece_blocks(nq)), dim3(DB_THREADS), 0, s, P.Q, c.g, db_band(radius),
+               c.pts, c.cell_start, c.cell_key, P.ks, P.vs, P.piece_start, P.npieces, out_count, out_moments);
+    return PCH_OK;
+}
+
+extern "C" int pch_shape_features_f64(const int32_t* count, const double* moments, int64_t nq, double* out4,
+                                      void* stream) {
+    PCH_DEVICE_GUARD(out4);
+    PCH_REQUIRE(nq >= 0 && (nq == 0 || (count && moments && out4)), "bad argument");
+    if (nq == 0) return PCH_OK;
+    PCH_LAUNCH("sf_features", sf_features_k, dim3((unsigned)ceil_div(nq, DB_THREADS)), dim3(DB_THREADS), 0,
+               (hipStream_t)stream, count, moments, nq, out4);
     return PCH_OK;
 }

@@ -16,6 +16,7 @@ One function per reference library call:
   merge_clusters    <- merge of neighbouring clusters (opt-in) test/tttt.py:93-175
   upright_boxes     <- upright box per cluster (opt-in)      test/008.py:302-331 (axis-aligned there)
   crop_boxes        <- per-tower box masks over the cloud    test/kuangxuan.py:60-79, ui/extract.py:345-420
+Beyond the reference, on a retained fit (DbscanFit): assign, kdist, shape (+ shape_features) - DESIGN.md sections 5a, 5b.
 """
 from __future__ import annotations
 
@@ -864,7 +865,7 @@ class DbscanFit:
 
     def __init__(self, xyz, eps=8.0, min_samples=80, chunk_size=0, aabb=None):
         xyz = _need_cuda(xyz, torch.float32, "xyz").reshape(-1, 3)
-        self.n, self.device = xyz.shape[0], xyz.device
+        self.n, self.device, self.eps = xyz.shape[0], xyz.device, float(eps)
         self.chunk_size = int(chunk_size) if 0 < int(chunk_size) < self.n else 0      # 0: one fit over all rows
         with torch.cuda.device(self.device):
             nb = int(_lib.lib().pch_dbscan_ws_bytes(self.n)) + 256
@@ -984,6 +985,79 @@ class DbscanFit:
                                                   qws.numel(), _ptr(self.workspace), self.workspace.numel(),
                                                   _stream()))
         return (d2, count) if want_count else d2
+
+    def shape(self, query, radius, sub=None, chunk=None):
+        """(count int32 [nq], moments float64 [nq,9]), device: for every float32 [nq,3] point the number of rows of the
+        fit, core or not, within ``radius`` under the library's float64 predicate, and the sums ``(Σdx, Σdy, Σdz, Σdx²,
+        Σdy², Σdz², Σdx·dy, Σdx·dz, Σdy·dz)`` of their float64 differences ``row - query`` (pch_dbscan_shape_f32) -
+        moments about the query, so a covariance formed from them loses nothing at the scale of projected
+        coordinates; ``ops.shape_features`` turns them into eigenvalue features.  ``radius`` must be finite, > 0 and
+        <= the fit's eps (ValueError before any device call): fit at the radius of interest.  ``sub``, ``chunk`` and
+        ``chunk="own"`` as for ``kdist``.  Reads the fit only and does not depend on labels.  Asynchronous."""
+        import ctypes as C
+        import numpy as np
+        check_shape_radius(radius, self.eps)
+        own = isinstance(chunk, str)
+        if own and chunk != "own":
+            raise ValueError('chunk must be an int32 tensor, None or "own"')
+        query = _need_cuda(query, torch.float32, "query").reshape(-1, 3)
+        nq = query.shape[0]
+        if own:
+            if nq != self.n:
+                raise ValueError('chunk="own" needs the fitted array itself: one query row per fitted row')
+            chunk = None
+        elif chunk is not None:
+            chunk = _need_cuda(chunk, torch.int32, "chunk").reshape(-1)
+            if chunk.numel() != nq:
+                raise ValueError("chunk must name one chunk per query row")
+        with torch.cuda.device(self.device):
+            if own and self.chunk_size:
+                chunk = (torch.arange(nq, dtype=torch.int64, device=self.device) // self.chunk_size).to(torch.int32)
+            count = torch.empty((nq,), dtype=torch.int32, device=self.device)
+            moments = torch.empty((nq, 9), dtype=torch.float64, device=self.device)
+            if nq:
+                L = _lib.lib()
+                s3 = None if sub is None else (C.c_float * 3)(*[float(np.float32(v)) for v in sub])
+                qws = torch.empty(int(L.pch_dbscan_shape_ws_bytes(nq)) + 256, dtype=torch.uint8, device=self.device)
+                _lib.check(L.pch_dbscan_shape_f32(_ptr(query), nq, None if s3 is None else C.cast(s3, C.c_void_p),
+                                                  _ptr(chunk), float(radius), self.n, _ptr(count), _ptr(moments),
+                                                  _ptr(qws), qws.numel(), _ptr(self.workspace),
+                                                  self.workspace.numel(), _stream()))
+        return count, moments
+
+
+def check_shape_radius(radius, eps):
+    """ValueError unless ``radius`` is finite, > 0 and <= ``eps`` (the grid of a fit reaches its eps and no further).
+    Touches no device."""
+    import math
+    r = float(radius)
+    if not (math.isfinite(r) and r > 0.0):
+        raise ValueError(f"radius must be finite and > 0, got {radius!r}")
+    if r > float(eps):
+        raise ValueError(f"radius {r} exceeds the fit's eps {float(eps)}: fit at the largest radius of interest")
+    return r
+
+
+def shape_features(count, moments):
+    """Eigenvalue features of the neighbourhoods ``DbscanFit.shape`` summed up: dict of float64 [nq] device tensors
+    ``l1 >= l2 >= l3`` (eigenvalues of the covariance ``M2/n - mu mu^T``, cyclic Jacobi in float64,
+    pch_shape_features_f64), ``verticality`` (|z| of the unit eigenvector of l1) and the ratios ``linearity =
+    (l1-l2)/l1``, ``planarity = (l2-l3)/l1``, ``scattering = l3/l1``, which are 0 where ``l1 <= 0`` (an empty
+    neighbourhood, or a single row).  Asynchronous."""
+    count = _need_cuda(count, torch.int32, "count").reshape(-1)
+    moments = _need_cuda(moments, torch.float64, "moments").reshape(-1, 9)
+    nq = count.numel()
+    if moments.shape[0] != nq:
+        raise ValueError("moments must hold nine sums per count")
+    with torch.cuda.device(count.device):
+        out4 = torch.empty((nq, 4), dtype=torch.float64, device=count.device)
+        _lib.check(_lib.lib().pch_shape_features_f64(_ptr(count), _ptr(moments), nq, _ptr(out4), _stream()))
+    l1, l2, l3, v = out4.unbind(1)
+    ok = l1 > 0
+    den = torch.where(ok, l1, torch.ones_like(l1))
+    zero = torch.zeros_like(l1)
+    return dict(l1=l1, l2=l2, l3=l3, verticality=v, linearity=torch.where(ok, (l1 - l2) / den, zero),
+                planarity=torch.where(ok, (l2 - l3) / den, zero), scattering=torch.where(ok, l3 / den, zero))
 
 
 def set_pair_counting(enable):

@@ -18,7 +18,7 @@ REF_CHUNK = 50000          # utils/tower_extraction.py:96
 
 def cluster_points(raw, eps=8.0, min_points=80, chunk_size=REF_CHUNK, pct=25.0, offset=3.0,
                    fallback_offset=1.0, min_keep=1000, want_index=False, segment=True, ground="percentile",
-                   plane=None, merge_threshold=None):
+                   plane=None, merge_threshold=None, drop_linear=None):
     """Stages B + C + D0 on a float32 [N,3] device tensor.
 
     Returns dict: ground (ops.ground_filter result), labels int32 [N_f] (device), nclusters,
@@ -36,9 +36,17 @@ def cluster_points(raw, eps=8.0, min_points=80, chunk_size=REF_CHUNK, pct=25.0, 
     the reference's test/tttt.py uses 6.0).  labels / nclusters / perm / offsets / stats are then the merged ones and
     ``merge`` holds map, centers and nclusters_before; with ``segment=False`` the grouping is made internally and only
     the labels are returned.
+
+    ``drop_linear`` (opt-in; None = off, today's path and result): a dict of keyword arguments for ``drop_linear_rows``
+    (radius, linearity, verticality, min_rows; ``{}`` takes its defaults).  The kept rows whose neighbourhood is a
+    nearly horizontal line - conductors - are removed between stage B and stage C, so that they do not join the towers
+    of a line into one cluster; use it with ``chunk_size=0``, ``merge_threshold`` or any mode in which file-order
+    chunks no longer cut the line.  The percentile rule then goes the unfused way (ops.ground_filter, the drop,
+    ops.dbscan, ops.segment_by_label) as the plane rules do; ``ground`` holds the rows that are left (labels index
+    them) and the result gains ``drop_linear = dict(n_dropped, dropped)``, ``dropped`` a bool mask over stage B's rows.
     """
     out = _cluster_points(raw, eps, min_points, chunk_size, pct, offset, fallback_offset, min_keep, want_index,
-                          segment or merge_threshold is not None, ground, plane)
+                          segment or merge_threshold is not None, ground, plane, drop_linear)
     return out if merge_threshold is None else _merged(out, merge_threshold, segment)
 
 
@@ -56,24 +64,78 @@ def _merged(out, merge_threshold, segment):
     return out
 
 
+def drop_linear_rows(gf, radius=2.0, linearity=0.9, verticality=0.5, min_rows=10):
+    """Opt-in wire removal between stage B and stage C: drops the kept rows whose neighbourhood is a nearly horizontal
+    line - conductors, which otherwise join the towers of a line into one cluster that ``_accept`` rejects for its
+    width.  ``gf`` is a stage-B result (ops.ground_filter and its kin).  One global ``ops.DbscanFit(points, eps=radius,
+    min_samples=1, chunk_size=0)`` - the rule is geometric, so file-order chunks play no part, and fitting at the
+    radius keeps the neighbour block as small as the rule allows -, ``fit.shape`` on its own rows, ``ops.shape_features``,
+    and the mask ``linearity >= L and verticality <= V and count >= min_rows`` (count includes the row itself).
+
+    Returns a copy of ``gf`` whose ``points``, ``index`` (if present), ``count`` and ``aabb`` are those of the rows NOT
+    dropped, in file order, plus ``dropped`` (bool [old count], device) and ``n_dropped``.  Stage B kept no row, or the
+    fit left no grid to ask (coordinates so spread that it took the compressed-coordinate path, rows that are not
+    finite): raises with the cause - nothing is dropped silently.  Synchronises."""
+    ops.check_shape_radius(radius, radius)
+    points = gf["points"]
+    n = int(points.shape[0])
+    if n == 0:
+        raise ValueError("drop_linear_rows: stage B kept no rows, so there is no neighbourhood to look at")
+    fit = ops.DbscanFit(points, eps=float(radius), min_samples=1, chunk_size=0)
+    try:
+        count, moments = fit.shape(points, float(radius), chunk="own")
+    except RuntimeError as e:
+        raise RuntimeError(f"drop_linear_rows: the fit of {n} rows at eps = {float(radius)} left no grid to ask "
+                           f"(compressed coordinates or rows that are not finite), so no row was examined: {e}") from e
+    f = ops.shape_features(count, moments)
+    dropped = (f["linearity"] >= float(linearity)) & (f["verticality"] <= float(verticality)) & (count >= int(min_rows))
+    del fit
+    keep = ~dropped
+    kept = points[keep]                                        # masked select: file order
+    m = int(kept.shape[0])
+    out = dict(gf)
+    out.update(points=kept, count=m, dropped=dropped, n_dropped=n - m,
+               index=None if gf.get("index") is None else gf["index"][keep])
+    if m:
+        out["aabb"] = torch.cat([kept.min(0).values, kept.max(0).values]).cpu().numpy()
+    return out
+
+
+def _drop_then_dbscan(gf, drop_linear, eps, min_points, chunk_size, segment):
+    """stage C and D0 on a stage-B result the unfused way, the opt-in drop in between"""
+    info = None
+    if drop_linear is not None:
+        if gf["count"]:
+            gf = drop_linear_rows(gf, **drop_linear)
+            info = dict(n_dropped=gf["n_dropped"], dropped=gf["dropped"])
+        else:
+            info = dict(n_dropped=0, dropped=torch.zeros((0,), dtype=torch.bool, device=gf["points"].device))
+    points = gf["points"]
+    if gf["count"]:
+        labels, _, k = ops.dbscan(points, eps, min_points, chunk_size, aabb=gf["aabb"])
+    else:
+        labels, k = torch.empty((0,), dtype=torch.int32, device=points.device), 0
+    out = dict(ground=gf, labels=labels, nclusters=k)
+    if info is not None:
+        out["drop_linear"] = info
+    if segment:
+        perm, offsets, stats = ops.segment_by_label(labels, points, k)
+        out.update(perm=perm, offsets=offsets, stats=stats)
+    return out
+
+
 def _cluster_points(raw, eps, min_points, chunk_size, pct, offset, fallback_offset, min_keep, want_index, segment,
-                    ground, plane):
+                    ground, plane, drop_linear=None):
     if ground in ("plane", "plane_tiles"):
         kw = dict(offset=offset, fallback_offset=fallback_offset, min_keep=min_keep, want_index=want_index)
         kw.update(plane or {})
         gf = (ops.ground_filter_plane if ground == "plane" else ops.ground_filter_plane_tiles)(raw, **kw)
-        points = gf["points"]
-        if gf["count"]:
-            labels, _, k = ops.dbscan(points, eps, min_points, chunk_size, aabb=gf["aabb"])
-        else:
-            labels, k = torch.empty((0,), dtype=torch.int32, device=points.device), 0
-        out = dict(ground=gf, labels=labels, nclusters=k)
-        if segment:
-            perm, offsets, stats = ops.segment_by_label(labels, points, k)
-            out.update(perm=perm, offsets=offsets, stats=stats)
-        return out
+        return _drop_then_dbscan(gf, drop_linear, eps, min_points, chunk_size, segment)
     if ground != "percentile":
         raise ValueError(f"ground must be 'percentile', 'plane' or 'plane_tiles', got {ground!r}")
+    if drop_linear is not None:
+        gf = ops.ground_filter(raw, pct, offset, fallback_offset, min_keep, want_index=want_index)
+        return _drop_then_dbscan(gf, drop_linear, eps, min_points, chunk_size, segment)
     gf, labels, k, perm, offsets, stats = ops.tower_clusters(
         raw, eps, min_points, chunk_size, pct, offset, fallback_offset, min_keep,
         want_index=want_index, segment=segment)
@@ -100,24 +162,17 @@ def check_frame(frame, ground="percentile"):
 
 def cluster_points_las(XYZ, scales, offsets, eps=8.0, min_points=80, chunk_size=REF_CHUNK, pct=25.0, offset=3.0,
                        fallback_offset=1.0, min_keep=1000, want_index=False, segment=True, merge_threshold=None,
-                       ground="percentile"):
+                       ground="percentile", drop_linear=None):
     """Stages B + C + D0 in the LAS-integer frame (opt-in) on the int32 [N,3] LAS records of a device tensor:
     ops.ground_filter_las, then ops.dbscan with its box, ops.segment_by_label and the optional merge.  Returns the dict
     of ``cluster_points`` - ``tower_table`` and ``tower_table_async`` take it unchanged; ground["centroid"] is the
-    float64 world centroid.  ``ground`` exists to say no: a plane rule raises ValueError before any device call."""
+    float64 world centroid.  ``ground`` exists to say no: a plane rule raises ValueError before any device call.
+    ``drop_linear``: as for ``cluster_points`` (None = off)."""
     check_frame("las", ground)
     if ground != "percentile":
         raise ValueError(f"ground must be 'percentile' in the 'las' frame, got {ground!r}")
     gf = ops.ground_filter_las(XYZ, scales, offsets, pct, offset, fallback_offset, min_keep, want_index=want_index)
-    points = gf["points"]
-    if gf["count"]:
-        labels, _, k = ops.dbscan(points, eps, min_points, chunk_size, aabb=gf["aabb"])
-    else:
-        labels, k = torch.empty((0,), dtype=torch.int32, device=points.device), 0
-    out = dict(ground=gf, labels=labels, nclusters=k)
-    if segment or merge_threshold is not None:
-        perm, offsets_, stats = ops.segment_by_label(labels, points, k)
-        out.update(perm=perm, offsets=offsets_, stats=stats)
+    out = _drop_then_dbscan(gf, drop_linear, eps, min_points, chunk_size, segment or merge_threshold is not None)
     return out if merge_threshold is None else _merged(out, merge_threshold, segment)
 
 

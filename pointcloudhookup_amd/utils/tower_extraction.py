@@ -45,6 +45,12 @@ straight to ops.ground_filter_las: exact integer centroid, rows centred on the i
 points.astype(float64) + the float64 world centroid.  It logs one extra line with the integer centroid and its world
 coordinates.  It is defined for ``GROUND_MODE`` "percentile"; with a plane mode, or an unknown value, the run ends as
 a logged failure of the filter step before anything touches the device.
+``DROP_LINEAR`` (env PCH_DROP_LINEAR="radius,linearity,verticality,min_rows", e.g. "2,0.9,0.5,10"; unset or empty =
+off, the reference's behaviour): between the ground rule and the clustering, in every ground mode and frame, the kept
+rows whose neighbourhood of ``radius`` metres is a nearly horizontal line - conductors - are removed
+(pipeline.drop_linear_rows), so that they do not join the towers of a line into one cluster.  It
+logs one extra line with the number of rows removed; a failure of the step is logged and ends the run like a failure
+of the filter.
 """
 from __future__ import annotations
 
@@ -73,6 +79,29 @@ def merge_threshold_from_env(value):
 
 
 MERGE_THRESHOLD = merge_threshold_from_env(os.environ.get("PCH_MERGE_THRESHOLD"))
+
+
+def drop_linear_from_env(value):
+    """DROP_LINEAR of an environment value: None (off) when unset or empty, else the keyword arguments of
+    pipeline.drop_linear_rows from "radius,linearity,verticality,min_rows" - four numbers, no fewer and no more;
+    radius must be finite and > 0, linearity and verticality numbers, min_rows an integer >= 0 (ValueError)"""
+    if value is None or not value.strip():
+        return None
+    parts = [t.strip() for t in value.split(",")]
+    if len(parts) != 4:
+        raise ValueError(f"PCH_DROP_LINEAR takes \"radius,linearity,verticality,min_rows\", got {value!r}")
+    radius, linearity, verticality = (float(t) for t in parts[:3])
+    min_rows = int(parts[3])
+    if not (np.isfinite(radius) and radius > 0.0):
+        raise ValueError(f"PCH_DROP_LINEAR: radius must be finite and > 0, got {parts[0]!r}")
+    if np.isnan(linearity) or np.isnan(verticality):
+        raise ValueError(f"PCH_DROP_LINEAR: linearity and verticality must be numbers, got {value!r}")
+    if min_rows < 0:
+        raise ValueError(f"PCH_DROP_LINEAR: min_rows must be >= 0, got {parts[3]!r}")
+    return dict(radius=radius, linearity=linearity, verticality=verticality, min_rows=min_rows)
+
+
+DROP_LINEAR = drop_linear_from_env(os.environ.get("PCH_DROP_LINEAR"))
 PRESTART_BYTES = 100 << 20                             # LAS files from here on get worker processes early
 CHUNK_SIZE = 50000                                     # utils/tower_extraction.py:96
 
@@ -204,6 +233,17 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
         return tower_obbs
     del raw
 
+    # ---- opt-in: rows on a nearly horizontal line (conductors) leave before the clustering
+    if DROP_LINEAR:
+        try:
+            n_before = int(gf["count"])
+            gf = pipeline.drop_linear_rows(gf, **DROP_LINEAR)
+            clock.mark("neighbourhood shapes + drop of linear rows")
+            log(drop_linear_line(gf, n_before, DROP_LINEAR))
+        except Exception as e:
+            log(f"⚠️ 导线点剔除失败: {str(e)}")
+            return tower_obbs
+
     # ---- chunked clustering (reference :96-122); all chunks run in one device pass
     filtered = gf["points"]
     n_f = int(filtered.shape[0])
@@ -316,6 +356,12 @@ def frame_line(gf):
     ci, cw = gf["centroid_int"], gf["centroid"]
     return (f"📐 LAS整数坐标系: 整数质心 ({int(ci[0])}, {int(ci[1])}, {int(ci[2])})，"
             f"世界坐标 ({cw[0]:.3f}, {cw[1]:.3f}, {cw[2]:.3f})")
+
+
+def drop_linear_line(gf, n_before, knob):
+    """the extra log line of DROP_LINEAR for a result of pipeline.drop_linear_rows"""
+    return (f"🧹 导线点剔除: 半径 {knob['radius']:g} m，线性度 ≥ {knob['linearity']:g}，垂直度 ≤ {knob['verticality']:g}，"
+            f"邻域 ≥ {knob['min_rows']} 点；剔除 {int(gf['n_dropped'])}/{int(n_before)} 点")
 
 
 def ground_tiles_line(gf):

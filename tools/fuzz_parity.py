@@ -9,6 +9,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(1, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import shape_cases                                    # noqa: E402  (the all-pairs statement of the shape rule)
 from oracle import dbscan as odb                      # noqa: E402
 from oracle import ground_filter as ogf               # noqa: E402
 from oracle import voxel as ovx                       # noqa: E402
@@ -146,6 +148,17 @@ while time.time() < t_end:
             assert np.array_equal(gd.cpu().numpy().view(np.uint64), wd.view(np.uint64)), ("kdist d2", n, m, eps, kk, it)
             stats["kdist"] = stats.get("kdist", 0) + 1
             stats["kdist_finite"] = stats.get("kdist_finite", 0) + int(np.isfinite(wd).sum())
+            # neighbourhood moments on the same fit and queries at a random radius <= eps, against all pairs
+            # (tests/shape_cases.py): counts exactly, moments within the bound of two summation orders
+            radius = eps * float(rng.choice([1.0, 0.5, 0.25, rng.uniform(0.05, 1.0)]))
+            sc_, sm_ = fit.shape(torch.from_numpy(Q).to(dev), radius, chunk=torch.from_numpy(qc).to(dev))
+            wc, wm = shape_cases.shape_reference(pts, Q, radius, cs, qc)
+            assert np.array_equal(sc_.cpu().numpy(), wc), ("shape count", n, m, eps, radius, chunk, it)
+            over = np.abs(sm_.cpu().numpy() - wm) > shape_cases.moment_bounds(wc, radius)
+            assert not over.any(), ("shape moments", n, m, eps, radius, chunk, it, int(over.sum()))
+            stats["shape"] = stats.get("shape", 0) + 1
+            stats["shape_compared"] = stats.get("shape_compared", 0) + 10 * len(Q)
+            stats["shape_rows_in_reach"] = stats.get("shape_rows_in_reach", 0) + int(wc.sum())
         g2, l2, k2, perm, offs, st = ops.tower_clusters(torch.from_numpy(pts + ref["centroid"]).to(dev), eps, ms,
                                                         chunk if chunk else 50000)
         assert g2["count"] <= m
