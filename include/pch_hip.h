@@ -474,6 +474,35 @@ int pch_dbscan_kdist_f32(const float* query, int64_t nq, const float* sub3_host,
                          int32_t k, int64_t n, double* out_d2, int32_t* out_count, void* qws, size_t qws_bytes,
                          void* ws, size_t ws_bytes, void* stream);
 
+/* The k nearest rows of points against that same last fit: WHICH rows the neighbours are, where pch_dbscan_kdist_f32
+ * gives one distance - the input of statistical outlier removal, normals, a kNN graph.  For query i:
+ *   q, c, d2(q, p) and the set of rows in reach are exactly those of pch_dbscan_kdist_f32: q = fl32(query[i] - sub3),
+ *       c = query_chunk[i], d2 the float64 sum in x, y, z order without FMA, and
+ *   R = the rows of the fit in chunk c, core or not, with d2 <= eps*eps for the fit's own eps (the float32 guard band
+ *       comes first, as everywhere in stage C);
+ *   R is ordered by (d2, row) ascending, row being the original file-order row of the fit - the GLOBAL row, not a
+ *       chunk-local one.  Rows are unique, so the order is total, and the answer depends neither on the sorted copy's
+ *       order nor on PCH_DBSCAN_SORT;
+ *   out_rows[i, j] and out_d2[i, j] are element j of that order for j < min(k, |R|); every further slot holds -1 and
+ *       +inf; out_count[i] = |R|, and out_count may be NULL.
+ * A query holding NaN or +-inf, a chunk index outside [0, nchunks) and a chunk that held NaN/inf give count 0 and k empty
+ * slots.  On the fit's own rows slot 0 is the row itself at 0.0, unless a duplicate with a smaller row exists: then that
+ * duplicate comes first - the order decides, not identity.
+ * query [nq,3] float32, query_chunk [nq] int32 or NULL (single-chunk fits only), out_rows [nq,k] int32, out_d2 [nq,k]
+ * float64, out_count [nq] int32 or NULL - all device; sub3_host 3 floats on the host or NULL.
+ * 1 <= k <= PCH_KNN_MAX_K, anything else is PCH_ERR_ARG: the bound lets the answer of one query sit in a wave's LDS while
+ * it is ordered.
+ * n, ws, ws_bytes, qws (>= pch_dbscan_knn_ws_bytes(nq) bytes: too small PCH_ERR_WORKSPACE, overlapping the fit's
+ * PCH_ERR_ARG), nq == 0 (success), nq >= 2^31 (PCH_ERR_ARG), compressed-coordinate fits (PCH_ERR_RANGE), refits,
+ * all-noise fits and retired fits (PCH_ERR_ARG, the fit stays remembered): exactly as for pch_dbscan_kdist_f32.
+ * Labels play no part.  The answer is truncated at the fit's eps, so fit at the radius of interest; cost follows the
+ * fit's eps.  Enqueues its work and returns; no host reads; the fit is only read, so the call may be repeated. */
+#define PCH_KNN_MAX_K 256
+size_t pch_dbscan_knn_ws_bytes(int64_t nq);
+int pch_dbscan_knn_f32(const float* query, int64_t nq, const float* sub3_host, const int32_t* query_chunk,
+                       int32_t k, int64_t n, int32_t* out_rows /* [nq,k] */, double* out_d2 /* [nq,k] */,
+                       int32_t* out_count, void* qws, size_t qws_bytes, void* ws, size_t ws_bytes, void* stream);
+
 /* What a neighbourhood looks like, against that same last fit: for every query the number of rows of the fit within
  * `radius` and their first and second moments about the query - the input of the covariance features that tell a
  * conductor (a line) from vegetation (a blob) and from a tower.  For query i:

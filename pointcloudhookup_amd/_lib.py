@@ -77,6 +77,8 @@ _SIGS = {
     "pch_dbscan_assign_f32": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _sz, _vp, _sz, _vp]),
     "pch_dbscan_kdist_ws_bytes": (_sz, [_i64]),
     "pch_dbscan_kdist_f32": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "pch_dbscan_knn_ws_bytes": (_sz, [_i64]),
+    "pch_dbscan_knn_f32": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "pch_dbscan_shape_ws_bytes": (_sz, [_i64]),
     "pch_dbscan_shape_f32": (C.c_int, [_vp, _i64, _vp, _vp, _f64, _i64, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "pch_shape_features_f64": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),

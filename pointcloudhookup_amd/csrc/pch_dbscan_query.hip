@@ -1,6 +1,7 @@
 // Stage C, continuations of a retained fit: the calls that carve the workspace of this thread's last pch_dbscan_f32
 // up again (db_continue) and go on with its cell table - relabel, first core rows, pair statistics, strip pairs, and
-// the three that hold new points against the fit: assign, k-th neighbour distances and neighbourhood moments.
+// the four that hold new points against the fit: assign, k-th neighbour distances, neighbourhood moments and the k
+// nearest rows.
 #include "pch_dbscan.h"
 
 namespace pch {
@@ -193,10 +194,11 @@ __device__ __forceinline__ uint32_t dk_runs(const DbGrid& g, const uint32_t* __r
     dk_sync();
     return T;
 }
-// f(in, key, dx, dy, dz) for every group of 64 candidates, called by all lanes: in = the lane holds a candidate with
-// d2 <= band.r2, key = the bit pattern of its d2, (dx, dy, dz) = candidate - query in float64 (exact: both are float32;
-// zeros where the lane holds no candidate or the float32 value already says outside).  d2 is db_d2's number: the
-// squares of p - q are those of q - p, and the sum runs in its order.
+// f(in, key, dx, dy, dz, row) for every group of 64 candidates, called by all lanes: in = the lane holds a candidate
+// with d2 <= band.r2, key = the bit pattern of its d2, (dx, dy, dz) = candidate - query in float64 (exact: both are
+// float32; zeros where the lane holds no candidate or the float32 value already says outside), row = the candidate's
+// row in file order (the w of the sorted copy; 0 where the lane holds no candidate).  d2 is db_d2's number: the squares
+// of p - q are those of q - p, and the sum runs in its order.
 template <typename F>
 __device__ __forceinline__ void dk_sweep(const DbBand& band, const float4* __restrict__ pts, const DkRuns& W,
                                          uint32_t T, const float4& q, F&& f) {
@@ -232,20 +234,42 @@ __device__ __forceinline__ void dk_sweep(const DbBand& band, const float4* __res
                     key = (uint64_t)__double_as_longlong(d2);
                 }
             }
-            f(in, key, dx, dy, dz);
+            f(in, key, dx, dy, dz, __float_as_uint(P[u].w));
         }
     }
 }
-// the k-th smallest d2 <= eps2 among the T candidates of the wave's piece, +inf if there are fewer; count: how many
-__device__ __forceinline__ double dk_select(const DbGrid& g, const float4* __restrict__ pts, DkWave& W, uint32_t T,
-                                            const float4& q, int32_t k, int& count_out) {
+// The bin of W.hist that holds rank kk (1-based; the bins hold kk keys at least): its number, and kk becomes the rank
+// inside it.  The wave scans the 256 bins, four per lane.
+__device__ __forceinline__ uint32_t dk_pick(const DkWave& W, uint32_t& kk) {
+    const int l = lane_id();
+    dk_sync();
+    uint32_t h[4], sum = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { h[u] = W.hist[4 * l + u]; sum += h[u]; }
+    const uint32_t incl = wave_scan_incl(sum);
+    uint32_t e = incl - sum, digit = 0, knew = 0;
+    const bool mine = e < kk && kk <= incl;                // one lane
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if (mine && e < kk && kk <= e + h[u]) { digit = 4u * l + u; knew = kk - e; }
+        e += h[u];
+    }
+    const int src = __ffsll((unsigned long long)__ballot(mine)) - 1;
+    kk = (uint32_t)__shfl((int)knew, src, 64);
+    return (uint32_t)__shfl((int)digit, src, 64);
+}
+// the k-th smallest d2 <= eps2 among the T candidates of the wave's piece, +inf if there are fewer; count: how many.
+// Where count >= k, slots is the rank of the k-th among the candidates whose d2 equals the answer (1-based: k - slots
+// candidates lie below it), and W.hist is left holding the last pass: bin (answer & 255) says how many they are.
+__device__ __forceinline__ double dk_select_rank(const DbGrid& g, const float4* __restrict__ pts, DkWave& W, uint32_t T,
+                                                 const float4& q, int32_t k, int& count_out, uint32_t& slots) {
     const int l = lane_id();
 #pragma unroll
     for (int u = 0; u < 4; ++u) W.hist[l + 64 * u] = 0u;
     dk_sync();
     const DbBand band = {g.eps2, g.eps2_lo, g.eps2_hi};
     uint32_t count = 0;
-    dk_sweep(band, pts, W.runs, T, q, [&](bool in, uint64_t key, double, double, double) {
+    dk_sweep(band, pts, W.runs, T, q, [&](bool in, uint64_t key, double, double, double, uint32_t) {
         const uint64_t m = __ballot(in);
         if (in) {
             const uint32_t pos = count + (uint32_t)__popcll(m & lanemask_lt());
@@ -260,21 +284,7 @@ __device__ __forceinline__ double dk_select(const DbGrid& g, const float4* __res
     uint64_t prefix = 0;
     uint32_t kk = (uint32_t)k;                              // rank among the keys that share the prefix, 1-based
     for (int shift = 56;; shift -= 8) {
-        dk_sync();
-        uint32_t h[4], sum = 0;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { h[u] = W.hist[4 * l + u]; sum += h[u]; }
-        const uint32_t incl = wave_scan_incl(sum);
-        uint32_t e = incl - sum, digit = 0, knew = 0;
-        const bool mine = e < kk && kk <= incl;            // one lane: the bins hold kk keys at least
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (mine && e < kk && kk <= e + h[u]) { digit = 4u * l + u; knew = kk - e; }
-            e += h[u];
-        }
-        const int src = __ffsll((unsigned long long)__ballot(mine)) - 1;
-        digit = (uint32_t)__shfl((int)digit, src, 64);
-        kk = (uint32_t)__shfl((int)knew, src, 64);
+        const uint32_t digit = dk_pick(W, kk);
         prefix |= (uint64_t)digit << shift;
         if (shift == 0) break;
         dk_sync();                                         // every lane has read its bins
@@ -282,7 +292,7 @@ __device__ __forceinline__ double dk_select(const DbGrid& g, const float4* __res
         for (int u = 0; u < 4; ++u) W.hist[l + 64 * u] = 0u;
         dk_sync();
         const int ns = shift - 8;
-        auto tally = [&](bool in, uint64_t key, double = 0.0, double = 0.0, double = 0.0) {
+        auto tally = [&](bool in, uint64_t key, double = 0.0, double = 0.0, double = 0.0, uint32_t = 0u) {
             const bool on = in && (key >> shift) == (prefix >> shift);
             dk_tally(W.hist, on, (uint32_t)(key >> ns) & 255u, __ballot(on));
         };
@@ -295,7 +305,13 @@ __device__ __forceinline__ double dk_select(const DbGrid& g, const float4* __res
             dk_sweep(band, pts, W.runs, T, q, tally);
         }
     }
+    slots = kk;
     return __longlong_as_double((long long)prefix);
+}
+__device__ __forceinline__ double dk_select(const DbGrid& g, const float4* __restrict__ pts, DkWave& W, uint32_t T,
+                                            const float4& q, int32_t k, int& count_out) {
+    uint32_t slots;
+    return dk_select_rank(g, pts, W, T, q, k, count_out, slots);
 }
 
 __global__ __launch_bounds__(DB_THREADS) void dq_kdist_k(DbQuery Q, DbGrid g, const float4* __restrict__ pts,
@@ -336,6 +352,136 @@ __global__ __launch_bounds__(DB_THREADS) void dq_kdist_k(DbQuery Q, DbGrid g, co
             if (have) {
                 out_d2[v & ~DQ_OUT] = res;
                 if (out_count) out_count[v & ~DQ_OUT] = res_count;
+            }
+        }
+    }
+}
+
+// ---- the k nearest rows of every query among the rows of the fit (pch_dbscan_knn_f32): which rows the neighbours
+// are, in (d2, row) order.  dq_kdist_k's skeleton and its LDS, per query:
+//   * dk_select_rank gives tau, the k-th smallest d2, with count, and how the rows that tie at tau stand to the cut:
+//     `slots` of them belong to the answer, and the last bin of the select says how many they are.  count <= k:
+//     everything in reach is the answer;
+//   * only where more rows tie than there are slots a second MSB-first radix select runs, over the 32-bit rows of
+//     the candidates with d2 == tau, by sweeps (dk_select_row): rho, the largest row admitted.  Else rho is all ones;
+//   * one emit sweep: a candidate belongs to the answer iff d2 < tau, or d2 == tau and row <= rho - min(k, count) of
+//     them, compacted by ballot into (key, row) arrays.  The select is over by then, so the arrays lie in W.buf: the
+//     kernel has dq_kdist_k's LDS and no more.  Keeping rows beside the kept keys to spare this sweep where count <=
+//     DK_CAP would cost 4 KiB a wave and the fourth workgroup of a CU;
+//   * a rank sort in the wave - the (key, row) pairs are distinct, so a lane counts for each of its (at most four)
+//     entries how many entries are smaller and stores it there -, then the lanes store out_rows and out_d2 of the
+//     query as contiguous runs, the empty slots (-1, +inf) behind the answer.  A query with nobody in reach (DQ_OUT,
+//     or T == 0) stores k empty slots the same way.
+// Nothing leaves the wave: no global atomics, no waiting on another workgroup.
+constexpr int KNN_K = PCH_KNN_MAX_K;
+static_assert(3 * KNN_K <= DK_CAP && KNN_K % 64 == 0, "the unsorted and the sorted answer lie in DkWave::buf");
+// the slots-th smallest row (1-based) among the candidates whose d2 has the bit pattern tau
+__device__ __forceinline__ uint32_t dk_select_row(const DbBand& band, const float4* __restrict__ pts, DkWave& W,
+                                                  uint32_t T, const float4& q, uint64_t tau, uint32_t slots) {
+    const int l = lane_id();
+    uint32_t prefix = 0, kk = slots;
+    for (int shift = 24;; shift -= 8) {
+        dk_sync();                                         // every lane has read its bins
+#pragma unroll
+        for (int u = 0; u < 4; ++u) W.hist[l + 64 * u] = 0u;
+        dk_sync();
+        dk_sweep(band, pts, W.runs, T, q, [&](bool in, uint64_t key, double, double, double, uint32_t row) {
+            const bool on = in && key == tau && (shift == 24 || (row >> (shift + 8)) == (prefix >> (shift + 8)));
+            dk_tally(W.hist, on, (row >> shift) & 255u, __ballot(on));
+        });
+        prefix |= dk_pick(W, kk) << shift;
+        if (shift == 0) break;
+    }
+    return prefix;
+}
+
+__global__ __launch_bounds__(DB_THREADS) void dq_knn_k(DbQuery Q, DbGrid g, const float4* __restrict__ pts,
+                                                       const uint32_t* __restrict__ cell_start,
+                                                       const uint64_t* __restrict__ cell_key,
+                                                       const uint64_t* __restrict__ keys,
+                                                       const uint32_t* __restrict__ vals,
+                                                       const uint32_t* __restrict__ piece_start,
+                                                       const uint32_t* __restrict__ npieces, int32_t k,
+                                                       int32_t* __restrict__ out_rows, double* __restrict__ out_d2,
+                                                       int32_t* __restrict__ out_count) {
+    __shared__ DkWave waves[DB_WAVES];
+    const int l = lane_id();
+    DkWave& W = waves[wave_id()];
+    uint64_t* akey = W.buf;                                              // the answer as the emit sweep meets it
+    uint32_t* arow = reinterpret_cast<uint32_t*>(W.buf + KNN_K);
+    uint64_t* skey = W.buf + KNN_K + KNN_K / 2;                          // and in (d2, row) order
+    uint32_t* srow = reinterpret_cast<uint32_t*>(W.buf + 2 * KNN_K + KNN_K / 2);
+    const DbBand band = {g.eps2, g.eps2_lo, g.eps2_hi};
+    const uint32_t np = *npieces;
+    for (uint32_t p = blockIdx.x * DB_WAVES + wave_id(); p < np; p += gridDim.x * DB_WAVES) {   // wave-uniform
+        const uint32_t ps = piece_start[p], pe = piece_start[p + 1];
+        const uint32_t T = dk_runs(g, cell_start, cell_key, keys[ps], W.runs);
+        for (uint32_t q0 = ps; q0 < pe; q0 += 64) {
+            const bool have = q0 + l < pe;
+            const uint32_t v = have ? vals[q0 + l] : DQ_OUT;
+            float4 mine;
+            mine.x = mine.y = mine.z = mine.w = 0.0f;
+            if (have && T != 0u && !(v & DQ_OUT)) mine = dq_point(Q, (int64_t)v);
+            const int cnt = (int)(pe - q0 < 64u ? pe - q0 : 64u);
+            for (int j = 0; j < cnt; ++j) {
+                const uint32_t vj = (uint32_t)__builtin_amdgcn_readlane((int)v, j);
+                uint32_t m = 0;                            // slots of the answer that hold a row
+                int count = 0;
+                if (T != 0u && !(vj & DQ_OUT)) {           // wave-uniform
+                    float4 qp;
+                    qp.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.x), j));
+                    qp.y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.y), j));
+                    qp.z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.z), j));
+                    qp.w = 0.0f;
+                    uint32_t slots = 0;
+                    const double d = dk_select_rank(g, pts, W, T, qp, k, count, slots);
+                    uint64_t tau = ~0ull;                  // above every d2: all in reach
+                    uint32_t rho = ~0u;
+                    if (count > k) {
+                        tau = (uint64_t)__double_as_longlong(d);
+                        if (W.hist[tau & 255u] > slots) rho = dk_select_row(band, pts, W, T, qp, tau, slots);
+                    }
+                    dk_sync();                             // the selects have read buf and hist
+                    dk_sweep(band, pts, W.runs, T, qp, [&](bool in, uint64_t key, double, double, double, uint32_t row) {
+                        const bool take = in && (key < tau || (key == tau && row <= rho));
+                        const uint64_t mk = __ballot(take);
+                        const uint32_t pos = m + (uint32_t)__popcll(mk & lanemask_lt());
+                        if (take && pos < (uint32_t)KNN_K) { akey[pos] = key; arow[pos] = row; }   // (pos < k: never outside)
+                        m += (uint32_t)__popcll(mk);
+                    });
+                    m = m < (uint32_t)k ? m : (uint32_t)k;
+                    dk_sync();
+                    uint64_t ek[KNN_K / 64];
+                    uint32_t er[KNN_K / 64], rank[KNN_K / 64];
+#pragma unroll
+                    for (int u = 0; u < KNN_K / 64; ++u) {
+                        const uint32_t i = (uint32_t)l + 64u * u;
+                        ek[u] = i < m ? akey[i] : 0ull;
+                        er[u] = i < m ? arow[i] : 0u;
+                        rank[u] = 0u;
+                    }
+                    for (uint32_t t = 0; t < m; ++t) {     // wave-uniform: every lane reads the same entry
+                        const uint64_t kt = akey[t];
+                        const uint32_t rt = arow[t];
+#pragma unroll
+                        for (int u = 0; u < KNN_K / 64; ++u)
+                            rank[u] += (kt < ek[u] || (kt == ek[u] && rt < er[u])) ? 1u : 0u;
+                    }
+#pragma unroll
+                    for (int u = 0; u < KNN_K / 64; ++u) {
+                        if ((uint32_t)l + 64u * u < m && rank[u] < m) { skey[rank[u]] = ek[u]; srow[rank[u]] = er[u]; }
+                    }
+                    dk_sync();
+                }
+                const int64_t row = (int64_t)(vj & ~DQ_OUT);
+                for (uint32_t i = (uint32_t)l; i < (uint32_t)k; i += 64u) {
+                    const bool full = i < m;
+                    out_rows[row * k + i] = full ? (int32_t)srow[i] : -1;
+                    out_d2[row * k + i] = full ? __longlong_as_double((long long)skey[i])
+                                               : __longlong_as_double(0x7FF0000000000000ll);
+                }
+                if (out_count && l == 0) out_count[row] = count;
+                dk_sync();                                 // the next query's select writes buf
             }
         }
     }
@@ -388,7 +534,7 @@ __global__ __launch_bounds__(DB_THREADS) void dq_shape_k(DbQuery Q, DbGrid g, Db
                     qp.y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.y), j));
                     qp.z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.z), j));
                     qp.w = 0.0f;
-                    dk_sweep(band, pts, W, T, qp, [&](bool in, uint64_t, double dx, double dy, double dz) {
+                    dk_sweep(band, pts, W, T, qp, [&](bool in, uint64_t, double dx, double dy, double dz, uint32_t) {
                         count += (uint32_t)__popcll(__ballot(in));
                         if (in) {
                             s[0] += dx; s[1] += dy; s[2] += dz;
@@ -624,8 +770,8 @@ extern "C" size_t pch_dbscan_assign_ws_bytes(int64_t nq) {
     return a.off;
 }
 
-// What pch_dbscan_assign_f32, pch_dbscan_kdist_f32 and pch_dbscan_shape_f32 share: the checks of a query call against the fit `entry`
-// continues (nq != 0, `out` its output), then the queries binned into the fit's cells, sorted and cut into pieces.
+// What pch_dbscan_assign_f32, pch_dbscan_kdist_f32, pch_dbscan_knn_f32 and pch_dbscan_shape_f32 share: the checks of a
+// query call against the fit `entry` continues (nq != 0, `out` its output), then the queries binned into the fit's cells, sorted and cut into pieces.
 struct DqPieces { DbQuery Q; const uint64_t* ks; const uint32_t* vs; const uint32_t *piece_start, *npieces; };
 template <int PIECE>
 static int dq_pieces(const char* entry, const float* query, int64_t nq, const float* sub3_host,
@@ -713,6 +859,28 @@ extern "C" int pch_dbscan_kdist_f32(const float* query, int64_t nq, const float*
     const DbCells& c = g_last.c;
     PCH_LAUNCH("dq_kdist", dq_kdist_k, dim3(dq_piece_blocks(nq)), dim3(DB_THREADS), 0, s, P.Q, c.g, c.pts,
                c.cell_start, c.cell_key, P.ks, P.vs, P.piece_start, P.npieces, k, out_d2, out_count);
+    return PCH_OK;
+}
+
+extern "C" size_t pch_dbscan_knn_ws_bytes(int64_t nq) { return pch_dbscan_assign_ws_bytes(nq); }
+
+extern "C" int pch_dbscan_knn_f32(const float* query, int64_t nq, const float* sub3_host, const int32_t* query_chunk,
+                                  int32_t k, int64_t n, int32_t* out_rows, double* out_d2, int32_t* out_count,
+                                  void* qws, size_t qws_bytes, void* ws, size_t ws_bytes, void* stream) {
+    PCH_DEVICE_GUARD(out_d2 ? (const void*)out_d2 : (const void*)ws);
+    hipStream_t s = (hipStream_t)stream;
+    PCH_REQUIRE(k >= 1 && k <= PCH_KNN_MAX_K, "k out of range [1, PCH_KNN_MAX_K]");
+    PCH_REQUIRE(nq >= 0 && nq < (int64_t(1) << 31), "nq out of range [0, 2^31)");
+    PCH_REQUIRE(n >= 0, "bad argument");
+    if (nq == 0) return PCH_OK;
+    PCH_REQUIRE(out_rows != nullptr, "null buffer");
+    DbWs w;
+    DqPieces P;
+    PCH_TRY(dq_pieces<DK_PIECE>(__func__, query, nq, sub3_host, query_chunk, n, out_d2, qws, qws_bytes, ws, ws_bytes, s, w,
+                                P));
+    const DbCells& c = g_last.c;
+    PCH_LAUNCH("dq_knn", dq_knn_k, dim3(dq_piece_blocks(nq)), dim3(DB_THREADS), 0, s, P.Q, c.g, c.pts, c.cell_start,
+               c.cell_key, P.ks, P.vs, P.piece_start, P.npieces, k, out_rows, out_d2, out_count);
     return PCH_OK;
 }
 

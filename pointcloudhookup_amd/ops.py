@@ -16,7 +16,8 @@ One function per reference library call:
   merge_clusters    <- merge of neighbouring clusters (opt-in) test/tttt.py:93-175
   upright_boxes     <- upright box per cluster (opt-in)      test/008.py:302-331 (axis-aligned there)
   crop_boxes        <- per-tower box masks over the cloud    test/kuangxuan.py:60-79, ui/extract.py:345-420
-Beyond the reference, on a retained fit (DbscanFit): assign, kdist, shape (+ shape_features) - DESIGN.md sections 5a, 5b.
+Beyond the reference, on a retained fit (DbscanFit): assign, kdist, shape (+ shape_features), knn (+ knn_mean_distance) -
+DESIGN.md sections 5a, 5b, 5c.
 """
 from __future__ import annotations
 
@@ -986,6 +987,46 @@ class DbscanFit:
                                                   _stream()))
         return (d2, count) if want_count else d2
 
+    def knn(self, query, k, sub=None, chunk=None, want_count=False):
+        """(rows int32 [nq,k], d2 float64 [nq,k]), device: for every float32 [nq,3] point its ``k`` nearest rows of the
+        fit, core or not, among those within the fit's eps under the library's float64 predicate, in ``(d2, row)``
+        order - ``row`` the global file-order row of the fitted array, so ties go to the smaller row
+        (pch_dbscan_knn_f32).  Slots beyond the rows in reach hold ``-1`` and ``+inf``.  ``1 <= k <= ops.KNN_MAX_K``
+        (ValueError before any device call).  The answer is truncated at the fit's eps: fit at the radius of interest.
+        ``sub``, ``chunk`` and ``chunk="own"`` as for ``kdist`` (on the fit's own rows slot 0 is the row itself at 0.0,
+        unless a duplicate with a smaller row comes first).  ``want_count``: also the int32 [nq] number of rows within
+        eps.  Reads the fit only and does not depend on labels.  Asynchronous."""
+        import ctypes as C
+        import numpy as np
+        k = check_knn_k(k)
+        own = isinstance(chunk, str)
+        if own and chunk != "own":
+            raise ValueError('chunk must be an int32 tensor, None or "own"')
+        query = _need_cuda(query, torch.float32, "query").reshape(-1, 3)
+        nq = query.shape[0]
+        if own:
+            if nq != self.n:
+                raise ValueError('chunk="own" needs the fitted array itself: one query row per fitted row')
+            chunk = None
+        elif chunk is not None:
+            chunk = _need_cuda(chunk, torch.int32, "chunk").reshape(-1)
+            if chunk.numel() != nq:
+                raise ValueError("chunk must name one chunk per query row")
+        with torch.cuda.device(self.device):
+            if own and self.chunk_size:
+                chunk = (torch.arange(nq, dtype=torch.int64, device=self.device) // self.chunk_size).to(torch.int32)
+            rows = torch.empty((nq, k), dtype=torch.int32, device=self.device)
+            d2 = torch.empty((nq, k), dtype=torch.float64, device=self.device)
+            count = torch.empty((nq,), dtype=torch.int32, device=self.device) if want_count else None
+            if nq:
+                L = _lib.lib()
+                s3 = None if sub is None else (C.c_float * 3)(*[float(np.float32(v)) for v in sub])
+                qws = torch.empty(int(L.pch_dbscan_knn_ws_bytes(nq)) + 256, dtype=torch.uint8, device=self.device)
+                _lib.check(L.pch_dbscan_knn_f32(_ptr(query), nq, None if s3 is None else C.cast(s3, C.c_void_p),
+                                                _ptr(chunk), k, self.n, _ptr(rows), _ptr(d2), _ptr(count), _ptr(qws),
+                                                qws.numel(), _ptr(self.workspace), self.workspace.numel(), _stream()))
+        return (rows, d2, count) if want_count else (rows, d2)
+
     def shape(self, query, radius, sub=None, chunk=None):
         """(count int32 [nq], moments float64 [nq,9]), device: for every float32 [nq,3] point the number of rows of the
         fit, core or not, within ``radius`` under the library's float64 predicate, and the sums ``(Σdx, Σdy, Σdz, Σdx²,
@@ -1024,6 +1065,34 @@ class DbscanFit:
                                                   _ptr(qws), qws.numel(), _ptr(self.workspace),
                                                   self.workspace.numel(), _stream()))
         return count, moments
+
+
+KNN_MAX_K = 256                                  # PCH_KNN_MAX_K of include/pch_hip.h
+
+
+def check_knn_k(k):
+    """``k`` as an int; ValueError unless ``1 <= k <= KNN_MAX_K``.  Touches no device."""
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= KNN_MAX_K:
+        raise ValueError(f"k must be an integer in 1..{KNN_MAX_K}, got {k!r}")
+    return int(k)
+
+
+def knn_mean_distance(d2, count, k):
+    """float64 [nq]: the mean distance ``sum_j sqrt(d2[:, j]) / k`` over the first ``k`` slots of ``DbscanFit.knn``'s
+    answer where ``count >= k``, ``+inf`` elsewhere (fewer than ``k`` rows in reach).  Plain torch arithmetic on the
+    tensors' device; the ``+inf`` slots of short answers do not enter the sum."""
+    k = check_knn_k(k)
+    if not (isinstance(d2, torch.Tensor) and d2.dtype == torch.float64 and d2.dim() == 2):
+        raise TypeError("d2 must be a float64 [nq, k] tensor")
+    if not (isinstance(count, torch.Tensor) and count.dtype == torch.int32 and count.dim() == 1):
+        raise TypeError("count must be an int32 [nq] tensor")
+    if d2.shape[1] < k or count.shape[0] != d2.shape[0]:
+        raise ValueError(f"d2 must hold at least k = {k} slots per row and one row per count, got {tuple(d2.shape)} "
+                         f"for {count.shape[0]} counts")
+    full = count >= k
+    near = torch.where(full[:, None], d2[:, :k], torch.zeros((), dtype=torch.float64, device=d2.device))
+    mean = torch.sqrt(near).sum(dim=1) / float(k)
+    return torch.where(full, mean, torch.full((), float("inf"), dtype=torch.float64, device=d2.device))
 
 
 def check_shape_radius(radius, eps):

@@ -18,7 +18,7 @@ REF_CHUNK = 50000          # utils/tower_extraction.py:96
 
 def cluster_points(raw, eps=8.0, min_points=80, chunk_size=REF_CHUNK, pct=25.0, offset=3.0,
                    fallback_offset=1.0, min_keep=1000, want_index=False, segment=True, ground="percentile",
-                   plane=None, merge_threshold=None, drop_linear=None):
+                   plane=None, merge_threshold=None, drop_linear=None, drop_sparse=None):
     """Stages B + C + D0 on a float32 [N,3] device tensor.
 
     Returns dict: ground (ops.ground_filter result), labels int32 [N_f] (device), nclusters,
@@ -44,9 +44,16 @@ def cluster_points(raw, eps=8.0, min_points=80, chunk_size=REF_CHUNK, pct=25.0, 
     chunks no longer cut the line.  The percentile rule then goes the unfused way (ops.ground_filter, the drop,
     ops.dbscan, ops.segment_by_label) as the plane rules do; ``ground`` holds the rows that are left (labels index
     them) and the result gains ``drop_linear = dict(n_dropped, dropped)``, ``dropped`` a bool mask over stage B's rows.
+
+    ``drop_sparse`` (opt-in; None = off, today's path and result): a dict of keyword arguments for ``drop_sparse_rows``
+    (k, radius, std_ratio; ``{}`` takes its defaults).  The kept rows with fewer than k rows within the radius and those
+    whose mean distance to their k nearest rows is an outlier - stray returns, which otherwise become border points of
+    a tower and widen its box - are removed between stage B and stage C, the unfused way as for ``drop_linear``.  When
+    both drops are given the sparse rows go first and ``drop_linear`` sees what is left: ``drop_sparse = dict(n_dropped,
+    dropped, threshold)`` then has its mask over stage B's rows, ``drop_linear`` its mask over the rows left after it.
     """
     out = _cluster_points(raw, eps, min_points, chunk_size, pct, offset, fallback_offset, min_keep, want_index,
-                          segment or merge_threshold is not None, ground, plane, drop_linear)
+                          segment or merge_threshold is not None, ground, plane, drop_linear, drop_sparse)
     return out if merge_threshold is None else _merged(out, merge_threshold, segment)
 
 
@@ -90,6 +97,14 @@ def drop_linear_rows(gf, radius=2.0, linearity=0.9, verticality=0.5, min_rows=10
     f = ops.shape_features(count, moments)
     dropped = (f["linearity"] >= float(linearity)) & (f["verticality"] <= float(verticality)) & (count >= int(min_rows))
     del fit
+    return _kept_rows(gf, dropped)
+
+
+def _kept_rows(gf, dropped):
+    """the copy of the stage-B result ``gf`` without the rows of the bool mask ``dropped``, as the opt-in drops return
+    it: points, index (if present), count and aabb of the rows left, in file order, plus dropped and n_dropped"""
+    points = gf["points"]
+    n = int(points.shape[0])
     keep = ~dropped
     kept = points[keep]                                        # masked select: file order
     m = int(kept.shape[0])
@@ -101,8 +116,57 @@ def drop_linear_rows(gf, radius=2.0, linearity=0.9, verticality=0.5, min_rows=10
     return out
 
 
-def _drop_then_dbscan(gf, drop_linear, eps, min_points, chunk_size, segment):
-    """stage C and D0 on a stage-B result the unfused way, the opt-in drop in between"""
+def drop_sparse_rows(gf, k=8, radius=2.0, std_ratio=2.0):
+    """Opt-in removal of stray returns between stage B and stage C, the twin of ``drop_linear_rows``: drops the kept
+    rows that are isolated or sparse.  ``gf`` is a stage-B result.  One global ``ops.DbscanFit(points, eps=radius,
+    min_samples=1, chunk_size=0)``, ``fit.knn`` on its own rows (the row itself is counted among its neighbours), and
+    ``m = ops.knn_mean_distance``: the mean distance to the ``k`` nearest rows, ``+inf`` where fewer than ``k`` rows lie
+    within ``radius``.  Over the rows with ``count >= k``: ``mu = mean(m)``, ``sd`` the sample standard deviation (n - 1)
+    and ``thr = mu + std_ratio * sd``.  A row is dropped iff ``count < k`` (isolated) or ``m > thr`` (sparse); with fewer
+    than two rows of ``count >= k`` only the isolated rows are dropped and ``thr`` is ``+inf``.
+
+    Returns the copy of ``gf`` that ``drop_linear_rows`` returns (``points``, ``index``, ``count``, ``aabb``,
+    ``dropped``, ``n_dropped``) plus ``threshold`` (a float).  Stage B kept no row, or the fit left no grid to ask:
+    raises with the cause - nothing is dropped silently.  Synchronises."""
+    k = ops.check_knn_k(k)
+    ops.check_shape_radius(radius, radius)
+    if std_ratio != std_ratio:
+        raise ValueError("std_ratio must be a number, got NaN")
+    points = gf["points"]
+    n = int(points.shape[0])
+    if n == 0:
+        raise ValueError("drop_sparse_rows: stage B kept no rows, so there is no neighbourhood to look at")
+    fit = ops.DbscanFit(points, eps=float(radius), min_samples=1, chunk_size=0)
+    try:
+        _, d2, count = fit.knn(points, k, chunk="own", want_count=True)
+    except RuntimeError as e:
+        raise RuntimeError(f"drop_sparse_rows: the fit of {n} rows at eps = {float(radius)} left no grid to ask "
+                           f"(compressed coordinates or rows that are not finite), so no row was examined: {e}") from e
+    m = ops.knn_mean_distance(d2, count, k)
+    del fit
+    full = count >= k
+    dense = m[full]
+    threshold = float("inf")
+    nd = int(dense.shape[0])
+    if nd >= 2:                                                # two passes, sums of non-negative terms (DESIGN.md 5c)
+        mu = dense.sum() / nd
+        sd = torch.sqrt(((dense - mu) ** 2).sum() / (nd - 1))
+        threshold = float(mu + float(std_ratio) * sd)
+    out = _kept_rows(gf, ~full | (m > threshold))
+    out["threshold"] = threshold
+    return out
+
+
+def _drop_then_dbscan(gf, drop_linear, eps, min_points, chunk_size, segment, drop_sparse=None):
+    """stage C and D0 on a stage-B result the unfused way, the opt-in drops in between: sparse rows first"""
+    sparse = None
+    if drop_sparse is not None:
+        if gf["count"]:
+            gf = drop_sparse_rows(gf, **drop_sparse)
+            sparse = dict(n_dropped=gf["n_dropped"], dropped=gf["dropped"], threshold=gf["threshold"])
+        else:
+            sparse = dict(n_dropped=0, dropped=torch.zeros((0,), dtype=torch.bool, device=gf["points"].device),
+                          threshold=float("inf"))
     info = None
     if drop_linear is not None:
         if gf["count"]:
@@ -116,6 +180,8 @@ def _drop_then_dbscan(gf, drop_linear, eps, min_points, chunk_size, segment):
     else:
         labels, k = torch.empty((0,), dtype=torch.int32, device=points.device), 0
     out = dict(ground=gf, labels=labels, nclusters=k)
+    if sparse is not None:
+        out["drop_sparse"] = sparse
     if info is not None:
         out["drop_linear"] = info
     if segment:
@@ -125,17 +191,17 @@ def _drop_then_dbscan(gf, drop_linear, eps, min_points, chunk_size, segment):
 
 
 def _cluster_points(raw, eps, min_points, chunk_size, pct, offset, fallback_offset, min_keep, want_index, segment,
-                    ground, plane, drop_linear=None):
+                    ground, plane, drop_linear=None, drop_sparse=None):
     if ground in ("plane", "plane_tiles"):
         kw = dict(offset=offset, fallback_offset=fallback_offset, min_keep=min_keep, want_index=want_index)
         kw.update(plane or {})
         gf = (ops.ground_filter_plane if ground == "plane" else ops.ground_filter_plane_tiles)(raw, **kw)
-        return _drop_then_dbscan(gf, drop_linear, eps, min_points, chunk_size, segment)
+        return _drop_then_dbscan(gf, drop_linear, eps, min_points, chunk_size, segment, drop_sparse)
     if ground != "percentile":
         raise ValueError(f"ground must be 'percentile', 'plane' or 'plane_tiles', got {ground!r}")
-    if drop_linear is not None:
+    if drop_linear is not None or drop_sparse is not None:
         gf = ops.ground_filter(raw, pct, offset, fallback_offset, min_keep, want_index=want_index)
-        return _drop_then_dbscan(gf, drop_linear, eps, min_points, chunk_size, segment)
+        return _drop_then_dbscan(gf, drop_linear, eps, min_points, chunk_size, segment, drop_sparse)
     gf, labels, k, perm, offsets, stats = ops.tower_clusters(
         raw, eps, min_points, chunk_size, pct, offset, fallback_offset, min_keep,
         want_index=want_index, segment=segment)
@@ -162,17 +228,18 @@ def check_frame(frame, ground="percentile"):
 
 def cluster_points_las(XYZ, scales, offsets, eps=8.0, min_points=80, chunk_size=REF_CHUNK, pct=25.0, offset=3.0,
                        fallback_offset=1.0, min_keep=1000, want_index=False, segment=True, merge_threshold=None,
-                       ground="percentile", drop_linear=None):
+                       ground="percentile", drop_linear=None, drop_sparse=None):
     """Stages B + C + D0 in the LAS-integer frame (opt-in) on the int32 [N,3] LAS records of a device tensor:
     ops.ground_filter_las, then ops.dbscan with its box, ops.segment_by_label and the optional merge.  Returns the dict
     of ``cluster_points`` - ``tower_table`` and ``tower_table_async`` take it unchanged; ground["centroid"] is the
     float64 world centroid.  ``ground`` exists to say no: a plane rule raises ValueError before any device call.
-    ``drop_linear``: as for ``cluster_points`` (None = off)."""
+    ``drop_linear``, ``drop_sparse``: as for ``cluster_points`` (None = off)."""
     check_frame("las", ground)
     if ground != "percentile":
         raise ValueError(f"ground must be 'percentile' in the 'las' frame, got {ground!r}")
     gf = ops.ground_filter_las(XYZ, scales, offsets, pct, offset, fallback_offset, min_keep, want_index=want_index)
-    out = _drop_then_dbscan(gf, drop_linear, eps, min_points, chunk_size, segment or merge_threshold is not None)
+    out = _drop_then_dbscan(gf, drop_linear, eps, min_points, chunk_size, segment or merge_threshold is not None,
+                            drop_sparse)
     return out if merge_threshold is None else _merged(out, merge_threshold, segment)
 
 

@@ -51,6 +51,12 @@ rows whose neighbourhood of ``radius`` metres is a nearly horizontal line - cond
 (pipeline.drop_linear_rows), so that they do not join the towers of a line into one cluster.  It
 logs one extra line with the number of rows removed; a failure of the step is logged and ends the run like a failure
 of the filter.
+``DROP_SPARSE`` (env PCH_DROP_SPARSE="k,radius,std_ratio", e.g. "8,2,2"; unset or empty = off, the reference's
+behaviour): before ``DROP_LINEAR`` and the clustering, the kept rows with fewer than ``k`` rows within ``radius`` metres
+(the row itself counted) and those whose mean distance to their ``k`` nearest rows exceeds the mean of that figure by
+``std_ratio`` standard deviations - stray returns, which otherwise become border points of a tower and widen its box -
+are removed (pipeline.drop_sparse_rows).  It logs one extra line; a failure of the step is logged
+and ends the run like a failure of the filter.
 """
 from __future__ import annotations
 
@@ -102,6 +108,29 @@ def drop_linear_from_env(value):
 
 
 DROP_LINEAR = drop_linear_from_env(os.environ.get("PCH_DROP_LINEAR"))
+
+
+def drop_sparse_from_env(value):
+    """DROP_SPARSE of an environment value: None (off) when unset or empty, else the keyword arguments of
+    pipeline.drop_sparse_rows from "k,radius,std_ratio" - three numbers, no fewer and no more; k an integer in 1..256,
+    radius finite and > 0, std_ratio a number (ValueError)"""
+    if value is None or not value.strip():
+        return None
+    parts = [t.strip() for t in value.split(",")]
+    if len(parts) != 3:
+        raise ValueError(f"PCH_DROP_SPARSE takes \"k,radius,std_ratio\", got {value!r}")
+    k = int(parts[0])
+    radius, std_ratio = float(parts[1]), float(parts[2])
+    if not 1 <= k <= 256:
+        raise ValueError(f"PCH_DROP_SPARSE: k must be in 1..256, got {parts[0]!r}")
+    if not (np.isfinite(radius) and radius > 0.0):
+        raise ValueError(f"PCH_DROP_SPARSE: radius must be finite and > 0, got {parts[1]!r}")
+    if np.isnan(std_ratio):
+        raise ValueError(f"PCH_DROP_SPARSE: std_ratio must be a number, got {parts[2]!r}")
+    return dict(k=k, radius=radius, std_ratio=std_ratio)
+
+
+DROP_SPARSE = drop_sparse_from_env(os.environ.get("PCH_DROP_SPARSE"))
 PRESTART_BYTES = 100 << 20                             # LAS files from here on get worker processes early
 CHUNK_SIZE = 50000                                     # utils/tower_extraction.py:96
 
@@ -233,6 +262,17 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
         return tower_obbs
     del raw
 
+    # ---- opt-in: isolated and sparse rows (stray returns) leave first
+    if DROP_SPARSE:
+        try:
+            n_before = int(gf["count"])
+            gf = pipeline.drop_sparse_rows(gf, **DROP_SPARSE)
+            clock.mark("k nearest rows + drop of sparse rows")
+            log(drop_sparse_line(gf, n_before, DROP_SPARSE))
+        except Exception as e:
+            log(f"⚠️ 稀疏点剔除失败: {str(e)}")
+            return tower_obbs
+
     # ---- opt-in: rows on a nearly horizontal line (conductors) leave before the clustering
     if DROP_LINEAR:
         try:
@@ -362,6 +402,12 @@ def drop_linear_line(gf, n_before, knob):
     """the extra log line of DROP_LINEAR for a result of pipeline.drop_linear_rows"""
     return (f"🧹 导线点剔除: 半径 {knob['radius']:g} m，线性度 ≥ {knob['linearity']:g}，垂直度 ≤ {knob['verticality']:g}，"
             f"邻域 ≥ {knob['min_rows']} 点；剔除 {int(gf['n_dropped'])}/{int(n_before)} 点")
+
+
+def drop_sparse_line(gf, n_before, knob):
+    """the extra log line of DROP_SPARSE for a result of pipeline.drop_sparse_rows"""
+    return (f"🧹 稀疏点剔除: k = {knob['k']}，半径 {knob['radius']:g} m，标准差倍数 {knob['std_ratio']:g}，"
+            f"阈值 {float(gf['threshold']):.4f} m；剔除 {int(gf['n_dropped'])}/{int(n_before)} 点")
 
 
 def ground_tiles_line(gf):

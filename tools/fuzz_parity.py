@@ -10,6 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(1, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import knn_cases                                      # noqa: E402  (the all-pairs statement of the knn rule)
 import shape_cases                                    # noqa: E402  (the all-pairs statement of the shape rule)
 from oracle import dbscan as odb                      # noqa: E402
 from oracle import ground_filter as ogf               # noqa: E402
@@ -159,6 +160,16 @@ while time.time() < t_end:
             stats["shape"] = stats.get("shape", 0) + 1
             stats["shape_compared"] = stats.get("shape_compared", 0) + 10 * len(Q)
             stats["shape_rows_in_reach"] = stats.get("shape_rows_in_reach", 0) + int(wc.sum())
+            # the k nearest rows on the same fit and queries, against all pairs (tests/knn_cases.py): rows, d2 and
+            # count bit for bit
+            kn_k = int(rng.choice([1, 2, min(ms, 256), min(ms + 1, 256), 50, 256]))
+            kr, kd, kc_ = fit.knn(torch.from_numpy(Q).to(dev), kn_k, chunk=torch.from_numpy(qc).to(dev), want_count=True)
+            wr, wd, wc = knn_cases.knn_reference(pts, Q, eps, kn_k, cs, qc)
+            assert np.array_equal(kc_.cpu().numpy(), wc), ("knn count", n, m, eps, chunk, kn_k, it)
+            assert np.array_equal(kd.cpu().numpy().view(np.uint64), wd.view(np.uint64)), ("knn d2", n, m, eps, kn_k, it)
+            assert np.array_equal(kr.cpu().numpy(), wr), ("knn rows", n, m, eps, chunk, kn_k, it)
+            stats["knn"] = stats.get("knn", 0) + 1
+            stats["knn_slots_filled"] = stats.get("knn_slots_filled", 0) + int((wr >= 0).sum())
         g2, l2, k2, perm, offs, st = ops.tower_clusters(torch.from_numpy(pts + ref["centroid"]).to(dev), eps, ms,
                                                         chunk if chunk else 50000)
         assert g2["count"] <= m
