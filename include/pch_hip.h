@@ -613,6 +613,54 @@ size_t pch_cluster_merge_ws_bytes(int32_t nclusters);
 int pch_cluster_merge_f32(const float* centers, int32_t nclusters, double merge_threshold, int32_t* labels, int64_t n,
                           int32_t* out_map, int32_t* out_nmerged, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ conductor spans, opt-in
+ * The rows that the wire rule of section 5b marks are grouped into wire pieces (a global fit, then the grouping of
+ * stage D0); these calls reduce every piece to the sums from which a sag curve dz = a + b s + c s^2 is fitted.
+ *
+ * The rule.  P: float32 rows [*,3].  perm (int32) and offsets (int64 [K+1]) as the grouping call writes them; cluster k
+ * owns rows_k = perm[offsets[k]:offsets[k+1]], n_k = len(rows_k).  All arithmetic is float64 without FMA (the library
+ * is built with -ffp-contract=off), with parentheses exactly as written here.
+ *   1 moments (pch_cluster_moments_f32): o_k = P[rows_k[0]] in float32; d = (double)p - (double)o_k per component - this
+ *     difference is exact; out_count[k] = n_k (int64); out_origin[k] = o_k; out_moments[k] = (Σdx, Σdy, Σdz, Σdx², Σdy²,
+ *     Σdz², Σdx·dy, Σdx·dz, Σdy·dz) over rows_k, the order of terms of pch_dbscan_shape_f32.  An empty cluster gives
+ *     count 0 and twelve zeros.  Non-finite rows propagate as IEEE arithmetic propagates them.
+ *   2 frame (no kernel, float64 on K records; ops.span_frames): with n = max(n_k, 1): μ = M[0:3]/n; cxx = M[3]/n - μx²,
+ *     cyy = M[4]/n - μy², cxy = M[6]/n - μx·μy; θ = ½·atan2(2cxy, cxx - cyy), (ux, uy) = (cos θ, sin θ), negated when
+ *     ux < 0, or when ux == 0 and uy < 0; λ = ½(cxx + cyy) + hypot(½(cxx - cyy), cxy); h = sqrt(3·max(λ, 0)), and h = 1
+ *     where that is 0 (for rows spread evenly along a line h is half the length);
+ *     frame_k = (ox + μx, oy + μy, oz + μz, ux, uy, 1/h), six float64 values f0..f5.
+ *   3 profile (pch_cluster_profile_f32), frames [K,6] float64 on the device.  Per row: dx = (double)px - f0,
+ *     dy = (double)py - f1, dz = (double)pz - f2; s = ((dx*f3) + (dy*f4))*f5; t = (dy*f3) - (dx*f4); s2 = s*s;
+ *     out_sums[k] = (Σs, Σs2, Σ(s2*s), Σ(s2*s2), Σdz, Σ(s*dz), Σ(s2*dz), Σ(dz*dz), Σt, Σ(t*t));
+ *     out_ext[k] = (min s, max s, min dz, max dz) - exact: the per-row arithmetic is fixed and min/max do not round (a
+ *     NaN is never smaller or larger than anything and so is skipped).  An empty cluster gives ten zeros and
+ *     (+inf, -inf, +inf, -inf).
+ *   4 fit (no kernel, float64 on K records; ops.span_fit): the normal equations G x = r of dz ≈ a + b·s + c·s² with
+ *     G = [[n, S1, S2], [S1, S2, S3], [S2, S3, S4]], r = (Σdz, Σs·dz, Σs2·dz).
+ * The order of summation is the library's own.  With u = 2^-53, every sum S of terms t lies within 2(n_k+1)·u·Σ|t| of
+ * the same sum taken in any other order.  It is a function of offsets alone: the same input gives the same bits on
+ * every run (no floating-point atomics, no waiting on another workgroup).
+ *
+ * How: perm is swept in fixed blocks of 512 entries, one wave each, whatever the cluster sizes - the sweep's time is
+ * linear in the number of grouped rows, not in the largest cluster.  A wave reduces every (cluster, block) segment it
+ * holds and writes one partial; a second kernel adds a cluster's partials in ascending block order, one thread per
+ * term: that part IS a serial chain of n_k/512 additions for cluster k (about 0.2 ms for ten million rows).
+ *
+ * n_grouped = the number of entries of perm (< 2^31).  Entries at and behind offsets[K] - the noise rows of the
+ * grouping - belong to nobody.  perm entries are trusted to be rows of xyz.  xyz [*,3] float32; out_count [K] int64,
+ * out_origin [K,3] float32, out_moments [K,9] float64, frames [K,6] float64, out_sums [K,10] float64, out_ext [K,4]
+ * float64 - all device.  ws: the caller's, at least the matching *_ws_bytes(n_grouped, nclusters) bytes (smaller:
+ * PCH_ERR_WORKSPACE).  nclusters == 0 is success; a null output, negative sizes and host pointers are PCH_ERR_ARG.
+ * Enqueue and return; no host read. */
+size_t pch_cluster_moments_ws_bytes(int64_t n_grouped, int32_t nclusters);
+int pch_cluster_moments_f32(const float* xyz, const int32_t* perm, const int64_t* offsets, int64_t n_grouped,
+                            int32_t nclusters, int64_t* out_count, float* out_origin /* [K,3] */,
+                            double* out_moments /* [K,9] */, void* ws, size_t ws_bytes, void* stream);
+size_t pch_cluster_profile_ws_bytes(int64_t n_grouped, int32_t nclusters);
+int pch_cluster_profile_f32(const float* xyz, const int32_t* perm, const int64_t* offsets, int64_t n_grouped,
+                            int32_t nclusters, const double* frames /* [K,6] */, double* out_sums /* [K,10] */,
+                            double* out_ext /* [K,4] */, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ stage D1, fast mode
  * The reference boxes every cluster with trimesh (utils/tower_extraction.py:137-139:
  * trimesh.PointCloud(cluster_points).bounding_box_oriented): qhull's 3-D hull of the whole cluster, then a

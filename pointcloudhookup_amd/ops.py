@@ -17,7 +17,7 @@ One function per reference library call:
   upright_boxes     <- upright box per cluster (opt-in)      test/008.py:302-331 (axis-aligned there)
   crop_boxes        <- per-tower box masks over the cloud    test/kuangxuan.py:60-79, ui/extract.py:345-420
 Beyond the reference, on a retained fit (DbscanFit): assign, kdist, shape (+ shape_features), knn (+ knn_mean_distance) -
-DESIGN.md sections 5a, 5b, 5c.
+DESIGN.md sections 5a, 5b, 5c; on a grouping: cluster_moments, span_frames, cluster_profile, span_fit - section 5d.
 """
 from __future__ import annotations
 
@@ -1320,6 +1320,179 @@ def merge_clusters(xyz, labels, perm, offsets, nclusters, merge_threshold=6.0):
     perm2, offsets2, stats2 = segment_by_label(merged, xyz, k2)
     return dict(labels=merged, nclusters=k2, perm=perm2, offsets=offsets2, stats=stats2, map=cmap, centers=centers,
                 nclusters_before=K)
+
+
+# ------------------------------------------------------------- conductor spans, opt-in
+def _grouping(xyz, perm, offsets, nclusters):
+    xyz = _need_cuda(xyz, torch.float32, "xyz").reshape(-1, 3)
+    perm = _need_cuda(perm, torch.int32, "perm").reshape(-1)
+    offsets = _need_cuda(offsets, torch.int64, "offsets").reshape(-1)
+    K = int(nclusters)
+    if K < 0 or offsets.numel() != K + 1:
+        raise ValueError("offsets must hold nclusters + 1 entries")
+    return xyz, perm, offsets, K
+
+
+def cluster_moments(xyz, perm, offsets, nclusters):
+    """(count int64 [K], origin float32 [K,3], moments float64 [K,9]), device: per cluster of the grouped rows (perm /
+    offsets of ``segment_by_label``) its size, its first row ``o`` and the float64 sums ``(Σdx, Σdy, Σdz, Σdx², Σdy²,
+    Σdz², Σdx·dy, Σdx·dz, Σdy·dz)`` of the exact differences ``row - o`` (pch_cluster_moments_f32; the rule is in
+    include/pch_hip.h).  perm is swept in fixed blocks whatever the cluster sizes, so the time is linear in the number
+    of grouped rows; the same input gives the same bits on every run.  An empty cluster gives count 0 and zeros.
+    Asynchronous."""
+    L = _lib.lib()
+    xyz, perm, offsets, K = _grouping(xyz, perm, offsets, nclusters)
+    dev = offsets.device
+    n = perm.numel()
+    with torch.cuda.device(dev):
+        count = torch.empty((K,), dtype=torch.int64, device=dev)
+        origin = torch.empty((K, 3), dtype=torch.float32, device=dev)
+        moments = torch.empty((K, 9), dtype=torch.float64, device=dev)
+        ws = _workspace(L.pch_cluster_moments_ws_bytes(n, K), dev)
+        _lib.check(L.pch_cluster_moments_f32(_ptr(xyz), _ptr(perm), _ptr(offsets), n, K, _ptr(count), _ptr(origin),
+                                             _ptr(moments), _ptr(ws), ws.numel(), _stream()))
+    return count, origin, moments
+
+
+def span_frames(count, origin, moments):
+    """float64 [K,6] device: per cluster ``(cx, cy, cz, ux, uy, 1/h)`` - the centre ``origin + mean``, the unit
+    direction of the larger eigenvalue of the horizontal covariance (``ux > 0``, or ``ux == 0`` and ``uy > 0``) and the
+    reciprocal of ``h = sqrt(3 λ)``, half the length of rows spread evenly along a line (``h = 1`` where that is 0).
+    Step 2 of include/pch_hip.h's rule: float64 torch arithmetic on K records, no kernel.  Asynchronous."""
+    count = _need_cuda(count, torch.int64, "count").reshape(-1)
+    origin = _need_cuda(origin, torch.float32, "origin").reshape(-1, 3)
+    M = _need_cuda(moments, torch.float64, "moments").reshape(-1, 9)
+    if origin.shape[0] != count.numel() or M.shape[0] != count.numel():
+        raise ValueError("count, origin and moments must describe the same clusters")
+    return _span_frames_of(count, origin, M)
+
+
+def _span_frames_of(count, origin, M):
+    """span_frames' arithmetic, on tensors of any device"""
+    n = torch.clamp(count, min=1).to(torch.float64)
+    mu = M[:, 0:3] / n[:, None]
+    cxx = M[:, 3] / n - mu[:, 0] * mu[:, 0]
+    cyy = M[:, 4] / n - mu[:, 1] * mu[:, 1]
+    cxy = M[:, 6] / n - mu[:, 0] * mu[:, 1]
+    theta = 0.5 * torch.atan2(2.0 * cxy, cxx - cyy)
+    ux, uy = torch.cos(theta), torch.sin(theta)
+    flip = (ux < 0) | ((ux == 0) & (uy < 0))
+    ux, uy = torch.where(flip, -ux, ux), torch.where(flip, -uy, uy)
+    lam = 0.5 * (cxx + cyy) + torch.hypot(0.5 * (cxx - cyy), cxy)
+    h = torch.sqrt(3.0 * torch.clamp(lam, min=0.0))
+    h = torch.where(h == 0, torch.ones_like(h), h)
+    h = torch.where(torch.isnan(lam), lam, h)
+    c = origin.to(torch.float64) + mu
+    return torch.stack([c[:, 0], c[:, 1], c[:, 2], ux, uy, 1.0 / h], dim=1).contiguous()
+
+
+def cluster_profile(xyz, perm, offsets, nclusters, frames):
+    """(sums float64 [K,10], ext float64 [K,4]), device: per cluster, in the frame ``span_frames`` gave it, the sums
+    ``(Σs, Σs², Σs³, Σs⁴, Σdz, Σs·dz, Σs²·dz, Σdz², Σt, Σt²)`` of the scaled along-track coordinate ``s``, the height
+    ``dz`` above the centre and the across-track offset ``t``, and ``(min s, max s, min dz, max dz)``, which are exact
+    (pch_cluster_profile_f32; the rule is in include/pch_hip.h).  The same sweep as ``cluster_moments``.  An empty
+    cluster gives zeros and ``(+inf, -inf, +inf, -inf)``.  Asynchronous."""
+    L = _lib.lib()
+    xyz, perm, offsets, K = _grouping(xyz, perm, offsets, nclusters)
+    frames = _need_cuda(frames, torch.float64, "frames").reshape(-1, 6)
+    if frames.shape[0] != K:
+        raise ValueError("frames must hold six values per cluster")
+    dev = offsets.device
+    n = perm.numel()
+    with torch.cuda.device(dev):
+        sums = torch.empty((K, 10), dtype=torch.float64, device=dev)
+        ext = torch.empty((K, 4), dtype=torch.float64, device=dev)
+        ws = _workspace(L.pch_cluster_profile_ws_bytes(n, K), dev)
+        _lib.check(L.pch_cluster_profile_f32(_ptr(xyz), _ptr(perm), _ptr(offsets), n, K, _ptr(frames), _ptr(sums),
+                                             _ptr(ext), _ptr(ws), ws.numel(), _stream()))
+    return sums, ext
+
+
+SPAN_TABLE_KEYS = ("count", "centre", "direction", "azimuth_deg", "length", "a", "b", "c", "sag", "z_low", "rms_z",
+                   "rms_t", "cond")
+
+
+def _sym3_extreme_eigenvalues(a11, a12, a13, a22, a23, a33):
+    """(largest, smallest) eigenvalue of symmetric 3x3 matrices given by their entries (the trigonometric closed form)"""
+    import math
+    q = (a11 + a22 + a33) / 3.0
+    p1 = a12 * a12 + a13 * a13 + a23 * a23
+    p2 = (a11 - q) ** 2 + (a22 - q) ** 2 + (a33 - q) ** 2 + 2.0 * p1
+    p = torch.sqrt(p2 / 6.0)
+    ps = torch.where(p > 0, p, torch.ones_like(p))
+    b11, b22, b33, b12, b13, b23 = (a11 - q) / ps, (a22 - q) / ps, (a33 - q) / ps, a12 / ps, a13 / ps, a23 / ps
+    det = b11 * (b22 * b33 - b23 * b23) - b12 * (b12 * b33 - b23 * b13) + b13 * (b12 * b23 - b22 * b13)
+    phi = torch.acos(torch.clamp(0.5 * det, -1.0, 1.0)) / 3.0
+    hi = q + 2.0 * p * torch.cos(phi)
+    lo = q + 2.0 * p * torch.cos(phi + 2.0 * math.pi / 3.0)
+    return hi, lo
+
+
+def span_fit(count, frames, sums, ext):
+    """The span table: a dict of device tensors over the K clusters, from ``cluster_profile``'s sums - the least-squares
+    parabola ``dz ≈ a + b·s + c·s²`` through the normal equations (step 4 of include/pch_hip.h's rule; float64 torch
+    arithmetic on K records, no kernel):
+
+    ``count`` int64; ``centre`` [K,3] and ``direction`` [K,2] (the frame's); ``azimuth_deg`` = atan2(uy, ux) in
+    degrees, from +x towards +y, in (-90, 90]; ``length`` = (max s - min s)·h in metres (0 for an empty cluster);
+    ``a`` (metres), ``b`` (per metre), ``c`` (per metre²): the curve over the along-track distance from the centre in
+    metres, heights above ``centre[2]``; ``sag`` = |c|·(length/2)²; ``z_low``: the curve's lowest height inside the
+    piece, absolute; ``rms_z`` and ``rms_t``: the residual of the curve and the across-track spread, metres; ``cond``:
+    the 2-norm condition number of the normal matrix (about 14 for rows spread evenly; +inf for a singular one).  Pieces of fewer than three
+    rows and pieces whose normal matrix is singular (determinant or smallest eigenvalue not > 0) have NaN in a, b, c, sag, z_low, rms_z."""
+    count = _need_cuda(count, torch.int64, "count").reshape(-1)
+    F = _need_cuda(frames, torch.float64, "frames").reshape(-1, 6)
+    S = _need_cuda(sums, torch.float64, "sums").reshape(-1, 10)
+    E = _need_cuda(ext, torch.float64, "ext").reshape(-1, 4)
+    K = count.numel()
+    if F.shape[0] != K or S.shape[0] != K or E.shape[0] != K:
+        raise ValueError("count, frames, sums and ext must describe the same clusters")
+    return _span_fit_of(count, F, S, E)
+
+
+def _span_fit_of(count, F, S, E):
+    """span_fit's arithmetic, on tensors of any device"""
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=count.device)
+    n = count.to(torch.float64)
+    n1 = torch.clamp(count, min=1).to(torch.float64)
+    S1, S2, S3, S4 = S[:, 0], S[:, 1], S[:, 2], S[:, 3]
+    r0, r1, r2, szz, st, stt = S[:, 4], S[:, 5], S[:, 6], S[:, 7], S[:, 8], S[:, 9]
+    # G = [[n, S1, S2], [S1, S2, S3], [S2, S3, S4]]: cofactors, determinant along the first row
+    c00 = S2 * S4 - S3 * S3
+    c01 = S2 * S3 - S1 * S4
+    c02 = S1 * S3 - S2 * S2
+    c11 = n * S4 - S2 * S2
+    c12 = S1 * S2 - n * S3
+    c22 = n * S2 - S1 * S1
+    det = (n * c00 + S1 * c01) + S2 * c02
+    hi, lo = _sym3_extreme_eigenvalues(n, S1, S2, S2, S3, S4)
+    pd = (det > 0) & (lo > 0)                                  # the normal matrix is positive definite
+    ok = (count >= 3) & pd
+    d = torch.where(ok, det, torch.ones_like(det))
+    a = torch.where(ok, ((c00 * r0 + c01 * r1) + c02 * r2) / d, nan)
+    b = torch.where(ok, ((c01 * r0 + c11 * r1) + c12 * r2) / d, nan)
+    c = torch.where(ok, ((c02 * r0 + c12 * r1) + c22 * r2) / d, nan)
+    cond = torch.where(pd, hi / torch.where(pd, lo, torch.ones_like(lo)), torch.full_like(hi, float("inf")))
+    h = 1.0 / F[:, 5]
+    smin, smax = E[:, 0], E[:, 1]
+    has = count > 0
+    zero = torch.zeros_like(n)
+    width = torch.where(has, smax - smin, zero)
+    # the lowest point of the curve inside [smin, smax]: an end, or the vertex when it is a minimum and lies inside
+    def curve(s):
+        return a + s * (b + c * s)
+    sv = -b / (2.0 * torch.where(c > 0, c, torch.ones_like(c)))
+    inside = (c > 0) & (sv >= smin) & (sv <= smax)
+    ends = torch.minimum(curve(smin), curve(smax))
+    low = torch.where(inside, torch.minimum(ends, curve(torch.where(inside, sv, zero))), ends)
+    res = szz - ((a * r0 + b * r1) + c * r2)
+    mt = st / n1
+    return dict(count=count, centre=F[:, 0:3].contiguous(), direction=F[:, 3:5].contiguous(),
+                azimuth_deg=torch.rad2deg(torch.atan2(F[:, 4], F[:, 3])), length=width * h,
+                a=a, b=b / h, c=c / (h * h), sag=torch.abs(c) * (0.5 * width) ** 2,
+                z_low=torch.where(ok & has, low + F[:, 2], nan),
+                rms_z=torch.sqrt(torch.clamp(res, min=0.0) / n1),
+                rms_t=torch.sqrt(torch.clamp(stt / n1 - mt * mt, min=0.0)), cond=cond)
 
 
 # ---------------------------------------------------------------------------- stage D1, fast mode

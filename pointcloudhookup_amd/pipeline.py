@@ -83,21 +83,73 @@ def drop_linear_rows(gf, radius=2.0, linearity=0.9, verticality=0.5, min_rows=10
     dropped, in file order, plus ``dropped`` (bool [old count], device) and ``n_dropped``.  Stage B kept no row, or the
     fit left no grid to ask (coordinates so spread that it took the compressed-coordinate path, rows that are not
     finite): raises with the cause - nothing is dropped silently.  Synchronises."""
+    return _kept_rows(gf, _linear_mask(gf["points"], radius, linearity, verticality, min_rows, "drop_linear_rows"))
+
+
+def _linear_mask(points, radius=2.0, linearity=0.9, verticality=0.5, min_rows=10, who="drop_linear_rows"):
+    """bool [n], device: the rows of ``points`` whose ``radius`` neighbourhood is a nearly horizontal line - the mask of
+    ``drop_linear_rows`` and of ``conductor_spans``; ``who`` names the caller in the errors"""
     ops.check_shape_radius(radius, radius)
-    points = gf["points"]
     n = int(points.shape[0])
     if n == 0:
-        raise ValueError("drop_linear_rows: stage B kept no rows, so there is no neighbourhood to look at")
+        raise ValueError(f"{who}: stage B kept no rows, so there is no neighbourhood to look at")
     fit = ops.DbscanFit(points, eps=float(radius), min_samples=1, chunk_size=0)
     try:
         count, moments = fit.shape(points, float(radius), chunk="own")
     except RuntimeError as e:
-        raise RuntimeError(f"drop_linear_rows: the fit of {n} rows at eps = {float(radius)} left no grid to ask "
+        raise RuntimeError(f"{who}: the fit of {n} rows at eps = {float(radius)} left no grid to ask "
                            f"(compressed coordinates or rows that are not finite), so no row was examined: {e}") from e
     f = ops.shape_features(count, moments)
-    dropped = (f["linearity"] >= float(linearity)) & (f["verticality"] <= float(verticality)) & (count >= int(min_rows))
+    mask = (f["linearity"] >= float(linearity)) & (f["verticality"] <= float(verticality)) & (count >= int(min_rows))
     del fit
-    return _kept_rows(gf, dropped)
+    return mask
+
+
+def conductor_spans(points, rule=None, eps=1.0, min_rows=5, towers=None, cut_radius=9.0, min_length=20.0,
+                    max_rms_z=0.25, max_rms_t=0.25):
+    """Conductors as a span table: the rows that ``drop_linear_rows`` would drop, grouped into wire
+    pieces, each with a fitted sag curve.  ``points``: float32 [n,3] on the device (stage B's rows); ``rule``: a dict
+    of ``drop_linear_rows``' keyword arguments (None or ``{}``: its defaults).
+
+    ``towers`` (optional, [T,2] or [T,3] centres in the frame of ``points``): wire rows with ``dx*dx + dy*dy <=
+    cut_radius**2`` (float64) to any tower are taken out, which cuts continuous conductors at the towers.  The rows
+    left are fitted once (``ops.dbscan(wire_rows, eps, min_rows, chunk_size=0)``), grouped (``ops.segment_by_label``)
+    and reduced (``ops.cluster_moments``, ``ops.span_frames``, ``ops.cluster_profile``, ``ops.span_fit``).  A piece is
+    accepted iff ``length >= min_length``, ``rms_z <= max_rms_z`` and ``rms_t <= max_rms_t``.
+
+    Returns dict: ``wire`` (bool [n], device: the rows that were grouped), ``labels`` (int32 over the wire rows, in
+    file order), ``nclusters``, ``perm`` / ``offsets`` (the grouping, indices into the wire rows), ``table`` (the
+    ``ops.span_fit`` dict over the K pieces) and ``accepted`` (bool [K]).  No wire rows: an empty table, nothing is
+    raised.  No rows at all, or a fit without a grid: raises as ``drop_linear_rows`` does.  Synchronises."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32:
+        raise TypeError("points must be a float32 CUDA/HIP tensor (no CPU fallback in the product path)")
+    points = points.reshape(-1, 3).contiguous()
+    dev = points.device
+    wire = _linear_mask(points, who="conductor_spans", **(rule or {}))
+    if towers is not None:
+        tw = np.asarray(towers.cpu() if isinstance(towers, torch.Tensor) else towers, dtype=np.float64)
+        if tw.size and (tw.ndim != 2 or tw.shape[1] not in (2, 3)):
+            raise ValueError("towers must be [T,2] or [T,3] centres")
+        if tw.size:
+            tw = torch.as_tensor(tw[:, :2].copy(), device=dev)
+            xy = points[:, :2].to(torch.float64)
+            dx = xy[:, None, 0] - tw[None, :, 0]
+            dy = xy[:, None, 1] - tw[None, :, 1]
+            near = ((dx * dx + dy * dy) <= float(cut_radius) * float(cut_radius)).any(dim=1)
+            wire = wire & ~near
+    rows = points[wire]
+    if int(rows.shape[0]):
+        labels, _, k = ops.dbscan(rows, float(eps), int(min_rows), 0)
+    else:
+        labels, k = torch.empty((0,), dtype=torch.int32, device=dev), 0
+    perm, offsets, _ = ops.segment_by_label(labels, rows, k)
+    count, origin, moments = ops.cluster_moments(rows, perm, offsets, k)
+    frames = ops.span_frames(count, origin, moments)
+    sums, ext = ops.cluster_profile(rows, perm, offsets, k, frames)
+    table = ops.span_fit(count, frames, sums, ext)
+    accepted = ((table["length"] >= float(min_length)) & (table["rms_z"] <= float(max_rms_z))
+                & (table["rms_t"] <= float(max_rms_t)))
+    return dict(wire=wire, labels=labels, nclusters=k, perm=perm, offsets=offsets, table=table, accepted=accepted)
 
 
 def _kept_rows(gf, dropped):

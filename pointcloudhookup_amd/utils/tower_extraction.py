@@ -57,6 +57,13 @@ behaviour): before ``DROP_LINEAR`` and the clustering, the kept rows with fewer 
 ``std_ratio`` standard deviations - stray returns, which otherwise become border points of a tower and widen its box -
 are removed (pipeline.drop_sparse_rows).  It logs one extra line; a failure of the step is logged
 and ends the run like a failure of the filter.
+``SPANS`` (env PCH_SPANS="eps,min_rows,cut_radius,min_length", e.g. "1,5,9,20"; unset or empty = off, the reference's
+behaviour): when towers were accepted, the conductors between them are reported (pipeline.conductor_spans on the rows
+the ground rule kept - before any drop -, the accepted towers' centres cutting the wires at ``cut_radius`` metres;
+DESIGN.md section 5d) and ``output_towers/spans_info.csv`` gets one line per accepted wire piece: its centre in world
+coordinates, direction, length, sag curve and residuals.  It logs one extra line; a failure of the step is logged and
+ends the run like a failure of the other opt-in steps (the towers found so far are returned, no xlsx is written).  The
+returned tower dicts are the same with and without it.
 """
 from __future__ import annotations
 
@@ -131,6 +138,32 @@ def drop_sparse_from_env(value):
 
 
 DROP_SPARSE = drop_sparse_from_env(os.environ.get("PCH_DROP_SPARSE"))
+
+
+def spans_from_env(value):
+    """SPANS of an environment value: None (off) when unset or empty, else the keyword arguments of
+    pipeline.conductor_spans from "eps,min_rows,cut_radius,min_length" - four numbers, no fewer and no more; eps finite
+    and > 0, min_rows an integer >= 1, cut_radius and min_length finite and >= 0 (ValueError)"""
+    if value is None or not value.strip():
+        return None
+    parts = [t.strip() for t in value.split(",")]
+    if len(parts) != 4:
+        raise ValueError(f"PCH_SPANS takes \"eps,min_rows,cut_radius,min_length\", got {value!r}")
+    eps, min_rows, cut_radius, min_length = float(parts[0]), int(parts[1]), float(parts[2]), float(parts[3])
+    if not (np.isfinite(eps) and eps > 0.0):
+        raise ValueError(f"PCH_SPANS: eps must be finite and > 0, got {parts[0]!r}")
+    if min_rows < 1:
+        raise ValueError(f"PCH_SPANS: min_rows must be >= 1, got {parts[1]!r}")
+    if not (np.isfinite(cut_radius) and cut_radius >= 0.0):
+        raise ValueError(f"PCH_SPANS: cut_radius must be finite and >= 0, got {parts[2]!r}")
+    if not (np.isfinite(min_length) and min_length >= 0.0):
+        raise ValueError(f"PCH_SPANS: min_length must be finite and >= 0, got {parts[3]!r}")
+    return dict(eps=eps, min_rows=min_rows, cut_radius=cut_radius, min_length=min_length)
+
+
+SPANS = spans_from_env(os.environ.get("PCH_SPANS"))
+SPANS_COLUMNS = ("ID", "count", "x", "y", "z", "azimuth_deg", "length", "a", "b", "c", "sag", "z_low", "rms_z", "rms_t",
+                 "cond")
 PRESTART_BYTES = 100 << 20                             # LAS files from here on get worker processes early
 CHUNK_SIZE = 50000                                     # utils/tower_extraction.py:96
 
@@ -261,6 +294,7 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
         log(f"⚠️ 高度过滤失败: {str(e)}")
         return tower_obbs
     del raw
+    stage_b_points = gf["points"] if SPANS else None           # the conductors are looked for before any drop
 
     # ---- opt-in: isolated and sparse rows (stray returns) leave first
     if DROP_SPARSE:
@@ -369,6 +403,21 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
     clock.mark("tower boxes + accept / de-dup (D1-D3)")
     clock.move("tower boxes + accept / de-dup (D1-D3)", "per-tower LAS files", las_seconds[0])
 
+    # ---- opt-in: the conductors between the accepted towers, as a span table
+    if SPANS and tower_obbs:
+        try:
+            cen = np.asarray(centroid, dtype=np.float64)
+            local = np.stack([np.asarray(t["center"], dtype=np.float64) - cen for t in tower_obbs])
+            spans = pipeline.conductor_spans(stage_b_points, towers=local, **SPANS)
+            rows = span_rows(spans, cen)
+            write_spans_csv(output_dir / "spans_info.csv", rows)
+            clock.mark("conductor spans")
+            log(spans_line(spans, len(rows), SPANS))
+        except (ValueError, RuntimeError) as e:            # the step's own refusals and library / device errors
+            log(f"⚠️ 导线档距提取失败: {str(e)}")
+            return tower_obbs
+    stage_b_points = None
+
     # ---- xlsx (reference :221-231)
     if tower_rows:
         try:
@@ -408,6 +457,37 @@ def drop_sparse_line(gf, n_before, knob):
     """the extra log line of DROP_SPARSE for a result of pipeline.drop_sparse_rows"""
     return (f"🧹 稀疏点剔除: k = {knob['k']}，半径 {knob['radius']:g} m，标准差倍数 {knob['std_ratio']:g}，"
             f"阈值 {float(gf['threshold']):.4f} m；剔除 {int(gf['n_dropped'])}/{int(n_before)} 点")
+
+
+def span_rows(spans, centroid):
+    """the lines of spans_info.csv for a result of pipeline.conductor_spans: one list per accepted piece in
+    SPANS_COLUMNS' order, the centre and z_low moved to world coordinates by ``centroid`` (3 float64)"""
+    acc = spans["accepted"].cpu().numpy()
+    T = {key: v.cpu().numpy() for key, v in spans["table"].items()}
+    rows = []
+    for k in np.flatnonzero(acc):
+        c = T["centre"][k] + centroid
+        rows.append([f"span_{int(k)}", int(T["count"][k]), c[0], c[1], c[2]]
+                    + [float(T[key][k]) for key in ("azimuth_deg", "length", "a", "b", "c", "sag")]
+                    + [float(T["z_low"][k] + centroid[2])] + [float(T[key][k]) for key in ("rms_z", "rms_t", "cond")])
+    return rows
+
+
+def write_spans_csv(path, rows):
+    """spans_info.csv: a header line (SPANS_COLUMNS) and one line per accepted piece, floats with repr's digits"""
+    import csv
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.writer(f)
+        w.writerow(SPANS_COLUMNS)
+        for r in rows:
+            w.writerow([repr(float(v)) if isinstance(v, (float, np.floating)) else v for v in r])
+
+
+def spans_line(spans, n_accepted, knob):
+    """the extra log line of SPANS for a result of pipeline.conductor_spans"""
+    return (f"🔌 导线档距: eps {knob['eps']:g} m，最少 {knob['min_rows']} 点，杆塔切除半径 {knob['cut_radius']:g} m，"
+            f"最短 {knob['min_length']:g} m；导线点 {int(spans['wire'].sum())}，线段 {int(spans['nclusters'])}，"
+            f"接受 {int(n_accepted)}")
 
 
 def ground_tiles_line(gf):
