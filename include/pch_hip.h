@@ -661,6 +661,66 @@ int pch_cluster_profile_f32(const float* xyz, const int32_t* perm, const int64_t
                             int32_t nclusters, const double* frames /* [K,6] */, double* out_sums /* [K,10] */,
                             double* out_ext /* [K,4] */, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ conductor clearance, opt-in
+ * The distance of every row of a cloud to the fitted span curves: what comes how close to the line.
+ *
+ * The rule.  All arithmetic is float64 without FMA (the library is built with -ffp-contract=off); parentheses are as
+ * written.
+ *   Curves (no kernel; ops.span_curves): float64 [K,10] = (cx, cy, cz, ux, uy, a, b, c, m0, m1).  The centre and the
+ *     direction are the frame's (f0..f4 above); a, b, c are the span table's (metres along the track);
+ *     m0 = ext[:,0]*h and m1 = ext[:,1]*h with h = 1.0 / f5: the piece's along-track interval in metres from its centre.
+ *   Polyline (no kernel; ops.span_segments), S segments, 1 <= S <= 128: float64 [K,S,5] = (m_j, z_j, dm_j, dz_j, inv_j).
+ *     step = (m1 - m0) / S; m_j = m0 + j*step for j < S, and m_S = m1; z_j = a + m_j*(b + c*m_j);
+ *     dm_j = m_{j+1} - m_j and dz_j = z_{j+1} - z_j; len2 = (dm*dm) + (dz*dz); inv_j = 1/len2 where len2 > 0,
+ *     otherwise 0.  The polyline lies within |c|*((m1 - m0)/S)^2/4 of the parabola, vertically, and above it for a
+ *     hanging wire: clearances to objects below are over-estimated by at most that (chord_error).
+ *   Per row and span (pch_clearance_f32).  xyz float32 [n,3]; an optional skip uint8 [n]; curves5 float64 [K,5] =
+ *     (cx, cy, cz, ux, uy); segs float64 [K,S,5]; radius and limit, finite, with 0 < limit <= radius;
+ *     r2 = radius*radius and l2 = limit*limit, taken in double on the host.  A span takes part if and only if all
+ *     5 + 5*S of its values are finite.  For row i with skip[i] == 0, spans are visited in ascending k:
+ *         dx = (double)px - cx;  dy = (double)py - cy;  w = (double)pz - cz
+ *         m = (dx*ux) + (dy*uy);  t = (dy*ux) - (dx*uy)
+ *         g = +inf
+ *         for j ascending:
+ *             rm = m - m_j;  rw = w - z_j
+ *             q = ((rm*dm_j) + (rw*dz_j))*inv_j
+ *             if q < 0: q = 0
+ *             if q > 1: q = 1
+ *             em = rm - (q*dm_j);  ew = rw - (q*dz_j)
+ *             d = (em*em) + (ew*ew)
+ *             if d < g: g = d
+ *         d2 = g + (t*t)
+ *         if d2 <= r2 and d2 < best: best = d2; who = k
+ *     out_dist2[i] = best (+inf if no span is within the radius); out_span[i] = who (-1 if no span is within the
+ *     radius).  A skipped row gets +inf and -1.  A row with a non-finite coordinate also gets +inf and -1: every
+ *     comparison with a NaN fails.  Ties between spans go to the lowest index.
+ *   Per span, over the rows with out_span[i] == k: out_count[k] (int64); out_violations[k] (int64): the rows with
+ *     dist2 <= l2; out_min_dist2[k] (float64): +inf if there is no row; out_min_row[k] (int64): the lowest row index
+ *     that attains out_min_dist2[k], or -1.
+ * Every row is attributed to its NEAREST span only: a row within the radius of two spans counts for the nearer one (the
+ * lower index on a tie) and is absent from the other's count, violations and minimum.
+ *
+ * How: a small kernel over the spans writes the "takes part" flag and conservative bounds of each polyline, widened
+ * by the radius; a sweep over tiles of 1024 rows walks, in ascending order, the spans whose bounds meet the tile's
+ * own bounding box; a finisher finds the lowest row of every minimum.  Culling skips only spans the rule cannot accept
+ * within the radius: the outputs are the rule's, whatever is culled.  The tallies are integer atomics and the minimum
+ * is an integer atomic on the bit pattern (non-negative doubles order as integers): the same input gives the same bits
+ * on every run; nothing waits on another workgroup.
+ *
+ * 0 <= n < 2^32, 0 <= nspans <= 4096, 1 <= nsegments <= 128 (else PCH_ERR_ARG, as a radius or limit that is not
+ * finite, limit <= 0, limit > radius, a null buffer that is needed and a host pointer).  All buffers device; skip may
+ * be NULL (no row is skipped); out_loops (int64 [2], may be NULL): the (row, span) segment loops run and the (tile,
+ * span) pairs walked - figures for measurement, not part of the rule.  ws: the caller's, at least
+ * pch_clearance_ws_bytes(n, nspans, nsegments) bytes - pure host code, 0 for sizes out of range (smaller:
+ * PCH_ERR_WORKSPACE).  n == 0 or nspans == 0: every row gets +inf / -1, the table is (0, 0, +inf, -1) per span, and no
+ * launch reads a null pointer.  Enqueues on the caller's stream and returns; no host read. */
+size_t pch_clearance_ws_bytes(int64_t n, int32_t nspans, int32_t nsegments);
+int pch_clearance_f32(const float* xyz, const uint8_t* skip, int64_t n, const double* curves5 /* [K,5] */,
+                      const double* segs /* [K,S,5] */, int32_t nspans, int32_t nsegments, double radius, double limit,
+                      double* out_dist2, int32_t* out_span, int64_t* out_count, int64_t* out_violations,
+                      double* out_min_dist2, int64_t* out_min_row, int64_t* out_loops, void* ws, size_t ws_bytes,
+                      void* stream);
+
 /* ------------------------------------------------------------------ stage D1, fast mode
  * The reference boxes every cluster with trimesh (utils/tower_extraction.py:137-139:
  * trimesh.PointCloud(cluster_points).bounding_box_oriented): qhull's 3-D hull of the whole cluster, then a

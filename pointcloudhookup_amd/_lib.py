@@ -95,6 +95,9 @@ _SIGS = {
     "pch_cluster_moments_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pch_cluster_profile_ws_bytes": (_sz, [_i64, _i32]),
     "pch_cluster_profile_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pch_clearance_ws_bytes": (_sz, [_i64, _i32, _i32]),
+    "pch_clearance_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _sz, _vp]),
     "pch_crop_aabb_ws_bytes": (_sz, [_i64]),
     "pch_crop_aabb_f64": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pch_crop_boxes_ws_bytes": (_sz, [_i64, _i32, _i64]),

@@ -17,7 +17,8 @@ One function per reference library call:
   upright_boxes     <- upright box per cluster (opt-in)      test/008.py:302-331 (axis-aligned there)
   crop_boxes        <- per-tower box masks over the cloud    test/kuangxuan.py:60-79, ui/extract.py:345-420
 Beyond the reference, on a retained fit (DbscanFit): assign, kdist, shape (+ shape_features), knn (+ knn_mean_distance) -
-DESIGN.md sections 5a, 5b, 5c; on a grouping: cluster_moments, span_frames, cluster_profile, span_fit - section 5d.
+DESIGN.md sections 5a, 5b, 5c; on a grouping: cluster_moments, span_frames, cluster_profile, span_fit - section 5d; on a cloud and the fitted
+curves: span_curves, span_segments, clearance - section 5e.
 """
 from __future__ import annotations
 
@@ -1493,6 +1494,126 @@ def _span_fit_of(count, F, S, E):
                 z_low=torch.where(ok & has, low + F[:, 2], nan),
                 rms_z=torch.sqrt(torch.clamp(res, min=0.0) / n1),
                 rms_t=torch.sqrt(torch.clamp(stt / n1 - mt * mt, min=0.0)), cond=cond)
+
+
+# ------------------------------------------------------------- conductor clearance, opt-in
+CLEARANCE_TILE = 1024          # rows per workgroup of the clearance sweep (cl_sweep_k): the sizes tests straddle
+CLEARANCE_MAX_SPANS = 4096
+CLEARANCE_MAX_SEGMENTS = 128
+
+
+def span_curves(table, frames, ext):
+    """float64 [K,10] device: per piece ``(cx, cy, cz, ux, uy, a, b, c, m0, m1)`` - the frame's centre and direction
+    (``span_frames``), the table's curve ``a, b, c`` (``span_fit``; metres along the track) and the piece's along-track
+    interval ``m0 = ext[:,0]·h``, ``m1 = ext[:,1]·h`` in metres from its centre, ``h = 1.0 / frames[:,5]``
+    (``cluster_profile``'s ext).  include/pch_hip.h's rule: float64 torch arithmetic on K records, no kernel.
+    Asynchronous."""
+    F = _need_cuda(frames, torch.float64, "frames").reshape(-1, 6)
+    E = _need_cuda(ext, torch.float64, "ext").reshape(-1, 4)
+    abc = [_need_cuda(table[key], torch.float64, key).reshape(-1) for key in ("a", "b", "c")]
+    if E.shape[0] != F.shape[0] or any(v.numel() != F.shape[0] for v in abc):
+        raise ValueError("table, frames and ext must describe the same pieces")
+    return _span_curves_of(abc[0], abc[1], abc[2], F, E)
+
+
+def _span_curves_of(a, b, c, F, E):
+    """span_curves' arithmetic, on tensors of any device"""
+    h = 1.0 / F[:, 5]
+    return torch.stack([F[:, 0], F[:, 1], F[:, 2], F[:, 3], F[:, 4], a, b, c, E[:, 0] * h, E[:, 1] * h],
+                       dim=1).contiguous()
+
+
+def check_segments(segments):
+    """the segment count of a polyline as an int; ValueError unless 1 <= segments <= 128"""
+    if isinstance(segments, bool) or int(segments) != segments or not 1 <= int(segments) <= CLEARANCE_MAX_SEGMENTS:
+        raise ValueError(f"segments must be an integer in 1..{CLEARANCE_MAX_SEGMENTS}, got {segments!r}")
+    return int(segments)
+
+
+def span_segments(curves, segments=32):
+    """(segs float64 [K,S,5], chord_error float64 [K]), device: the polyline of S segments that stands for each curve of
+    ``span_curves`` - per segment ``(m_j, z_j, Δm_j, Δz_j, inv_j)``: its first vertex (metres along the track, height
+    above the centre), the step to the next vertex and ``1 / (Δm² + Δz²)`` (0 where that is not > 0) - and the bound
+    ``|c|·((m1 − m0)/S)²/4`` on the polyline's vertical distance from the parabola: the polyline lies above a hanging
+    wire, so clearances to objects below are over-estimated by at most that.  include/pch_hip.h's rule: float64 torch
+    arithmetic on K·S records, no kernel.  Asynchronous."""
+    S = check_segments(segments)
+    curves = _need_cuda(curves, torch.float64, "curves").reshape(-1, 10)
+    return _span_segments_of(curves, S)
+
+
+def _span_segments_of(curves, S):
+    """span_segments' arithmetic, on tensors of any device"""
+    a, b, c, m0, m1 = (curves[:, i:i + 1] for i in range(5, 10))
+    step = (m1 - m0) / float(S)
+    j = torch.arange(S, dtype=torch.float64, device=curves.device)[None, :]
+    m = torch.cat([m0 + j * step, m1], dim=1)                                # [K,S+1]: m_S = m1
+    z = a + m * (b + c * m)
+    dm = m[:, 1:] - m[:, :-1]
+    dz = z[:, 1:] - z[:, :-1]
+    len2 = (dm * dm) + (dz * dz)
+    pos = len2 > 0
+    inv = torch.where(pos, torch.ones_like(len2) / torch.where(pos, len2, torch.ones_like(len2)),
+                      torch.zeros_like(len2))
+    segs = torch.stack([m[:, :-1], z[:, :-1], dm, dz, inv], dim=2).contiguous()
+    chord = ((torch.abs(c) * (step * step)) / 4.0).reshape(-1)
+    return segs, chord
+
+
+def clearance(xyz, curves, segs, radius, limit, skip=None, want_stats=False):
+    """The distance of every row of float32 [n,3] to the span polylines (pch_clearance_f32; the rule is in
+    include/pch_hip.h): a dict of device tensors - ``dist2`` float64 [n], the squared distance to the nearest span
+    within ``radius`` (+inf if none), ``span`` int32 [n], that span (-1 if none; the lowest index on a tie), and over the
+    K spans ``count`` int64 (the rows attributed to it - every row to its nearest span only), ``violations`` int64 (those
+    with ``dist2 <= limit²``), ``min_dist2`` float64 (+inf without a row) and ``min_row`` int64 (the lowest row that
+    attains it, or -1).  ``curves`` float64 [K,5] or [K,10] (``span_curves``; the first five columns are used), ``segs``
+    float64 [K,S,5] (``span_segments``), ``skip`` an optional uint8 or bool [n]: rows with a non-zero entry get +inf and
+    -1, as rows with a non-finite coordinate do.  A span with a non-finite value takes no part.  ``want_stats`` adds
+    ``loops`` int64 [2]: the (row, span) segment loops run and the (tile, span) pairs walked.  ValueError: radius or
+    limit not finite, limit <= 0 or > radius, more than 4096 spans, S outside 1..128.  The same input gives the same
+    bits on every run.  Asynchronous."""
+    import math
+    L = _lib.lib()
+    xyz = _need_cuda(xyz, torch.float32, "xyz").reshape(-1, 3)
+    curves = _need_cuda(curves, torch.float64, "curves")
+    segs = _need_cuda(segs, torch.float64, "segs")
+    if curves.dim() != 2 or curves.shape[1] not in (5, 10):
+        raise ValueError("curves must be [K,5] or [K,10]")
+    K = curves.shape[0]
+    if segs.dim() != 3 or segs.shape[0] != K or segs.shape[2] != 5:
+        raise ValueError("segs must be [K,S,5] for the K spans of curves")
+    S = check_segments(segs.shape[1])
+    if K > CLEARANCE_MAX_SPANS:
+        raise ValueError(f"clearance takes at most {CLEARANCE_MAX_SPANS} spans per call, got {K}")
+    radius, limit = float(radius), float(limit)
+    if not (math.isfinite(radius) and math.isfinite(limit) and 0.0 < limit <= radius):
+        raise ValueError(f"radius and limit must be finite with 0 < limit <= radius, got {radius!r}, {limit!r}")
+    n, dev = xyz.shape[0], xyz.device
+    if n >= 1 << 32:
+        raise ValueError("clearance takes fewer than 2^32 rows per call")
+    if skip is not None:
+        if isinstance(skip, torch.Tensor) and skip.dtype == torch.bool:
+            skip = skip.view(torch.uint8)
+        skip = _need_cuda(skip, torch.uint8, "skip").reshape(-1)
+        if skip.numel() != n:
+            raise ValueError("skip must hold one entry per row")
+    curves5 = curves[:, :5].contiguous()
+    with torch.cuda.device(dev):
+        dist2 = torch.empty((n,), dtype=torch.float64, device=dev)
+        span = torch.empty((n,), dtype=torch.int32, device=dev)
+        count = torch.empty((K,), dtype=torch.int64, device=dev)
+        violations = torch.empty((K,), dtype=torch.int64, device=dev)
+        min_dist2 = torch.empty((K,), dtype=torch.float64, device=dev)
+        min_row = torch.empty((K,), dtype=torch.int64, device=dev)
+        loops = torch.empty((2,), dtype=torch.int64, device=dev) if want_stats else None
+        ws = _workspace(L.pch_clearance_ws_bytes(n, K, S), dev)
+        _lib.check(L.pch_clearance_f32(_ptr(xyz), _ptr(skip), n, _ptr(curves5), _ptr(segs), K, S, radius, limit,
+                                       _ptr(dist2), _ptr(span), _ptr(count), _ptr(violations), _ptr(min_dist2),
+                                       _ptr(min_row), _ptr(loops), _ptr(ws), ws.numel(), _stream()))
+    out = dict(dist2=dist2, span=span, count=count, violations=violations, min_dist2=min_dist2, min_row=min_row)
+    if want_stats:
+        out["loops"] = loops
+    return out
 
 
 # ---------------------------------------------------------------------------- stage D1, fast mode

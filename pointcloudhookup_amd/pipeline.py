@@ -119,24 +119,17 @@ def conductor_spans(points, rule=None, eps=1.0, min_rows=5, towers=None, cut_rad
 
     Returns dict: ``wire`` (bool [n], device: the rows that were grouped), ``labels`` (int32 over the wire rows, in
     file order), ``nclusters``, ``perm`` / ``offsets`` (the grouping, indices into the wire rows), ``table`` (the
-    ``ops.span_fit`` dict over the K pieces) and ``accepted`` (bool [K]).  No wire rows: an empty table, nothing is
-    raised.  No rows at all, or a fit without a grid: raises as ``drop_linear_rows`` does.  Synchronises."""
+    ``ops.span_fit`` dict over the K pieces), ``accepted`` (bool [K]) and ``frames`` / ``ext`` (``ops.span_frames``'
+    and ``ops.cluster_profile``'s tensors, which ``conductor_clearance`` turns into curves).  No wire rows: an empty
+    table, nothing is raised.  No rows at all, or a fit without a grid: raises as ``drop_linear_rows`` does.  Synchronises."""
     if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32:
         raise TypeError("points must be a float32 CUDA/HIP tensor (no CPU fallback in the product path)")
     points = points.reshape(-1, 3).contiguous()
     dev = points.device
     wire = _linear_mask(points, who="conductor_spans", **(rule or {}))
-    if towers is not None:
-        tw = np.asarray(towers.cpu() if isinstance(towers, torch.Tensor) else towers, dtype=np.float64)
-        if tw.size and (tw.ndim != 2 or tw.shape[1] not in (2, 3)):
-            raise ValueError("towers must be [T,2] or [T,3] centres")
-        if tw.size:
-            tw = torch.as_tensor(tw[:, :2].copy(), device=dev)
-            xy = points[:, :2].to(torch.float64)
-            dx = xy[:, None, 0] - tw[None, :, 0]
-            dy = xy[:, None, 1] - tw[None, :, 1]
-            near = ((dx * dx + dy * dy) <= float(cut_radius) * float(cut_radius)).any(dim=1)
-            wire = wire & ~near
+    near = _near_towers(points, towers, cut_radius)
+    if near is not None:
+        wire = wire & ~near
     rows = points[wire]
     if int(rows.shape[0]):
         labels, _, k = ops.dbscan(rows, float(eps), int(min_rows), 0)
@@ -149,7 +142,78 @@ def conductor_spans(points, rule=None, eps=1.0, min_rows=5, towers=None, cut_rad
     table = ops.span_fit(count, frames, sums, ext)
     accepted = ((table["length"] >= float(min_length)) & (table["rms_z"] <= float(max_rms_z))
                 & (table["rms_t"] <= float(max_rms_t)))
-    return dict(wire=wire, labels=labels, nclusters=k, perm=perm, offsets=offsets, table=table, accepted=accepted)
+    return dict(wire=wire, labels=labels, nclusters=k, perm=perm, offsets=offsets, table=table, accepted=accepted,
+                frames=frames, ext=ext)
+
+
+def _near_towers(points, towers, cut_radius):
+    """bool [n], device: the rows of ``points`` with ``dx*dx + dy*dy <= cut_radius**2`` (float64) to any tower centre -
+    the cut of ``conductor_spans`` and of ``conductor_clearance``; None without towers"""
+    if towers is None:
+        return None
+    tw = np.asarray(towers.cpu() if isinstance(towers, torch.Tensor) else towers, dtype=np.float64)
+    if tw.size and (tw.ndim != 2 or tw.shape[1] not in (2, 3)):
+        raise ValueError("towers must be [T,2] or [T,3] centres")
+    if not tw.size:
+        return None
+    tw = torch.as_tensor(tw[:, :2].copy(), device=points.device)
+    xy = points[:, :2].to(torch.float64)
+    dx = xy[:, None, 0] - tw[None, :, 0]
+    dy = xy[:, None, 1] - tw[None, :, 1]
+    return ((dx * dx + dy * dy) <= float(cut_radius) * float(cut_radius)).any(dim=1)
+
+
+CLEARANCE_TABLE_KEYS = ("count", "violations", "min_distance", "min_row", "min_point", "chord_error")
+
+
+def conductor_clearance(points, spans, radius=10.0, limit=6.0, segments=32, towers=None, cut_radius=9.0):
+    """How close anything that is not the line comes to it: the distance of every row of ``points``
+    (float32 [n,3] on the device) to the sag curves of the accepted pieces of ``spans``, the dict ``conductor_spans``
+    returned for the same ``points``.  Each accepted piece becomes a polyline of ``segments`` segments
+    (``ops.span_curves``, ``ops.span_segments``); the rows that are the conductors (``spans["wire"]``) and, with
+    ``towers``, the rows within ``cut_radius`` (horizontal, float64) of a tower - ``conductor_spans``' own predicate -
+    are skipped; ``ops.clearance`` does the rest.  Every row is attributed to its nearest piece only.
+
+    Returns dict: ``dist2`` (float64 [n]: the squared distance to the nearest accepted piece within ``radius``, +inf if
+    none or skipped), ``span`` (int32 [n]: that piece's id in the span table, -1 if none), ``violating`` (bool [n]:
+    ``dist2 <= limit²``) and ``table``, a dict over the K pieces of the span table: ``count`` and ``violations``
+    (int64), ``min_distance`` (metres; +inf without a row), ``min_row`` (the lowest row at that distance, -1 without),
+    ``min_point`` ([K,3] float32: that row's coordinates, NaN without) and ``chord_error`` (metres: by how much at most
+    the polyline over-estimates a clearance below the wire; NaN for a piece that was not accepted).  No accepted piece:
+    every row +inf / -1 and a table without rows attributed; nothing is raised.  Synchronises."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32:
+        raise TypeError("points must be a float32 CUDA/HIP tensor (no CPU fallback in the product path)")
+    points = points.reshape(-1, 3).contiguous()
+    n, dev = int(points.shape[0]), points.device
+    wire = spans["wire"]
+    if wire.numel() != n:
+        raise ValueError("spans must be conductor_spans' result for the same points")
+    segments = ops.check_segments(segments)
+    K = int(spans["nclusters"])
+    idx = torch.nonzero(spans["accepted"]).reshape(-1)                        # accepted pieces, ascending
+    curves = ops.span_curves(spans["table"], spans["frames"], spans["ext"])[idx].contiguous()
+    segs, chord = ops.span_segments(curves, segments)
+    near = _near_towers(points, towers, cut_radius)
+    skip = wire if near is None else (wire | near)
+    res = ops.clearance(points, curves, segs, radius, limit, skip=skip)
+    span = res["span"]                                                        # (all -1 without an accepted piece)
+    if idx.numel():
+        span = torch.where(span >= 0, idx.to(torch.int32)[span.clamp(min=0).long()], torch.full_like(span, -1))
+    nan64 = float("nan")
+    count = torch.zeros((K,), dtype=torch.int64, device=dev)
+    violations = torch.zeros((K,), dtype=torch.int64, device=dev)
+    min_distance = torch.full((K,), float("inf"), dtype=torch.float64, device=dev)
+    min_row = torch.full((K,), -1, dtype=torch.int64, device=dev)
+    chord_error = torch.full((K,), nan64, dtype=torch.float64, device=dev)
+    count[idx], violations[idx] = res["count"], res["violations"]
+    min_distance[idx], min_row[idx], chord_error[idx] = torch.sqrt(res["min_dist2"]), res["min_row"], chord
+    min_point = torch.full((K, 3), nan64, dtype=torch.float32, device=dev)
+    has = min_row >= 0
+    if n:
+        min_point[has] = points[min_row[has]]
+    table = dict(count=count, violations=violations, min_distance=min_distance, min_row=min_row, min_point=min_point,
+                 chord_error=chord_error)
+    return dict(dist2=res["dist2"], span=span, violating=res["dist2"] <= float(limit) * float(limit), table=table)
 
 
 def _kept_rows(gf, dropped):

@@ -64,6 +64,13 @@ DESIGN.md section 5d) and ``output_towers/spans_info.csv`` gets one line per acc
 coordinates, direction, length, sag curve and residuals.  It logs one extra line; a failure of the step is logged and
 ends the run like a failure of the other opt-in steps (the towers found so far are returned, no xlsx is written).  The
 returned tower dicts are the same with and without it.
+``CLEARANCE`` (env PCH_CLEARANCE="radius,limit[,segments]", e.g. "10,6" or "10,6,32"; unset or empty = off; needs
+``SPANS`` - importing the module with PCH_CLEARANCE set and PCH_SPANS unset raises ValueError): behind the span table,
+the distance of every row the ground rule kept to the accepted pieces' sag curves (pipeline.conductor_clearance; the
+conductors themselves and the rows within the spans' ``cut_radius`` of an accepted tower are left out; DESIGN.md section
+5e) and ``output_towers/clearance_info.csv`` gets one line per accepted wire piece: the rows nearer than ``radius``
+metres, those nearer than ``limit``, the smallest distance and the nearest point in world coordinates.  It logs one extra
+line; a failure is handled like one of ``SPANS``.  The returned tower dicts are the same with and without it.
 """
 from __future__ import annotations
 
@@ -164,7 +171,34 @@ def spans_from_env(value):
 SPANS = spans_from_env(os.environ.get("PCH_SPANS"))
 SPANS_COLUMNS = ("ID", "count", "x", "y", "z", "azimuth_deg", "length", "a", "b", "c", "sag", "z_low", "rms_z", "rms_t",
                  "cond")
-PRESTART_BYTES = 100 << 20                             # LAS files from here on get worker processes early
+
+
+def clearance_from_env(value, spans=True):
+    """CLEARANCE of an environment value: None (off) when unset or empty, else the keyword arguments of
+    pipeline.conductor_clearance from "radius,limit[,segments]" - two or three numbers; radius and limit finite with
+    0 < limit <= radius, segments an integer in 1..128 (default 32).  ``spans``: whether SPANS is on - the clearance is
+    measured to its pieces, so a value without it is refused (ValueError)"""
+    if value is None or not value.strip():
+        return None
+    parts = [t.strip() for t in value.split(",")]
+    if len(parts) not in (2, 3):
+        raise ValueError(f"PCH_CLEARANCE takes \"radius,limit[,segments]\", got {value!r}")
+    radius, limit = float(parts[0]), float(parts[1])
+    segments = int(parts[2]) if len(parts) == 3 else 32
+    if not (np.isfinite(radius) and radius > 0.0):
+        raise ValueError(f"PCH_CLEARANCE: radius must be finite and > 0, got {parts[0]!r}")
+    if not (np.isfinite(limit) and 0.0 < limit <= radius):
+        raise ValueError(f"PCH_CLEARANCE: limit must be finite with 0 < limit <= radius, got {parts[1]!r}")
+    if not 1 <= segments <= 128:
+        raise ValueError(f"PCH_CLEARANCE: segments must be in 1..128, got {parts[2]!r}")
+    if not spans:
+        raise ValueError("PCH_CLEARANCE needs PCH_SPANS: the clearance is measured to the span table's pieces")
+    return dict(radius=radius, limit=limit, segments=segments)
+
+
+CLEARANCE = clearance_from_env(os.environ.get("PCH_CLEARANCE"), spans=SPANS is not None)
+CLEARANCE_COLUMNS = ("ID", "count", "violations", "min_distance", "min_row", "x", "y", "z", "chord_error")
+PRESTART_BYTES = 100 << 20                           # LAS files from here on get worker processes early
 CHUNK_SIZE = 50000                                     # utils/tower_extraction.py:96
 
 
@@ -416,6 +450,18 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
         except (ValueError, RuntimeError) as e:            # the step's own refusals and library / device errors
             log(f"⚠️ 导线档距提取失败: {str(e)}")
             return tower_obbs
+        # ---- opt-in: what comes how close to those conductors
+        if CLEARANCE:
+            try:
+                clear = pipeline.conductor_clearance(stage_b_points, spans, towers=local,
+                                                     cut_radius=SPANS["cut_radius"], **CLEARANCE)
+                rows = clearance_rows(spans, clear, cen)
+                write_clearance_csv(output_dir / "clearance_info.csv", rows)
+                clock.mark("conductor clearance")
+                log(clearance_line(clear, rows, CLEARANCE))
+            except (ValueError, RuntimeError) as e:
+                log(f"⚠️ 导线净空计算失败: {str(e)}")
+                return tower_obbs
     stage_b_points = None
 
     # ---- xlsx (reference :221-231)
@@ -488,6 +534,41 @@ def spans_line(spans, n_accepted, knob):
     return (f"🔌 导线档距: eps {knob['eps']:g} m，最少 {knob['min_rows']} 点，杆塔切除半径 {knob['cut_radius']:g} m，"
             f"最短 {knob['min_length']:g} m；导线点 {int(spans['wire'].sum())}，线段 {int(spans['nclusters'])}，"
             f"接受 {int(n_accepted)}")
+
+
+def clearance_rows(spans, clear, centroid):
+    """the lines of clearance_info.csv for a result of pipeline.conductor_clearance: one list per accepted piece in
+    CLEARANCE_COLUMNS' order, the nearest point moved to world coordinates by ``centroid`` (3 float64; NaN without a
+    row)"""
+    acc = spans["accepted"].cpu().numpy()
+    T = {key: v.cpu().numpy() for key, v in clear["table"].items()}
+    rows = []
+    for k in np.flatnonzero(acc):
+        p = T["min_point"][k].astype(np.float64) + centroid
+        rows.append([f"span_{int(k)}", int(T["count"][k]), int(T["violations"][k]), float(T["min_distance"][k]),
+                     int(T["min_row"][k]), float(p[0]), float(p[1]), float(p[2]), float(T["chord_error"][k])])
+    return rows
+
+
+def write_clearance_csv(path, rows):
+    """clearance_info.csv: a header line (CLEARANCE_COLUMNS) and one line per accepted piece, floats with repr's
+    digits"""
+    import csv
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.writer(f)
+        w.writerow(CLEARANCE_COLUMNS)
+        for r in rows:
+            w.writerow([repr(float(v)) if isinstance(v, (float, np.floating)) else v for v in r])
+
+
+def clearance_line(clear, rows, knob):
+    """the extra log line of CLEARANCE for a result of pipeline.conductor_clearance and its csv lines"""
+    near = sum(r[1] for r in rows)
+    breached = sum(1 for r in rows if r[2] > 0)
+    closest = min([r[3] for r in rows], default=float("inf"))
+    return (f"📏 导线净空: 半径 {knob['radius']:g} m，限距 {knob['limit']:g} m，折线 {knob['segments']} 段；"
+            f"半径内 {int(near)} 点，越限 {int(clear['violating'].sum())} 点，越限线段 {int(breached)}/{len(rows)}，"
+            f"最小净空 {closest:.3f} m")
 
 
 def ground_tiles_line(gf):
