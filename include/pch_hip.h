@@ -721,6 +721,97 @@ int pch_clearance_f32(const float* xyz, const uint8_t* skip, int64_t n, const do
                       double* out_min_dist2, int64_t* out_min_row, int64_t* out_loops, void* ws, size_t ws_bytes,
                       void* stream);
 
+/* ------------------------------------------------------------------ terrain grid, opt-in
+ * A ground model that can be sampled: the lowest return per cell of an xy grid, the cells that are ground by a
+ * morphological opening, the rest filled from their neighbours; then the height of every row above that ground and the
+ * ground under any position - what a sag curve's ground clearance is measured against.
+ *
+ * The rule.  All arithmetic is float64 without FMA (the library is built with -ffp-contract=off), with parentheses as
+ * written.  tests/terrain_cases.py follows it literally in numpy.
+ *   Grid.  PchTerrainGrid { double x0, y0, cell; int32_t nx, ny; }, host side, with the conventions of PchPlaneGrid.
+ *     cell > 0 and finite; nx, ny >= 1; nx * ny <= 2^24.  Anything else is PCH_ERR_ARG.  Cell c = fy * nx + fx.
+ *   Row frame.  P = fl32(xyz[i] - sub3) per component.  This is a float32 subtraction, the arithmetic of
+ *     raw - centroid, as in pch_dbscan_assign_f32.  sub3_host == NULL means no subtraction.  X, Y, Z = (double)P.
+ *   Cell of a row.  fx = floor((X - x0) / cell) and fy = floor((Y - y0) / cell).  The row is inside the grid iff
+ *     0 <= fx < nx and 0 <= fy < ny.  NaN and inf fail these comparisons.  A row takes part iff it is inside the grid,
+ *     Z is finite, and skip[i] == 0.  skip is an optional uint8 [n].
+ *   Lowest return (pch_terrain_low_f32).  count[c] (int32) is the number of rows that take part in cell c.  low[c]
+ *     (float32) is the row value P.z with the smallest key, where
+ *         key(z) = bits(z) ^ (bits(z) >> 31 ? 0xFFFFFFFF : 0x80000000)
+ *     This is the usual order-preserving map, so -0.0 sorts below +0.0.  low[c] is NaN where count[c] == 0.
+ *   Ground cells and fill (pch_terrain_ground_f32), with window radius R in cells (0 <= R <= 64), dh >= 0 finite, and
+ *     gap G in cells (0 <= G <= 256).
+ *     Opening.  Erosion then dilation with the square window (2R+1)^2, clipped at the grid edge.  Both are separable:
+ *       first along x, then along y.  Erosion is the minimum over the window's non-NaN cells, NaN if there is none.
+ *       Dilation is the maximum over the eroded grid's non-NaN cells, NaN if there is none.  All four passes are in
+ *       float32.  They are exact, since min and max round nothing.  A pass walks its window in ascending index and
+ *       replaces what it holds only by a value that compares smaller (larger): of -0.0 and +0.0 the first met stays.
+ *       The result is open[c].
+ *     Ground.  Cell c is ground iff low[c] is not NaN and ((double)low[c] - (double)open[c]) <= dh.  With R == 0, every
+ *       cell that has a row is ground.
+ *     Fill.  A ground cell gets ground[c] = low[c].  Any other cell looks in the four directions, in the order
+ *       -x, +x, -y, +y.  In each direction it walks d = 1..G and takes the first ground cell.  It stops at the grid
+ *       edge.  Start with num = 0.0; den = 0.0.  For each direction that found a cell, in that order, add
+ *           num = num + ((double)low_k / (double)d_k)   and   den = den + (1.0 / (double)d_k)
+ *       ground[c] = (float)(num / den) if a cell was found, otherwise NaN.
+ *     State.  state[c] (uint8) has bit 0 set for ground, bit 1 for filled from neighbours, and bit 2 when the cell had
+ *       rows (low not NaN).  So 5 is a ground cell, 6 is a cell with rows that was rejected and filled (a roof, a
+ *       crown), 2 is an empty cell that was filled, and 0 or 4 has no ground value.
+ *   Ground under a position, g(X, Y) in doubles.  One __device__ function serves both entry points below.
+ *     The position's cell is (fx, fy) by the cell rule.  Outside the grid, g is NaN.
+ *         u = ((X - x0) / cell) - 0.5
+ *         i0 = floor(u), clamped to [0, max(nx - 2, 0)];  i1 = min(i0 + 1, nx - 1)
+ *         a = u - (double)i0;  if a < 0: a = 0;  if a > 1: a = 1
+ *     v, j0, j1 and b are the same along y.  With g00 = ground[j0][i0], g10 = ground[j0][i1], g01 = ground[j1][i0] and
+ *     g11 = ground[j1][i1] as doubles: if none of the four is NaN,
+ *         g = (((g00*(1 - a)) + (g10*a))*(1 - b)) + (((g01*(1 - a)) + (g11*a))*b)
+ *     Otherwise g = (double)ground[fy][fx], which may be NaN.
+ *     pch_terrain_height_f32 works on rows: out_height[i] = (float)(Z - g(X, Y)); the optional out_ground[i] = (float)g.
+ *     A row with a non-finite coordinate gets NaN in both.  There is no skip here: every row is answered.
+ *     pch_terrain_sample_f64 takes xy as double [m,2] and writes out double [m] = g, with no subtraction.
+ *   Span ground clearance.  This needs no kernel of its own: torch arithmetic on K*(S+1) records plus one
+ *     pch_terrain_sample_f64 call (ops.span_ground_profile).  The vertices j = 0..S of a piece's polyline are exactly
+ *     the m_j, z_j of the polyline above (m_S = m1).  X = cx + (m*ux), Y = cy + (m*uy), W = cz + z,
+ *     clr = W - g(X, Y).  Per piece: clearance and ground ([K, S+1] float64; NaN where g is NaN), covered (int64: the
+ *     vertices with a ground value), min_clearance (the smallest clr over the covered vertices, +inf if there is
+ *     none), min_vertex (the lowest j that attains it, -1 if none), min_at ([K,3] = (X, Y, g) at that vertex, NaN
+ *     without one) and violation (min_clearance <= limit).  The polyline lies above the parabola by at most
+ *     chord_error, so a ground clearance is over-estimated by at most that.
+ *
+ * How: tiles of 1024 rows are combined in an open-addressed table of 2048 slots in LDS (cell id, smallest key, count;
+ * 1024 rows give at most 1024 distinct cells, so it cannot fill), and every occupied slot then issues one integer
+ * atomicMin on the key grid and one atomicAdd on the counts; a small kernel decodes the keys.  The opening is four
+ * grid-sized passes of 2R+1 reads, the fill one walk of at most 4*G reads per cell.  Integer atomics only, nothing waits
+ * on another workgroup: the same input gives the same bits on every run.
+ *
+ * 0 <= n < 2^31 and 0 <= m < 2^31 (else PCH_ERR_ARG, as a grid, R, dh or G outside the limits above, a null buffer that
+ * is needed and a host pointer where a device pointer is needed).  xyz float32 [n,3], skip uint8 [n] or NULL, low /
+ * ground / out_open float32 [nx*ny], out_count int32 [nx*ny], out_state uint8 [nx*ny], out_height / out_ground float32
+ * [n] - all device; sub3_host 3 floats on the host or NULL; grid_host on the host.  out_stats (int64 [2], device, may
+ * be NULL): the rows that took part and the (tile, cell) flushes - figures for measurement, not part of the rule.  ws:
+ * the caller's, at least the matching *_ws_bytes bytes - pure host code, 0 for sizes out of range (smaller:
+ * PCH_ERR_WORKSPACE).  With n == 0, every cell is NaN with count 0, ground is NaN, and state is 0.  No launch reads a
+ * null pointer.  Every call enqueues on the caller's stream and returns; no host read. */
+typedef struct PchTerrainGrid {
+    double  x0, y0, cell;     /* origin and cell edge in the row frame */
+    int32_t nx, ny;           /* cells along x and y; cell c = fy * nx + fx */
+} PchTerrainGrid;
+#define PCH_TERRAIN_MAX_CELLS  (1 << 24)
+#define PCH_TERRAIN_MAX_WINDOW 64
+#define PCH_TERRAIN_MAX_GAP    256
+size_t pch_terrain_low_ws_bytes(int64_t n, int32_t ncells);
+int pch_terrain_low_f32(const float* xyz, const uint8_t* skip, int64_t n, const float* sub3_host,
+                        const PchTerrainGrid* grid_host, float* out_low, int32_t* out_count,
+                        int64_t* out_stats /* [2], may be NULL */, void* ws, size_t ws_bytes, void* stream);
+size_t pch_terrain_ground_ws_bytes(int32_t ncells);
+int pch_terrain_ground_f32(const float* low, const PchTerrainGrid* grid_host, int32_t window_cells, double dh,
+                           int32_t max_gap, float* out_open /* may be NULL */, float* out_ground,
+                           uint8_t* out_state, void* ws, size_t ws_bytes, void* stream);
+int pch_terrain_height_f32(const float* xyz, int64_t n, const float* sub3_host, const PchTerrainGrid* grid_host,
+                           const float* ground, float* out_height, float* out_ground /* may be NULL */, void* stream);
+int pch_terrain_sample_f64(const double* xy, int64_t m, const PchTerrainGrid* grid_host, const float* ground,
+                           double* out, void* stream);
+
 /* ------------------------------------------------------------------ stage D1, fast mode
  * The reference boxes every cluster with trimesh (utils/tower_extraction.py:137-139:
  * trimesh.PointCloud(cluster_points).bounding_box_oriented): qhull's 3-D hull of the whole cluster, then a

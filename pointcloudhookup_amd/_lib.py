@@ -98,6 +98,12 @@ _SIGS = {
     "pch_clearance_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "pch_clearance_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _sz, _vp]),
+    "pch_terrain_low_ws_bytes": (_sz, [_i64, _i32]),
+    "pch_terrain_low_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pch_terrain_ground_ws_bytes": (_sz, [_i32]),
+    "pch_terrain_ground_f32": (C.c_int, [_vp, _vp, _i32, _f64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pch_terrain_height_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pch_terrain_sample_f64": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "pch_crop_aabb_ws_bytes": (_sz, [_i64]),
     "pch_crop_aabb_f64": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pch_crop_boxes_ws_bytes": (_sz, [_i64, _i32, _i64]),
@@ -160,6 +166,11 @@ class UprightBoxC(C.Structure):
     _fields_ = [("status", C.c_int32), ("j", C.c_int32), ("j0", C.c_int32), ("reserved", C.c_int32),
                 ("n", C.c_int64), ("umin", C.c_double), ("umax", C.c_double), ("vmin", C.c_double),
                 ("vmax", C.c_double), ("zmin", C.c_double), ("zmax", C.c_double)]
+
+
+class TerrainGridC(C.Structure):
+    """PchTerrainGrid (include/pch_hip.h)."""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32)]
 
 
 class PlaneGridC(C.Structure):

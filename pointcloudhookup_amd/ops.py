@@ -18,7 +18,8 @@ One function per reference library call:
   crop_boxes        <- per-tower box masks over the cloud    test/kuangxuan.py:60-79, ui/extract.py:345-420
 Beyond the reference, on a retained fit (DbscanFit): assign, kdist, shape (+ shape_features), knn (+ knn_mean_distance) -
 DESIGN.md sections 5a, 5b, 5c; on a grouping: cluster_moments, span_frames, cluster_profile, span_fit - section 5d; on a cloud and the fitted
-curves: span_curves, span_segments, clearance - section 5e.
+curves: span_curves, span_segments, clearance - section 5e; on a cloud and a grid: terrain_grid, terrain_low,
+terrain_ground, terrain_height, terrain_sample, span_ground_profile - section 5f.
 """
 from __future__ import annotations
 
@@ -1544,11 +1545,8 @@ def span_segments(curves, segments=32):
 
 def _span_segments_of(curves, S):
     """span_segments' arithmetic, on tensors of any device"""
-    a, b, c, m0, m1 = (curves[:, i:i + 1] for i in range(5, 10))
-    step = (m1 - m0) / float(S)
-    j = torch.arange(S, dtype=torch.float64, device=curves.device)[None, :]
-    m = torch.cat([m0 + j * step, m1], dim=1)                                # [K,S+1]: m_S = m1
-    z = a + m * (b + c * m)
+    c = curves[:, 7:8]
+    m, z, step = _span_vertices_of(curves, S)
     dm = m[:, 1:] - m[:, :-1]
     dz = z[:, 1:] - z[:, :-1]
     len2 = (dm * dm) + (dz * dz)
@@ -1558,6 +1556,17 @@ def _span_segments_of(curves, S):
     segs = torch.stack([m[:, :-1], z[:, :-1], dm, dz, inv], dim=2).contiguous()
     chord = ((torch.abs(c) * (step * step)) / 4.0).reshape(-1)
     return segs, chord
+
+
+def _span_vertices_of(curves, S):
+    """(m, z float64 [K,S+1], step [K,1]): the vertices of the S-segment polyline of each curve, m_S = m1 - the first
+    lines of span_segments' arithmetic, shared with span_ground_profile"""
+    a, b, c, m0, m1 = (curves[:, i:i + 1] for i in range(5, 10))
+    step = (m1 - m0) / float(S)
+    j = torch.arange(S, dtype=torch.float64, device=curves.device)[None, :]
+    m = torch.cat([m0 + j * step, m1], dim=1)                                # [K,S+1]: m_S = m1
+    z = a + m * (b + c * m)
+    return m, z, step
 
 
 def clearance(xyz, curves, segs, radius, limit, skip=None, want_stats=False):
@@ -1614,6 +1623,241 @@ def clearance(xyz, curves, segs, radius, limit, skip=None, want_stats=False):
     if want_stats:
         out["loops"] = loops
     return out
+
+
+# ------------------------------------------------------------- terrain grid, opt-in
+TERRAIN_TILE = 1024            # rows per workgroup of the lowest-return sweep (tl_low_k): the sizes tests straddle
+TERRAIN_MAX_CELLS = 1 << 24
+TERRAIN_MAX_WINDOW = 64        # cells
+TERRAIN_MAX_GAP = 256          # cells
+
+
+def _sub3(sub):
+    """three floats for a sub3_host argument (a ctypes array, which the caller keeps alive over the call), or None"""
+    import ctypes as C
+    import numpy as np
+    if sub is None:
+        return None
+    v = np.asarray(sub.detach().cpu() if isinstance(sub, torch.Tensor) else sub, dtype=np.float32).reshape(-1)
+    if v.size != 3:
+        raise ValueError("sub must hold three values")
+    return (C.c_float * 3)(*[float(x) for x in v])
+
+
+def _sub3_ptr(s3):
+    import ctypes as C
+    return None if s3 is None else C.cast(s3, C.c_void_p)
+
+
+def terrain_grid(points, cell, sub=None):
+    """The xy grid of a terrain model over the rows of float32 [n,3] that are finite in all three coordinates:
+    dict(x0, y0, cell, nx, ny) with x0 = (double)fl32(min_x - sub_x), nx = floor((max - x0) / cell) + 1, likewise y
+    (PchTerrainGrid, include/pch_hip.h; derived as ``plane_tile_grid`` derives its grid).  The bounds come from a torch
+    reduction; one small host read.  ValueError beyond 2^24 cells, naming the smallest cell size that fits."""
+    import math
+    import numpy as np
+    points = _need_cuda(points, torch.float32, "points").reshape(-1, 3)
+    cell = float(cell)
+    if not (cell > 0.0 and math.isfinite(cell)):
+        raise ValueError(f"cell must be positive and finite, got {cell!r}")
+    s3 = _sub3(sub)
+    inf = torch.tensor(float("inf"), dtype=torch.float32, device=points.device)
+    fin = torch.isfinite(points).all(dim=1, keepdim=True)
+    lo = torch.where(fin, points[:, :2], inf).amin(dim=0) if points.shape[0] else inf.expand(2)
+    hi = torch.where(fin, points[:, :2], -inf).amax(dim=0) if points.shape[0] else (-inf).expand(2)
+    host = torch.cat([lo, hi]).cpu().numpy()
+    return _terrain_grid_of(host[0:2], host[2:4], np.zeros(2, np.float32) if s3 is None else np.float32(s3[:2]), cell)
+
+
+def _terrain_grid_of(lo, hi, sub, cell):
+    """the grid from the float32 bounds of the finite rows' x, y (inf / -inf without any) and the float32 offset"""
+    import math
+    import numpy as np
+    out, ext = dict(cell=float(cell)), [0.0, 0.0]
+    for k, name in enumerate(("x", "y")):
+        if not lo[k] <= hi[k]:                          # no finite row: one cell at the origin
+            out[name + "0"], out["n" + name] = 0.0, 1
+            continue
+        with np.errstate(over="ignore"):
+            a, b = float(np.float32(lo[k]) - np.float32(sub[k])), float(np.float32(hi[k]) - np.float32(sub[k]))
+        if not (math.isfinite(a) and math.isfinite(b)):
+            raise ValueError("the bounds of the cloud in the row frame are not finite")
+        out[name + "0"], out["n" + name], ext[k] = a, int(math.floor((b - a) / cell)) + 1, b - a
+    if out["nx"] * out["ny"] > TERRAIN_MAX_CELLS:
+        fits = lambda s: (math.floor(ext[0] / s) + 1) * (math.floor(ext[1] / s) + 1) <= TERRAIN_MAX_CELLS
+        lo_s, hi_s = cell, max(ext) + 1.0                              # hi_s: one cell, fits
+        for _ in range(100):
+            mid = 0.5 * (lo_s + hi_s)
+            lo_s, hi_s = (lo_s, mid) if fits(mid) else (mid, hi_s)
+        digit = 10.0 ** (math.floor(math.log10(hi_s)) - 5)               # six digits, rounded up: the figure shown fits
+        raise ValueError(f"cell {cell:g} gives {out['nx']} x {out['ny']} cells, more than 2^24 = {TERRAIN_MAX_CELLS}; "
+                         f"the smallest cell that fits is {math.ceil(hi_s / digit) * digit:.6g}")
+    return out
+
+
+def _terrain_grid_c(grid):
+    import math
+    g = _lib.TerrainGridC(float(grid["x0"]), float(grid["y0"]), float(grid["cell"]), int(grid["nx"]), int(grid["ny"]))
+    if not (g.cell > 0.0 and math.isfinite(g.cell)) or g.nx < 1 or g.ny < 1 or g.nx * g.ny > TERRAIN_MAX_CELLS:
+        raise ValueError(f"the grid needs a positive finite cell and between 1 and 2^24 cells, got cell {g.cell!r}, "
+                         f"{g.nx} x {g.ny}")
+    return g
+
+
+def _grid_ptr(grid_c):
+    import ctypes as C
+    return C.cast(C.pointer(grid_c), C.c_void_p)
+
+
+def _terrain_cells(t, dtype, name, g):
+    t = _need_cuda(t, dtype, name).reshape(-1)
+    if t.numel() != g.nx * g.ny:
+        raise ValueError(f"{name} must hold one value per cell of the {g.nx} x {g.ny} grid")
+    return t
+
+
+def terrain_low(points, grid, sub=None, skip=None, want_stats=False):
+    """The lowest return per cell (pch_terrain_low_f32; the rule is in include/pch_hip.h): dict of device tensors -
+    ``low`` float32 [ny,nx], the smallest z of ``fl32(points - sub)`` over the rows that take part in the cell (inside
+    the grid, finite z, not skipped; -0.0 below +0.0), NaN for a cell without one, and ``count`` int32 [ny,nx].
+    ``points`` float32 [n,3]; ``grid`` a dict as ``terrain_grid`` returns it; ``sub`` three floats subtracted in float32
+    (None: nothing); ``skip`` an optional uint8 or bool [n].  ``want_stats`` adds ``stats`` int64 [2]: the rows that
+    took part and the (tile, cell) flushes.  The same input gives the same bits on every run.  Asynchronous."""
+    L = _lib.lib()
+    points = _need_cuda(points, torch.float32, "points").reshape(-1, 3)
+    g = _terrain_grid_c(grid)
+    n, dev, ncells = points.shape[0], points.device, g.nx * g.ny
+    if n >= 1 << 31:
+        raise ValueError("terrain_low takes fewer than 2^31 rows per call")
+    if skip is not None:
+        if isinstance(skip, torch.Tensor) and skip.dtype == torch.bool:
+            skip = skip.view(torch.uint8)
+        skip = _need_cuda(skip, torch.uint8, "skip").reshape(-1)
+        if skip.numel() != n:
+            raise ValueError("skip must hold one entry per row")
+    s3 = _sub3(sub)
+    with torch.cuda.device(dev):
+        low = torch.empty((g.ny, g.nx), dtype=torch.float32, device=dev)
+        count = torch.empty((g.ny, g.nx), dtype=torch.int32, device=dev)
+        stats = torch.empty((2,), dtype=torch.int64, device=dev) if want_stats else None
+        ws = _workspace(L.pch_terrain_low_ws_bytes(n, ncells), dev)
+        _lib.check(L.pch_terrain_low_f32(_ptr(points), _ptr(skip), n, _sub3_ptr(s3), _grid_ptr(g), _ptr(low),
+                                         _ptr(count), _ptr(stats), _ptr(ws), ws.numel(), _stream()))
+    out = dict(low=low, count=count)
+    if want_stats:
+        out["stats"] = stats
+    return out
+
+
+def terrain_ground(low, grid, window_cells, dh, max_gap, want_open=False):
+    """Ground cells and fill (pch_terrain_ground_f32): dict of device tensors - ``ground`` float32 [ny,nx] (``low`` in a
+    ground cell, the inverse-distance mean of the first ground cells within ``max_gap`` cells in -x, +x, -y, +y
+    elsewhere, NaN without one) and ``state`` uint8 [ny,nx] (bit 0 ground, bit 1 filled, bit 2 the cell had rows).  A
+    cell is ground iff ``low - open <= dh`` with ``open`` the opening of ``low`` by a square window of radius
+    ``window_cells``; ``want_open`` adds ``open``.  ValueError: window_cells outside 0..64, max_gap outside 0..256, dh
+    negative or not finite.  Asynchronous."""
+    import math
+    L = _lib.lib()
+    g = _terrain_grid_c(grid)
+    low = _terrain_cells(low, torch.float32, "low", g)
+    for name, v, top in (("window_cells", window_cells, TERRAIN_MAX_WINDOW), ("max_gap", max_gap, TERRAIN_MAX_GAP)):
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= top:
+            raise ValueError(f"{name} must be an integer in 0..{top}, got {v!r}")
+    dh = float(dh)
+    if not (math.isfinite(dh) and dh >= 0.0):
+        raise ValueError(f"dh must be finite and >= 0, got {dh!r}")
+    dev, ncells = low.device, g.nx * g.ny
+    with torch.cuda.device(dev):
+        ground = torch.empty((g.ny, g.nx), dtype=torch.float32, device=dev)
+        state = torch.empty((g.ny, g.nx), dtype=torch.uint8, device=dev)
+        opened = torch.empty((g.ny, g.nx), dtype=torch.float32, device=dev) if want_open else None
+        ws = _workspace(L.pch_terrain_ground_ws_bytes(ncells), dev)
+        _lib.check(L.pch_terrain_ground_f32(_ptr(low), _grid_ptr(g), int(window_cells), dh, int(max_gap), _ptr(opened),
+                                            _ptr(ground), _ptr(state), _ptr(ws), ws.numel(), _stream()))
+    out = dict(ground=ground, state=state)
+    if want_open:
+        out["open"] = opened
+    return out
+
+
+def terrain_height(points, grid, ground, sub=None, want_ground=False):
+    """float32 [n], device: the height of every row of ``fl32(points - sub)`` above the ground under it, the bilinear
+    value between the four cell centres around it (its own cell's where one of them has no ground); NaN outside the
+    grid, over a cell without ground and for a row that is not finite (pch_terrain_height_f32).  ``want_ground``:
+    (height, ground under the row), both float32 [n].  Asynchronous."""
+    L = _lib.lib()
+    points = _need_cuda(points, torch.float32, "points").reshape(-1, 3)
+    g = _terrain_grid_c(grid)
+    ground = _terrain_cells(ground, torch.float32, "ground", g)
+    n, dev = points.shape[0], points.device
+    if n >= 1 << 31:
+        raise ValueError("terrain_height takes fewer than 2^31 rows per call")
+    s3 = _sub3(sub)
+    with torch.cuda.device(dev):
+        height = torch.empty((n,), dtype=torch.float32, device=dev)
+        under = torch.empty((n,), dtype=torch.float32, device=dev) if want_ground else None
+        _lib.check(L.pch_terrain_height_f32(_ptr(points), n, _sub3_ptr(s3), _grid_ptr(g), _ptr(ground), _ptr(height),
+                                            _ptr(under), _stream()))
+    return (height, under) if want_ground else height
+
+
+def terrain_sample(xy, grid, ground):
+    """float64 [m], device: the ground under the float64 positions [m,2], in doubles, by the rule of ``terrain_height``
+    (pch_terrain_sample_f64; no subtraction).  Asynchronous."""
+    L = _lib.lib()
+    xy = _need_cuda(xy, torch.float64, "xy").reshape(-1, 2)
+    g = _terrain_grid_c(grid)
+    ground = _terrain_cells(ground, torch.float32, "ground", g)
+    m, dev = xy.shape[0], xy.device
+    if m >= 1 << 31:
+        raise ValueError("terrain_sample takes fewer than 2^31 positions per call")
+    with torch.cuda.device(dev):
+        out = torch.empty((m,), dtype=torch.float64, device=dev)
+        _lib.check(L.pch_terrain_sample_f64(_ptr(xy), m, _grid_ptr(g), _ptr(ground), _ptr(out), _stream()))
+    return out
+
+
+def span_ground_profile(curves, segments, grid, ground, limit):
+    """How high each curve of ``span_curves`` hangs above the ground (include/pch_hip.h's rule): the vertices of its
+    polyline of ``segments`` segments - ``span_segments``' own - are placed in the frame of the grid, the ground under
+    them comes from one ``terrain_sample`` call, the rest is float64 torch arithmetic on K·(S+1) records.  Dict of
+    device tensors: ``clearance`` and ``ground`` float64 [K,S+1] (NaN where there is no ground), ``covered`` int64 [K],
+    ``min_clearance`` float64 [K] (+inf without a covered vertex), ``min_vertex`` int64 [K] (the lowest vertex that
+    attains it, -1 without), ``min_at`` float64 [K,3] = (x, y, ground) at that vertex (NaN without) and ``violation``
+    bool [K]: ``min_clearance <= limit``.  The polyline lies above the curve by at most ``span_segments``'
+    chord_error, so a clearance is over-estimated by at most that.  Asynchronous."""
+    S = check_segments(segments)
+    curves = _need_cuda(curves, torch.float64, "curves").reshape(-1, 10)
+    m, z, _ = _span_vertices_of(curves, S)
+    X, Y, W = _span_vertex_positions_of(curves, m, z)
+    g = terrain_sample(torch.stack([X, Y], dim=2).reshape(-1, 2), grid, ground).reshape(-1, S + 1)
+    return _span_ground_minima_of(X, Y, W, g, float(limit))
+
+
+def _span_vertex_positions_of(curves, m, z):
+    """(X, Y, W float64 [K,S+1]): the polyline's vertices in the frame of the curves' centres, on tensors of any
+    device"""
+    cx, cy, cz, ux, uy = (curves[:, i:i + 1] for i in range(5))
+    return cx + (m * ux), cy + (m * uy), cz + z
+
+
+def _span_ground_minima_of(X, Y, W, g, limit):
+    """span_ground_profile's arithmetic behind the sample, on tensors of any device"""
+    K, V = g.shape
+    has = ~torch.isnan(g)
+    clr = W - g
+    inf = torch.full_like(clr, float("inf"))
+    key = torch.where(has, clr, inf)
+    minc = key.amin(dim=1)
+    j = torch.arange(V, dtype=torch.int64, device=g.device)[None, :].expand(K, V)
+    first = torch.where(has & (key == minc[:, None]), j, torch.full_like(j, V)).amin(dim=1)
+    found = first < V
+    at = first.clamp(max=V - 1)[:, None]
+    nan = torch.full((K, 3), float("nan"), dtype=torch.float64, device=g.device)
+    xyz = torch.cat([X.gather(1, at), Y.gather(1, at), g.gather(1, at)], dim=1)
+    return dict(clearance=clr, ground=g, covered=has.sum(dim=1), min_clearance=minc,
+                min_vertex=torch.where(found, first, torch.full_like(first, -1)),
+                min_at=torch.where(found[:, None], xyz, nan), violation=minc <= limit)
 
 
 # ---------------------------------------------------------------------------- stage D1, fast mode

@@ -216,6 +216,92 @@ def conductor_clearance(points, spans, radius=10.0, limit=6.0, segments=32, towe
     return dict(dist2=res["dist2"], span=span, violating=res["dist2"] <= float(limit) * float(limit), table=table)
 
 
+def terrain_cells(cell, window, max_gap):
+    """(R, G): the opening's window radius and the fill's gap in cells for ``window`` and ``max_gap`` in metres -
+    ``R = ceil(window / (2·cell))``, ``G = ceil(max_gap / cell)``; ValueError beyond the library's limits"""
+    import math
+    cell, window, max_gap = float(cell), float(window), float(max_gap)
+    if not (math.isfinite(cell) and cell > 0.0):
+        raise ValueError(f"cell must be finite and > 0, got {cell!r}")
+    if not (math.isfinite(window) and window >= 0.0 and math.isfinite(max_gap) and max_gap >= 0.0):
+        raise ValueError(f"window and max_gap must be finite and >= 0, got {window!r}, {max_gap!r}")
+    R, G = math.ceil(window / (2.0 * cell)), math.ceil(max_gap / cell)
+    if R > ops.TERRAIN_MAX_WINDOW:
+        raise ValueError(f"window {window:g} m at cell {cell:g} m is a radius of {R} cells; the limit is "
+                         f"{ops.TERRAIN_MAX_WINDOW} cells ({2 * ops.TERRAIN_MAX_WINDOW * cell:g} m)")
+    if G > ops.TERRAIN_MAX_GAP:
+        raise ValueError(f"max_gap {max_gap:g} m at cell {cell:g} m is {G} cells; the limit is "
+                         f"{ops.TERRAIN_MAX_GAP} cells ({ops.TERRAIN_MAX_GAP * cell:g} m)")
+    return int(R), int(G)
+
+
+def terrain_model(raw, sub=None, cell=1.0, window=12.0, dh=0.5, max_gap=16.0, skip=None):
+    """A ground model that can be sampled: over the rows of ``raw`` (float32 [n,3] on the device, ground
+    included; ``sub``: three floats subtracted in float32, e.g. stage B's centroid) a grid of ``cell`` metres with the
+    lowest return per cell (``ops.terrain_grid``, ``ops.terrain_low``); the cells whose lowest return stays within
+    ``dh`` of its opening by a window of ``window`` metres are ground - roofs, crowns and anything else narrower than
+    the window are not -, the others get the inverse-distance mean of the nearest ground cells within ``max_gap`` metres
+    along x and y (``ops.terrain_ground``).
+
+    Returns dict: ``grid`` (x0, y0, cell, nx, ny), ``low`` float32 and ``count`` int32 [ny,nx], ``ground`` float32
+    [ny,nx] (NaN without a value), ``state`` uint8 [ny,nx] (bit 0 ground, bit 1 filled, bit 2 the cell had rows),
+    ``n_ground``, ``n_filled`` and ``n_unfilled`` (cells).  ValueError: a window or a gap beyond the library's limits
+    (64 and 256 cells), a grid beyond 2^24 cells.  Synchronises."""
+    if not isinstance(raw, torch.Tensor) or not raw.is_cuda or raw.dtype != torch.float32:
+        raise TypeError("raw must be a float32 CUDA/HIP tensor (no CPU fallback in the product path)")
+    R, G = terrain_cells(cell, window, max_gap)
+    raw = raw.reshape(-1, 3).contiguous()
+    grid = ops.terrain_grid(raw, cell, sub=sub)
+    low = ops.terrain_low(raw, grid, sub=sub, skip=skip)
+    res = ops.terrain_ground(low["low"], grid, R, dh, G)
+    state = res["state"]
+    tally = torch.stack([(state & 1).ne(0).sum(), (state & 2).ne(0).sum(), (state & 3).eq(0).sum()]).cpu()
+    return dict(grid=grid, low=low["low"], count=low["count"], ground=res["ground"], state=state,
+                n_ground=int(tally[0]), n_filled=int(tally[1]), n_unfilled=int(tally[2]))
+
+
+def height_above_ground(points, terrain, sub=None):
+    """float32 [n], device: the height of every row of ``fl32(points - sub)`` above the ground of ``terrain``
+    (``terrain_model``'s dict), NaN where the model has no value (``ops.terrain_height``).  Asynchronous."""
+    return ops.terrain_height(points, terrain["grid"], terrain["ground"], sub=sub)
+
+
+GROUND_CLEARANCE_TABLE_KEYS = ("min_clearance", "min_vertex", "min_at", "covered", "violation", "chord_error")
+
+
+def span_ground_clearance(spans, terrain, segments=32, limit=7.0):
+    """How high the accepted pieces of ``spans`` (``conductor_spans``' dict) hang above the ground of ``terrain``
+    (``terrain_model``'s dict, in the same frame) and where they are lowest: each accepted piece becomes
+    ``conductor_clearance``'s polyline of ``segments`` segments, whose vertices are held against the ground under them
+    (``ops.span_ground_profile``).
+
+    Returns dict: ``pieces`` (int64: the accepted pieces' ids, ascending), ``clearance`` and ``ground`` (float64
+    [len(pieces), segments + 1]) and ``table``, a dict over the K pieces of the span table, keyed like
+    ``CLEARANCE_TABLE_KEYS``: ``min_clearance`` (metres; +inf without a vertex over ground or for a piece that was not
+    accepted), ``min_vertex`` (-1 without), ``min_at`` ([K,3] float64: x, y and the ground's z there, NaN without),
+    ``covered`` (int64: the vertices over ground), ``violation`` (bool: ``min_clearance <= limit``) and ``chord_error``
+    (metres: by how much at most the polyline over-estimates a clearance; NaN for a piece that was not accepted).  No
+    accepted piece: an empty ``pieces`` and a table without a clearance; nothing is raised.  Asynchronous."""
+    segments = ops.check_segments(segments)
+    K = int(spans["nclusters"])
+    idx = torch.nonzero(spans["accepted"]).reshape(-1)                        # accepted pieces, ascending
+    dev = spans["accepted"].device
+    curves = ops.span_curves(spans["table"], spans["frames"], spans["ext"])[idx].contiguous()
+    _, chord = ops.span_segments(curves, segments)
+    res = ops.span_ground_profile(curves, segments, terrain["grid"], terrain["ground"], limit)
+    nan64 = float("nan")
+    table = dict(min_clearance=torch.full((K,), float("inf"), dtype=torch.float64, device=dev),
+                 min_vertex=torch.full((K,), -1, dtype=torch.int64, device=dev),
+                 min_at=torch.full((K, 3), nan64, dtype=torch.float64, device=dev),
+                 covered=torch.zeros((K,), dtype=torch.int64, device=dev),
+                 violation=torch.zeros((K,), dtype=torch.bool, device=dev),
+                 chord_error=torch.full((K,), nan64, dtype=torch.float64, device=dev))
+    for key in ("min_clearance", "min_vertex", "min_at", "covered", "violation"):
+        table[key][idx] = res[key]
+    table["chord_error"][idx] = chord
+    return dict(pieces=idx, clearance=res["clearance"], ground=res["ground"], table=table)
+
+
 def _kept_rows(gf, dropped):
     """the copy of the stage-B result ``gf`` without the rows of the bool mask ``dropped``, as the opt-in drops return
     it: points, index (if present), count and aabb of the rows left, in file order, plus dropped and n_dropped"""

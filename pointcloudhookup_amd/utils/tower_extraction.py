@@ -71,6 +71,15 @@ conductors themselves and the rows within the spans' ``cut_radius`` of an accept
 5e) and ``output_towers/clearance_info.csv`` gets one line per accepted wire piece: the rows nearer than ``radius``
 metres, those nearer than ``limit``, the smallest distance and the nearest point in world coordinates.  It logs one extra
 line; a failure is handled like one of ``SPANS``.  The returned tower dicts are the same with and without it.
+``TERRAIN`` (env PCH_TERRAIN="cell,window,dh[,limit]", e.g. "1,12,0.5,7"; unset or empty = off; needs ``SPANS`` and the
+"reference" frame - importing the module with PCH_TERRAIN set and PCH_SPANS unset, or with PCH_FRAME=las, raises
+ValueError): right after the ground rule, a terrain grid of ``cell`` metres is built from the whole cloud, ground included
+(pipeline.terrain_model: lowest return per cell, ground cells by an opening of ``window`` metres within ``dh``, the rest
+filled over at most 16 m), and behind the span table ``output_towers/ground_clearance_info.csv``
+gets one line per accepted wire piece: its length, the smallest height of its sag curve above that ground, where that
+is in world coordinates, the ground's z there, the vertices over ground, the chord error and whether the height is at
+most ``limit`` metres (default 7).  It logs one extra line; a failure is handled like one of ``SPANS``.  The returned
+tower dicts are the same with and without it.
 """
 from __future__ import annotations
 
@@ -198,6 +207,42 @@ def clearance_from_env(value, spans=True):
 
 CLEARANCE = clearance_from_env(os.environ.get("PCH_CLEARANCE"), spans=SPANS is not None)
 CLEARANCE_COLUMNS = ("ID", "count", "violations", "min_distance", "min_row", "x", "y", "z", "chord_error")
+
+
+def terrain_from_env(value, spans=True, frame="reference"):
+    """TERRAIN of an environment value: None (off) when unset or empty, else dict(cell, window, dh, limit) from
+    "cell,window,dh[,limit]" - three or four numbers; cell finite and > 0, window and dh finite and >= 0 with the
+    window's radius ceil(window / (2 cell)) at most 64 cells, limit finite (default 7.0).  ``spans``: whether SPANS is
+    on - the clearance is that of its pieces; ``frame``: FRAME - the grid is built from the float32 rows, which the
+    LAS-integer frame never makes.  A value without the one or with the other is refused (ValueError)"""
+    if value is None or not value.strip():
+        return None
+    parts = [t.strip() for t in value.split(",")]
+    if len(parts) not in (3, 4):
+        raise ValueError(f"PCH_TERRAIN takes \"cell,window,dh[,limit]\", got {value!r}")
+    cell, window, dh = float(parts[0]), float(parts[1]), float(parts[2])
+    limit = float(parts[3]) if len(parts) == 4 else 7.0
+    if not (np.isfinite(cell) and cell > 0.0):
+        raise ValueError(f"PCH_TERRAIN: cell must be finite and > 0, got {parts[0]!r}")
+    if not (np.isfinite(window) and window >= 0.0):
+        raise ValueError(f"PCH_TERRAIN: window must be finite and >= 0, got {parts[1]!r}")
+    if int(np.ceil(window / (2.0 * cell))) > TERRAIN_MAX_WINDOW_CELLS:
+        raise ValueError(f"PCH_TERRAIN: window {parts[1]!r} at cell {parts[0]!r} is a radius of more than "
+                         f"{TERRAIN_MAX_WINDOW_CELLS} cells, the library's limit")
+    if not (np.isfinite(dh) and dh >= 0.0):
+        raise ValueError(f"PCH_TERRAIN: dh must be finite and >= 0, got {parts[2]!r}")
+    if not np.isfinite(limit):
+        raise ValueError(f"PCH_TERRAIN: limit must be finite, got {parts[3]!r}")
+    if not spans:
+        raise ValueError("PCH_TERRAIN needs PCH_SPANS: the ground clearance is that of the span table's pieces")
+    if frame == "las":
+        raise ValueError("PCH_TERRAIN is not defined for PCH_FRAME=las: the terrain grid is built from the float32 rows")
+    return dict(cell=cell, window=window, dh=dh, limit=limit)
+
+
+TERRAIN_MAX_WINDOW_CELLS = 64                        # PCH_TERRAIN_MAX_WINDOW of include/pch_hip.h
+TERRAIN = terrain_from_env(os.environ.get("PCH_TERRAIN"), spans=SPANS is not None, frame=FRAME)
+TERRAIN_COLUMNS = ("ID", "length", "min_clearance", "x", "y", "z", "ground_z", "covered", "chord_error", "violation")
 PRESTART_BYTES = 100 << 20                           # LAS files from here on get worker processes early
 CHUNK_SIZE = 50000                                     # utils/tower_extraction.py:96
 
@@ -327,6 +372,16 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
     except Exception as e:
         log(f"⚠️ 高度过滤失败: {str(e)}")
         return tower_obbs
+    terrain = None
+    if TERRAIN:
+        # ---- opt-in: the ground as a grid, from the whole cloud in stage B's frame, while the cloud is still here
+        try:
+            terrain = pipeline.terrain_model(raw, sub=gf["centroid"], cell=TERRAIN["cell"], window=TERRAIN["window"],
+                                             dh=TERRAIN["dh"])
+            clock.mark("terrain grid")
+        except (ValueError, RuntimeError) as e:
+            log(f"⚠️ 地形网格构建失败: {str(e)}")
+            return tower_obbs
     del raw
     stage_b_points = gf["points"] if SPANS else None           # the conductors are looked for before any drop
 
@@ -462,7 +517,19 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
             except (ValueError, RuntimeError) as e:
                 log(f"⚠️ 导线净空计算失败: {str(e)}")
                 return tower_obbs
-    stage_b_points = None
+        # ---- opt-in: how high those conductors hang above the ground
+        if TERRAIN:
+            try:
+                over = pipeline.span_ground_clearance(spans, terrain, limit=TERRAIN["limit"],
+                                                      segments=CLEARANCE["segments"] if CLEARANCE else 32)
+                rows = ground_clearance_rows(spans, over, cen)
+                write_ground_clearance_csv(output_dir / "ground_clearance_info.csv", rows)
+                clock.mark("span ground clearance")
+                log(ground_clearance_line(terrain, rows, TERRAIN))
+            except (ValueError, RuntimeError) as e:
+                log(f"⚠️ 导线对地净空计算失败: {str(e)}")
+                return tower_obbs
+    stage_b_points = terrain = None
 
     # ---- xlsx (reference :221-231)
     if tower_rows:
@@ -569,6 +636,43 @@ def clearance_line(clear, rows, knob):
     return (f"📏 导线净空: 半径 {knob['radius']:g} m，限距 {knob['limit']:g} m，折线 {knob['segments']} 段；"
             f"半径内 {int(near)} 点，越限 {int(clear['violating'].sum())} 点，越限线段 {int(breached)}/{len(rows)}，"
             f"最小净空 {closest:.3f} m")
+
+
+def ground_clearance_rows(spans, over, centroid):
+    """the lines of ground_clearance_info.csv for a result of pipeline.span_ground_clearance: one list per accepted
+    piece in TERRAIN_COLUMNS' order, the lowest point and the ground under it moved to world coordinates by ``centroid``
+    (3 float64; NaN for a piece without a vertex over ground)"""
+    acc = spans["accepted"].cpu().numpy()
+    length = spans["table"]["length"].cpu().numpy()
+    T = {key: v.cpu().numpy() for key, v in over["table"].items()}
+    rows = []
+    for k in np.flatnonzero(acc):
+        x, y, g = (float(v) for v in T["min_at"][k] + centroid)
+        rows.append([f"span_{int(k)}", float(length[k]), float(T["min_clearance"][k]), x, y,
+                     g + float(T["min_clearance"][k]), g, int(T["covered"][k]), float(T["chord_error"][k]),
+                     int(bool(T["violation"][k]))])
+    return rows
+
+
+def write_ground_clearance_csv(path, rows):
+    """ground_clearance_info.csv: a header line (TERRAIN_COLUMNS) and one line per accepted piece, floats with repr's
+    digits"""
+    import csv
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.writer(f)
+        w.writerow(TERRAIN_COLUMNS)
+        for r in rows:
+            w.writerow([repr(float(v)) if isinstance(v, (float, np.floating)) else v for v in r])
+
+
+def ground_clearance_line(terrain, rows, knob):
+    """the extra log line of TERRAIN for a result of pipeline.terrain_model and the csv lines"""
+    breached = sum(1 for r in rows if r[9])
+    lowest = min([r[2] for r in rows], default=float("inf"))
+    g = terrain["grid"]
+    return (f"⛰️ 导线对地净空: 网格 {knob['cell']:g} m（{g['nx']}×{g['ny']}），开窗 {knob['window']:g} m，高差 {knob['dh']:g} m，"
+            f"限距 {knob['limit']:g} m；地面格 {terrain['n_ground']}，填补 {terrain['n_filled']}，无值 {terrain['n_unfilled']}；"
+            f"越限线段 {int(breached)}/{len(rows)}，最小对地净空 {lowest:.3f} m")
 
 
 def ground_tiles_line(gf):
