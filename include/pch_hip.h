@@ -989,8 +989,11 @@ int pch_decimate_f64(const double* xyz, int64_t n, int64_t k, uint64_t seed,
  *             keeps more: PCH_ERR_WORKSPACE, info->count says how many (retry with nf_cap >= it)
  * k_cap       capacity of out_offsets / out_stats; more clusters: PCH_ERR_RANGE (labels and
  *             info are valid, group with pch_segment_by_label)
- * info_host   HOST struct, filled on return.  Synchronises (three times: kept count, cell count,
- *             cluster count); the device outputs are complete once `stream` is.
+ * info_host   HOST struct, filled on return.  Synchronises (two times: kept count together with the
+ *             cell count, cluster count); the device outputs are complete once `stream` is.
+ *             info->reserved is the route word: 1 = the head of stage C was planned on the device and
+ *             ran without the host reading the kept count first, 0 = the host planned it (fallback
+ *             threshold, nothing kept, another sort route, a grid the cell key does not hold, ...).
  */
 typedef struct PchTowerClusters {
     float   centroid[3];      /* np.mean(raw.astype(f32), axis=0)            (:62-63) */
@@ -1001,7 +1004,7 @@ typedef struct PchTowerClusters {
     float   aabb[6];          /* min xyz, max xyz of the kept (centred) points */
     int64_t count;            /* points kept */
     int32_t nclusters;
-    int32_t reserved;
+    int32_t reserved;         /* route word, see above */
 } PchTowerClusters;
 size_t pch_tower_clusters_ws_bytes(int64_t n, int64_t nf_cap, int32_t k_cap);
 int pch_tower_clusters_f32(const float* raw, int64_t n, double pct, float offset,

@@ -113,19 +113,30 @@ int peek_wait(void* dst, size_t bytes);
 // xyz), 0, 0} - decoded in place by the grouping stage (segment_run, stats_encoded).  done: set by the run when the
 // table was filled (not on the per-chunk fallback for grids beyond the 64-bit key).
 struct DbBoxOut { uint32_t* acc; int32_t cap; bool done; };
-// stage B (pch_filter.hip): pch_ground_filter_f32's body.  early (optional): `bytes` device bytes at `dev` - they must
-// cover out_scalars, out_count and out_aabb - are queued for the host (peek_enqueue) directly behind the FIRST sweep and
-// its gf_finalize, i.e. in front of the launches of the fallback threshold, which return at once unless fewer than
-// min_keep rows survived.  The caller waits for that copy (peek_wait); if out_scalars[5] (fallback used) is set in
-// it, the values are not final yet and it queues and waits for a second copy, which then lies behind everything.
-struct GfEarly { const void* dev; size_t bytes; };
+// stage B (pch_filter.hip): pch_ground_filter_f32's body.  early (optional): the run stops behind the FIRST sweep and
+// its gf_finalize, which publishes out_scalars, out_count and out_aabb: they are final unless out_scalars[5] (fallback
+// used: fewer than min_keep rows survived) is set.  *early receives what the launches of the fallback threshold and the
+// second gf_finalize take; the caller queues them (ground_filter_follow_up) when it reads that flag, before anything
+// touches the workspace.  Without early the whole sequence is queued here.
+struct GfFollowUp {
+    bool cand_made; dim3 cgrid, grid;
+    const float* slots; const uint32_t* counts; const float* tcand; int64_t nblk;
+    const float* raw; int64_t n; const float* centroid; const float* scal; void* st; uint64_t* status_fb;
+    long long min_keep; float* out_points; int32_t* out_index; float* out_scalars; int64_t* out_count; float* out_aabb;
+};
 int ground_filter_run(const float* raw, int64_t n, double pct, float offset, float fallback_offset, int64_t min_keep,
                       float* out_points, int32_t* out_index, float* out_scalars, int64_t* out_count, float* out_aabb,
-                      void* ws, size_t ws_bytes, hipStream_t s, const GfEarly* early);
-// stage C with an early host copy of the cluster count (pch_dbscan.hip); k_host and box may be null
+                      void* ws, size_t ws_bytes, hipStream_t s, GfFollowUp* early);
+int ground_filter_follow_up(const GfFollowUp& f, hipStream_t s);
+// stage C with an early host copy of the cluster count (pch_dbscan.hip); k_host and box may be null.  head (the fused
+// call): the workspace is carved for head->plan_n rows (>= n) and, where the head of the stage was queued unread
+// (head->dev), the run goes on behind it if its own plan agrees with the device's (head->host); head->route says so
+struct DbHead;
+struct DbHeadRun { int64_t plan_n; const DbHead* host; int route; };
 int dbscan_run(const float* xyz, int64_t n, double eps, int32_t min_samples, int64_t chunk_size,
                const float* aabb_host, int32_t* labels, uint8_t* core, int32_t* out_nclusters,
-               void* ws, size_t ws_bytes, hipStream_t s, int32_t* k_host, DbBoxOut* box = nullptr);
+               void* ws, size_t ws_bytes, hipStream_t s, int32_t* k_host, DbBoxOut* box = nullptr,
+               DbHeadRun* head = nullptr);
 // stage D0 (pch_segment.hip); stats_encoded: out_stats already holds the table a DbBoxOut run left there
 int segment_run(const int32_t* labels, const float* xyz, int64_t n, int32_t nclusters, int32_t* out_perm,
                 int64_t* out_offsets, float* out_stats, void* ws, size_t ws_bytes, hipStream_t s, bool stats_encoded);

@@ -39,6 +39,75 @@ inline DbBand db_band(double r) {
     return b;
 }
 
+// ---- the part of the grid that depends on the rows' box: one function for the host (db_grid) and for db_headplan_k ----
+__host__ __device__ inline int db_bits_for(uint64_t count) {    // bits_for (pch_common.h), for both sides
+    int b = 0;
+    while (b < 64 && (uint64_t(1) << b) < count) ++b;
+    return b;
+}
+// g.inv_cell is set (it depends on eps alone).  Sets the origin, mx..mz and bx..bz of g and the bits of a cell
+// (cellbits) and of a key (nbits, with the chunk).  Returns true when that key does not fit 64 bits.  A difference, a
+// product, a compare and a truncation per axis: nothing a compiler could contract into a fused multiply-add.
+__host__ __device__ inline bool db_plan_grid(const float* box, int64_t nchunks, DbGrid& g, int& cellbits, int& nbits) {
+    g.ox = box[0]; g.oy = box[1]; g.oz = box[2];
+    int mc[3] = {0, 0, 0};
+    bool overflow = false;
+    for (int k = 0; k < 3; ++k) {
+        const double ext = ((double)box[3 + k] - (double)box[k]) * g.inv_cell;
+        if (!(ext < 2.0e9)) overflow = true;
+        else mc[k] = (int)ext + 1;            // +1: slack for the rounding of the division
+    }
+    g.mx = mc[0]; g.my = mc[1]; g.mz = mc[2];
+    g.bx = db_bits_for((uint64_t)mc[0] + 1); g.by = db_bits_for((uint64_t)mc[1] + 1);
+    g.bz = db_bits_for((uint64_t)mc[2] + 1);
+    cellbits = g.bx + g.by + g.bz;
+    nbits = cellbits + db_bits_for((uint64_t)nchunks);
+    return overflow || nbits > 64;
+}
+__host__ __device__ inline bool db_box_finite(const float* box) {
+    for (int k = 0; k < 6; ++k)
+        if (!(box[k] == box[k]) || box[k] > 3.0e38f || box[k] < -3.0e38f) return false;
+    return true;
+}
+
+constexpr int64_t CS_MAX_CHUNK = 1 << 17;     // larger chunks use the global sort
+constexpr int64_t CS_MIN_CHUNKS = 96;         // fewer chunks: the global sort keeps more of the GPU busy
+constexpr int64_t DB_TABLE_MAX_CHUNKS = 16384;  // beyond: db_cellscatter_k<false>, the table is read off the keys
+
+// The head of stage C planned on the device (the fused call, pch_pipeline.hip): db_headplan_k, one workgroup behind
+// stage B's results, plans the grid from the kept rows' box and count as dbscan_run would; db_cellscatter_k<true>,
+// db_chunksort_k, db_chunkcells_k and db_celltab_k, launched for the largest count the caller allows for, take n,
+// nchunks and the grid from here and return at once when go is clear.  The host reads the block in the wait it makes
+// in front of db_celltab_k, plans again on the same box and goes on behind db_celltab_k if both plans agree.
+struct DbHead {
+    uint32_t go;                 // 1: the staged chunk route runs with the values below
+    int32_t  nchunks;
+    int64_t  n;                  // rows (stage B's kept count)
+    int32_t  cellbits, nbits;
+    uint32_t status, ncells, route;     // db_chunkcells_k: DbMeta::status, ncells and the route word, for the host
+    uint32_t pad;
+    DbGrid   g;
+};
+// what the host knows when it queues db_headplan_k
+struct DbHeadArgs {
+    const float*   scalars;      // stage B: [5] != 0 says the fallback threshold applies (the values are not final)
+    const int64_t* count;        // stage B: rows kept (< 0: a look-back gave up)
+    const float*   aabb;         // stage B: box of the kept rows
+    int64_t  plan_n;             // most rows the launches and the workspace are sized for
+    int64_t  chunk_size;         // as the caller gave it
+    int      sort_mode;          // db_tuning().sort_mode
+    uint32_t* clear_from;        // DbWs::clear_from() ..
+    uint32_t* chunk_cells;       // .. up to chunk_cells[nchunks + 1], rounded to 16 bytes: zeroed when go is set
+};
+// a head kernel's first lines: false - return
+__device__ __forceinline__ bool db_head_take(const DbHead* __restrict__ head, int64_t& n, DbGrid& g) {
+    if (!head) return true;
+    if (head->go == 0u || (int64_t)blockIdx.x >= (int64_t)head->nchunks) return false;
+    n = head->n;
+    g = head->g;
+    return true;
+}
+
 // (dy,dz) rows ordered by distance so that early exits trigger as soon as possible (static: a copy per
 // translation unit)
 static __constant__ int8_t DB_ROW_DY[DB_ROWS] = {0, 1, -1, 0, 0, 1, 1, -1, -1, 2, -2, 0, 0,
@@ -116,8 +185,6 @@ constexpr int CS_TILE    = CS_THREADS * CS_ROUNDS;
 constexpr int CS_PASSES  = 4;
 constexpr int CS_HREP    = 4;         // copies of every digit histogram (power of two)
 constexpr int CS_BINS    = 512;       // digits of up to 9 bits
-constexpr int64_t CS_MAX_CHUNK = 1 << 17;     // larger chunks use the global sort
-constexpr int64_t CS_MIN_CHUNKS = 96;         // fewer chunks: the global sort keeps more of the GPU busy
 
 // cell key of a row inside its chunk (0 when the row is outside the grid); ok = inside
 __device__ __forceinline__ uint32_t cs_cell_key(const DbGrid& g, float x, float y, float z, bool& ok) {
@@ -381,8 +448,10 @@ struct DbCells {
 
 // the run whose workspace the entries of pch_dbscan_query.hip continue, and its cell table
 // (nchunks and compressed: what pch_dbscan_assign_f32 needs to know about the grid beyond the cell table; eps: the
-// largest radius pch_dbscan_shape_f32 may ask for)
-struct DbLastRun { void* ws; size_t ws_bytes; int64_t n; DbCells c; int64_t nchunks; bool compressed; double eps; };
+// largest radius pch_dbscan_shape_f32 may ask for; plan_n: the rows the workspace was carved for, n or the fused call's
+// nf_cap)
+struct DbLastRun { void* ws; size_t ws_bytes; int64_t n; DbCells c; int64_t nchunks; bool compressed; double eps;
+                   int64_t plan_n; };
 extern thread_local DbLastRun g_last;
 
 // The entry points that continue the grid the last pch_dbscan_f32 of this thread left in `ws` carve it up again
@@ -395,6 +464,7 @@ static unsigned db_stride_blocks(int64_t n) { return (unsigned)std::min(ceil_div
 // what the steps of dbscan_run share: the run's rows, outputs, stream and carved workspace
 struct DbRun {
     const float* xyz; int64_t n, chunk_size, nchunks;
+    int64_t plan_n;              // >= n: what the workspace is carved for (db_plan)
     int32_t* labels; uint8_t* core; int32_t* out_nclusters;
     hipStream_t s; DbWs w;
 };
@@ -410,6 +480,15 @@ int db_first_bad(const float* xyz, int64_t n, unsigned long long* first, hipStre
 int db_compress(const DbRun& r, DbGrid& g, int& cellbits, bool& done);
 int db_sorted_keys(const DbRun& r, const DbGrid& g, int cellbits, int nbits, bool compressed, int sort_mode,
                    const uint64_t*& ks, bool& staged);
-int db_cell_table(const DbRun& r, const DbGrid& g, int cellbits, const uint64_t* ks, bool staged, DbMeta& back);
+// head (the fused call's host copy of DbHead): db_celltab_k is queued and status / ncells / route were read
+int db_cell_table(const DbRun& r, const DbGrid& g, int cellbits, const uint64_t* ks, bool staged, DbMeta& back,
+                  const DbHead* head);
+// the fused call: db_headplan_k and the four head kernels on the workspace carved for a.plan_n rows, the peek of
+// `peek_bytes` at `peek_dev` (they cover *head) queued in front of db_celltab_k
+int db_head_launch(const float* xyz, const DbHeadArgs& a, const DbGrid& proto, const DbWs& w, DbHead* head,
+                   const void* peek_dev, size_t peek_bytes, hipStream_t s);
+// pch_dbscan.hip, for pch_pipeline.hip
+int dbscan_head(const float* xyz, DbHeadArgs a, double eps, int32_t min_samples, void* ws, size_t ws_bytes,
+                DbHead* head, const void* peek_dev, size_t peek_bytes, hipStream_t s, bool* queued);
 
 }  // namespace pch

@@ -1550,7 +1550,7 @@ static DbTuning db_tuning() {
 }
 
 // the retained fit of this thread: one per thread, dropped by ws_touched
-thread_local DbLastRun g_last = {nullptr, 0, 0, {}, 0, false, 0.0};
+thread_local DbLastRun g_last = {nullptr, 0, 0, {}, 0, false, 0.0, 0};
 
 void ws_touched(const void* base, size_t bytes) {
     if (!g_last.ws) return;
@@ -1567,7 +1567,7 @@ int db_continue(const char* entry, int64_t n, void* ws, size_t ws_bytes, DbWs& w
         return PCH_ERR_ARG;
     }
     Arena a(ws, ws_bytes, true);
-    db_plan(a, n, w);
+    db_plan(a, g_last.plan_n, w);            // as the run carved it (the fused call: for nf_cap rows)
     return PCH_OK;
 }
 
@@ -1606,11 +1606,9 @@ static int db_bounds(const DbRun& r, const float* aabb_host, float (&box)[6], bo
         }
         for (int k = 0; k < 6; ++k) box[k] = host_unordered(back.box_key[k]);
     }
-    for (int k = 0; k < 6; ++k) {
-        if (!(box[k] == box[k]) || box[k] > 3.0e38f || box[k] < -3.0e38f) {
-            set_error("bounding box is not finite");
-            return PCH_ERR_ARG;
-        }
+    if (!db_box_finite(box)) {
+        set_error("bounding box is not finite");
+        return PCH_ERR_ARG;
     }
     return PCH_OK;
 }
@@ -1622,29 +1620,27 @@ int db_cell_bits(DbGrid& g, int mx, int my, int mz) {
     return g.bx + g.by + g.bz;
 }
 
-// the grid of cells of side eps/sqrt(3) over the box, and the bits of its key: a cell (cellbits), then the chunk
-// (nbits in all).  Returns true when that key does not fit 64 bits.
-static bool db_grid(const DbRun& r, const float (&box)[6], double eps, int32_t min_samples, DbGrid& g, int& cellbits,
-                    int& nbits) {
-    g.ox = box[0]; g.oy = box[1]; g.oz = box[2];
+// the part of the grid that eps, min_samples and the workspace give: everything but the origin, mx..mz and bx..bz
+static DbGrid db_grid_proto(const DbWs& w, int64_t chunk_size, double eps, int32_t min_samples) {
+    DbGrid g;
+    memset(&g, 0, sizeof(g));
     g.cell = eps / 1.7320508075688772 * (1.0 - 1.0 / 65536.0);
     g.inv_cell = 1.0 / g.cell;
     const DbBand band = db_band(eps);
     g.eps2 = band.r2; g.eps2_lo = band.lo; g.eps2_hi = band.hi;
-    g.chunk_size = r.chunk_size;
-    g.chunk_bad = r.w.chunk_bad;
-    g.chunk_cells = r.w.chunk_cells;
+    g.chunk_size = chunk_size;
+    g.chunk_bad = w.chunk_bad;
+    g.chunk_cells = w.chunk_cells;
     g.min_samples = min_samples;
-    int mc[3] = {0, 0, 0};
-    bool overflow = false;
-    for (int k = 0; k < 3; ++k) {
-        const double ext = ((double)box[3 + k] - (double)box[k]) * g.inv_cell;
-        if (!(ext < 2.0e9)) overflow = true;
-        else mc[k] = (int)ext + 1;            // +1: slack for the rounding of the division
-    }
-    cellbits = db_cell_bits(g, mc[0], mc[1], mc[2]);
-    nbits = cellbits + bits_for((uint64_t)r.nchunks);
-    return overflow || nbits > 64;
+    return g;
+}
+
+// the grid of cells of side eps/sqrt(3) over the box, and the bits of its key: a cell (cellbits), then the chunk
+// (nbits in all).  Returns true when that key does not fit 64 bits.
+static bool db_grid(const DbRun& r, const float (&box)[6], double eps, int32_t min_samples, DbGrid& g, int& cellbits,
+                    int& nbits) {
+    g = db_grid_proto(r.w, r.chunk_size, eps, min_samples);
+    return db_plan_grid(box, r.nchunks, g, cellbits, nbits);
 }
 
 // key beyond 64 bits, several chunks: every chunk on its own, with its own bounding box (the reference fits them one
@@ -1655,7 +1651,7 @@ static int db_run_chunks(const DbRun& r, double eps, int32_t min_samples, void* 
         const int64_t lo = c * r.chunk_size, cn = (r.n - lo) < r.chunk_size ? (r.n - lo) : r.chunk_size;
         int32_t kc = 0;
         PCH_TRY(dbscan_run(r.xyz + 3 * lo, cn, eps, min_samples, 0, nullptr, r.labels + lo,
-                           r.core ? r.core + lo : nullptr, r.out_nclusters, ws, ws_bytes, r.s, &kc));
+                           r.core ? r.core + lo : nullptr, r.out_nclusters, ws, ws_bytes, r.s, &kc, nullptr, nullptr));
         if (kc > 0 && offset > 0)
             PCH_LAUNCH("db_add_offset", db_add_offset_k, dim3((unsigned)ceil_div(cn, DB_THREADS)), dim3(DB_THREADS), 0,
                        r.s, r.labels + lo, cn, offset);
@@ -1671,10 +1667,10 @@ static int db_run_chunks(const DbRun& r, double eps, int32_t min_samples, void* 
 // the cells of the sorted keys (db_cell_table), their row table, the core flags and the per-cell statistics; c: the
 // cell table
 static int db_cells_core(const DbRun& r, const DbGrid& g, int cellbits, const uint64_t* ks, bool staged,
-                         bool count_pairs, DbCells& c) {
+                         bool count_pairs, DbCells& c, const DbHead* head) {
     const DbWs& w = r.w; const hipStream_t s = r.s; const int64_t n = r.n;
     DbMeta back;                             // status, ncells ... the route word
-    PCH_TRY(db_cell_table(r, g, cellbits, ks, staged, back));
+    PCH_TRY(db_cell_table(r, g, cellbits, ks, staged, back, head));
     const int m = (int)back.ncells;
     const unsigned gc = (unsigned)ceil_div(m, DB_WAVES);
     c = {g, w.pts, w.cell_start, w.cell_key, m, m <= w.rowtab_cells ? w.rowtab : nullptr, w.core_s, w.cell_ncore,
@@ -1811,8 +1807,10 @@ extern "C" size_t pch_dbscan_ws_bytes(int64_t n) {
 
 int pch::dbscan_run(const float* xyz, int64_t n, double eps, int32_t min_samples, int64_t chunk_size,
                     const float* aabb_host, int32_t* labels, uint8_t* core, int32_t* out_nclusters, void* ws,
-                    size_t ws_bytes, hipStream_t s, int32_t* k_host, DbBoxOut* boxes) {
+                    size_t ws_bytes, hipStream_t s, int32_t* k_host, DbBoxOut* boxes, DbHeadRun* head) {
     if (k_host) *k_host = 0;
+    if (head) head->route = 0;
+    const int64_t plan_n = head ? head->plan_n : n;
     if (boxes) boxes->done = false;
     PCH_REQUIRE(n >= 0 && n < (int64_t(1) << 31), "n out of range [0, 2^31)");
     PCH_REQUIRE(eps > 0.0, "eps must be > 0 (sklearn: InvalidParameterError)");
@@ -1823,12 +1821,13 @@ int pch::dbscan_run(const float* xyz, int64_t n, double eps, int32_t min_samples
         return PCH_OK;
     }
     PCH_REQUIRE(xyz && labels && ws, "null buffer");
+    PCH_REQUIRE(plan_n >= n, "more rows than the workspace was planned for");
     Arena a(ws, ws_bytes);
     DbWs w;
-    db_plan(a, n, w);
+    db_plan(a, plan_n, w);
     if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
     if (chunk_size <= 0 || chunk_size > n) chunk_size = n;
-    const DbRun r = {xyz, n, chunk_size, ceil_div(n, chunk_size), labels, core, out_nclusters, s, w};
+    const DbRun r = {xyz, n, chunk_size, ceil_div(n, chunk_size), plan_n, labels, core, out_nclusters, s, w};
     const DbTuning tune = db_tuning();
 
     float box[6];
@@ -1849,11 +1848,47 @@ int pch::dbscan_run(const float* xyz, int64_t n, double eps, int32_t min_samples
     const uint64_t* ks;
     DbCells c;
     bool staged;
-    PCH_TRY(db_sorted_keys(r, g, cellbits, nbits, overflow, tune.sort_mode, ks, staged));
-    PCH_TRY(db_cells_core(r, g, cellbits, ks, staged, tune.count_pairs, c));
+    // the fused call queued the head of this stage unread, up to db_celltab_k: go on behind it if the device planned
+    // what was planned here - the same rows, chunks, origin (bit for bit), cell ranges and key bits.  Anything else:
+    // from the top, with this plan (the head's launches wrote nothing that the run does not write again)
+    const DbHead* const dh = head ? head->host : nullptr;
+    const bool unread = dh && dh->go == 1u && !overflow && dh->n == n && dh->nchunks == r.nchunks &&
+                        dh->g.chunk_size == r.chunk_size && memcmp(&dh->g.ox, &g.ox, 3 * sizeof(float)) == 0 &&
+                        dh->g.mx == g.mx && dh->g.my == g.my && dh->g.mz == g.mz && dh->g.bx == g.bx &&
+                        dh->g.by == g.by && dh->g.bz == g.bz && dh->cellbits == cellbits && dh->nbits == nbits;
+    if (unread) {
+        ks = w.k1;
+        staged = true;
+        head->route = 1;
+    } else {
+        PCH_TRY(db_sorted_keys(r, g, cellbits, nbits, overflow, tune.sort_mode, ks, staged));
+    }
+    PCH_TRY(db_cells_core(r, g, cellbits, ks, staged, tune.count_pairs, c, unread ? dh : nullptr));
     PCH_TRY(db_union(r, c));
     PCH_TRY(db_labels(r, c, k_host, boxes));
-    g_last = {ws, ws_bytes, n, c, r.nchunks, overflow, eps};
+    g_last = {ws, ws_bytes, n, c, r.nchunks, overflow, eps, plan_n};
+    return PCH_OK;
+}
+
+// The fused call, behind stage B's first results (a.scalars / count / aabb on the device): queue the head of the stage
+// unread if the arguments allow the staged chunk route at all.  *queued says whether it was; dbscan_run then takes
+// the host copy of *head in its DbHeadRun.  The workspace is carved as dbscan_run will carve it for a.plan_n rows.
+int pch::dbscan_head(const float* xyz, DbHeadArgs a, double eps, int32_t min_samples, void* ws, size_t ws_bytes,
+                     DbHead* head, const void* peek_dev, size_t peek_bytes, hipStream_t s, bool* queued) {
+    *queued = false;
+    a.sort_mode = db_tuning().sort_mode;
+    const int64_t cap_chunks = (a.chunk_size <= 0 || a.chunk_size > a.plan_n) ? 1 : ceil_div(a.plan_n, a.chunk_size);
+    if (!(eps > 0.0) || min_samples < 1 || !xyz || a.plan_n < 1 || a.plan_n >= (int64_t(1) << 31) ||
+        a.sort_mode == 2 || cap_chunks > DB_TABLE_MAX_CHUNKS || (a.sort_mode != 1 && cap_chunks < CS_MIN_CHUNKS))
+        return PCH_OK;                       // dbscan_run says what is wrong, or takes another route anyway
+    Arena ar(ws, ws_bytes);
+    DbWs w;
+    db_plan(ar, a.plan_n, w);
+    if (ar.overflow) return PCH_OK;
+    a.clear_from = static_cast<uint32_t*>(w.clear_from());
+    a.chunk_cells = w.chunk_cells;
+    PCH_TRY(db_head_launch(xyz, a, db_grid_proto(w, a.chunk_size, eps, min_samples), w, head, peek_dev, peek_bytes, s));
+    *queued = true;
     return PCH_OK;
 }
 

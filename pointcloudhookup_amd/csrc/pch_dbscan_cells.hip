@@ -185,7 +185,8 @@ __device__ __forceinline__ void cs_rows_in_place(const DbGrid& g, const Row3* __
 __global__ __launch_bounds__(CS_THREADS) void db_chunksort_k(
     const float* __restrict__ xyz, int64_t n, DbGrid g, const uint32_t* __restrict__ gate, uint32_t* __restrict__ bad,
     float4* __restrict__ xbuf, float4* __restrict__ pts, uint64_t* __restrict__ keys_out,
-    uint32_t* __restrict__ status, unsigned long long* __restrict__ stamps) {
+    uint32_t* __restrict__ status, unsigned long long* __restrict__ stamps, const DbHead* __restrict__ head) {
+    if (!db_head_take(head, n, g)) return;              // (the fused call's unread launch: n and g from *head)
     if (gate[blockIdx.x] == 0u) return;                 // workgroup-uniform
 #ifdef PCH_CS_STAMPS                                    // phase timing of one workgroup (tuning builds only)
     int stamp_i = 0;
@@ -420,7 +421,9 @@ __device__ __forceinline__ uint32_t ct_hash(uint32_t k) { return (k * 0x9E3779B1
 template <bool TABLE>
 __global__ __launch_bounds__(CS_THREADS) void db_cellscatter_k(
     const float* __restrict__ xyz, int64_t n, DbGrid g, uint32_t* __restrict__ bad, uint32_t* __restrict__ ovf,
-    float4* __restrict__ pts, uint64_t* __restrict__ keys_out, DbStage st, uint32_t* __restrict__ status) {
+    float4* __restrict__ pts, uint64_t* __restrict__ keys_out, DbStage st, uint32_t* __restrict__ status,
+    const DbHead* __restrict__ head) {
+    if (!db_head_take(head, n, g)) return;              // (the fused call's unread launch: n and g from *head)
     __shared__ uint32_t tkey[CT_SLOTS];
     __shared__ uint32_t tcnt[CT_SLOTS];         // sweep 1: rows per cell; sweep 2: the cell's next position
     __shared__ uint32_t tmin[TABLE ? CT_SLOTS : 1];     // sweep 1: the cell's smallest row of the chunk
@@ -675,7 +678,6 @@ __global__ __launch_bounds__(DB_THREADS) void db_cells_k(const uint64_t* __restr
 // rows, which it also finds) then runs over the chunks' lists.  *route clear: it writes the table.  *route set (some
 // chunk went through db_chunksort_k, which writes keys): it writes the keys of all OTHER chunks' rows instead, and
 // the host, which reads the word in the wait it makes anyway, launches db_heads_k / db_cells_k on them.
-constexpr int64_t DB_TABLE_MAX_CHUNKS = 16384;  // beyond: db_cellscatter_k<false>, the table is read off the keys
 constexpr int CC_THREADS = 1024;
 constexpr int CC_ITEMS = (int)(DB_TABLE_MAX_CHUNKS / CC_THREADS);     // consecutive chunks per thread
 
@@ -690,7 +692,11 @@ __device__ __forceinline__ uint32_t ct_staged_cells(const uint32_t* __restrict__
 __global__ __launch_bounds__(CC_THREADS) void db_chunkcells_k(
     const uint32_t* __restrict__ ncell, const uint32_t* __restrict__ ovf, int nchunks, int64_t n, int64_t chunk_size,
     uint32_t* __restrict__ chunk_cells, uint32_t* __restrict__ cell_start, uint32_t* __restrict__ ncells,
-    uint32_t* __restrict__ route) {
+    uint32_t* __restrict__ route, DbHead* __restrict__ head, const uint32_t* __restrict__ status) {
+    if (head) {                                         // the fused call's unread launch
+        if (head->go == 0u) return;
+        nchunks = head->nchunks; n = head->n; chunk_size = head->g.chunk_size;
+    }
     __shared__ uint32_t wsum[CC_THREADS / 64];
     const int tid = threadIdx.x, c0 = tid * CC_ITEMS;
     uint32_t v[CC_ITEMS], sum = 0;
@@ -724,6 +730,8 @@ __global__ __launch_bounds__(CC_THREADS) void db_chunkcells_k(
             cell_start[total] = (uint32_t)n;            // total <= n
             *ncells = total;
         }
+        // the words the host reads in front of db_celltab_k, beside the plan: one copy brings both
+        if (head) { head->status = *status; head->ncells = over ? 0u : total; head->route = over ? 1u : 0u; }
     }
 }
 
@@ -737,7 +745,9 @@ __global__ __launch_bounds__(CC_THREADS) void db_chunkcells_k(
 __global__ __launch_bounds__(CS_THREADS) void db_celltab_k(
     const uint32_t* __restrict__ route, DbStage st, const uint32_t* __restrict__ ovf, DbGrid g, int64_t n,
     uint32_t* __restrict__ cell_start, uint64_t* __restrict__ cell_key, int* __restrict__ cell_min,
-    uint32_t* __restrict__ bits, int2* __restrict__ rowtab, int64_t rowtab_cells, uint64_t* __restrict__ keys_out) {
+    uint32_t* __restrict__ bits, int2* __restrict__ rowtab, int64_t rowtab_cells, uint64_t* __restrict__ keys_out,
+    const DbHead* __restrict__ head) {
+    if (!db_head_take(head, n, g)) return;              // (the fused call's unread launch: n and g from *head)
     __shared__ uint32_t key[CT_CELLS];
     const int tid = threadIdx.x, l = lane_id();
     const int64_t c = blockIdx.x, lo = c * g.chunk_size;
@@ -785,7 +795,64 @@ __global__ __launch_bounds__(CS_THREADS) void db_celltab_k(
     }
 }
 
+// ---- the head of stage C planned on the device (DbHead, pch_dbscan.h): one workgroup behind stage B's first results.
+// go is set when dbscan_run, reading the same words, would take the staged chunk route; the workgroup then zeroes what
+// db_sorted_keys clears with a fill.  go clear: nothing but *head is written - the fallback sweep of stage B may still
+// need its scratch, which shares the workspace.
+constexpr int HP_THREADS = 256;
+__global__ __launch_bounds__(HP_THREADS) void db_headplan_k(DbHeadArgs a, DbGrid g, DbHead* __restrict__ head) {
+    __shared__ uint32_t sgo;
+    __shared__ int snchunks;
+    if (threadIdx.x == 0) {
+        const int64_t n = *a.count;
+        float box[6];
+        for (int k = 0; k < 6; ++k) box[k] = a.aabb[k];
+        bool go = a.scalars[5] == 0.0f && n > 0 && n <= a.plan_n;
+        const int64_t cs = (a.chunk_size <= 0 || a.chunk_size > n) ? n : a.chunk_size;     // as dbscan_run
+        const int64_t nchunks = go ? (n + cs - 1) / cs : 0;
+        g.chunk_size = cs;
+        int cellbits = 0, nbits = 0;
+        go = go && db_box_finite(box);
+        if (go) go = !db_plan_grid(box, nchunks, g, cellbits, nbits);
+        go = go && cellbits <= 31 && cs <= CS_MAX_CHUNK && a.sort_mode != 2 &&
+             (a.sort_mode == 1 || nchunks >= CS_MIN_CHUNKS) && nchunks <= DB_TABLE_MAX_CHUNKS;
+        head->go = go ? 1u : 0u;
+        head->nchunks = go ? (int32_t)nchunks : 0;
+        head->n = n;
+        head->cellbits = cellbits; head->nbits = nbits;
+        head->status = 0u; head->ncells = 0u; head->route = 0u; head->pad = 0u;
+        head->g = g;
+        sgo = go ? 1u : 0u;
+        snchunks = go ? (int)nchunks : 0;
+    }
+    __syncthreads();
+    if (sgo == 0u) return;
+    // DbWs::clear_bytes(nchunks): a.clear_from is 16-byte aligned and the arrays behind chunk_cells[nchunks] go on
+    const size_t bytes = ((size_t)((char*)(a.chunk_cells + snchunks + 1) - (char*)a.clear_from) + 15) & ~size_t(15);
+    uint4* const z = reinterpret_cast<uint4*>(a.clear_from);
+    for (size_t i = threadIdx.x; i < bytes / 16; i += HP_THREADS) z[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 // ---- host side ----
+int db_head_launch(const float* xyz, const DbHeadArgs& a, const DbGrid& proto, const DbWs& w, DbHead* head,
+                   const void* peek_dev, size_t peek_bytes, hipStream_t s) {
+    // grids for the most chunks a.plan_n rows make; the workgroups beyond the device's nchunks return at once
+    const int64_t cap_chunks = (a.chunk_size <= 0 || a.chunk_size > a.plan_n) ? 1 : ceil_div(a.plan_n, a.chunk_size);
+    const dim3 gh((unsigned)cap_chunks), blk(CS_THREADS);
+    PCH_LAUNCH("db_headplan", db_headplan_k, dim3(1), dim3(HP_THREADS), 0, s, a, proto, head);
+    // (n, the grid and the chunk counts passed by value are not read: *head overrides them)
+    PCH_LAUNCH("db_cellscatter", db_cellscatter_k<true>, gh, blk, 0, s, xyz, a.plan_n, proto, w.chunk_bad, w.chunk_ovf,
+               w.pts, w.k1, w.stage, &w.meta->status, (const DbHead*)head);
+    PCH_LAUNCH("db_chunksort", db_chunksort_k, gh, blk, 0, s, xyz, a.plan_n, proto, w.chunk_ovf, w.chunk_bad, w.xbuf,
+               w.pts, w.k1, &w.meta->status, w.cs_stamps, (const DbHead*)head);
+    PCH_LAUNCH("db_chunkcells", db_chunkcells_k, dim3(1), dim3(CC_THREADS), 0, s, w.stage.ncell, w.chunk_ovf,
+               (int)cap_chunks, a.plan_n, proto.chunk_size, w.chunk_cells, w.cell_start, &w.meta->ncells, w.cell_route,
+               head, (const uint32_t*)&w.meta->status);
+    PCH_TRY(peek_enqueue(peek_dev, peek_bytes, s));
+    PCH_LAUNCH("db_celltab", db_celltab_k, gh, blk, 0, s, w.cell_route, w.stage, w.chunk_ovf, proto, a.plan_n,
+               w.cell_start, w.cell_key, w.cell_min, w.bits, w.rowtab, w.rowtab_cells, w.k1, (const DbHead*)head);
+    return PCH_OK;
+}
 int db_first_bad(const float* xyz, int64_t n, unsigned long long* first, hipStream_t s) {
     PCH_LAUNCH("db_first_bad", db_first_bad_k, dim3(db_stride_blocks(n)), dim3(DB_THREADS), 0, s, xyz, n, first);
     return PCH_OK;
@@ -852,12 +919,13 @@ int db_sorted_keys(const DbRun& r, const DbGrid& g, int cellbits, int nbits, boo
         staged = nchunks <= DB_TABLE_MAX_CHUNKS;
         const auto cellscatter = staged ? db_cellscatter_k<true> : db_cellscatter_k<false>;
         PCH_LAUNCH("db_cellscatter", cellscatter, dim3((unsigned)nchunks), dim3(CS_THREADS), 0, s, r.xyz, n, g,
-                   w.chunk_bad, w.chunk_ovf, w.pts, w.k1, w.stage, &w.meta->status);
+                   w.chunk_bad, w.chunk_ovf, w.pts, w.k1, w.stage, &w.meta->status, (const DbHead*)nullptr);
         PCH_LAUNCH("db_chunksort", db_chunksort_k, dim3((unsigned)nchunks), dim3(CS_THREADS), 0, s, r.xyz, n, g,
-                   w.chunk_ovf, w.chunk_bad, w.xbuf, w.pts, w.k1, &w.meta->status, w.cs_stamps);
+                   w.chunk_ovf, w.chunk_bad, w.xbuf, w.pts, w.k1, &w.meta->status, w.cs_stamps, (const DbHead*)nullptr);
         if (staged)
             PCH_LAUNCH("db_chunkcells", db_chunkcells_k, dim3(1), dim3(CC_THREADS), 0, s, w.stage.ncell, w.chunk_ovf,
-                       (int)nchunks, n, r.chunk_size, w.chunk_cells, w.cell_start, &w.meta->ncells, w.cell_route);
+                       (int)nchunks, n, r.chunk_size, w.chunk_cells, w.cell_start, &w.meta->ncells, w.cell_route,
+                       (DbHead*)nullptr, (const uint32_t*)nullptr);
 #ifdef PCH_CS_STAMPS
         {
             unsigned long long t[11];                    // start | sweep B | sweep H | one per pass | heads
@@ -891,19 +959,23 @@ int db_sorted_keys(const DbRun& r, const DbGrid& g, int cellbits, int nbits, boo
 
 // the cells of the sorted keys: the cell table (on the staged route the row table, cell_min and the cleared row bitmap
 // too).  back: the host's copy of status, ncells and the route word (set: the table was read off the keys)
-int db_cell_table(const DbRun& r, const DbGrid& g, int cellbits, const uint64_t* ks, bool staged, DbMeta& back) {
+int db_cell_table(const DbRun& r, const DbGrid& g, int cellbits, const uint64_t* ks, bool staged, DbMeta& back,
+                  const DbHead* head) {
     const DbWs& w = r.w; const hipStream_t s = r.s; const int64_t n = r.n;
     const int64_t ntile = ceil_div(n, (int64_t)SCAN_TILE);
     // the cell count sizes the next grids: fetch it while the kernel that writes the table (sized by n) runs
     constexpr size_t peek_bytes = offsetof(DbMeta, pad) + sizeof(uint32_t) - offsetof(DbMeta, status);
     back.pad[0] = 1u;
-    if (staged) {
+    if (head) {                              // db_head_launch queued db_celltab_k; the words came with the plan
+        back.status = head->status; back.ncells = head->ncells; back.pad[0] = head->route;
+    } else if (staged) {
         // db_chunkcells_k left ncells and the route word; db_celltab_k reads the word itself and writes either the
         // table (and the row table) or the keys that db_chunksort_k did not (then the table is read off the keys
         // below, as ever)
         PCH_TRY(peek_enqueue(&w.meta->status, peek_bytes, s));
         PCH_LAUNCH("db_celltab", db_celltab_k, dim3((unsigned)r.nchunks), dim3(CS_THREADS), 0, s, w.cell_route, w.stage,
-                   w.chunk_ovf, g, n, w.cell_start, w.cell_key, w.cell_min, w.bits, w.rowtab, w.rowtab_cells, w.k1);
+                   w.chunk_ovf, g, n, w.cell_start, w.cell_key, w.cell_min, w.bits, w.rowtab, w.rowtab_cells, w.k1,
+                   (const DbHead*)nullptr);
         PCH_TRY(peek_wait(&back.status, peek_bytes));
     }
     if (back.pad[0] != 0u) {

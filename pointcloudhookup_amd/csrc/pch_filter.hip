@@ -1165,7 +1165,7 @@ extern "C" int pch_ground_filter_f32(const float* raw, int64_t n, double pct, fl
 int pch::ground_filter_run(const float* raw, int64_t n, double pct, float offset, float fallback_offset,
                            int64_t min_keep, float* out_points, int32_t* out_index, float* out_scalars,
                            int64_t* out_count, float* out_aabb, void* ws, size_t ws_bytes, hipStream_t s,
-                           const GfEarly* early) {
+                           GfFollowUp* early) {
     PCH_REQUIRE(n >= 1 && n < (int64_t(1) << 31), "n out of range [1, 2^31) (numpy raises on empty input)");
     PCH_REQUIRE(raw && out_points && out_scalars && out_count && ws, "null buffer");
     PCH_REQUIRE(pct >= 0.0 && pct <= 100.0, "Percentiles must be in the range [0, 100]");
@@ -1235,18 +1235,27 @@ int pch::ground_filter_run(const float* raw, int64_t n, double pct, float offset
                    out_points, out_index);
     PCH_LAUNCH("gf_compact", gf_compact_k<0>, grid, blk, 0, s, raw, n, (const float*)w.centroid,
                (const float*)w.sel.scal, w.st, w.status, (long long)min_keep, out_points, out_index, tcand);
-    if (early) {
+    GfFollowUp fu = {cand_made, cgrid, grid, (const float*)w.cand.slots, (const uint32_t*)w.cand.counts, tcand, nblk, raw, n,
+                     (const float*)w.centroid, (const float*)w.sel.scal, w.st, w.status + nb, (long long)min_keep,
+                     out_points, out_index, out_scalars, out_count, out_aabb};
+    if (early) {                                        // the caller queues the rest when the first results ask for it
         PCH_LAUNCH("gf_finalize", gf_finalize_k, dim3(1), dim3(64), 0, s, (const GfState*)w.st,
                    (const float*)w.centroid, (const float*)w.sel.scal, out_scalars, out_count, out_aabb);
-        PCH_TRY(peek_enqueue(early->dev, early->bytes, s));
+        *early = fu;
+        return PCH_OK;
     }
-    if (cand_made)
-        PCH_LAUNCH("gf_cand_fb", gf_cand_k<1>, cgrid, blk, 0, s, (const float*)w.cand.slots,
-                   (const uint32_t*)w.cand.counts, tcand, nblk, (const float*)w.centroid, (const float*)w.sel.scal, w.st,
-                   w.status + nb, (long long)min_keep, out_points, out_index);
-    PCH_LAUNCH("gf_compact_fb", gf_compact_k<1>, grid, blk, 0, s, raw, n, (const float*)w.centroid,
-               (const float*)w.sel.scal, w.st, w.status + nb, (long long)min_keep, out_points, out_index, tcand);
-    PCH_LAUNCH("gf_finalize", gf_finalize_k, dim3(1), dim3(64), 0, s, (const GfState*)w.st,
-               (const float*)w.centroid, (const float*)w.sel.scal, out_scalars, out_count, out_aabb);
+    return ground_filter_follow_up(fu, s);
+}
+
+int pch::ground_filter_follow_up(const GfFollowUp& f, hipStream_t s) {
+    const dim3 blk(GF_THREADS);
+    GfState* const st = static_cast<GfState*>(f.st);
+    if (f.cand_made)
+        PCH_LAUNCH("gf_cand_fb", gf_cand_k<1>, f.cgrid, blk, 0, s, f.slots, f.counts, f.tcand, f.nblk, f.centroid, f.scal,
+                   st, f.status_fb, f.min_keep, f.out_points, f.out_index);
+    PCH_LAUNCH("gf_compact_fb", gf_compact_k<1>, f.grid, blk, 0, s, f.raw, f.n, f.centroid, f.scal, st, f.status_fb,
+               f.min_keep, f.out_points, f.out_index, f.tcand);
+    PCH_LAUNCH("gf_finalize", gf_finalize_k, dim3(1), dim3(64), 0, s, (const GfState*)st, f.centroid, f.scal,
+               f.out_scalars, f.out_count, f.out_aabb);
     return PCH_OK;
 }

@@ -3,8 +3,10 @@
 // three stage entry points are called back to back on the caller's stream, sharing one
 // workspace (a stage's scratch is dead once the next stage starts) and reading the two host-side
 // sizes the next launch needs (points kept, clusters found) without a trip through the host
-// language in between.
-#include "pch_common.h"
+// language in between.  The kept count is not waited for where stage C starts: the head of that stage is planned on
+// the device and queued unread (DbHead, pch_dbscan.h), and the host reads stage B's results together with the plan in
+// the wait stage C makes anyway, in front of db_celltab_k.
+#include "pch_dbscan.h"
 
 #include <cstring>
 
@@ -19,6 +21,12 @@ struct DevInfo {
     int32_t nclusters;
     int32_t pad2;
 };
+// the first 256 bytes of the workspace, outside both stages' arenas: one copy brings them to the host
+struct TcHead {
+    DevInfo info;
+    DbHead  head;
+};
+static_assert(sizeof(TcHead) <= 256, "fits the pinned peek buffer and the block pch_tower_clusters_ws_bytes reserves");
 
 static size_t max3(size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
 
@@ -29,7 +37,7 @@ using namespace pch;
 extern "C" size_t pch_tower_clusters_ws_bytes(int64_t n, int64_t nf_cap, int32_t k_cap) {
     if (n < 0 || nf_cap < 0 || k_cap < 0) return 0;
     Arena a;
-    a.take<DevInfo>(1);
+    a.take<TcHead>(1);
     return a.off + max3(pch_ground_filter_ws_bytes(n), pch_dbscan_ws_bytes(nf_cap),
                         pch_segment_by_label_ws_bytes(nf_cap, k_cap));
 }
@@ -47,7 +55,8 @@ extern "C" int pch_tower_clusters_f32(const float* raw, int64_t n, double pct, f
     memset(info_host, 0, sizeof(*info_host));
     PCH_REQUIRE(ws != nullptr && nf_cap >= 0 && k_cap >= 0, "bad argument");
     Arena a(ws, ws_bytes);
-    DevInfo* dev = a.take<DevInfo>(1);
+    TcHead* const tc = a.take<TcHead>(1);
+    DevInfo* const dev = &tc->info;
     if (a.overflow || ws_bytes < pch_tower_clusters_ws_bytes(n, nf_cap, k_cap)) {
         set_error("workspace too small: need %zu bytes", pch_tower_clusters_ws_bytes(n, nf_cap, k_cap));
         return PCH_ERR_WORKSPACE;
@@ -55,19 +64,27 @@ extern "C" int pch_tower_clusters_f32(const float* raw, int64_t n, double pct, f
     void* sub = static_cast<char*>(ws) + a.off;
     const size_t sub_bytes = ws_bytes - a.off;
 
-    // ---- stage B
-    // the filter queues the copy of its results for the host directly behind its first sweep; the launches of the
-    // fallback threshold behind it return at once unless the fallback applies - the host is preparing stage C by then
-    static_assert(sizeof(DevInfo) <= 256, "fits the pinned peek buffer");
-    const GfEarly early = {dev, sizeof(DevInfo)};
+    // ---- stage B, up to the results of its first threshold; they are final unless the fallback flag is set
+    GfFollowUp fallback;
     PCH_TRY(ground_filter_run(raw, n, pct, offset, fallback_offset, min_keep, out_points, out_index,
-                              dev->scalars, &dev->count, dev->aabb, sub, sub_bytes, s, &early));
-    DevInfo h;
-    PCH_TRY(peek_wait(&h, sizeof(DevInfo)));
-    if (h.scalars[5] != 0.0f && h.count >= 0) {          // the fallback threshold applies: the final values lie behind it
-        PCH_TRY(peek_enqueue(dev, sizeof(DevInfo), s));
-        PCH_TRY(peek_wait(&h, sizeof(DevInfo)));
+                              dev->scalars, &dev->count, dev->aabb, sub, sub_bytes, s, &fallback));
+    // ---- the head of stage C, unread: db_headplan_k stands down (and the four kernels behind it return at once) unless
+    // those results are final and make the staged chunk route.  One copy brings stage B's results and the plan
+    bool queued = false;
+    if (out_labels && nf_cap > 0) {
+        DbHeadArgs ha = {dev->scalars, &dev->count, dev->aabb, nf_cap, chunk_size, 0, nullptr, nullptr};
+        PCH_TRY(dbscan_head(out_points, ha, eps, min_samples, sub, sub_bytes, &tc->head, tc, sizeof(TcHead), s, &queued));
     }
+    if (!queued) PCH_TRY(peek_enqueue(tc, sizeof(TcHead), s));
+    TcHead hh;
+    PCH_TRY(peek_wait(&hh, sizeof(TcHead)));
+    if (hh.info.scalars[5] != 0.0f && hh.info.count >= 0) {   // the fallback threshold applies: sweep again, read again
+        PCH_TRY(ground_filter_follow_up(fallback, s));
+        PCH_TRY(peek_enqueue(tc, sizeof(TcHead), s));
+        PCH_TRY(peek_wait(&hh, sizeof(TcHead)));
+        queued = false;                                  // (the head stood down: its words are not a plan)
+    }
+    const DevInfo& h = hh.info;
     memcpy(info_host->centroid, h.scalars, 3 * sizeof(float));
     info_host->base = h.scalars[3];
     info_host->threshold = h.scalars[4];
@@ -98,9 +115,11 @@ extern "C" int pch_tower_clusters_f32(const float* raw, int64_t n, double pct, f
     // the cluster boxes of stage D0 are gathered where the labels are made (no pass of their own): out_stats holds
     // the encoded table until pch_segment's offsets kernel decodes it in place
     DbBoxOut box = {reinterpret_cast<uint32_t*>(out_stats), (out_perm && out_offsets && out_stats) ? k_cap : 0, false};
+    DbHeadRun hr = {nf_cap, queued ? &hh.head : nullptr, 0};
     PCH_TRY(dbscan_run(out_points, nf, eps, min_samples, chunk_size, h.aabb, out_labels, nullptr,
-                       &dev->nclusters, sub, sub_bytes, s, &k, &box));
+                       &dev->nclusters, sub, sub_bytes, s, &k, &box, &hr));
     info_host->nclusters = k;
+    info_host->reserved = hr.route;                      // 1: the head of stage C ran unread, 0: planned by the host
     // ---- stage D0
     if (out_perm && out_offsets) {
         if (k > k_cap) {

@@ -1155,6 +1155,13 @@ def first_nonfinite_row(xyz):
 
 # ---------------------------------------------------------------------- stages B + C + D0
 _nf_hint = {}          # device index -> fraction of points the previous call kept (sizes the next workspace)
+_tower_clusters_route = 0
+
+
+def last_tower_clusters_route():
+    """Route word of this process's last ``tower_clusters`` call (PchTowerClusters.reserved): 1 = the head of stage C
+    was planned on the device and ran before the host read the kept count, 0 = the host planned it."""
+    return _tower_clusters_route
 
 
 def tower_clusters(raw, eps=8.0, min_samples=80, chunk_size=50000, pct=25.0, offset=3.0,
@@ -1193,6 +1200,8 @@ def tower_clusters(raw, eps=8.0, min_samples=80, chunk_size=50000, pct=25.0, off
                 continue                                   # kept more than the hint allowed for: once more, sized n
             break
         nf, k = int(info.count), int(info.nclusters)
+        global _tower_clusters_route
+        _tower_clusters_route = int(info.reserved)
         if rc == -4 and segment and k > k_cap:             # more clusters than k_cap: group separately
             perm, offsets, stats = segment_by_label(labels[:nf], out_points[:nf], k)
             rc = 0
