@@ -812,6 +812,67 @@ int pch_terrain_height_f32(const float* xyz, int64_t n, const float* sub3_host, 
 int pch_terrain_sample_f64(const double* xy, int64_t m, const PchTerrainGrid* grid_host, const float* ground,
                            double* out, void* stream);
 
+/* ------------------------------------------------------------------ tower profile, opt-in
+ * Where a tower has its cross-arms and how high it stands: per (table, height slice) the row count and the horizontal
+ * extents of the grouped rows, in a horizontal frame per cluster.  Every output is a count or a minimum / maximum, so
+ * it is exact, free of any order and the same bits on every run.
+ *
+ * The rule.  All arithmetic is float64 without FMA (the library is built with -ffp-contract=off), with parentheses as
+ * written.  tests/tower_profile_cases.py follows it literally in numpy.
+ *   Grouping is as in pch_cluster_moments_f32: cluster k owns rows_k = perm[offsets[k]:offsets[k+1]].  Entries at and
+ *     behind offsets[K] belong to nobody.
+ *   frames5[k] = (cx, cy, z0, ux, uy).  slot[k] is the table row that cluster k writes to.  T = ntables, B = nslices.
+ *   Cluster k takes part iff 0 <= slot[k] < T and all five frame values are finite.  A slot of -1 or out of range, or a
+ *     non-finite frame, takes no part.  u need not be unit.
+ *   Per row p of a cluster that takes part:
+ *         dx = (double)px - cx;  dy = (double)py - cy;  h = (double)pz - z0
+ *         s = (dx*ux) + (dy*uy);  t = (dy*ux) - (dx*uy);  q = floor(h / dz)
+ *     If q < 0: out_outside[slot,0] += 1.
+ *     If q >= B: out_outside[slot,1] += 1.
+ *     A NaN q counts nowhere.
+ *     The row is binned iff 0 <= q < B and s and t are finite, with b = (int)q.  Then:
+ *         out_count[slot,b] += 1;
+ *         out_ext[slot,b] = (min s, max s, min t, max t), where min and max are taken by the order-preserving key of
+ *         the double's bit pattern, key(v) = bits(v) ^ (bits(v) >> 63 ? 0xFFFFFFFFFFFFFFFF : 0x8000000000000000), so
+ *         -0.0 sorts below +0.0.
+ *   A slice without a row holds (+inf, -inf, +inf, -inf) and count 0.
+ *   Clusters that share a slot are combined as if they were one.
+ *   Limits: 0 <= n_grouped < 2^31, nclusters >= 0, 1 <= T <= 4096, 1 <= B <= 256, T*B <= 2^20, dz finite and > 0.
+ *   Anything else is PCH_ERR_ARG, as is a needed null buffer or a host pointer.
+ *   A workspace that is too small is PCH_ERR_WORKSPACE.
+ *   pch_cluster_slices_ws_bytes is pure host code and returns 0 for sizes out of range.
+ *   A refused call writes nothing.
+ *   With n_grouped == 0 or K == 0 the tables are still written (zeros and infinities).
+ *   The call enqueues and returns, with no host read.
+ *   Levels (no kernel; ops.tower_levels: float64 torch on [T,B] records).  With min_rows, arm_window, arm_excess,
+ *     max_levels and G = ceil(arm_window / dz): occ[b] = count[b] >= min_rows; w[b] = max(ext[b,1] - ext[b,0],
+ *     ext[b,3] - ext[b,2]) where occupied, else NaN; body[b] = the smallest w[b'] over the occupied b' with
+ *     |b' - b| <= G; arm[b] = occ[b] and (w[b] - body[b]) >= arm_excess.  A level is a maximal run [b_lo, b_hi] of arm
+ *     slices, the lowest first, at most max_levels kept: z_low = z0 + b_lo*dz, z_high = z0 + (b_hi + 1)*dz,
+ *     width = max w over the run, rows = the sum of count over the run.  top = z0 + (b_top + 1)*dz for the highest
+ *     occupied slice, NaN without one.  An arm thicker than 2G + 1 slices is not found.
+ *
+ * How: perm is swept in fixed blocks of 512 entries, one wave each, as pch_cluster_moments_f32 sweeps it - the time is
+ * linear in the number of grouped rows, not in the largest cluster.  A wave combines each (cluster, block) segment it
+ * holds in its own LDS table of B slices (a count and four 64-bit keys) with integer LDS atomics, then looks at the
+ * slices between the lowest and the highest one the segment touched: every occupied one issues one integer atomicAdd
+ * and four 64-bit atomicMin / atomicMax on the global tables and is cleared again.  A small kernel decodes the keys.
+ * Integer atomics only, no barrier, nothing waits on another workgroup.
+ *
+ * xyz float32 [*,3], perm int32 [n_grouped], offsets int64 [K+1], frames5 float64 [K,5], slot int32 [K], out_count int32
+ * [T,B], out_ext float64 [T,B,4], out_outside int64 [T,2] - all device; perm entries are trusted to be rows of xyz.
+ * xyz and perm may be NULL when n_grouped == 0 or K == 0; offsets, frames5 and slot when K == 0.  ws: the caller's, at
+ * least pch_cluster_slices_ws_bytes(n_grouped, nclusters, ntables, nslices) bytes. */
+#define PCH_SLICES_MAX         256
+#define PCH_SLICES_MAX_TABLES  4096
+#define PCH_SLICES_MAX_ENTRIES (1 << 20)
+size_t pch_cluster_slices_ws_bytes(int64_t n_grouped, int32_t nclusters, int32_t ntables, int32_t nslices);
+int pch_cluster_slices_f32(const float* xyz, const int32_t* perm, const int64_t* offsets, int64_t n_grouped,
+                           int32_t nclusters, const double* frames5 /* [K,5] */, const int32_t* slot /* [K] */,
+                           int32_t ntables, double dz, int32_t nslices,
+                           int32_t* out_count /* [T,B] */, double* out_ext /* [T,B,4] */,
+                           int64_t* out_outside /* [T,2] */, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ stage D1, fast mode
  * The reference boxes every cluster with trimesh (utils/tower_extraction.py:137-139:
  * trimesh.PointCloud(cluster_points).bounding_box_oriented): qhull's 3-D hull of the whole cluster, then a

@@ -1869,6 +1869,148 @@ def _span_ground_minima_of(X, Y, W, g, limit):
                 min_at=torch.where(found[:, None], xyz, nan), violation=minc <= limit)
 
 
+# ------------------------------------------------------------- tower profile, opt-in
+SLICES_BLOCK = 512             # entries of perm per wave of the slice sweep (sl_sweep_k): the sizes tests straddle
+SLICES_MAX = 256               # PCH_SLICES_MAX: slices per table row
+SLICES_MAX_TABLES = 4096       # PCH_SLICES_MAX_TABLES
+SLICES_MAX_ENTRIES = 1 << 20   # PCH_SLICES_MAX_ENTRIES: table rows x slices
+
+
+def cluster_slices(xyz, perm, offsets, nclusters, frames5, slot, ntables, dz, nslices):
+    """The slice table of the grouped rows (pch_cluster_slices_f32; the rule is in include/pch_hip.h): dict of device
+    tensors - ``count`` int32 [T,B], ``ext`` float64 [T,B,4] = (min s, max s, min t, max t) and ``outside`` int64 [T,2]
+    (the rows below slice 0 and at or above slice B).  Cluster k of the grouping (perm / offsets of
+    ``segment_by_label``) is looked at in its frame ``frames5[k] = (cx, cy, z0, ux, uy)`` (float64 [K,5]): ``s`` along
+    ``u``, ``t`` across it, slice ``floor((z - z0) / dz)``; it writes to table row ``slot[k]`` (int32 [K]; -1 or out of
+    range: the cluster takes no part, as with a frame that is not finite; clusters that share a row are combined).  A
+    slice without a row holds ``(+inf, -inf, +inf, -inf)`` and count 0.  perm is swept in fixed blocks whatever the
+    cluster sizes; counts, minima and maxima only, so the same input gives the same bits on every run.  ValueError:
+    ntables outside 1..4096, nslices outside 1..256, more than 2^20 entries, dz not finite or not > 0, 2^31 or more
+    grouped rows.  Asynchronous."""
+    import math
+    L = _lib.lib()
+    xyz, perm, offsets, K = _grouping(xyz, perm, offsets, nclusters)
+    frames5 = _need_cuda(frames5, torch.float64, "frames5").reshape(-1, 5)
+    slot = _need_cuda(slot, torch.int32, "slot").reshape(-1)
+    if frames5.shape[0] != K or slot.numel() != K:
+        raise ValueError("frames5 must hold five values and slot one entry per cluster")
+    for name, v, top in (("ntables", ntables, SLICES_MAX_TABLES), ("nslices", nslices, SLICES_MAX)):
+        if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= top:
+            raise ValueError(f"{name} must be an integer in 1..{top}, got {v!r}")
+    T, B = int(ntables), int(nslices)
+    if T * B > SLICES_MAX_ENTRIES:
+        raise ValueError(f"ntables * nslices must not exceed 2^20 = {SLICES_MAX_ENTRIES}, got {T} * {B}")
+    dz = float(dz)
+    if not (math.isfinite(dz) and dz > 0.0):
+        raise ValueError(f"dz must be finite and > 0, got {dz!r}")
+    dev, n = offsets.device, perm.numel()
+    if n >= 1 << 31:
+        raise ValueError("cluster_slices takes fewer than 2^31 grouped rows per call")
+    with torch.cuda.device(dev):
+        count = torch.empty((T, B), dtype=torch.int32, device=dev)
+        ext = torch.empty((T, B, 4), dtype=torch.float64, device=dev)
+        outside = torch.empty((T, 2), dtype=torch.int64, device=dev)
+        ws = _workspace(L.pch_cluster_slices_ws_bytes(n, K, T, B), dev)
+        _lib.check(L.pch_cluster_slices_f32(_ptr(xyz), _ptr(perm), _ptr(offsets), n, K, _ptr(frames5), _ptr(slot), T, dz,
+                                            B, _ptr(count), _ptr(ext), _ptr(outside), _ptr(ws), ws.numel(), _stream()))
+    return dict(count=count, ext=ext, outside=outside)
+
+
+TOWER_LEVEL_KEYS = ("n_levels", "z_low", "z_high", "width", "rows", "top")
+
+
+def tower_levels(count, ext, z0, dz, ground=None, min_rows=3, arm_window=3.0, arm_excess=4.0, max_levels=8):
+    """Cross-arm levels of ``cluster_slices``' tables (include/pch_hip.h's rule; float64 torch arithmetic on [T,B]
+    records, no kernel).  With ``G = ceil(arm_window / dz)``: a slice is occupied when it holds at least ``min_rows``
+    rows; its width ``w`` is the larger of its two extents; ``body`` is the smallest width among the occupied slices
+    at most G slices away; it is an arm slice when ``w - body >= arm_excess``.  A level is a maximal run of arm slices.
+
+    Returns dict of device tensors: ``n_levels`` int64 [T] (at most ``max_levels``, the lowest are kept); ``z_low``,
+    ``z_high``, ``width``, ``rows`` float64 [T, max_levels], NaN-padded - the lower edge ``z0 + b_lo·dz`` and the upper
+    edge ``z0 + (b_hi + 1)·dz`` of the run, its largest width and its row count; ``top`` float64 [T] = ``z0 + (b_top +
+    1)·dz`` for the highest occupied slice, NaN without one.  ``z0``: float64 [T] or a number.  With ``ground`` (float64
+    [T]) also ``tower_height = top - ground`` and ``nominal_height`` = ``z_low`` of the lowest level ``- ground``, NaN
+    without a level.  An arm thicker than ``2G + 1`` slices is not found: a slice in its middle sees only arm slices
+    within G, so its ``body`` is the arm's own width (an arm of up to ``2G`` slices is found whole; from ``2G + 1`` on
+    its middle is missing and it shows as two thin levels at its edges).  Asynchronous."""
+    count = _need_cuda(count, torch.int32, "count")
+    if count.dim() != 2:
+        raise ValueError("count must be [T,B]")
+    T, B = count.shape
+    ext = _need_cuda(ext, torch.float64, "ext").reshape(-1, 4)
+    if ext.shape[0] != T * B:
+        raise ValueError("ext must hold four values per entry of count")
+    z0 = _levels_column(z0, T, count.device, "z0")
+    if ground is not None:
+        ground = _levels_column(ground, T, count.device, "ground")
+    return _tower_levels_of(count, ext.reshape(T, B, 4), z0, dz, ground, min_rows, arm_window, arm_excess, max_levels)
+
+
+def _levels_column(v, T, dev, name):
+    if isinstance(v, torch.Tensor):
+        v = _need_cuda(v, torch.float64, name).reshape(-1)
+        if v.numel() != T:
+            raise ValueError(f"{name} must hold one value per table row")
+        return v
+    return torch.full((T,), float(v), dtype=torch.float64, device=dev)
+
+
+def _tower_levels_of(count, ext, z0, dz, ground=None, min_rows=3, arm_window=3.0, arm_excess=4.0, max_levels=8):
+    """tower_levels' arithmetic, on tensors of any device"""
+    import math
+    dz, arm_window, arm_excess = float(dz), float(arm_window), float(arm_excess)
+    if not (math.isfinite(dz) and dz > 0.0):
+        raise ValueError(f"dz must be finite and > 0, got {dz!r}")
+    if not (math.isfinite(arm_window) and arm_window >= 0.0) or math.isnan(arm_excess):
+        raise ValueError(f"arm_window must be finite and >= 0 and arm_excess a number, got {arm_window!r}, {arm_excess!r}")
+    if isinstance(max_levels, bool) or int(max_levels) != max_levels or int(max_levels) < 1:
+        raise ValueError(f"max_levels must be an integer >= 1, got {max_levels!r}")
+    L, G = int(max_levels), int(math.ceil(arm_window / dz))
+    T, B = count.shape
+    dev = count.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    z0 = z0.to(torch.float64).reshape(T)
+    nan = torch.full((), float("nan"), **f64)
+    inf = torch.full((), float("inf"), **f64)
+    occ = count >= int(min_rows)
+    wide = torch.maximum(ext[:, :, 1] - ext[:, :, 0], ext[:, :, 3] - ext[:, :, 2])
+    w = torch.where(occ, wide, nan)
+    # body: the sliding minimum of the occupied widths over |b' - b| <= G, one shifted copy per offset
+    held = torch.where(occ, wide, inf)
+    reach = min(G, max(B - 1, 0))
+    padded = torch.nn.functional.pad(held, (reach, reach), value=float("inf"))
+    body = held
+    for d in range(2 * reach + 1):
+        body = torch.minimum(body, padded[:, d:d + B])
+    arm = occ & ((w - body) >= arm_excess)
+    before = torch.nn.functional.pad(arm[:, :-1], (1, 0), value=False)
+    start = arm & ~before
+    level = torch.cumsum(start.to(torch.int64), dim=1) - 1                  # the run an arm slice belongs to
+    found = start.sum(dim=1)
+    kept = arm & (level < L)
+    at = torch.where(kept, level, torch.full_like(level, L))                # what is not kept goes to a spare column
+    b = torch.arange(B, **f64)[None, :].expand(T, B).contiguous()
+    b_lo = torch.full((T, L + 1), float("inf"), **f64).scatter_reduce(1, at, b, "amin", include_self=True)[:, :L]
+    b_hi = torch.full((T, L + 1), float("-inf"), **f64).scatter_reduce(1, at, b, "amax", include_self=True)[:, :L]
+    width = torch.full((T, L + 1), float("-inf"), **f64).scatter_reduce(
+        1, at, torch.where(kept, wide, -inf), "amax", include_self=True)[:, :L]
+    rows = torch.zeros((T, L + 1), **f64).scatter_add(1, at, count.to(torch.float64))[:, :L]
+    has = torch.arange(L, dtype=torch.int64, device=dev)[None, :] < found[:, None]
+    zero = torch.zeros((), **f64)
+    out = dict(n_levels=torch.clamp(found, max=L),
+               z_low=torch.where(has, z0[:, None] + torch.where(has, b_lo, zero) * dz, nan),
+               z_high=torch.where(has, z0[:, None] + (torch.where(has, b_hi, zero) + 1.0) * dz, nan),
+               width=torch.where(has, width, nan), rows=torch.where(has, rows, nan))
+    b_top = torch.where(occ, b, -inf).amax(dim=1) if B else torch.full((T,), float("-inf"), **f64)
+    any_occ = occ.any(dim=1)
+    out["top"] = torch.where(any_occ, z0 + (torch.where(any_occ, b_top, zero) + 1.0) * dz, nan)
+    if ground is not None:
+        ground = ground.to(torch.float64).reshape(T)
+        out["tower_height"] = out["top"] - ground
+        out["nominal_height"] = out["z_low"][:, 0] - ground
+    return out
+
+
 # ---------------------------------------------------------------------------- stage D1, fast mode
 def obb_shell(xyz, perm, offsets, nclusters):
     """uint8 [offsets[K]] in grouped order: 1 for the points of every cluster that can be vertices of its

@@ -302,6 +302,109 @@ def span_ground_clearance(spans, terrain, segments=32, limit=7.0):
     return dict(pieces=idx, clearance=res["clearance"], ground=res["ground"], table=table)
 
 
+TOWER_PROFILE_TABLE_KEYS = ("ground", "ground_from", "top", "tower_height", "nominal_height", "n_levels", "z_low",
+                            "z_high", "width", "rows", "lowest_wire")
+TOWER_PROFILE_MAX_LEVELS = 8
+
+
+def tower_profile(clusters, which=None, terrain=None, spans=None, dz=0.5, height=64.0, min_rows=3, arm_window=3.0,
+                  arm_excess=4.0, reach=12.0):
+    """Where the towers have their cross-arms and how high they stand.  ``clusters``: ``cluster_points``'
+    dict (``ground["points"]``, ``perm``, ``offsets``, ``stats``, ``nclusters``); ``which``: the cluster ids to profile,
+    ascending (None: all of them; more than 4096 is a ValueError).  Every cluster gets a horizontal frame over the whole
+    grouping (``ops.cluster_moments``, ``ops.span_frames``: the centre, and the principal horizontal direction, which
+    for a tower with arms is the arm axis); the rows of the chosen ones are binned into ``B = ceil(height / dz)`` slices
+    of ``dz`` metres from ``z0`` upwards (``ops.cluster_slices``; ``B > 256`` is a ValueError) and the cross-arm levels
+    are read off the slice table (``ops.tower_levels`` with ``min_rows``, ``arm_window``, ``arm_excess``).
+
+    ``terrain`` (``terrain_model``'s dict, in the frame of the points): ``z0`` and the ground are the model's value under
+    the tower's axis (``ops.terrain_sample``) and ``ground_from`` is "terrain"; where the model has none there, or
+    without ``terrain``, both are the cluster's lowest z (``stats``) and ``ground_from`` is "cluster" - a stage-B cluster
+    has lost its feet, so heights are then measured from where the cluster begins.  ``spans`` (``conductor_spans``' dict,
+    same frame): ``lowest_wire`` is the smallest height above the ground, over the two ends of the accepted pieces that
+    lie within ``reach`` metres horizontally of the tower's axis, of the piece's sag curve there; NaN without such an
+    end or without ``spans``.
+
+    Returns dict: ``which`` (int64 [T], device), ``frames5`` (float64 [T,5] = cx, cy, z0, ux, uy), ``count`` (int32
+    [T,B]), ``ext`` (float64 [T,B,4]), ``outside`` (int64 [T,2]) and ``table``, keyed like ``TOWER_PROFILE_TABLE_KEYS``:
+    ``ground``, ``top``, ``tower_height``, ``nominal_height`` (the lower edge of the lowest level above the ground),
+    ``lowest_wire`` float64 [T]; ``n_levels`` int64 [T]; ``z_low``, ``z_high``, ``width``, ``rows`` float64 [T, 8],
+    NaN-padded; ``ground_from`` a list of T strings.  No cluster selected: empty tables, nothing is raised.
+    Synchronises."""
+    import math
+    dz, height, reach = float(dz), float(height), float(reach)
+    if not (math.isfinite(dz) and dz > 0.0 and math.isfinite(height) and height > 0.0):
+        raise ValueError(f"dz and height must be finite and > 0, got {dz!r}, {height!r}")
+    if not (math.isfinite(reach) and reach >= 0.0):
+        raise ValueError(f"reach must be finite and >= 0, got {reach!r}")
+    B = int(math.ceil(height / dz))
+    if B > ops.SLICES_MAX:
+        raise ValueError(f"height {height:g} m at dz {dz:g} m is {B} slices; the limit is {ops.SLICES_MAX} slices "
+                         f"({ops.SLICES_MAX * dz:g} m)")
+    points = clusters["ground"]["points"]
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32:
+        raise TypeError("the clustered points must be a float32 CUDA/HIP tensor (no CPU fallback in the product path)")
+    points = points.reshape(-1, 3).contiguous()
+    dev = points.device
+    K = int(clusters["nclusters"]) if "perm" in clusters else 0
+    ids = np.arange(K, dtype=np.int64) if which is None else np.asarray(
+        which.cpu() if isinstance(which, torch.Tensor) else which, dtype=np.int64).reshape(-1)
+    if len(ids) > ops.SLICES_MAX_TABLES:
+        raise ValueError(f"tower_profile takes at most {ops.SLICES_MAX_TABLES} clusters per call, got {len(ids)}")
+    if len(ids) and (ids[0] < 0 or ids[-1] >= K or (np.diff(ids) <= 0).any()):
+        raise ValueError("which must hold cluster ids in 0..nclusters-1, ascending")
+    T, L = len(ids), TOWER_PROFILE_MAX_LEVELS
+    which_t = torch.as_tensor(ids, device=dev)
+    nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
+    if T == 0:
+        table = dict(ground=nan(0), ground_from=[], top=nan(0), tower_height=nan(0), nominal_height=nan(0),
+                     n_levels=torch.zeros((0,), dtype=torch.int64, device=dev), z_low=nan(0, L), z_high=nan(0, L),
+                     width=nan(0, L), rows=nan(0, L), lowest_wire=nan(0))
+        return dict(which=which_t, frames5=nan(0, 5), count=torch.zeros((0, B), dtype=torch.int32, device=dev),
+                    ext=nan(0, B, 4), outside=torch.zeros((0, 2), dtype=torch.int64, device=dev), table=table)
+    perm, offsets = clusters["perm"], clusters["offsets"]
+    count, origin, moments = ops.cluster_moments(points, perm, offsets, K)
+    frames = ops.span_frames(count, origin, moments)
+    lowest = clusters["stats"][:K, 2].to(torch.float64)
+    if terrain is not None:
+        under = ops.terrain_sample(frames[:, 0:2].contiguous(), terrain["grid"], terrain["ground"])
+        modelled = ~torch.isnan(under)
+        z0 = torch.where(modelled, under, lowest)
+    else:
+        modelled = torch.zeros((K,), dtype=torch.bool, device=dev)
+        z0 = lowest
+    frames5 = torch.stack([frames[:, 0], frames[:, 1], z0, frames[:, 3], frames[:, 4]], dim=1).contiguous()
+    slot = torch.full((K,), -1, dtype=torch.int32, device=dev)
+    slot[which_t] = torch.arange(T, dtype=torch.int32, device=dev)
+    res = ops.cluster_slices(points, perm, offsets, K, frames5, slot, T, dz, B)
+    ground = z0[which_t].contiguous()
+    table = ops.tower_levels(res["count"], res["ext"], ground, dz, ground=ground, min_rows=min_rows,
+                             arm_window=arm_window, arm_excess=arm_excess, max_levels=L)
+    table["ground"] = ground
+    table["ground_from"] = ["terrain" if m else "cluster" for m in modelled[which_t].cpu().tolist()]
+    table["lowest_wire"] = _lowest_wire(spans, frames5[which_t], ground, reach) if spans is not None else nan(T)
+    return dict(which=which_t, frames5=frames5[which_t].contiguous(), count=res["count"], ext=res["ext"],
+                outside=res["outside"], table={key: table[key] for key in TOWER_PROFILE_TABLE_KEYS})
+
+
+def _lowest_wire(spans, frames5, ground, reach):
+    """float64 [T]: per tower axis the smallest height above ``ground`` of an accepted piece's sag curve at one of its
+    two ends (``m0``, ``m1`` of ``ops.span_curves``: ``cz + a + m(b + c·m)``) within ``reach`` metres horizontally; NaN
+    without such an end.  Torch arithmetic on pieces x towers records."""
+    idx = torch.nonzero(spans["accepted"]).reshape(-1)
+    curves = ops.span_curves(spans["table"], spans["frames"], spans["ext"])[idx]
+    cx, cy, cz, ux, uy, a, b, c = (curves[:, i:i + 1] for i in range(8))
+    m = curves[:, 8:10]                                                       # [P,2]: the two ends
+    X, Y, W = cx + (m * ux), cy + (m * uy), cz + (a + m * (b + c * m))
+    dx = X[:, :, None] - frames5[None, None, :, 0]                            # [P,2,T]
+    dy = Y[:, :, None] - frames5[None, None, :, 1]
+    near = ((dx * dx) + (dy * dy)) <= reach * reach
+    inf = torch.full((), float("inf"), dtype=torch.float64, device=ground.device)
+    held = torch.where(near & ~torch.isnan(W)[:, :, None], W[:, :, None].expand_as(dx), inf)
+    low = held.reshape(-1, ground.numel()).amin(dim=0) if idx.numel() else inf.expand(ground.numel())
+    return torch.where(torch.isinf(low), torch.full_like(ground, float("nan")), low - ground)
+
+
 def _kept_rows(gf, dropped):
     """the copy of the stage-B result ``gf`` without the rows of the bool mask ``dropped``, as the opt-in drops return
     it: points, index (if present), count and aabb of the rows left, in file order, plus dropped and n_dropped"""

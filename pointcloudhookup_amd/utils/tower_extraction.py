@@ -80,6 +80,16 @@ gets one line per accepted wire piece: its length, the smallest height of its sa
 is in world coordinates, the ground's z there, the vertices over ground, the chord error and whether the height is at
 most ``limit`` metres (default 7).  It logs one extra line; a failure is handled like one of ``SPANS``.  The returned
 tower dicts are the same with and without it.
+``TOWER_PROFILE`` (env PCH_TOWER_PROFILE="dz[,height[,arm_window,arm_excess]]", e.g. "0.5"; unset or empty = off; needs
+no other knob): behind the tower table, the accepted towers' clusters are cut into height slices of ``dz`` metres over
+``height`` metres (default 64; at most 256 slices) and their cross-arm levels are read off the slice widths
+(pipeline.tower_profile; a slice is an arm when it is ``arm_excess`` metres, default 4, wider than the narrowest slice
+within ``arm_window`` metres, default 3).  ``output_towers/tower_profile_info.csv`` gets one line
+per accepted tower: its axis in world coordinates, the ground under it (``TERRAIN``'s model when that knob is on, else
+the cluster's lowest point, named in ``ground_from``), the tower's height above it, the nominal height (呼高: the lower
+edge of the lowest cross-arm above the ground), the lowest conductor end near the tower (``SPANS``' table when that knob
+is on) and the levels as ``low:high:width`` triples.  It logs one extra line; a failure is logged and the towers are
+returned.  The returned tower dicts and towers_info.xlsx are the same with and without it.
 """
 from __future__ import annotations
 
@@ -243,6 +253,39 @@ def terrain_from_env(value, spans=True, frame="reference"):
 TERRAIN_MAX_WINDOW_CELLS = 64                        # PCH_TERRAIN_MAX_WINDOW of include/pch_hip.h
 TERRAIN = terrain_from_env(os.environ.get("PCH_TERRAIN"), spans=SPANS is not None, frame=FRAME)
 TERRAIN_COLUMNS = ("ID", "length", "min_clearance", "x", "y", "z", "ground_z", "covered", "chord_error", "violation")
+
+
+def tower_profile_from_env(value):
+    """TOWER_PROFILE of an environment value: None (off) when unset or empty, else dict(dz, height, arm_window,
+    arm_excess) from "dz[,height[,arm_window,arm_excess]]" - one, two or four numbers; dz and height finite and > 0
+    (height defaults to 64) with ceil(height / dz) at most 256 slices, arm_window finite and >= 0 (default 3), arm_excess
+    finite (default 4) (ValueError)"""
+    if value is None or not value.strip():
+        return None
+    parts = [t.strip() for t in value.split(",")]
+    if len(parts) not in (1, 2, 4):
+        raise ValueError(f"PCH_TOWER_PROFILE takes \"dz[,height[,arm_window,arm_excess]]\", got {value!r}")
+    dz = float(parts[0])
+    height = float(parts[1]) if len(parts) >= 2 else 64.0
+    arm_window, arm_excess = (float(parts[2]), float(parts[3])) if len(parts) == 4 else (3.0, 4.0)
+    if not (np.isfinite(dz) and dz > 0.0):
+        raise ValueError(f"PCH_TOWER_PROFILE: dz must be finite and > 0, got {parts[0]!r}")
+    if not (np.isfinite(height) and height > 0.0):
+        raise ValueError(f"PCH_TOWER_PROFILE: height must be finite and > 0, got {parts[1]!r}")
+    if int(np.ceil(height / dz)) > TOWER_PROFILE_MAX_SLICES:
+        raise ValueError(f"PCH_TOWER_PROFILE: height {height:g} at dz {dz:g} is more than {TOWER_PROFILE_MAX_SLICES} "
+                         "slices, the library's limit")
+    if not (np.isfinite(arm_window) and arm_window >= 0.0):
+        raise ValueError(f"PCH_TOWER_PROFILE: arm_window must be finite and >= 0, got {parts[2]!r}")
+    if not np.isfinite(arm_excess):
+        raise ValueError(f"PCH_TOWER_PROFILE: arm_excess must be finite, got {parts[3]!r}")
+    return dict(dz=dz, height=height, arm_window=arm_window, arm_excess=arm_excess)
+
+
+TOWER_PROFILE_MAX_SLICES = 256                       # PCH_SLICES_MAX of include/pch_hip.h
+TOWER_PROFILE = tower_profile_from_env(os.environ.get("PCH_TOWER_PROFILE"))
+TOWER_PROFILE_COLUMNS = ("ID", "x", "y", "ground_z", "ground_from", "tower_height", "nominal_height", "lowest_wire",
+                         "n_levels", "levels")
 PRESTART_BYTES = 100 << 20                           # LAS files from here on get worker processes early
 CHUNK_SIZE = 50000                                     # utils/tower_extraction.py:96
 
@@ -493,6 +536,7 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
     clock.move("tower boxes + accept / de-dup (D1-D3)", "per-tower LAS files", las_seconds[0])
 
     # ---- opt-in: the conductors between the accepted towers, as a span table
+    spans = None
     if SPANS and tower_obbs:
         try:
             cen = np.asarray(centroid, dtype=np.float64)
@@ -529,7 +573,20 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
             except (ValueError, RuntimeError) as e:
                 log(f"⚠️ 导线对地净空计算失败: {str(e)}")
                 return tower_obbs
-    stage_b_points = terrain = None
+    # ---- opt-in: the accepted towers' slice tables, cross-arm levels and nominal height
+    if TOWER_PROFILE and tower_rows:
+        try:
+            ids = [r["ID"] for r in tower_rows]                    # "tower_<cluster label>", in the order of towers_info
+            profile = pipeline.tower_profile(clusters, which=sorted(int(i[len("tower_"):]) for i in ids),
+                                             terrain=terrain, spans=spans, **TOWER_PROFILE)
+            rows = tower_profile_rows(profile, ids, np.asarray(centroid, dtype=np.float64))
+            write_tower_profile_csv(output_dir / "tower_profile_info.csv", rows)
+            clock.mark("tower profile")
+            log(tower_profile_line(rows, TOWER_PROFILE))
+        except (ValueError, RuntimeError) as e:
+            log(f"⚠️ 杆塔剖面计算失败: {str(e)}")
+            return tower_obbs
+    stage_b_points = terrain = spans = None
 
     # ---- xlsx (reference :221-231)
     if tower_rows:
@@ -673,6 +730,48 @@ def ground_clearance_line(terrain, rows, knob):
     return (f"⛰️ 导线对地净空: 网格 {knob['cell']:g} m（{g['nx']}×{g['ny']}），开窗 {knob['window']:g} m，高差 {knob['dh']:g} m，"
             f"限距 {knob['limit']:g} m；地面格 {terrain['n_ground']}，填补 {terrain['n_filled']}，无值 {terrain['n_unfilled']}；"
             f"越限线段 {int(breached)}/{len(rows)}，最小对地净空 {lowest:.3f} m")
+
+
+def tower_profile_rows(profile, ids, centroid):
+    """the lines of tower_profile_info.csv for a result of pipeline.tower_profile: one list per tower of ``ids``
+    ("tower_<cluster label>", towers_info's ids in its order) in TOWER_PROFILE_COLUMNS' order, the axis and the ground
+    moved to world coordinates by ``centroid`` (3 float64); ``levels`` = "low:high:width" triples joined by ";", low and
+    high in world coordinates"""
+    at = {int(k): i for i, k in enumerate(profile["which"].cpu().tolist())}
+    f5 = profile["frames5"].cpu().numpy()
+    T = {key: (v.cpu().numpy() if hasattr(v, "cpu") else v) for key, v in profile["table"].items()}
+    rows = []
+    for name in ids:
+        i = at[int(name[len("tower_"):])]
+        n = int(T["n_levels"][i])
+        levels = ";".join(f"{float(T['z_low'][i, j] + centroid[2])!r}:{float(T['z_high'][i, j] + centroid[2])!r}:"
+                          f"{float(T['width'][i, j])!r}" for j in range(n))
+        rows.append([name, float(f5[i, 0] + centroid[0]), float(f5[i, 1] + centroid[1]),
+                     float(T["ground"][i] + centroid[2]), T["ground_from"][i], float(T["tower_height"][i]),
+                     float(T["nominal_height"][i]), float(T["lowest_wire"][i]), n, levels])
+    return rows
+
+
+def write_tower_profile_csv(path, rows):
+    """tower_profile_info.csv: a header line (TOWER_PROFILE_COLUMNS) and one line per accepted tower, floats with repr's
+    digits"""
+    import csv
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.writer(f)
+        w.writerow(TOWER_PROFILE_COLUMNS)
+        for r in rows:
+            w.writerow([repr(float(v)) if isinstance(v, (float, np.floating)) else v for v in r])
+
+
+def tower_profile_line(rows, knob):
+    """the extra log line of TOWER_PROFILE for the csv lines"""
+    with_level = sum(1 for r in rows if r[8] > 0)
+    nominal = [r[6] for r in rows if r[6] == r[6]]
+    span = f"{min(nominal):.1f}–{max(nominal):.1f} m" if nominal else "无"
+    from_terrain = sum(1 for r in rows if r[4] == "terrain")
+    return (f"🗼 杆塔剖面: 层厚 {knob['dz']:g} m，高度 {knob['height']:g} m，横担窗口 {knob['arm_window']:g} m，"
+            f"横担超宽 {knob['arm_excess']:g} m；杆塔 {len(rows)}，有横担 {int(with_level)}，地形地面 {int(from_terrain)}，"
+            f"呼高 {span}")
 
 
 def ground_tiles_line(gf):
