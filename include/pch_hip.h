@@ -160,6 +160,12 @@ int pch_cast_f64_f32(const double* in, int64_t count, float* out, void* stream);
 size_t pch_mean_seq_f32_ws_bytes(int64_t n);
 int pch_mean_seq_f32(const float* xyz, int64_t n, float* out_centroid,
                      void* ws, size_t ws_bytes, void* stream);
+/* Slices of pch_mean_seq_f32 and of the centroid inside pch_ground_filter_f32 / the fused call: the summary pass is
+ * cut into k launches over consecutive row ranges, and the serial walk of every slice but the last runs on a stream
+ * of the library's own beside the summary of the next slice.  0 (default) = automatic: one launch below 2^26 rows,
+ * two equal slices from there; 1..8 = forced, equal shares, clamped to the number of 65 536-row groups.  Per thread;
+ * the result does not depend on it (tests slice small clouds with it).  pch_mean_seq_partial_f32 ignores it. */
+void pch_mean_set_slices(int k);
 /* One file-order SHARD of that sequential sum (config 4: every rank holds a consecutive slice of the rows and the
  * three running sums travel down the line, 12 bytes per hop): continues the float32 running sums sum_in3 (device
  * float[3]; NULL = +0.0, the first shard) over these n rows, exactly as numpy's loop would.

@@ -45,6 +45,7 @@ _SIGS = {
     "pch_mean_seq_f32": (C.c_int, [_vp, _i64, _vp, _vp, _sz, _vp]),
     "pch_mean_seq_partial_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _sz, _vp]),
     "pch_mean_seq_serial_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "pch_mean_set_slices": (None, [C.c_int]),
     "pch_percentile_f32_ws_bytes": (_sz, [_i64]),
     "pch_percentile_f32": (C.c_int, [_vp, _i64, _i64, _vp, _f64, _vp, _vp, _sz, _vp]),
     "pch_select_hist_f32": (C.c_int, [_vp, _i64, _i64, _i32, C.c_uint32, _vp, _vp, _vp, _sz, _vp]),

@@ -1183,8 +1183,9 @@ int pch::ground_filter_run(const float* raw, int64_t n, double pct, float offset
     w.sel.also_zero = reinterpret_cast<uint32_t*>(w.st);
     w.sel.also_words = (int64_t)(w.clear_bytes / 4);
     SideStream& ss = side_stream();
-    // Two strands.  `s`: summary, level 2, walk - no cross-stream hop inside the chain.  Side stream: at once the
-    // select's init kernel, then - behind the summary - the exact select; joined in front of the interpolation
+    // Two strands.  `s`: summary, level 2, walk - no cross-stream hop inside the chain (a large cloud's summary comes
+    // in slices, and the walk of all but the last slice runs on a third stream beside it: mean_seq_launch).  Side
+    // stream: at once the select's init kernel, then - behind the summary - the exact select; joined in front of the interpolation
     // (measured: the other assignment, select on `s` and walk on the side stream, loses 45 us to the hops).  Without a
     // side stream the select follows the walk on `s`.
     // Where the summary emits candidate slots it brackets the percentile too (MsBracket, pch_mean.h) and the select
@@ -1206,8 +1207,12 @@ int pch::ground_filter_run(const float* raw, int64_t n, double pct, float offset
     PCH_LAUNCH("sel_init", sel_init_k, dim3((unsigned)ceil_div(9 * SEL_BINS, 256)), dim3(256), 0, sel_s, w.sel.hist,
                9 * SEL_BINS, w.sel.run, 3, 0ull, 0ull, (unsigned long long)pi.k0, w.sel.br, w.sel.also_zero,
                w.sel.also_words);
-    PCH_TRY(mean_seq_launch(raw, n, w.centroid, w.ms, nullptr, s, ss.ok ? ss.ev_fork : nullptr, nullptr, MS_DIVIDE_BY_N,
-                            MS_PHASE_BOTH, &w.cand, &cand_made));
+    MsLaunch ml;
+    ml.ev_summary = ss.ok ? ss.ev_fork : nullptr;
+    ml.cand = &w.cand;
+    ml.cand_made = &cand_made;
+    ml.may_slice = true;
+    PCH_TRY(mean_seq_launch(raw, n, w.centroid, w.ms, nullptr, s, ml));
     PCH_REQUIRE(!bracket || cand_made, "bracket route without candidate slots");
     if (ss.ok) PCH_HIP_TRY(hipStreamWaitEvent(ss.s, ss.ev_fork, 0));
     if (bracket) {

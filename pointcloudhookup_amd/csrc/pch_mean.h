@@ -75,9 +75,21 @@ constexpr int MS_PHASE_BOTH = 0, MS_PHASE_TABLES = 1, MS_PHASE_WALK = 2;
 // estimate, i.e. more than 65 536 rows - a second group of 64 blocks - and prediction enabled): ms_makes_cand(n) tells
 // beforehand.
 // With cand->bracket the z values inside the bracket go to the fronts of cand->zseg's segments.
+// may_slice (phase both, no sum_in): a large cloud - or any, with pch_mean_set_slices - is summarised in file-order
+// slices, and level 2 and the walk of every slice but the last run on a stream of their own beside the summary of
+// the next one (pch_mean.hip, "the centroid in file-order slices").  ev_summary is then recorded behind the last
+// slice.  Same tables, same result.
 bool ms_makes_cand(int64_t n);
+struct MsLaunch {                // the optional arguments described above
+    hipEvent_t    ev_summary = nullptr;
+    const float*  sum_in = nullptr;
+    int64_t       divide_n = MS_DIVIDE_BY_N;
+    int           phase = MS_PHASE_BOTH;
+    const MsCand* cand = nullptr;
+    bool*         cand_made = nullptr;
+    bool          may_slice = false;
+};
 int mean_seq_launch(const float* xyz, int64_t n, float* out, MsWs& w, float* zcol, hipStream_t s,
-                    hipEvent_t ev_summary = nullptr, const float* sum_in = nullptr, int64_t divide_n = MS_DIVIDE_BY_N,
-                    int phase = MS_PHASE_BOTH, const MsCand* cand = nullptr, bool* cand_made = nullptr);
+                    const MsLaunch& opt = MsLaunch());
 
 }  // namespace pch

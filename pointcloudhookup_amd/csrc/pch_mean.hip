@@ -328,11 +328,14 @@ __global__ __launch_bounds__(64 * MS_WAVES) void ms_summary_k(const float* __res
                                                              float* __restrict__ cslots, uint32_t* __restrict__ ccounts,
                                                              const float* __restrict__ tcand,
                                                              const MsBracket* __restrict__ brk,
-                                                             MsBrRec* __restrict__ brec, float* __restrict__ zseg) {
+                                                             MsBrRec* __restrict__ brec, float* __restrict__ zseg,
+                                                             int64_t blk_first, int64_t blk_count) {
     __shared__ __attribute__((aligned(16))) float lds[MS_WAVES][MSB * 3];
     __shared__ MsRec stage[MS_WAVES];                    // a record is assembled here, stored as whole lines
-    const int64_t blk = (int64_t)blockIdx.x * MS_WAVES + wave_id();
-    if (blk >= nb) return;
+    // this launch summarises the blocks [blk_first, blk_first + blk_count) (a file-order slice, see mean_seq_launch);
+    // blk and everything indexed by it are those of the whole array
+    const int64_t blk = blk_first + (int64_t)blockIdx.x * MS_WAVES + wave_id();
+    if (blk >= blk_first + blk_count) return;
     const int l = lane_id();
     const int64_t p0 = blk * MSB;
     const int cnt = (int)((n - p0) < MSB ? (n - p0) : MSB);
@@ -917,15 +920,16 @@ constexpr int MS_L2_PITCH = sizeof(MsRec) / 4 + 1;       // words per child in L
 
 __global__ __launch_bounds__(256) void ms_level2_k(const MsRec* __restrict__ recs, int64_t nb,
                                                    int64_t nb2, MsHdr* __restrict__ hdr2,
-                                                   long long* __restrict__ rows2) {
+                                                   long long* __restrict__ rows2, int64_t row_first,
+                                                   int64_t row_count) {
     // one workgroup per (column, row): the 64 child records are contiguous (24 KiB), copied to LDS
     // with coalesced 16-byte loads; lane l of every wave then reads the record of child l, and
     // each of the four waves composes six of the 24 candidates
     __shared__ uint32_t sh[64 * MS_L2_PITCH];
     __shared__ uint32_t tie_sh, miss_sh;
     const int64_t w = blockIdx.x;
-    const int c = (int)(w / nb2);
-    const int64_t g = w % nb2;
+    const int c = (int)(w / row_count);                   // the rows [row_first, row_first + row_count) of every column
+    const int64_t g = row_first + w % row_count;
     const int l = lane_id();
     const int64_t bb = g * 64 + l;
     const bool valid = bb < nb;
@@ -1147,17 +1151,18 @@ __device__ __forceinline__ uint32_t ms_walk_children(const float* __restrict__ x
 // pch_mean_seq_partial_f32); divide_n: 0 = store the running sum itself, else divide by float32(divide_n)
 __global__ __launch_bounds__(64 * MS_XW) void ms_walk_k(const float* __restrict__ xyz, int64_t n, MsTables T,
                                                 const float* __restrict__ sum_in, int64_t divide_n, int divide,
-                                                float* __restrict__ out, int* __restrict__ stats) {
+                                                float* __restrict__ out, int* __restrict__ stats,
+                                                int64_t row_begin, int64_t row_end, int stats_add) {
     __shared__ MsExact stage_x;
     MsExact* stage = &stage_x;
     const int c = blockIdx.x;
     const int l = lane_id();
     uint32_t sb = sum_in ? __float_as_uint(sum_in[c]) : 0u;      // bits of the running sum (+0.0 at the start)
-    int64_t b = 0;                                     // next level-2 row
+    int64_t b = row_begin;                             // next level-2 row (of [row_begin, row_end): a file-order slice)
     int n_exact = 0, n_batches = 0, n_desc = 0, n_miss = 0;
     int dbg[3] = {0, 0, 0};                            // passes / serially added elements / calls of the exact path
     int streak = 0;                                    // blocks added without asking the tables (ms_walk_children)
-    while (b < T.nb2) {
+    while (b < row_end) {
         ++n_batches;
         const uint32_t ef = (sb >> 23) & 0xFFu;
         if (ef == 255u && (sb & 0x7FFFFFu)) break;     // NaN is absorbing
@@ -1166,7 +1171,7 @@ __global__ __launch_bounds__(64 * MS_XW) void ms_walk_k(const float* __restrict_
         const bool s_neg = (sb >> 31) != 0;
         const int E = (int)ef - 127;
         const int64_t bb = b + l;
-        const bool valid = bb < T.nb2;
+        const bool valid = bb < row_end;
         MsHdr h;
         h.emax = 0; h.tie = 0; h.flags = MS_ALLZERO; h.mask = MS_ALLCAND;
         if (valid) h = T.hdr2[(int64_t)c * T.nb2 + bb];
@@ -1201,9 +1206,11 @@ __global__ __launch_bounds__(64 * MS_XW) void ms_walk_k(const float* __restrict_
         // n == 0 -> 0/0 = NaN like numpy
         out[c] = divide ? __uint_as_float(sb) / (float)divide_n : __uint_as_float(sb);
         if (stats) {
-            stats[4 * c + 0] = n_batches; stats[4 * c + 1] = n_miss;     // n_miss: exact blocks the window caused
-            stats[4 * c + 2] = n_exact; stats[4 * c + 3] = n_desc;
-            stats[16 + 4 * c + 0] = dbg[0]; stats[16 + 4 * c + 1] = dbg[1]; stats[16 + 4 * c + 2] = dbg[2];
+            // (the walk of a later slice adds to what the slices in front of it stored: the totals of one centroid)
+            auto put = [&](int i, int v) { stats[i] = stats_add ? stats[i] + v : v; };
+            put(4 * c + 0, n_batches); put(4 * c + 1, n_miss);           // n_miss: exact blocks the window caused
+            put(4 * c + 2, n_exact); put(4 * c + 3, n_desc);
+            put(16 + 4 * c + 0, dbg[0]); put(16 + 4 * c + 1, dbg[1]); put(16 + 4 * c + 2, dbg[2]);
 #ifdef PCH_MS_STAMPS
             if (c == 2) for (int i = 0; i < 5; ++i) { stats[27 + i] = (int)(ms_stamp_acc[i] >> 6); ms_stamp_acc[i] = 0; }
 #endif
@@ -1243,7 +1250,9 @@ __global__ __launch_bounds__(256) void mean_seq_k(const float* __restrict__ xyz,
 void ms_plan(Arena& a, int64_t n, MsWs& w) {
     const int64_t nb = ceil_div(n > 0 ? n : 1, MSB);
     const int64_t nb2 = ceil_div(nb, 64);
-    w.stats = a.take<int>(32);               // [3][4] walk statistics, [16 + 4 c ..] exact-path counters
+    // [3][4] walk statistics, [16 + 4 c ..] exact-path counters; [32..34] and [36..38]: the float32 running sums
+    // one slice's walk hands to the next (mean_seq_launch), written in turn
+    w.stats = a.take<int>(64);
     w.pred = a.take<MsPred>(3 * nb2);
     w.rec = a.take<MsRec>(3 * nb);
     w.hdr2 = a.take<MsHdr>(3 * nb2);
@@ -1261,12 +1270,83 @@ bool ms_makes_cand(int64_t n) {
     return n > 0 && !no_cand && ms_predicts(n, MS_PHASE_BOTH);
 }
 
+// ---- the centroid in file-order slices (MS_PHASE_BOTH of a whole array only) ------------------------------------
+// The walk is a serial chain of three workgroups, and nearly all of its descents and exact blocks lie at the front of
+// the file (the sum climbs through binade k after about 2^k rows).  It consumes the level-2 rows strictly in file
+// order and carries nothing but the running sums, so the summary is cut into K launches over consecutive row ranges
+// and, while slice k + 1 is summarised on `s`, level 2 and the walk of slice k run on a second stream, handing the
+// undivided sums on in a 3-float word.  The last slice's level 2 and walk run on `s` itself (no cross-stream hop on
+// the critical chain).  Ordering comes from stream events only; the tables are those of the whole array.
+constexpr int MS_MAX_SLICES = 8;
+// Automatic choice (measured on 100 M points, profiles/README.md round 14): a boundary costs about 40 us of the
+// summary (17 us between the launches, and each part runs out and fills up again), so there is ONE, in the middle,
+// and only for clouds of at least MS_SLICE_MIN_ROWS level-2 rows (2^26 points): 10 M points are slower in two slices,
+// 30 M and 50 M no faster.  Every boundary also makes the three columns wait for each other: a slice's walk takes as
+// long as its slowest column, so a cut between the hard stretches of two columns costs what used to overlap (the
+// local frame with a first slice of 2^25 points: 0.45 ms).
+constexpr int64_t MS_SLICE_MIN_ROWS = 1024;
+constexpr int MS_AUTO_SLICES = 2;
+static thread_local int g_ms_slices = 0;                // pch_mean_set_slices: 0 = automatic, else forced
+
+struct MsWalkStream { hipStream_t s; hipEvent_t ev_slice[MS_MAX_SLICES]; hipEvent_t ev_walk; bool ok; };
+struct MsWalkStreams {                                  // one per device this thread has used; gone with the thread
+    MsWalkStream ws[PCH_MAX_DEVICES];
+    MsWalkStreams() { for (auto& x : ws) { x.s = nullptr; x.ev_walk = nullptr; x.ok = false; for (auto& e : x.ev_slice) e = nullptr; } }
+    ~MsWalkStreams() {
+        if (!may_release_hip_objects()) return;
+        for (auto& x : ws)
+            if (x.ok) {
+                for (auto& e : x.ev_slice) (void)hipEventDestroy(e);
+                (void)hipEventDestroy(x.ev_walk);
+                (void)hipStreamDestroy(x.s);
+            }
+    }
+};
+static MsWalkStream& ms_walk_stream() {
+    static thread_local MsWalkStreams all;
+    MsWalkStream& x = all.ws[current_device_slot()];
+    if (!x.ok && !x.s) {
+        bool ok = hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking) == hipSuccess &&
+                  hipEventCreateWithFlags(&x.ev_walk, hipEventDisableTiming) == hipSuccess;
+        for (auto& e : x.ev_slice) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+        x.ok = ok;
+    }
+    return x;
+}
+// number of slices for nb2 level-2 rows
+static int ms_slice_count(int64_t nb2) {
+    int64_t k = g_ms_slices > 0 ? g_ms_slices : (nb2 >= MS_SLICE_MIN_ROWS ? MS_AUTO_SLICES : 1);
+    k = k > MS_MAX_SLICES ? MS_MAX_SLICES : k;
+    k = k > nb2 ? nb2 : k;
+    return k < 1 ? 1 : (int)k;
+}
+
 int mean_seq_launch(const float* xyz, int64_t n, float* out, MsWs& w, float* zcol, hipStream_t s,
-                    hipEvent_t ev_summary, const float* sum_in, int64_t divide_n, int phase, const MsCand* cand,
-                    bool* cand_made) {
+                    const MsLaunch& opt) {
+    const hipEvent_t ev_summary = opt.ev_summary;
+    const float* const sum_in = opt.sum_in;
+    const int64_t divide_n = opt.divide_n;
+    const int phase = opt.phase;
+    const MsCand* const cand = opt.cand;
+    bool* const cand_made = opt.cand_made;
+    const bool may_slice = opt.may_slice;
     if (cand_made) *cand_made = false;
     const int64_t nb = n > 0 ? ceil_div(n, MSB) : 0;
     const int64_t nb2 = ceil_div(nb, 64);
+    // slices: whole level-2 rows [row0[k], row0[k + 1]), equal shares.  K = 1 is the plain sequence of launches.
+    int K = 1;
+    MsWalkStream* ws = nullptr;
+    if (may_slice && phase == MS_PHASE_BOTH && !sum_in && n > 0 && ms_slice_count(nb2) > 1) {
+        ws = &ms_walk_stream();
+        if (ws->ok) K = ms_slice_count(nb2);
+    }
+    int64_t row0[MS_MAX_SLICES + 1];
+    for (int k = 0; k <= K; ++k) row0[k] = nb2 * k / K;
+    auto blocks_of = [&](int k, int64_t& first, int64_t& count) {
+        first = row0[k] * 64;
+        const int64_t end = row0[k + 1] * 64 < nb ? row0[k + 1] * 64 : nb;
+        count = end - first;
+    };
     if (n > 0 && phase != MS_PHASE_WALK) {
         const MsPred* pred = nullptr;
         bool bracket = false;
@@ -1292,26 +1372,57 @@ int mean_seq_launch(const float* xyz, int64_t n, float* out, MsWs& w, float* zco
             if (mk && cand_made) *cand_made = true;
         }
         const bool emit = cand && cand_made && *cand_made;
-        PCH_LAUNCH("mean_summary", ms_summary_k, dim3((unsigned)ceil_div(nb, MS_WAVES)), dim3(64 * MS_WAVES),
-                   0, s, xyz, n, nb, w.rec, zcol, pred, nb2,
-                   emit ? cand->slots : (float*)nullptr, emit ? cand->counts : (uint32_t*)nullptr,
-                   emit ? (const float*)cand->tcand : (const float*)nullptr,
-                   bracket ? (const MsBracket*)cand->bracket : (const MsBracket*)nullptr,
-                   bracket ? cand->brec : (MsBrRec*)nullptr, bracket ? cand->zseg : (float*)nullptr);
+        for (int k = 0; k < K; ++k) {
+            int64_t first, count;
+            blocks_of(k, first, count);
+            PCH_LAUNCH("mean_summary", ms_summary_k, dim3((unsigned)ceil_div(count, MS_WAVES)), dim3(64 * MS_WAVES),
+                       0, s, xyz, n, nb, w.rec, zcol, pred, nb2,
+                       emit ? cand->slots : (float*)nullptr, emit ? cand->counts : (uint32_t*)nullptr,
+                       emit ? (const float*)cand->tcand : (const float*)nullptr,
+                       bracket ? (const MsBracket*)cand->bracket : (const MsBracket*)nullptr,
+                       bracket ? cand->brec : (MsBrRec*)nullptr, bracket ? cand->zseg : (float*)nullptr, first, count);
+            if (k + 1 < K) PCH_HIP_TRY(hipEventRecord(ws->ev_slice[k], s));
+        }
         // (with the bracket too: what waits for the event is then a short gather, sel_collect_k.  Recorded behind
         // level 2 instead, that kernel ran alone - 27 us for 49 - but the walk had the gather and the three histogram
         // passes beside it for longer: 226 us for 192, a loss of 12 on the critical path)
         if (ev_summary) PCH_HIP_TRY(hipEventRecord(ev_summary, s));
-        PCH_LAUNCH("mean_level2", ms_level2_k, dim3((unsigned)(3 * nb2)), dim3(256), 0, s,
-                   (const MsRec*)w.rec, nb, nb2, w.hdr2, w.rows2);
     }
-    if (phase == MS_PHASE_TABLES) return PCH_OK;
     MsTables T;
     T.rec = w.rec; T.nb = nb;
     T.hdr2 = w.hdr2; T.rows2 = w.rows2; T.nb2 = nb2;
+    // slices 0 .. K-2 on the walk stream, each behind its summary (the first event also orders everything the caller
+    // queued in front of this call - the rows, the previous user of the workspace - in front of that stream's work)
+    const float* carry = sum_in;
+    auto early_slices = [&]() -> int {
+        for (int k = 0; k + 1 < K; ++k) {
+            float* next = reinterpret_cast<float*>(w.stats + 32 + 4 * (k & 1));
+            PCH_HIP_TRY(hipStreamWaitEvent(ws->s, ws->ev_slice[k], 0));
+            PCH_LAUNCH("mean_level2", ms_level2_k, dim3((unsigned)(3 * (row0[k + 1] - row0[k]))), dim3(256), 0, ws->s,
+                       (const MsRec*)w.rec, nb, nb2, w.hdr2, w.rows2, row0[k], row0[k + 1] - row0[k]);
+            PCH_LAUNCH("mean_walk", ms_walk_k, dim3(3), dim3(64 * MS_XW), 0, ws->s, xyz, n, T, carry, (int64_t)0, 0,
+                       next, w.stats, row0[k], row0[k + 1], k > 0 ? 1 : 0);
+            carry = next;
+        }
+        return PCH_OK;
+    };
+    if (K > 1) {
+        // whatever was queued on the walk stream is joined into `s`, after a failure too: the caller may then free or
+        // reuse the workspace behind `s` as after any other call
+        const int rc = early_slices();
+        const hipError_t e1 = hipEventRecord(ws->ev_walk, ws->s);
+        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(s, ws->ev_walk, 0) : e1;
+        if (rc != PCH_OK) return rc;
+        PCH_HIP_TRY(e2);
+    }
+    // the last slice (K = 1: the whole array) on `s`
+    if (n > 0 && phase != MS_PHASE_WALK)
+        PCH_LAUNCH("mean_level2", ms_level2_k, dim3((unsigned)(3 * (nb2 - row0[K - 1]))), dim3(256), 0, s,
+                   (const MsRec*)w.rec, nb, nb2, w.hdr2, w.rows2, row0[K - 1], nb2 - row0[K - 1]);
+    if (phase == MS_PHASE_TABLES) return PCH_OK;
     const int divide = divide_n != MS_NO_DIVIDE;
-    PCH_LAUNCH("mean_walk", ms_walk_k, dim3(3), dim3(64 * MS_XW), 0, s, xyz, n, T, sum_in,
-               divide_n == MS_DIVIDE_BY_N ? n : divide_n, divide, out, w.stats);
+    PCH_LAUNCH("mean_walk", ms_walk_k, dim3(3), dim3(64 * MS_XW), 0, s, xyz, n, T, carry,
+               divide_n == MS_DIVIDE_BY_N ? n : divide_n, divide, out, w.stats, row0[K - 1], nb2, K > 1 ? 1 : 0);
     return PCH_OK;
 }
 
@@ -1336,8 +1447,12 @@ extern "C" int pch_mean_seq_f32(const float* xyz, int64_t n, float* out_centroid
     MsWs w;
     ms_plan(a, n, w);
     if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
-    return mean_seq_launch(xyz, n, out_centroid, w, nullptr, (hipStream_t)stream);
+    MsLaunch ml;
+    ml.may_slice = true;
+    return mean_seq_launch(xyz, n, out_centroid, w, nullptr, (hipStream_t)stream, ml);
 }
+
+extern "C" void pch_mean_set_slices(int k) { g_ms_slices = k < 0 ? 0 : (k > MS_MAX_SLICES ? MS_MAX_SLICES : k); }
 
 extern "C" int pch_mean_seq_partial_f32(const float* xyz, int64_t n, const float* sum_in3, int64_t total_n,
                                         float* out3, float* zcol_out, int32_t phase, void* ws, size_t ws_bytes,
@@ -1350,8 +1465,11 @@ extern "C" int pch_mean_seq_partial_f32(const float* xyz, int64_t n, const float
     MsWs w;
     ms_plan(a, n, w);
     if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
-    return mean_seq_launch(xyz, n, out3, w, zcol_out, (hipStream_t)stream, nullptr, sum_in3,
-                           total_n > 0 ? total_n : MS_NO_DIVIDE, phase);
+    MsLaunch ml;                                         // (may_slice stays off: a shard keeps its single launches)
+    ml.sum_in = sum_in3;
+    ml.divide_n = total_n > 0 ? total_n : MS_NO_DIVIDE;
+    ml.phase = phase;
+    return mean_seq_launch(xyz, n, out3, w, zcol_out, (hipStream_t)stream, ml);
 }
 
 extern "C" int pch_mean_seq_serial_f32(const float* xyz, int64_t n, float* out_centroid, void* stream) {

@@ -1131,6 +1131,12 @@ def shape_features(count, moments):
                 planarity=torch.where(ok, (l2 - l3) / den, zero), scattering=torch.where(ok, l3 / den, zero))
 
 
+def set_mean_slices(k):
+    """Slices of the centroid's summary pass for the calls this thread makes from now on: 0 = automatic (by size),
+    1..8 = forced (clamped to the number of 65 536-row groups).  Same result whatever it is."""
+    _lib.lib().pch_mean_set_slices(int(k))
+
+
 def set_pair_counting(enable):
     """Counting variant of the radius-count kernel for the fits this thread makes from now on (measurement only)."""
     _lib.lib().pch_dbscan_set_pair_counting(1 if enable else 0)
