@@ -879,6 +879,85 @@ int pch_cluster_slices_f32(const float* xyz, const int32_t* perm, const int64_t*
                            int32_t* out_count /* [T,B] */, double* out_ext /* [T,B,4] */,
                            int64_t* out_outside /* [T,2] */, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ tree fall, opt-in
+ * Which vegetation, standing where it stands, reaches a conductor if it falls towards the line: the distance from every
+ * row's ground foot to the fitted span curves, held against that row's own height above the ground.
+ *
+ * The rule.  All arithmetic is float64 without FMA (the library is built with -ffp-contract=off); parentheses are as
+ * written.  tests/treefall_cases.py follows it literally in numpy.
+ *   Inputs.  xyz float32 [n,3]; an optional skip uint8 [n]; sub3_host, 3 floats on the host, or NULL; grid_host
+ *     (PchTerrainGrid) and ground float32 [nx*ny], exactly as pch_terrain_height_f32 takes them; curves5 float64 [K,5]
+ *     and segs float64 [K,S,5], exactly as pch_clearance_f32 takes them; h_min, h_max, grow, limit: doubles, all
+ *     finite, with 0 <= h_min <= h_max, grow >= 0 and limit >= 0.  Anything else is PCH_ERR_ARG.
+ *   Span participation.  A span takes part iff all 5 + 5*S of its values are finite (the clearance rule).
+ *   Row frame and ground.  P = fl32(xyz[i] - sub3) and X, Y, Z = (double)P (the terrain rule).  g = g(X, Y) by the
+ *     terrain rule's bilinear function; one __device__ function serves terrain and this call.
+ *         H = Z - g
+ *   Row participation.  A row takes part iff skip[i] == 0, X, Y, Z are finite, g is not NaN, and
+ *         h_min <= H and H <= h_max
+ *     A row that fails only the g test is tallied as uncovered.
+ *   Reach.
+ *         reach = H + grow;  s2 = reach*reach
+ *         R = reach + limit;  R2 = R*R
+ *   Distance.  Spans that take part are visited in ascending k.  The measured point is the foot (X, Y, g):
+ *         dx = X - cx;  dy = Y - cy;  w = g - cz
+ *     m, t, the segment loop over j and d2 = gmin + (t*t) are exactly as in the clearance rule, with this w:
+ *         m = (dx*ux) + (dy*uy);  t = (dy*ux) - (dx*uy)
+ *         gmin = +inf
+ *         for j ascending:
+ *             rm = m - m_j;  rw = w - z_j
+ *             q = ((rm*dm_j) + (rw*dz_j))*inv_j
+ *             if q < 0: q = 0
+ *             if q > 1: q = 1
+ *             em = rm - (q*dm_j);  ew = rw - (q*dz_j)
+ *             d = (em*em) + (ew*ew)
+ *             if d < gmin: gmin = d
+ *         d2 = gmin + (t*t)
+ *         if d2 <= R2 and d2 < best: best = d2; who = k
+ *     Ties go to the lowest k.
+ *   Per-row outputs.  out_dist2[i] (float64) is best; +inf if there is none or the row takes no part.  out_span[i]
+ *     (int32) is who, or -1.  out_height[i] (float32) is (float)H for every row with finite coordinates, whether it
+ *     takes part or not; otherwise it is NaN.  It equals pch_terrain_height_f32's out_height bit for bit (NaN where g is
+ *     NaN).  out_class[i] (uint8) is one of
+ *         PCH_TREEFALL_CLEAR  = 0: no span within R, or the row takes no part
+ *         PCH_TREEFALL_NEAR   = 1: best <= R2 and best > s2 - the row comes within limit of a conductor after falling
+ *         PCH_TREEFALL_STRIKE = 2: best <= s2 - the row strikes
+ *   Per-span outputs, over the rows with out_span[i] == k: out_count[k] (int64); out_strikes[k] (int64): the rows of
+ *     class 2; out_min_dist2[k] (float64): +inf if there is no row; out_min_row[k] (int64): the lowest row that attains
+ *     it, or -1; out_max_height[k] (float32): the largest out_height by the order-preserving key (key(z) of the terrain
+ *     rule), NaN without a row; out_max_row[k] (int64): the lowest row that attains it, or -1.
+ *   Statistics.  out_stats (int64 [4], may be NULL): [0] the rows that took part and [1] the uncovered rows are part of
+ *     the rule; [2] the (row, span) segment loops run and [3] the (tile, span) pairs walked are figures for measurement
+ *     only.
+ * Every row is attributed to its NEAREST span within its own R only, by the distance of its FOOT: the row's own position
+ * enters through H alone.
+ *
+ * How: pch_clearance_f32's bounds kernel runs at radius Rmax = (h_max + grow) + limit.  Rounding is monotone, so every
+ * row that takes part has R <= Rmax and the bounds' derivation holds unchanged.  A sweep over tiles of 1024 rows samples
+ * the ground under every row once, boxes the FEET (X, Y, g) of the rows that take part and walks, in ascending order,
+ * the spans whose bounds meet that box; the tests in front of the segment loop use the row's own R2.  A finisher finds
+ * the lowest rows of the two extremes.  Culling skips only what the rule cannot accept: the outputs are the rule's,
+ * whatever is culled.  The tallies are integer atomics, the minimum an integer atomic on the bit pattern, the maximum
+ * one on the key: the same input gives the same bits on every run; nothing waits on another workgroup.
+ *
+ * 0 <= n < 2^31, 0 <= nspans <= 4096, 1 <= nsegments <= 128; the grid limits are terrain's (else PCH_ERR_ARG, as a null
+ * buffer that is needed and a host pointer).  All buffers device, except sub3_host and grid_host.  ws: the caller's, at
+ * least pch_treefall_ws_bytes(n, nspans, nsegments) bytes - pure host code, 0 for sizes out of range (smaller:
+ * PCH_ERR_WORKSPACE).  n == 0 or nspans == 0: every row gets +inf / -1 / class 0 and its height, the table is
+ * (0, 0, +inf, -1, NaN, -1) per span, and no launch reads a null pointer.  Enqueues on the caller's stream and returns;
+ * no host read. */
+#define PCH_TREEFALL_CLEAR  0
+#define PCH_TREEFALL_NEAR   1
+#define PCH_TREEFALL_STRIKE 2
+size_t pch_treefall_ws_bytes(int64_t n, int32_t nspans, int32_t nsegments);
+int pch_treefall_f32(const float* xyz, const uint8_t* skip, int64_t n, const float* sub3_host,
+                     const PchTerrainGrid* grid_host, const float* ground, const double* curves5 /* [K,5] */,
+                     const double* segs /* [K,S,5] */, int32_t nspans, int32_t nsegments, double h_min, double h_max,
+                     double grow, double limit, double* out_dist2, int32_t* out_span, float* out_height,
+                     uint8_t* out_class, int64_t* out_count, int64_t* out_strikes, double* out_min_dist2,
+                     int64_t* out_min_row, float* out_max_height, int64_t* out_max_row,
+                     int64_t* out_stats /* [4], may be NULL */, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ stage D1, fast mode
  * The reference boxes every cluster with trimesh (utils/tower_extraction.py:137-139:
  * trimesh.PointCloud(cluster_points).bounding_box_oriented): qhull's 3-D hull of the whole cluster, then a

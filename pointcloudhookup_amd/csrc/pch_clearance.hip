@@ -11,23 +11,13 @@
 //   finish  : one pass over dist2 and span - the lowest row that attains a span's smallest distance; the table
 // No inline assembly, no floating-point atomic, nothing waits on another workgroup; the same bits on every run.
 #include "pch_common.h"
+#include "pch_spancull.h"
 
 #include <math.h>
 
 namespace pch {
 
-constexpr int CL_THREADS = 256;
-constexpr int CL_ROUNDS  = 4;
-constexpr int CL_TILE    = CL_THREADS * CL_ROUNDS;          // 1024 rows per workgroup
-constexpr int CL_WAVES   = CL_THREADS / 64;
-constexpr int CL_MAXSPAN = 4096;
-constexpr int CL_MAXSEG  = 128;
-constexpr int CL_WORDS   = CL_MAXSPAN / 64;                 // words of the active-span bitmap
-
 struct ClRow { float x, y, z; };
-// what the sweep knows of a span beside the caller's records: cull bounds (world), along-track and height intervals
-// (span frame)
-struct ClSpan { double lo[3], hi[3], flo, fhi, wlo, whi; };
 
 // ---- the cull bounds.  The rule accepts row p for span k only if d2 = g + t*t <= r2, where g is the smallest of the
 // d = em*em + ew*ew over the segments.  Write x_j = m_j + q*dm_j and y_j = z_j + q*dz_j for the point of segment j the
@@ -107,17 +97,11 @@ __global__ __launch_bounds__(CL_THREADS) void cl_bounds_k(const double* __restri
     out[k] = s;
 }
 
-// next set bit of the tile's span bitmap at or behind (word, bits): wave-uniform (cb_next_box)
-__device__ __forceinline__ int cl_next_span(const uint64_t* active, int nwords, int& word, uint64_t& bits) {
-    while (bits == 0) {
-        if (++word >= nwords) return -1;
-        const uint64_t v = active[word];
-        bits = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) |
-               (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
-    }
-    const int t = word * 64 + (int)__builtin_ctzll(bits);
-    bits &= bits - 1;
-    return t;
+int cl_bounds_run(const double* curves5, const double* segs, int nspans, int nseg, double radius, ClSpan* out,
+                  uint32_t* take, hipStream_t s) {
+    PCH_LAUNCH("clearance_bounds", cl_bounds_k, dim3((unsigned)ceil_div(nspans, CL_THREADS)), dim3(CL_THREADS), 0, s,
+               curves5, segs, nspans, nseg, radius, out, take);
+    return PCH_OK;
 }
 
 // tally / viol / maxinv: per span, zeroed by the caller.  maxinv holds the largest ~bits(d2) seen, i.e. the complement
@@ -364,8 +348,7 @@ extern "C" int pch_clearance_f32(const float* xyz, const uint8_t* skip, int64_t 
     if (nspans == 0 && out_loops) PCH_HIP_TRY(hipMemsetAsync(out_loops, 0, 2 * sizeof(int64_t), s));
     if (nspans > 0) {
         PCH_HIP_TRY(hipMemsetAsync(out_min_row, 0xFF, sizeof(int64_t) * (size_t)nspans, s));
-        PCH_LAUNCH("clearance_bounds", cl_bounds_k, dim3((unsigned)ceil_div(nspans, CL_THREADS)), dim3(CL_THREADS), 0, s,
-                   curves5, segs, (int)nspans, (int)nsegments, radius, w.sp, w.take);
+        PCH_TRY(cl_bounds_run(curves5, segs, (int)nspans, (int)nsegments, radius, w.sp, w.take, s));
     }
     if (n > 0)
         PCH_LAUNCH("clearance_sweep", cl_sweep_k, dim3((unsigned)ceil_div(n, CL_TILE)), dim3(CL_THREADS), 0, s, xyz, skip,

@@ -1875,8 +1875,92 @@ def _span_ground_minima_of(X, Y, W, g, limit):
                 min_at=torch.where(found[:, None], xyz, nan), violation=minc <= limit)
 
 
+# ------------------------------------------------------------- tree fall, opt-in
+TREEFALL_TILE = 1024           # rows per workgroup of the tree-fall sweep (tf_sweep_k): the sizes tests straddle
+TREEFALL_CLEAR, TREEFALL_NEAR, TREEFALL_STRIKE = 0, 1, 2       # PCH_TREEFALL_* of include/pch_hip.h
+TREEFALL_OUTPUTS = ("dist2", "span", "height", "hazard", "count", "strikes", "min_dist2", "min_row", "max_height",
+                    "max_row")
+
+
+def check_treefall_rule(h_min, h_max, grow, limit):
+    """(h_min, h_max, grow, limit) as floats; ValueError unless all are finite with 0 <= h_min <= h_max, grow >= 0 and
+    limit >= 0"""
+    import math
+    h_min, h_max, grow, limit = float(h_min), float(h_max), float(grow), float(limit)
+    if not (all(math.isfinite(v) for v in (h_min, h_max, grow, limit)) and 0.0 <= h_min <= h_max and grow >= 0.0
+            and limit >= 0.0):
+        raise ValueError("h_min, h_max, grow and limit must be finite with 0 <= h_min <= h_max, grow >= 0 and "
+                         f"limit >= 0, got {h_min!r}, {h_max!r}, {grow!r}, {limit!r}")
+    return h_min, h_max, grow, limit
+
+
+def treefall(points, curves, segs, grid, ground, h_min, h_max, grow, limit, sub=None, skip=None, want_stats=False):
+    """Which rows reach a conductor if they fall towards the line (pch_treefall_f32; the rule is in include/pch_hip.h):
+    for every row of ``fl32(points - sub)`` (float32 [n,3]) its height ``H`` above the ground grid, and for the rows with
+    ``h_min <= H <= h_max`` the squared distance from the ground foot ``(x, y, ground)`` to the nearest span polyline
+    within the row's own ``R = (H + grow) + limit``.  A dict of device tensors - ``dist2`` float64 [n] (+inf if none),
+    ``span`` int32 [n] (-1 if none; the lowest index on a tie), ``height`` float32 [n] (``terrain_height``'s, bit for
+    bit), ``hazard`` uint8 [n] (0: clear, 1: within ``limit`` of a conductor after falling, 2: strikes) and over the K
+    spans ``count`` and ``strikes`` int64, ``min_dist2`` float64 (+inf without a row), ``min_row`` int64 (-1 without),
+    ``max_height`` float32 (NaN without) and ``max_row`` int64 (-1 without) - every row attributed to its nearest span
+    only.  ``curves`` float64 [K,5] or [K,10] and ``segs`` float64 [K,S,5] as ``clearance`` takes them; ``grid`` and
+    ``ground`` as ``terrain_height`` takes them; ``skip`` an optional uint8 or bool [n].  ``want_stats`` adds ``stats``
+    int64 [4]: the rows that took part, the rows without ground under them, the (row, span) segment loops run and the
+    (tile, span) pairs walked.  ValueError: a bound that is not finite or negative, h_min > h_max, more than 4096
+    spans, S outside 1..128.  The same input gives the same bits on every run.  Asynchronous."""
+    L = _lib.lib()
+    points = _need_cuda(points, torch.float32, "points").reshape(-1, 3)
+    curves = _need_cuda(curves, torch.float64, "curves")
+    segs = _need_cuda(segs, torch.float64, "segs")
+    if curves.dim() != 2 or curves.shape[1] not in (5, 10):
+        raise ValueError("curves must be [K,5] or [K,10]")
+    K = curves.shape[0]
+    if segs.dim() != 3 or segs.shape[0] != K or segs.shape[2] != 5:
+        raise ValueError("segs must be [K,S,5] for the K spans of curves")
+    S = check_segments(segs.shape[1])
+    if K > CLEARANCE_MAX_SPANS:
+        raise ValueError(f"treefall takes at most {CLEARANCE_MAX_SPANS} spans per call, got {K}")
+    h_min, h_max, grow, limit = check_treefall_rule(h_min, h_max, grow, limit)
+    g = _terrain_grid_c(grid)
+    ground = _terrain_cells(ground, torch.float32, "ground", g)
+    n, dev = points.shape[0], points.device
+    if n >= 1 << 31:
+        raise ValueError("treefall takes fewer than 2^31 rows per call")
+    if skip is not None:
+        if isinstance(skip, torch.Tensor) and skip.dtype == torch.bool:
+            skip = skip.view(torch.uint8)
+        skip = _need_cuda(skip, torch.uint8, "skip").reshape(-1)
+        if skip.numel() != n:
+            raise ValueError("skip must hold one entry per row")
+    s3 = _sub3(sub)
+    curves5 = curves[:, :5].contiguous()
+    with torch.cuda.device(dev):
+        dist2 = torch.empty((n,), dtype=torch.float64, device=dev)
+        span = torch.empty((n,), dtype=torch.int32, device=dev)
+        height = torch.empty((n,), dtype=torch.float32, device=dev)
+        hazard = torch.empty((n,), dtype=torch.uint8, device=dev)
+        count = torch.empty((K,), dtype=torch.int64, device=dev)
+        strikes = torch.empty((K,), dtype=torch.int64, device=dev)
+        min_dist2 = torch.empty((K,), dtype=torch.float64, device=dev)
+        min_row = torch.empty((K,), dtype=torch.int64, device=dev)
+        max_height = torch.empty((K,), dtype=torch.float32, device=dev)
+        max_row = torch.empty((K,), dtype=torch.int64, device=dev)
+        stats = torch.empty((4,), dtype=torch.int64, device=dev) if want_stats else None
+        ws = _workspace(L.pch_treefall_ws_bytes(n, K, S), dev)
+        _lib.check(L.pch_treefall_f32(_ptr(points), _ptr(skip), n, _sub3_ptr(s3), _grid_ptr(g), _ptr(ground),
+                                      _ptr(curves5), _ptr(segs), K, S, h_min, h_max, grow, limit, _ptr(dist2),
+                                      _ptr(span), _ptr(height), _ptr(hazard), _ptr(count), _ptr(strikes),
+                                      _ptr(min_dist2), _ptr(min_row), _ptr(max_height), _ptr(max_row), _ptr(stats),
+                                      _ptr(ws), ws.numel(), _stream()))
+    out = dict(dist2=dist2, span=span, height=height, hazard=hazard, count=count, strikes=strikes, min_dist2=min_dist2,
+               min_row=min_row, max_height=max_height, max_row=max_row)
+    if want_stats:
+        out["stats"] = stats
+    return out
+
+
 # ------------------------------------------------------------- tower profile, opt-in (DESIGN.md 5g)
-SLICES_BLOCK = 512             # entries of perm per wave of the slice sweep (sl_sweep_k): the sizes tests straddle
+SLICES_BLOCK = 512            # entries of perm per wave of the slice sweep (sl_sweep_k): the sizes tests straddle
 SLICES_MAX = 256               # PCH_SLICES_MAX: slices per table row
 SLICES_MAX_TABLES = 4096       # PCH_SLICES_MAX_TABLES
 SLICES_MAX_ENTRIES = 1 << 20   # PCH_SLICES_MAX_ENTRIES: table rows x slices

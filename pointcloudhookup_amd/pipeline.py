@@ -302,6 +302,103 @@ def span_ground_clearance(spans, terrain, segments=32, limit=7.0):
     return dict(pieces=idx, clearance=res["clearance"], ground=res["ground"], table=table)
 
 
+TREEFALL_TABLE_KEYS = ("count", "strikes", "min_distance", "min_row", "max_height", "max_row", "chord_error")
+TREEFALL_TREE_KEYS = ("row", "x", "y", "ground", "height", "span", "distance", "margin", "hazard")
+
+
+def danger_trees(points, spans, terrain, sub=None, h_min=2.0, h_max=45.0, grow=0.0, limit=3.0, segments=32, towers=None,
+                 cut_radius=9.0, cell=2.0):
+    """Which vegetation, standing where it stands, reaches a conductor if it falls towards the line:
+    for every row of ``points`` (float32 [n,3] on the device) its height ``H`` above the ground of ``terrain``
+    (``terrain_model``'s dict) and, for the rows with ``h_min <= H <= h_max``, the distance from the ground foot under
+    the row to the sag curves of the accepted pieces of ``spans`` (``conductor_spans``' dict for the same ``points``),
+    held against ``H + grow`` - ``grow`` being the growth allowed for until the next inspection.  ``points``, ``spans``
+    and ``terrain`` are in one frame, as in ``conductor_clearance`` and ``span_ground_clearance``; with ``sub`` the rows
+    are ``fl32(points - sub)``, as in ``height_above_ground``, and ``towers`` are in that frame too.  Each accepted piece
+    becomes ``conductor_clearance``'s polyline of ``segments`` segments; the rows that are the conductors and, with
+    ``towers``, the rows within ``cut_radius`` of a tower are skipped with ``conductor_clearance``'s own predicate;
+    ``ops.treefall`` does the rest.  Every row is attributed to its nearest piece only.
+
+    Returns dict: ``dist2`` (float64 [n]: the squared distance from the row's foot to the nearest accepted piece within
+    ``(H + grow) + limit``, +inf if none), ``span`` (int32 [n]: that piece's id in the span table, -1 if none),
+    ``height`` (float32 [n]: ``height_above_ground``'s), ``hazard`` (uint8 [n]: 0 clear, 1 within ``limit`` of a
+    conductor after falling, 2 strikes), ``table``, a dict over the K pieces of the span table (TREEFALL_TABLE_KEYS):
+    ``count`` and ``strikes`` (int64), ``min_distance`` (metres; +inf without a row), ``min_row`` (-1 without),
+    ``max_height`` (float32, NaN without), ``max_row`` (-1 without) and ``chord_error`` (metres: the polyline lies above
+    a hanging wire, so distances from below are over-estimated by at most that; NaN for a piece that was not accepted) -
+    and ``trees``, a list of dicts (TREEFALL_TREE_KEYS): the hazard rows (class >= 1) are binned into xy cells of
+    ``cell`` metres (``floor(x / cell)``, ``floor(y / cell)`` in the rows' frame) and per occupied cell the tallest
+    hazard row is reported, ties to the lowest row index, ordered by (span, row): ``row``, ``x``, ``y``, ``ground``,
+    ``height``, ``span``, ``distance``, ``margin = distance - (height + grow)`` and ``hazard``.  No accepted piece:
+    every row +inf / -1 / 0, an empty ``trees``; nothing is raised.  Synchronises."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32:
+        raise TypeError("points must be a float32 CUDA/HIP tensor (no CPU fallback in the product path)")
+    points = points.reshape(-1, 3).contiguous()
+    n, dev = int(points.shape[0]), points.device
+    wire = spans["wire"]
+    if wire.numel() != n:
+        raise ValueError("spans must be conductor_spans' result for the same points")
+    segments = ops.check_segments(segments)
+    h_min, h_max, grow, limit = ops.check_treefall_rule(h_min, h_max, grow, limit)
+    cell = float(cell)
+    if not (np.isfinite(cell) and cell > 0.0):
+        raise ValueError(f"cell must be finite and > 0, got {cell!r}")
+    K = int(spans["nclusters"])
+    idx = torch.nonzero(spans["accepted"]).reshape(-1)                        # accepted pieces, ascending
+    curves = ops.span_curves(spans["table"], spans["frames"], spans["ext"])[idx].contiguous()
+    segs, chord = ops.span_segments(curves, segments)
+    s3 = ops._sub3(sub)
+    framed = points if s3 is None else points - torch.tensor(list(s3), dtype=torch.float32, device=dev)
+    near = _near_towers(framed, towers, cut_radius)
+    skip = wire if near is None else (wire | near)
+    res = ops.treefall(points, curves, segs, terrain["grid"], terrain["ground"], h_min, h_max, grow, limit, sub=sub,
+                       skip=skip)
+    span = res["span"]                                                        # (all -1 without an accepted piece)
+    if idx.numel():
+        span = torch.where(span >= 0, idx.to(torch.int32)[span.clamp(min=0).long()], torch.full_like(span, -1))
+    nan64 = float("nan")
+    table = dict(count=torch.zeros((K,), dtype=torch.int64, device=dev),
+                 strikes=torch.zeros((K,), dtype=torch.int64, device=dev),
+                 min_distance=torch.full((K,), float("inf"), dtype=torch.float64, device=dev),
+                 min_row=torch.full((K,), -1, dtype=torch.int64, device=dev),
+                 max_height=torch.full((K,), nan64, dtype=torch.float32, device=dev),
+                 max_row=torch.full((K,), -1, dtype=torch.int64, device=dev),
+                 chord_error=torch.full((K,), nan64, dtype=torch.float64, device=dev))
+    for key in ("count", "strikes", "min_row", "max_height", "max_row"):
+        table[key][idx] = res[key]
+    table["min_distance"][idx], table["chord_error"][idx] = torch.sqrt(res["min_dist2"]), chord
+    # the hazard rows are few: compacted on the device, the records made on the host
+    rows = torch.nonzero(res["hazard"] >= ops.TREEFALL_NEAR).reshape(-1)
+    at = framed[rows]
+    under = ops.terrain_sample(at[:, :2].to(torch.float64), terrain["grid"], terrain["ground"])
+    trees = _tree_records(rows.cpu().numpy(), at.cpu().numpy(), under.cpu().numpy(), res["height"][rows].cpu().numpy(),
+                          span[rows].cpu().numpy(), res["dist2"][rows].cpu().numpy(), res["hazard"][rows].cpu().numpy(),
+                          cell, grow)
+    return dict(dist2=res["dist2"], span=span, height=res["height"], hazard=res["hazard"], table=table, trees=trees)
+
+
+def _tree_records(rows, xyz, under, height, span, dist2, hazard, cell, grow):
+    """danger_trees' records from the compacted hazard rows (numpy, ascending row index; ``under``: the ground under
+    each): per occupied xy cell the tallest row, ties to the lowest row index; ordered by (span, row)."""
+    if not len(rows):
+        return []
+    fx = np.floor(xyz[:, 0].astype(np.float64) / cell).astype(np.int64)
+    fy = np.floor(xyz[:, 1].astype(np.float64) / cell).astype(np.int64)
+    # by (cell, tallest first, lowest row first): the first of every cell's run is its record
+    order = np.lexsort((rows, -height.astype(np.float64), fy, fx))
+    first = np.ones(len(order), dtype=bool)
+    first[1:] = (fx[order][1:] != fx[order][:-1]) | (fy[order][1:] != fy[order][:-1])
+    pick = order[first]
+    pick = pick[np.lexsort((rows[pick], span[pick]))]
+    distance = np.sqrt(dist2[pick])
+    h = height[pick].astype(np.float64)
+    ground = under[pick]
+    margin = distance - (h + float(grow))
+    return [dict(row=int(rows[p]), x=float(xyz[p, 0]), y=float(xyz[p, 1]), ground=float(ground[j]), height=float(h[j]),
+                 span=int(span[p]), distance=float(distance[j]), margin=float(margin[j]), hazard=int(hazard[p]))
+            for j, p in enumerate(pick)]
+
+
 TOWER_PROFILE_TABLE_KEYS = ("ground", "ground_from", "top", "tower_height", "nominal_height", "n_levels", "z_low",
                             "z_high", "width", "rows", "lowest_wire")
 TOWER_PROFILE_MAX_LEVELS = 8

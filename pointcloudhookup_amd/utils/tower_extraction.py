@@ -80,6 +80,15 @@ gets one line per accepted wire piece: its length, the smallest height of its sa
 is in world coordinates, the ground's z there, the vertices over ground, the chord error and whether the height is at
 most ``limit`` metres (default 7).  It logs one extra line; a failure is handled like one of ``SPANS``.  The returned
 tower dicts are the same with and without it.
+``TREEFALL`` (env PCH_TREEFALL="h_min,limit[,grow[,h_max]]", e.g. "2,3" or "2,3,1.5,45"; unset or empty = off; needs
+``SPANS`` and ``TERRAIN`` - importing the module with PCH_TREEFALL set and either unset, or with PCH_FRAME=las, raises
+ValueError): behind the ground-clearance table, every row the ground rule kept whose height above the terrain grid lies
+in [``h_min``, ``h_max``] is held against the accepted pieces' sag curves - the distance from the ground under the row
+to the curve against the row's height plus ``grow`` (pipeline.danger_trees, with ``CLEARANCE``'s ``segments`` when that
+knob is on) - and ``output_towers/tree_fall_info.csv`` gets one line per danger tree: the tallest
+row of every 2 m cell that strikes a conductor when it falls or comes within ``limit`` metres of one, in world
+coordinates, with its height, piece, distance and margin.  It logs one extra line; a failure is handled like one of
+``SPANS``.  The returned tower dicts are the same with and without it.
 ``TOWER_PROFILE`` (env PCH_TOWER_PROFILE="dz[,height[,arm_window,arm_excess]]", e.g. "0.5"; unset or empty = off; needs
 no other knob): behind the tower table, the accepted towers' clusters are cut into height slices of ``dz`` metres over
 ``height`` metres (default 64; at most 256 slices) and their cross-arm levels are read off the slice widths
@@ -253,6 +262,42 @@ def terrain_from_env(value, spans=True, frame="reference"):
 TERRAIN_MAX_WINDOW_CELLS = 64                        # PCH_TERRAIN_MAX_WINDOW of include/pch_hip.h
 TERRAIN = terrain_from_env(os.environ.get("PCH_TERRAIN"), spans=SPANS is not None, frame=FRAME)
 TERRAIN_COLUMNS = ("ID", "length", "min_clearance", "x", "y", "z", "ground_z", "covered", "chord_error", "violation")
+
+
+def treefall_from_env(value, spans=True, terrain=True, frame="reference"):
+    """TREEFALL of an environment value: None (off) when unset or empty, else dict(h_min, limit, grow, h_max) from
+    "h_min,limit[,grow[,h_max]]" - two to four numbers, all finite; 0 <= h_min <= h_max (default 45), limit >= 0,
+    grow >= 0 (default 0).  ``spans`` / ``terrain``: whether SPANS and TERRAIN are on - the distance is measured from the
+    terrain grid's ground to the span table's pieces; ``frame``: FRAME - the terrain grid is not defined for the
+    LAS-integer frame.  A value without the first two or with the last is refused (ValueError)"""
+    if value is None or not value.strip():
+        return None
+    parts = [t.strip() for t in value.split(",")]
+    if len(parts) not in (2, 3, 4):
+        raise ValueError(f"PCH_TREEFALL takes \"h_min,limit[,grow[,h_max]]\", got {value!r}")
+    h_min, limit = float(parts[0]), float(parts[1])
+    grow = float(parts[2]) if len(parts) >= 3 else 0.0
+    h_max = float(parts[3]) if len(parts) == 4 else 45.0
+    if not (np.isfinite(h_min) and h_min >= 0.0):
+        raise ValueError(f"PCH_TREEFALL: h_min must be finite and >= 0, got {parts[0]!r}")
+    if not (np.isfinite(limit) and limit >= 0.0):
+        raise ValueError(f"PCH_TREEFALL: limit must be finite and >= 0, got {parts[1]!r}")
+    if not (np.isfinite(grow) and grow >= 0.0):
+        raise ValueError(f"PCH_TREEFALL: grow must be finite and >= 0, got {parts[2]!r}")
+    if not (np.isfinite(h_max) and h_max >= h_min):
+        raise ValueError(f"PCH_TREEFALL: h_max must be finite and >= h_min, got {h_max!r}")
+    if not spans:
+        raise ValueError("PCH_TREEFALL needs PCH_SPANS: the distance is measured to the span table's pieces")
+    if frame == "las":
+        raise ValueError("PCH_TREEFALL is not defined for PCH_FRAME=las: the terrain grid is built from the float32 rows")
+    if not terrain:
+        raise ValueError("PCH_TREEFALL needs PCH_TERRAIN: a row's height and its foot come from the terrain grid")
+    return dict(h_min=h_min, limit=limit, grow=grow, h_max=h_max)
+
+
+TREEFALL = treefall_from_env(os.environ.get("PCH_TREEFALL"), spans=SPANS is not None, terrain=TERRAIN is not None,
+                             frame=FRAME)
+TREEFALL_COLUMNS = ("ID", "row", "x", "y", "ground_z", "height", "span", "distance", "margin", "hazard")
 
 
 def tower_profile_from_env(value):
@@ -573,6 +618,19 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
             except (ValueError, RuntimeError) as e:
                 log(f"⚠️ 导线对地净空计算失败: {str(e)}")
                 return tower_obbs
+        # ---- opt-in: which vegetation reaches those conductors if it falls
+        if TREEFALL:
+            try:
+                fall = pipeline.danger_trees(stage_b_points, spans, terrain, towers=local,
+                                             cut_radius=SPANS["cut_radius"],
+                                             segments=CLEARANCE["segments"] if CLEARANCE else 32, **TREEFALL)
+                rows = treefall_rows(fall, cen)
+                write_treefall_csv(output_dir / "tree_fall_info.csv", rows)
+                clock.mark("tree fall")
+                log(treefall_line(fall, rows, TREEFALL))
+            except (ValueError, RuntimeError) as e:
+                log(f"⚠️ 倒树隐患计算失败: {str(e)}")
+                return tower_obbs
     # ---- opt-in: the accepted towers' slice tables, cross-arm levels and nominal height
     if TOWER_PROFILE and tower_rows:
         try:
@@ -730,6 +788,36 @@ def ground_clearance_line(terrain, rows, knob):
     return (f"⛰️ 导线对地净空: 网格 {knob['cell']:g} m（{g['nx']}×{g['ny']}），开窗 {knob['window']:g} m，高差 {knob['dh']:g} m，"
             f"限距 {knob['limit']:g} m；地面格 {terrain['n_ground']}，填补 {terrain['n_filled']}，无值 {terrain['n_unfilled']}；"
             f"越限线段 {int(breached)}/{len(rows)}，最小对地净空 {lowest:.3f} m")
+
+
+def treefall_rows(fall, centroid):
+    """the lines of tree_fall_info.csv for a result of pipeline.danger_trees: one list per ``trees`` record in
+    TREEFALL_COLUMNS' order, the position and the ground under it moved to world coordinates by ``centroid`` (3
+    float64)"""
+    return [[f"tree_{j}", int(t["row"]), t["x"] + float(centroid[0]), t["y"] + float(centroid[1]),
+             t["ground"] + float(centroid[2]), t["height"], f"span_{int(t['span'])}", t["distance"], t["margin"],
+             int(t["hazard"])] for j, t in enumerate(fall["trees"])]
+
+
+def write_treefall_csv(path, rows):
+    """tree_fall_info.csv: a header line (TREEFALL_COLUMNS) and one line per record, floats with repr's digits"""
+    import csv
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.writer(f)
+        w.writerow(TREEFALL_COLUMNS)
+        for r in rows:
+            w.writerow([repr(float(v)) if isinstance(v, (float, np.floating)) else v for v in r])
+
+
+def treefall_line(fall, rows, knob):
+    """the extra log line of TREEFALL for a result of pipeline.danger_trees and its csv lines"""
+    hazard = fall["hazard"]
+    strikes = sum(1 for r in rows if r[9] == 2)
+    pieces = len({r[6] for r in rows})
+    tightest = min([r[8] for r in rows], default=float("inf"))
+    return (f"🌲 倒树隐患: 树高 {knob['h_min']:g}–{knob['h_max']:g} m，生长量 {knob['grow']:g} m，限距 {knob['limit']:g} m；"
+            f"隐患点 {int((hazard >= 1).sum())}（可触线 {int((hazard == 2).sum())}），隐患树 {len(rows)} 处（可触线 {strikes}），"
+            f"涉及线段 {pieces}，最小裕度 {tightest:.3f} m")
 
 
 def tower_profile_rows(profile, ids, centroid):
