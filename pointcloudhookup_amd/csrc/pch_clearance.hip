@@ -3,11 +3,13 @@
 // rule is spelled out in include/pch_hip.h; every output is the rule's, bit for bit, whatever is culled here.
 //   bounds  : one thread per span - the "takes part" flag (all 5 + 5 S values finite), the cull bounds of the polyline
 //             and the along-track and height intervals outside which no row can lie within the radius
-//   sweep   : tiles of 1024 rows (cb_sweep_k's structure): the tile's bounding box over its finite rows that are not
-//             skipped, a bitmap of the spans whose bounds meet it, the spans walked wave-uniformly in ascending order
-//             with the segment records through wave-uniform (scalar) loads; dist2 and span for every row of the tile,
-//             count and violations tallied per span in LDS and added once per (tile, span), the smallest distance folded
-//             with a 64-bit integer atomic on the bit pattern
+//   sweep   : tiles of 1024 rows.  Its own: the loads, the lane's box over its finite rows that are not skipped; dist2
+//             and span for every row of the tile; per owning span the count and the violations tallied in LDS and the
+//             smallest distance folded with a 64-bit integer atomic on cl_minkey.  Shared (pch_spancull.h,
+//             pch_tilecull.h): the tile's box and the bitmap of the spans whose bounds meet it (cl_tile_spans), the
+//             spans walked wave-uniformly in ascending order with the segment records through scalar loads
+//             (cl_walk_spans), the loop over a round's owning spans (cl_fold_owners), the tallies added once per
+//             (tile, span) (cl_flush_hist)
 //   finish  : one pass over dist2 and span - the lowest row that attains a span's smallest distance; the table
 // No inline assembly, no floating-point atomic, nothing waits on another workgroup; the same bits on every run.
 #include "pch_common.h"
@@ -104,9 +106,8 @@ int cl_bounds_run(const double* curves5, const double* segs, int nspans, int nse
     return PCH_OK;
 }
 
-// tally / viol / maxinv: per span, zeroed by the caller.  maxinv holds the largest ~bits(d2) seen, i.e. the complement
-// of the smallest bit pattern (non-negative doubles order as integers): zero = no row yet.  loops (2 words): the
-// (row, span) segment loops run and the (tile, span) pairs walked - what the probe reports.
+// tally / viol / maxinv: ClWs's tally / second / maxinv, zeroed by the caller.  loops (2 words): the (row, span) segment
+// loops run and the (tile, span) pairs walked - what the probe reports.
 __global__ __launch_bounds__(CL_THREADS) void cl_sweep_k(const float* __restrict__ xyz, const uint8_t* __restrict__ skip,
                                                          int64_t n, const double* __restrict__ curves5,
                                                          const double* __restrict__ segs, int nspans, int nseg,
@@ -121,10 +122,10 @@ __global__ __launch_bounds__(CL_THREADS) void cl_sweep_k(const float* __restrict
     __shared__ uint32_t hist[CL_MAXSPAN];                // count in the low half, violations in the high half
     __shared__ double wlo[CL_WAVES][3], whi[CL_WAVES][3];
     const int w = wave_id(), l = lane_id();
-    const int nwords = (nspans + 63) >> 6;
     const int64_t base = (int64_t)blockIdx.x * CL_TILE + (int64_t)w * (64 * CL_ROUNDS);
     const ClRow* __restrict__ rows = reinterpret_cast<const ClRow*>(xyz);
-    // every load of the tile is issued before anything is waited for; none stands under a condition
+    // every load of the tile is issued before anything is waited for, and none stands under a condition: a load behind
+    // a branch is waited for on the spot, one after the other
     ClRow q[CL_ROUNDS];
     uint8_t sk[CL_ROUNDS];
 #pragma unroll
@@ -151,120 +152,34 @@ __global__ __launch_bounds__(CL_THREADS) void cl_sweep_k(const float* __restrict
             lo[2] = fmin(lo[2], (double)q[r].z); hi[2] = fmax(hi[2], (double)q[r].z);
         }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = wave_reduce_min(lo[a]);
-        hi[a] = wave_reduce_max(hi[a]);
-        if (l == 0) { wlo[w][a] = lo[a]; whi[w][a] = hi[a]; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int w2 = 0; w2 < CL_WAVES; ++w2) { lo[a] = fmin(lo[a], wlo[w2][a]); hi[a] = fmax(hi[a], whi[w2][a]); }
-    // the spans this tile has to walk, as a bitmap in span order: those that take part and whose bounds are not all
-    // finite or meet the tile's box
-    for (int c = w; c < nwords; c += CL_WAVES) {
-        const int t = c * 64 + l;
-        bool on = false;
-        if (t < nspans && take[t]) {
-            const ClSpan& b = sp[t];
-            bool finite = true, meets = true;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                finite = finite && isfinite(b.lo[a]) && isfinite(b.hi[a]);
-                meets = meets && lo[a] <= b.hi[a] && hi[a] >= b.lo[a];
-            }
-            on = !finite || meets;
-        }
-        const uint64_t m = __ballot(on);
-        if (l == 0) active[c] = m;
-    }
-    __syncthreads();
+    cl_tile_spans(active, nspans, sp, take, lo, hi, wlo, whi);
 
     double best[CL_ROUNDS];
     int who[CL_ROUNDS];
-#pragma unroll
-    for (int r = 0; r < CL_ROUNDS; ++r) { best[r] = INFINITY; who[r] = -1; }
-    uint32_t ran = 0, walked = 0;
-    int word = -1;
-    uint64_t bits = 0;
-    for (int k = cl_next_span(active, nwords, word, bits); k >= 0; k = cl_next_span(active, nwords, word, bits)) {
-        const double* __restrict__ c = curves5 + 5 * (size_t)k;
-        const double cx = c[0], cy = c[1], cz = c[2], ux = c[3], uy = c[4];
-        const double flo = sp[k].flo, fhi = sp[k].fhi, hlo = sp[k].wlo, hhi = sp[k].whi;
-        double m[CL_ROUNDS], h[CL_ROUNDS], tt[CL_ROUNDS], g[CL_ROUNDS];
-        bool go[CL_ROUNDS];
-        bool some = false;
-#pragma unroll
-        for (int r = 0; r < CL_ROUNDS; ++r) {
-            const double dx = (double)q[r].x - cx, dy = (double)q[r].y - cy;
-            h[r] = (double)q[r].z - cz;
-            m[r] = (dx * ux) + (dy * uy);
-            const double t = (dy * ux) - (dx * uy);
-            tt[r] = t * t;
-            // d2 = g + t*t >= t*t (g >= 0), so a row with t*t > r2 or t*t >= best cannot be taken; nor can one with m
-            // outside [flo, fhi] or w outside [wlo, whi] (the derivation above).  A NaN fails every comparison, as it
-            // does in the rule.
-            go[r] = ok[r] && tt[r] <= r2 && tt[r] < best[r] && m[r] >= flo && m[r] <= fhi && h[r] >= hlo && h[r] <= hhi;
-            g[r] = INFINITY;
-            some = some || go[r];
-        }
-        ++walked;
-        const uint64_t any = __ballot(some);
-        if (any == 0) continue;                          // (wave-uniform)
-#pragma unroll
-        for (int r = 0; r < CL_ROUNDS; ++r) ran += (uint32_t)__popcll(__ballot(go[r]));
-        const double* __restrict__ sg = segs + 5 * (size_t)k * nseg;
-        for (int j = 0; j < nseg; ++j) {
-            const double mj = sg[5 * j], zj = sg[5 * j + 1], dm = sg[5 * j + 2], dz = sg[5 * j + 3], inv = sg[5 * j + 4];
-#pragma unroll
-            for (int r = 0; r < CL_ROUNDS; ++r) {
-                const double rm = m[r] - mj, rw = h[r] - zj;
-                double qq = ((rm * dm) + (rw * dz)) * inv;
-                if (qq < 0.0) qq = 0.0;
-                if (qq > 1.0) qq = 1.0;
-                const double em = rm - (qq * dm), ew = rw - (qq * dz);
-                const double d = (em * em) + (ew * ew);
-                if (d < g[r]) g[r] = d;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < CL_ROUNDS; ++r) {
-            const double d2 = g[r] + tt[r];
-            if (go[r] && d2 <= r2 && d2 < best[r]) { best[r] = d2; who[r] = k; }
-        }
-    }
+    uint32_t ran, walked;
+    cl_walk_spans(active, nspans, curves5, segs, nseg, sp, q, ok, [&](int r) { return (double)q[r].z; },
+                  [&](int) { return r2; }, best, who, ran, walked);
 
     // dist2 and span for every row of the tile; per span of a wave's round one LDS add and one fold of the smallest
 #pragma unroll
     for (int r = 0; r < CL_ROUNDS; ++r) {
         const int64_t i = base + r * 64 + l;
         if (i < n) { out_dist2[i] = best[r]; out_span[i] = who[r]; }
-        uint64_t pend = __ballot(who[r] >= 0);
-        while (pend) {
-            const int k = __builtin_amdgcn_readlane(who[r], (int)__builtin_ctzll(pend));
-            const bool same = who[r] == k;
-            const uint64_t mask = __ballot(same);
+        cl_fold_owners(who[r], [&](int k, bool same, uint32_t owned) {
             const uint32_t nv = (uint32_t)__popcll(__ballot(same && best[r] <= l2));
             const double v = wave_reduce_min(same ? best[r] : (double)INFINITY);
             if (l == 0) {
-                atomicAdd(&hist[k], (uint32_t)__popcll(mask) + (nv << 16));
-                atomicMax(&maxinv[k], ~(unsigned long long)__double_as_longlong(v));
+                atomicAdd(&hist[k], owned + (nv << 16));
+                atomicMax(&maxinv[k], cl_minkey(v));
             }
-            pend &= ~mask;
-        }
+        });
     }
     if (loops && l == 0 && (ran || walked)) {
         if (ran) atomicAdd(&loops[0], (unsigned long long)ran);
         if (w == 0) atomicAdd(&loops[1], (unsigned long long)walked);
     }
     __syncthreads();
-    for (int j = threadIdx.x; j < nspans; j += CL_THREADS) {
-        const uint32_t hv = hist[j];
-        if (hv & 0xFFFFu) atomicAdd(&tally[j], (unsigned long long)(hv & 0xFFFFu));
-        if (hv >> 16) atomicAdd(&viol[j], (unsigned long long)(hv >> 16));
-    }
+    cl_flush_hist(hist, nspans, tally, viol);
 }
 
 // the table, and the lowest row that attains a span's smallest distance (out_min_row arrives as all ones = -1)
@@ -283,33 +198,21 @@ __global__ __launch_bounds__(CL_THREADS) void cl_finish_k(const double* __restri
     if (i < nspans) {
         out_count[i] = (int64_t)tally[i];
         out_violations[i] = (int64_t)viol[i];
-        const unsigned long long v = maxinv[i];
-        out_min_dist2[i] = v ? __longlong_as_double((long long)~v) : (double)INFINITY;
+        out_min_dist2[i] = cl_minkey_value(maxinv[i]);
     }
     if (out_loops && i < 2) out_loops[i] = (int64_t)loops[i];
     if (i >= n) return;
     const int32_t k = span[i];
     if (k < 0 || k >= nspans) return;
-    if (~(unsigned long long)__double_as_longlong(dist2[i]) == maxinv[k]) atomicMin(&out_min_row[k], (unsigned long long)i);
+    if (cl_minkey(dist2[i]) == maxinv[k]) atomicMin(&out_min_row[k], (unsigned long long)i);
 }
 
-struct ClWs {
-    unsigned long long *tally, *viol, *maxinv, *loops;
-    ClSpan* sp;
-    uint32_t* take;
-};
 static void cl_plan(Arena& a, int32_t nspans, ClWs& w) {
-    const size_t K = nspans > 0 ? (size_t)nspans : 1;
-    // the tallies in front: one fill zeroes them
-    w.tally = a.take<unsigned long long>(K);
-    w.viol = a.take<unsigned long long>(K);
-    w.maxinv = a.take<unsigned long long>(K);
-    w.loops = a.take<unsigned long long>(2);
-    w.sp = a.take<ClSpan>(K);
-    w.take = a.take<uint32_t>(K);
+    cl_plan_front(a, nspans, 2, w);
+    cl_plan_back(a, nspans, w);
 }
 static bool cl_sizes_ok(int64_t n, int32_t nspans, int32_t nseg) {
-    return n >= 0 && n < (int64_t(1) << 32) && nspans >= 0 && nspans <= CL_MAXSPAN && nseg >= 1 && nseg <= CL_MAXSEG;
+    return n >= 0 && n < (int64_t(1) << 32) && cl_spans_ok(nspans, nseg);
 }
 
 }  // namespace pch
@@ -344,7 +247,7 @@ extern "C" int pch_clearance_f32(const float* xyz, const uint8_t* skip, int64_t 
     if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
     if (n == 0 && nspans == 0) return PCH_OK;
     const double r2 = radius * radius, l2 = limit * limit;
-    PCH_HIP_TRY(hipMemsetAsync(ws, 0, (size_t)(reinterpret_cast<char*>(w.sp) - static_cast<char*>(ws)), s));
+    PCH_HIP_TRY(hipMemsetAsync(ws, 0, cl_front_bytes(ws, w), s));
     if (nspans == 0 && out_loops) PCH_HIP_TRY(hipMemsetAsync(out_loops, 0, 2 * sizeof(int64_t), s));
     if (nspans > 0) {
         PCH_HIP_TRY(hipMemsetAsync(out_min_row, 0xFF, sizeof(int64_t) * (size_t)nspans, s));
@@ -353,13 +256,13 @@ extern "C" int pch_clearance_f32(const float* xyz, const uint8_t* skip, int64_t 
     if (n > 0)
         PCH_LAUNCH("clearance_sweep", cl_sweep_k, dim3((unsigned)ceil_div(n, CL_TILE)), dim3(CL_THREADS), 0, s, xyz, skip,
                    n, curves5, segs, (int)nspans, (int)nsegments, (const ClSpan*)w.sp, (const uint32_t*)w.take, r2, l2,
-                   out_dist2, out_span, w.tally, w.viol, w.maxinv, w.loops);
+                   out_dist2, out_span, w.tally, w.second, w.maxinv, w.counters);
     const int64_t most = n > nspans ? n : (int64_t)nspans;
     if (nspans > 0)
         PCH_LAUNCH("clearance_finish", cl_finish_k, dim3((unsigned)ceil_div(most, CL_THREADS)), dim3(CL_THREADS), 0, s,
                    (const double*)out_dist2, (const int32_t*)out_span, n, (int)nspans,
-                   (const unsigned long long*)w.tally, (const unsigned long long*)w.viol,
-                   (const unsigned long long*)w.maxinv, (const unsigned long long*)w.loops, out_count, out_violations,
-                   out_min_dist2, reinterpret_cast<unsigned long long*>(out_min_row), out_loops);
+                   (const unsigned long long*)w.tally, (const unsigned long long*)w.second,
+                   (const unsigned long long*)w.maxinv, (const unsigned long long*)w.counters, out_count,
+                   out_violations, out_min_dist2, reinterpret_cast<unsigned long long*>(out_min_row), out_loops);
     return PCH_OK;
 }

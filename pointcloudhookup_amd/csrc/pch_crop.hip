@@ -1,8 +1,9 @@
 // Crop of a cloud by MANY boxes in one sweep (axis-aligned and oriented): what the viewer does per tower with one
 // boolean mask over the whole cloud (test/kuangxuan.py:60-79, the scaled oriented boxes of ui/extract.py:345-420).
 //   sweep   : tiles of 2048 rows by ticket, every row tested against the boxes whose cull bounds meet the tile's own
-//             bounding box; the hits leave as (box, row) pairs in (row, box) order (one look-back per tile, as
-//             crop_aabb_k), the tile adds its hits per box to the box's count
+//             bounding box (the box, the bitmap of those boxes and its walk: pch_tilecull.h); the hits leave as
+//             (box, row) pairs in (row, box) order (one look-back per tile, as crop_aabb_k), the tile adds its hits
+//             per box to the box's count
 //   offsets : exclusive scan of the per-box counts, the total
 //   group   : stable radix sort of the pairs by box (pch_prims.h) - rows stay ascending inside a box
 //   gather  : the points (and rows) of the grouped pairs
@@ -12,6 +13,7 @@
 
 #include "pch_lookback.h"
 #include "pch_prims.h"
+#include "pch_tilecull.h"
 
 namespace pch {
 
@@ -84,20 +86,6 @@ __device__ __forceinline__ bool cb_inside(const CbRow& q, const PchCropBox& b) {
            u2 <= b.half[2];
 }
 
-// next set bit of the tile's box bitmap at or behind (word, bits): wave-uniform, so that the box record behind it
-// comes through scalar loads.  bits = what is left of word `word`; returns the box id or -1.
-__device__ __forceinline__ int cb_next_box(const uint64_t* active, int nwords, int& word, uint64_t& bits) {
-    while (bits == 0) {
-        if (++word >= nwords) return -1;
-        const uint64_t v = active[word];
-        bits = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) |
-               (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
-    }
-    const int t = word * 64 + (int)__builtin_ctzll(bits);
-    bits &= bits - 1;
-    return t;
-}
-
 __global__ __launch_bounds__(CB_THREADS) void cb_sweep_k(const double* __restrict__ xyz, int64_t n,
                                                          const CbBox* __restrict__ boxes, int nboxes,
                                                          CbState* __restrict__ st, uint64_t* __restrict__ status,
@@ -134,36 +122,13 @@ __global__ __launch_bounds__(CB_THREADS) void cb_sweep_k(const double* __restric
             lo[2] = fmin(lo[2], q[r].z); hi[2] = fmax(hi[2], q[r].z);
         }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = wave_reduce_min(lo[a]);
-        hi[a] = wave_reduce_max(hi[a]);
-        if (l == 0) { wlo[w][a] = lo[a]; whi[w][a] = hi[a]; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int w2 = 0; w2 < CB_WAVES; ++w2) { lo[a] = fmin(lo[a], wlo[w2][a]); hi[a] = fmax(hi[a], whi[w2][a]); }
-    // the boxes this tile has to test, as a bitmap in box order: every box whose cull bounds are not all finite,
-    // and every other one whose cull bounds meet the tile's box
-    for (int c = w; c < nwords; c += CB_WAVES) {
-        const int t = c * 64 + l;
-        bool on = false;
-        if (t < nboxes) {
-            const double* cb = boxes[t].cull;
-            bool finite = true, meets = true;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                finite = finite && isfinite(cb[a]) && isfinite(cb[3 + a]);
-                meets = meets && lo[a] <= cb[3 + a] && hi[a] >= cb[a];
-            }
-            on = !finite || meets;
-        }
-        const uint64_t m = __ballot(on);
-        if (l == 0) active[c] = m;
-    }
-    __syncthreads();
+    // the boxes this tile has to test: every box takes part
+    cull_tile_box(lo, hi, wlo, whi);
+    cull_tile_bitmap<CB_WAVES>(active, nboxes, lo, hi, [&](int t, const double*& blo, const double*& bhi) {
+        blo = boxes[t].cull;
+        bhi = boxes[t].cull + 3;
+        return true;
+    });
     // first pass: hits per row and round, hits per box
     uint32_t cnt[CB_ROUNDS];
 #pragma unroll
@@ -172,7 +137,7 @@ __global__ __launch_bounds__(CB_THREADS) void cb_sweep_k(const double* __restric
     {
         int word = -1;
         uint64_t bits = 0;
-        for (int t = cb_next_box(active, nwords, word, bits); t >= 0; t = cb_next_box(active, nwords, word, bits)) {
+        for (int t = cull_next_bit(active, nwords, word, bits); t >= 0; t = cull_next_bit(active, nwords, word, bits)) {
             const PchCropBox& b = boxes[t].b;
             uint32_t got = 0;
 #pragma unroll
@@ -218,7 +183,7 @@ __global__ __launch_bounds__(CB_THREADS) void cb_sweep_k(const double* __restric
     }
     int word = -1;
     uint64_t bits = 0;
-    for (int t = cb_next_box(active, nwords, word, bits); t >= 0; t = cb_next_box(active, nwords, word, bits)) {
+    for (int t = cull_next_bit(active, nwords, word, bits); t >= 0; t = cull_next_bit(active, nwords, word, bits)) {
         if (__builtin_amdgcn_readfirstlane((int)hist[t]) == 0) continue;
         const PchCropBox& b = boxes[t].b;
 #pragma unroll
