@@ -958,6 +958,77 @@ int pch_treefall_f32(const float* xyz, const uint8_t* skip, int64_t n, const flo
                      int64_t* out_min_row, float* out_max_height, int64_t* out_max_row,
                      int64_t* out_stats /* [4], may be NULL */, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ wind swing clearance, opt-in
+ * The distance of every row of a cloud to the conductors under the largest wind deviation: each wire swung sideways
+ * about the line between its attachment points, towards the row, by at most the angle Theta.
+ *
+ * The rule.  All arithmetic is float64 without FMA (the library is built with -ffp-contract=off); parentheses are as
+ * written.  The only other operations are / and sqrt, both IEEE correctly rounded.  There is no trigonometry on the
+ * device: the host supplies sin Theta and cos Theta.  tests/swing_cases.py follows it literally in numpy.
+ *   Model.  A wire point at station m hangs f(m) = zc(m) - z(m) below the chord, where the chord runs through the
+ *     polyline's two ends.  Under wind this hanging vector turns about the horizontal along-track axis through the chord
+ *     point, by an angle in [-Theta, Theta].  The swung point is (m, f*s, z + f*(1 - c)) in the span frame (along the
+ *     track, lateral, height); (s, c) is the sine and cosine of the turn.  At rest s = 0 and c = 1, and the vertex is
+ *     exactly (m, 0, z).  Insulator strings swinging with the wire are not modelled.
+ *   Tables (no kernel; ops.swing_heads, ops.swing_segments), from ops.span_curves' [K,10].  The vertices m_j, z_j for
+ *     j = 0..S are exactly those of ops.span_segments (the polyline of the clearance rule).
+ *         kap = (z_S - z_0) / (m_S - m_0)
+ *         zc_j = z_0 + ((m_j - m_0)*kap)
+ *         f_j = zc_j - z_j
+ *     Segment record, float64 [K,S,6] = (m_j, z_j, f_j, dm_j, dz_j, df_j), with dm_j = m_{j+1} - m_j,
+ *     dz_j = z_{j+1} - z_j and df_j = f_{j+1} - f_j.  Head record, float64 [K,11] = (cx, cy, cz, ux, uy, mA, mB, zA, kap,
+ *     sT, cT), with mA = m_0, mB = m_S, zA = z_0, sT = sin Theta and cT = cos Theta.
+ *   Span participation.  A span takes part if and only if all 11 + 6*S values are finite, mB > mA, 0 <= sT <= 1,
+ *     0 < cT <= 1 and |((sT*sT) + (cT*cT)) - 1| <= 1e-6.
+ *   Per row and span (pch_swing_clearance_f32).  Rows, skip, radius, limit, r2 and l2 are exactly as in
+ *     pch_clearance_f32.  Spans are visited in ascending k:
+ *         dx, dy, w, m, t                       as in pch_clearance_f32
+ *         mh = m;  if mh < mA: mh = mA;  if mh > mB: mh = mB
+ *         bb = (zA + ((mh - mA)*kap)) - w                     # depth of the row below the chord at its own station
+ *         if bb > 0 and (fabs(t)*cT) <= (bb*sT):              # inside the swing sector: the wire can point at the row
+ *             rho = sqrt((t*t) + (bb*bb));  s = t/rho;  c = bb/rho
+ *         else:                                               # the end of the sector on the row's side
+ *             s = (t >= 0) ? sT : -sT;  c = cT
+ *         e = 1.0 - c
+ *         g = +inf
+ *         for j ascending:
+ *             py = f_j*s;  pw = z_j + (f_j*e);  ey = df_j*s;  ez = dz_j + (df_j*e)
+ *             rm = m - m_j;  rt = t - py;  rw = w - pw
+ *             len2 = ((dm_j*dm_j) + (ey*ey)) + (ez*ez)
+ *             q = len2 > 0 ? (((rm*dm_j) + (rt*ey)) + (rw*ez)) / len2 : 0
+ *             if q < 0: q = 0
+ *             if q > 1: q = 1
+ *             vm = rm - (q*dm_j);  vt = rt - (q*ey);  vw = rw - (q*ez)
+ *             d = ((vm*vm) + (vt*vt)) + (vw*vw);  if d < g: g = d
+ *         if g <= r2 and g < best: best = g; who = k; sin = s
+ *   Row outputs.  out_dist2[i] (float64) = best, out_span[i] (int32) = who and out_sin[i] (float64) = sin: the sine of
+ *     the angle at which the winning span is nearest; its sign tells the side.  A row without a span gets +inf, -1 and
+ *     NaN.  So does a skipped row and a row with a non-finite coordinate.  Ties go to the lowest span index.
+ *   Span outputs.  The same table as the clearance call, over each row's nearest span only: out_count, out_violations
+ *     (dist2 <= l2), out_min_dist2, out_min_row.  out_loops is also as there.
+ * One angle per (row, span): the angle is chosen in the row's own cross-section; distance is then measured to the whole
+ * polyline swung to that angle.  With sT = 0, cT = 1 the call is the clearance call's geometry; the roundings differ (a
+ * division per segment, a three-term sum), so agreement with pch_clearance_f32 is to rounding, not to the bit.
+ *
+ * How: a small kernel over the spans writes the "takes part" flag and conservative bounds of the whole swung family,
+ * widened by the radius; a sweep over tiles of 1024 rows walks, in ascending order, the spans whose bounds meet the
+ * tile's own bounding box; pch_clearance_f32's finisher finds the lowest row of every minimum.  Culling skips only what
+ * the rule cannot accept: the outputs are the rule's, whatever is culled.  The same input gives the same bits on every
+ * run; nothing waits on another workgroup.
+ *
+ * 0 <= n < 2^32, 0 <= nspans <= 4096, 1 <= nsegments <= 128 (else PCH_ERR_ARG, as a radius or limit that is not
+ * finite, limit <= 0, limit > radius, a null buffer that is needed and a host pointer).  All buffers device; skip may
+ * be NULL; out_loops (int64 [2]) may be NULL.  ws: the caller's, at least pch_swing_clearance_ws_bytes(n, nspans,
+ * nsegments) bytes - pure host code, 0 for sizes out of range (smaller: PCH_ERR_WORKSPACE).  n == 0 or nspans == 0:
+ * every row gets +inf / -1 / NaN, the table is (0, 0, +inf, -1) per span, and no launch reads a null pointer.  Enqueues
+ * on the caller's stream and returns; no host read. */
+size_t pch_swing_clearance_ws_bytes(int64_t n, int32_t nspans, int32_t nsegments);
+int pch_swing_clearance_f32(const float* xyz, const uint8_t* skip, int64_t n, const double* heads /* [K,11] */,
+                            const double* segs /* [K,S,6] */, int32_t nspans, int32_t nsegments, double radius,
+                            double limit, double* out_dist2, int32_t* out_span, double* out_sin, int64_t* out_count,
+                            int64_t* out_violations, double* out_min_dist2, int64_t* out_min_row,
+                            int64_t* out_loops /* [2], may be NULL */, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ stage D1, fast mode
  * The reference boxes every cluster with trimesh (utils/tower_extraction.py:137-139:
  * trimesh.PointCloud(cluster_points).bounding_box_oriented): qhull's 3-D hull of the whole cluster, then a

@@ -11,6 +11,7 @@
 //             (cl_walk_spans), the loop over a round's owning spans (cl_fold_owners), the tallies added once per
 //             (tile, span) (cl_flush_hist)
 //   finish  : one pass over dist2 and span - the lowest row that attains a span's smallest distance; the table
+//             (cl_finish_run: the launch pch_swing.hip shares, as pch_treefall.hip shares cl_bounds_run)
 // No inline assembly, no floating-point atomic, nothing waits on another workgroup; the same bits on every run.
 #include "pch_common.h"
 #include "pch_spancull.h"
@@ -207,6 +208,17 @@ __global__ __launch_bounds__(CL_THREADS) void cl_finish_k(const double* __restri
     if (cl_minkey(dist2[i]) == maxinv[k]) atomicMin(&out_min_row[k], (unsigned long long)i);
 }
 
+int cl_finish_run(const double* dist2, const int32_t* span, int64_t n, int nspans, const unsigned long long* tally,
+                  const unsigned long long* second, const unsigned long long* maxinv,
+                  const unsigned long long* counters, int64_t* out_count, int64_t* out_second, double* out_min_dist2,
+                  int64_t* out_min_row, int64_t* out_loops, hipStream_t s) {
+    const int64_t most = n > nspans ? n : (int64_t)nspans;
+    PCH_LAUNCH("clearance_finish", cl_finish_k, dim3((unsigned)ceil_div(most, CL_THREADS)), dim3(CL_THREADS), 0, s, dist2,
+               span, n, nspans, tally, second, maxinv, counters, out_count, out_second, out_min_dist2,
+               reinterpret_cast<unsigned long long*>(out_min_row), out_loops);
+    return PCH_OK;
+}
+
 static void cl_plan(Arena& a, int32_t nspans, ClWs& w) {
     cl_plan_front(a, nspans, 2, w);
     cl_plan_back(a, nspans, w);
@@ -257,12 +269,8 @@ extern "C" int pch_clearance_f32(const float* xyz, const uint8_t* skip, int64_t 
         PCH_LAUNCH("clearance_sweep", cl_sweep_k, dim3((unsigned)ceil_div(n, CL_TILE)), dim3(CL_THREADS), 0, s, xyz, skip,
                    n, curves5, segs, (int)nspans, (int)nsegments, (const ClSpan*)w.sp, (const uint32_t*)w.take, r2, l2,
                    out_dist2, out_span, w.tally, w.second, w.maxinv, w.counters);
-    const int64_t most = n > nspans ? n : (int64_t)nspans;
     if (nspans > 0)
-        PCH_LAUNCH("clearance_finish", cl_finish_k, dim3((unsigned)ceil_div(most, CL_THREADS)), dim3(CL_THREADS), 0, s,
-                   (const double*)out_dist2, (const int32_t*)out_span, n, (int)nspans,
-                   (const unsigned long long*)w.tally, (const unsigned long long*)w.second,
-                   (const unsigned long long*)w.maxinv, (const unsigned long long*)w.counters, out_count,
-                   out_violations, out_min_dist2, reinterpret_cast<unsigned long long*>(out_min_row), out_loops);
+        PCH_TRY(cl_finish_run(out_dist2, out_span, n, (int)nspans, w.tally, w.second, w.maxinv, w.counters, out_count,
+                              out_violations, out_min_dist2, out_min_row, out_loops, s));
     return PCH_OK;
 }

@@ -1,4 +1,5 @@
-// What the sweeps of row tiles over span polylines share (pch_clearance.hip, pch_treefall.hip) on top of pch_tilecull.h:
+// What the sweeps of row tiles over span polylines share (pch_clearance.hip, pch_treefall.hip, pch_swing.hip) on top of
+// pch_tilecull.h:
 // the tile geometry, the per-span cull record that cl_bounds_k writes (its derivation stands in front of the kernel, in
 // pch_clearance.hip), the walk of a tile's spans that carries the rule of include/pch_hip.h, the fold of a round's
 // answers per owning span, the per-span tallies and the front of the workspace that holds them.
@@ -24,6 +25,14 @@ struct ClSpan { double lo[3], hi[3], flo, fhi, wlo, whi; };
 // row of the sweep behind it is measured with (nspans > 0)
 int cl_bounds_run(const double* curves5, const double* segs, int nspans, int nseg, double radius, ClSpan* out,
                   uint32_t* take, hipStream_t s);
+
+// cl_finish_k on the stream: the table out of the zeroed front of a ClWs (tally, second, maxinv, counters) and, over
+// dist2 and span of the n rows, the lowest row that attains a span's smallest distance (out_min_row arrives as all ones
+// = -1; nspans > 0; out_loops may be null)
+int cl_finish_run(const double* dist2, const int32_t* span, int64_t n, int nspans, const unsigned long long* tally,
+                  const unsigned long long* second, const unsigned long long* maxinv,
+                  const unsigned long long* counters, int64_t* out_count, int64_t* out_second, double* out_min_dist2,
+                  int64_t* out_min_row, int64_t* out_loops, hipStream_t s);
 
 static bool cl_spans_ok(int32_t nspans, int32_t nseg) {
     return nspans >= 0 && nspans <= CL_MAXSPAN && nseg >= 1 && nseg <= CL_MAXSEG;

@@ -19,7 +19,8 @@ One function per reference library call:
 Beyond the reference, on a retained fit (DbscanFit): assign, kdist, shape (+ shape_features), knn (+ knn_mean_distance) -
 DESIGN.md sections 5a, 5b, 5c; on a grouping: cluster_moments, span_frames, cluster_profile, span_fit - section 5d; on a cloud and the fitted
 curves: span_curves, span_segments, clearance - section 5e; on a cloud and a grid: terrain_grid, terrain_low,
-terrain_ground, terrain_height, terrain_sample, span_ground_profile - section 5f.
+terrain_ground, terrain_height, terrain_sample, span_ground_profile - section 5f; on a cloud and the curves swung by
+wind: swing_heads, swing_segments, swing_clearance - section 5i.
 """
 from __future__ import annotations
 
@@ -1635,6 +1636,122 @@ def clearance(xyz, curves, segs, radius, limit, skip=None, want_stats=False):
                                        _ptr(dist2), _ptr(span), _ptr(count), _ptr(violations), _ptr(min_dist2),
                                        _ptr(min_row), _ptr(loops), _ptr(ws), ws.numel(), _stream()))
     out = dict(dist2=dist2, span=span, count=count, violations=violations, min_dist2=min_dist2, min_row=min_row)
+    if want_stats:
+        out["loops"] = loops
+    return out
+
+
+# ------------------------------------------------------------- wind swing clearance, opt-in
+def swing_angle(angle_deg, K):
+    """(sT, cT) float64 numpy [K]: numpy's sine and cosine of the largest swing angle in degrees, a scalar or one value
+    per span; ValueError unless every angle is finite with 0 <= angle < 90"""
+    import numpy as np
+    a = np.asarray(angle_deg.detach().cpu() if isinstance(angle_deg, torch.Tensor) else angle_deg, dtype=np.float64)
+    if a.ndim == 0:
+        a = np.full((K,), float(a), dtype=np.float64)
+    a = a.reshape(-1)
+    if a.shape[0] != K:
+        raise ValueError(f"angle must be a scalar or hold one value per span ({K}), got {a.shape[0]}")
+    if not (np.isfinite(a) & (a >= 0.0) & (a < 90.0)).all():
+        raise ValueError("the swing angle must be finite with 0 <= angle < 90 degrees")
+    rad = np.radians(a)
+    return np.sin(rad), np.cos(rad)
+
+
+def swing_heads(curves, angle_deg):
+    """float64 [K,11] device: per span of ``span_curves``' [K,10] the head record of the swing rule ``(cx, cy, cz, ux, uy,
+    mA, mB, zA, kap, sT, cT)`` - the frame, the polyline's ends ``mA = m0``, ``mB = m1``, the height ``zA`` of its first
+    vertex, the chord's slope ``kap = (z_S − z_0) / (m_S − m_0)`` and numpy's sine and cosine of ``angle_deg`` (degrees;
+    a scalar or [K]; ``0 <= angle < 90``).  The chord runs through the ends of the curve, which are the end vertices of
+    every polyline of ``span_segments``, so the record does not depend on S.  include/pch_hip.h's rule: float64 torch
+    arithmetic on K records, no kernel.  Insulator strings that swing with the wire are not modelled.  Asynchronous."""
+    curves = _need_cuda(curves, torch.float64, "curves").reshape(-1, 10)
+    sT, cT = swing_angle(angle_deg, curves.shape[0])
+    return _swing_heads_of(curves, torch.from_numpy(sT).to(curves.device), torch.from_numpy(cT).to(curves.device))
+
+
+def _swing_heads_of(curves, sT, cT):
+    """swing_heads' arithmetic, on tensors of any device"""
+    a, b, c, m0, m1 = (curves[:, i] for i in range(5, 10))
+    z0 = a + m0 * (b + c * m0)
+    z1 = a + m1 * (b + c * m1)
+    kap = (z1 - z0) / (m1 - m0)
+    return torch.stack([curves[:, 0], curves[:, 1], curves[:, 2], curves[:, 3], curves[:, 4], m0, m1, z0, kap,
+                        sT.reshape(-1), cT.reshape(-1)], dim=1).contiguous()
+
+
+def swing_segments(curves, segments=32):
+    """float64 [K,S,6] device: the segment records of the swing rule for each curve of ``span_curves`` - per segment
+    ``(m_j, z_j, f_j, Δm_j, Δz_j, Δf_j)``: ``span_segments``' vertex, how far it hangs below the chord through the
+    polyline's two ends (``f_j = zc_j − z_j``, ``zc_j = z_0 + (m_j − m_0)·kap``) and the steps to the next vertex.
+    include/pch_hip.h's rule: float64 torch arithmetic on K·S records, no kernel.  Asynchronous."""
+    S = check_segments(segments)
+    curves = _need_cuda(curves, torch.float64, "curves").reshape(-1, 10)
+    return _swing_segments_of(curves, S)
+
+
+def _swing_segments_of(curves, S):
+    """swing_segments' arithmetic, on tensors of any device"""
+    m, z, _ = _span_vertices_of(curves, S)
+    kap = (z[:, S:] - z[:, :1]) / (m[:, S:] - m[:, :1])
+    zc = z[:, :1] + ((m - m[:, :1]) * kap)
+    f = zc - z
+    return torch.stack([m[:, :-1], z[:, :-1], f[:, :-1], m[:, 1:] - m[:, :-1], z[:, 1:] - z[:, :-1],
+                        f[:, 1:] - f[:, :-1]], dim=2).contiguous()
+
+
+def swing_clearance(xyz, heads, segs, radius, limit, skip=None, want_stats=False):
+    """The distance of every row of float32 [n,3] to the span polylines as the wind can swing them
+    (pch_swing_clearance_f32; the rule is in include/pch_hip.h): a dict of device tensors - ``dist2`` float64 [n], the
+    squared distance to the nearest swung span within ``radius`` (+inf if none), ``span`` int32 [n], that span (-1 if
+    none; the lowest index on a tie), ``sin`` float64 [n], the sine of the angle at which that span is nearest (its sign
+    tells the side; NaN if none) and over the K spans ``count``, ``violations``, ``min_dist2`` and ``min_row`` as
+    ``clearance`` returns them.  ``heads`` float64 [K,11] (``swing_heads``), ``segs`` float64 [K,S,6]
+    (``swing_segments``), ``skip`` as ``clearance`` takes it.  A span with a non-finite value, without length
+    (``mB <= mA``) or whose (sT, cT) is not the sine and cosine of an angle in [0°, 90°) takes no part.  ``want_stats``
+    adds ``loops`` int64 [2].  ValueError as ``clearance``.  The same input gives the same bits on every run.
+    Asynchronous."""
+    import math
+    L = _lib.lib()
+    xyz = _need_cuda(xyz, torch.float32, "xyz").reshape(-1, 3)
+    heads = _need_cuda(heads, torch.float64, "heads")
+    segs = _need_cuda(segs, torch.float64, "segs")
+    if heads.dim() != 2 or heads.shape[1] != 11:
+        raise ValueError("heads must be [K,11]")
+    K = heads.shape[0]
+    if segs.dim() != 3 or segs.shape[0] != K or segs.shape[2] != 6:
+        raise ValueError("segs must be [K,S,6] for the K spans of heads")
+    S = check_segments(segs.shape[1])
+    if K > CLEARANCE_MAX_SPANS:
+        raise ValueError(f"swing_clearance takes at most {CLEARANCE_MAX_SPANS} spans per call, got {K}")
+    radius, limit = float(radius), float(limit)
+    if not (math.isfinite(radius) and math.isfinite(limit) and 0.0 < limit <= radius):
+        raise ValueError(f"radius and limit must be finite with 0 < limit <= radius, got {radius!r}, {limit!r}")
+    n, dev = xyz.shape[0], xyz.device
+    if n >= 1 << 32:
+        raise ValueError("swing_clearance takes fewer than 2^32 rows per call")
+    if skip is not None:
+        if isinstance(skip, torch.Tensor) and skip.dtype == torch.bool:
+            skip = skip.view(torch.uint8)
+        skip = _need_cuda(skip, torch.uint8, "skip").reshape(-1)
+        if skip.numel() != n:
+            raise ValueError("skip must hold one entry per row")
+    with torch.cuda.device(dev):
+        dist2 = torch.empty((n,), dtype=torch.float64, device=dev)
+        span = torch.empty((n,), dtype=torch.int32, device=dev)
+        sin = torch.empty((n,), dtype=torch.float64, device=dev)
+        count = torch.empty((K,), dtype=torch.int64, device=dev)
+        violations = torch.empty((K,), dtype=torch.int64, device=dev)
+        min_dist2 = torch.empty((K,), dtype=torch.float64, device=dev)
+        min_row = torch.empty((K,), dtype=torch.int64, device=dev)
+        loops = torch.empty((2,), dtype=torch.int64, device=dev) if want_stats else None
+        ws = _workspace(L.pch_swing_clearance_ws_bytes(n, K, S), dev)
+        _lib.check(L.pch_swing_clearance_f32(_ptr(xyz), _ptr(skip), n, _ptr(heads), _ptr(segs), K, S, radius, limit,
+                                             _ptr(dist2), _ptr(span), _ptr(sin), _ptr(count), _ptr(violations),
+                                             _ptr(min_dist2), _ptr(min_row), _ptr(loops), _ptr(ws), ws.numel(),
+                                             _stream()))
+    out = dict(dist2=dist2, span=span, sin=sin, count=count, violations=violations, min_dist2=min_dist2,
+               min_row=min_row)
     if want_stats:
         out["loops"] = loops
     return out

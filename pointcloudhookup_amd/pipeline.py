@@ -216,6 +216,67 @@ def conductor_clearance(points, spans, radius=10.0, limit=6.0, segments=32, towe
     return dict(dist2=res["dist2"], span=span, violating=res["dist2"] <= float(limit) * float(limit), table=table)
 
 
+WIND_TABLE_KEYS = CLEARANCE_TABLE_KEYS + ("min_angle",)
+
+
+def wind_clearance(points, spans, angle, radius=10.0, limit=6.0, segments=32, towers=None, cut_radius=9.0):
+    """How close anything that is not the line comes to it under the largest wind deviation: the
+    distance of every row of ``points`` (float32 [n,3] on the device) to the sag curves of the accepted pieces of
+    ``spans`` (``conductor_spans``' dict for the same ``points``), each swung sideways about the chord between its
+    ends by up to ``angle`` degrees (a scalar, ``0 <= angle < 90``) towards the row.  The pieces, their polylines of
+    ``segments`` segments and the skipped rows are ``conductor_clearance``'s; ``ops.swing_heads``,
+    ``ops.swing_segments`` and ``ops.swing_clearance`` do the rest.  Every row is attributed to its nearest piece only.
+    Insulator strings that swing with the wire are not modelled.
+
+    Returns dict: ``distance`` (float64 [n], metres: to the nearest swung piece within ``radius``, +inf if none or
+    skipped), ``span`` (int32 [n]: that piece's id in the span table, -1 if none), ``angle`` (float64 [n], degrees: the
+    swing at which that piece is nearest, ``arcsin`` of the call's sine taken on the host, its sign the side; NaN if
+    none), ``violating`` (bool [n]: ``dist2 <= limit²``) and ``table``, a dict over the K pieces of the span table with
+    ``conductor_clearance``'s keys and ``min_angle`` (degrees: the angle of ``min_row``, NaN without).  No accepted piece:
+    every row +inf / -1 / NaN and a table without rows attributed; nothing is raised.  Synchronises."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32:
+        raise TypeError("points must be a float32 CUDA/HIP tensor (no CPU fallback in the product path)")
+    points = points.reshape(-1, 3).contiguous()
+    n, dev = int(points.shape[0]), points.device
+    wire = spans["wire"]
+    if wire.numel() != n:
+        raise ValueError("spans must be conductor_spans' result for the same points")
+    segments = ops.check_segments(segments)
+    if np.ndim(angle) != 0:
+        raise ValueError("angle must be a scalar in degrees")
+    K = int(spans["nclusters"])
+    idx = torch.nonzero(spans["accepted"]).reshape(-1)                        # accepted pieces, ascending
+    curves = ops.span_curves(spans["table"], spans["frames"], spans["ext"])[idx].contiguous()
+    heads = ops.swing_heads(curves, float(angle))
+    segs = ops.swing_segments(curves, segments)
+    _, chord = ops.span_segments(curves, segments)
+    near = _near_towers(points, towers, cut_radius)
+    skip = wire if near is None else (wire | near)
+    res = ops.swing_clearance(points, heads, segs, radius, limit, skip=skip)
+    span = res["span"]                                                        # (all -1 without an accepted piece)
+    if idx.numel():
+        span = torch.where(span >= 0, idx.to(torch.int32)[span.clamp(min=0).long()], torch.full_like(span, -1))
+    deg = torch.from_numpy(np.degrees(np.arcsin(res["sin"].cpu().numpy()))).to(dev)
+    nan64 = float("nan")
+    count = torch.zeros((K,), dtype=torch.int64, device=dev)
+    violations = torch.zeros((K,), dtype=torch.int64, device=dev)
+    min_distance = torch.full((K,), float("inf"), dtype=torch.float64, device=dev)
+    min_row = torch.full((K,), -1, dtype=torch.int64, device=dev)
+    chord_error = torch.full((K,), nan64, dtype=torch.float64, device=dev)
+    count[idx], violations[idx] = res["count"], res["violations"]
+    min_distance[idx], min_row[idx], chord_error[idx] = torch.sqrt(res["min_dist2"]), res["min_row"], chord
+    min_point = torch.full((K, 3), nan64, dtype=torch.float32, device=dev)
+    min_angle = torch.full((K,), nan64, dtype=torch.float64, device=dev)
+    has = min_row >= 0
+    if n:
+        min_point[has] = points[min_row[has]]
+        min_angle[has] = deg[min_row[has]]
+    table = dict(count=count, violations=violations, min_distance=min_distance, min_row=min_row, min_point=min_point,
+                 chord_error=chord_error, min_angle=min_angle)
+    return dict(distance=torch.sqrt(res["dist2"]), span=span, angle=deg,
+                violating=res["dist2"] <= float(limit) * float(limit), table=table)
+
+
 def terrain_cells(cell, window, max_gap):
     """(R, G): the opening's window radius and the fill's gap in cells for ``window`` and ``max_gap`` in metres -
     ``R = ceil(window / (2·cell))``, ``G = ceil(max_gap / cell)``; ValueError beyond the library's limits"""

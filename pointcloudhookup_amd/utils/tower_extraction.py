@@ -71,6 +71,14 @@ conductors themselves and the rows within the spans' ``cut_radius`` of an accept
 5e) and ``output_towers/clearance_info.csv`` gets one line per accepted wire piece: the rows nearer than ``radius``
 metres, those nearer than ``limit``, the smallest distance and the nearest point in world coordinates.  It logs one extra
 line; a failure is handled like one of ``SPANS``.  The returned tower dicts are the same with and without it.
+``WIND`` (env PCH_WIND="angle_deg,limit[,radius]", e.g. "45,6" or "45,6,10"; unset or empty = off; needs ``SPANS`` -
+importing the module with PCH_WIND set and PCH_SPANS unset raises ValueError): behind the clearance step, the same
+rows are held against the accepted pieces' sag curves swung sideways by the wind, each by up to ``angle_deg`` degrees
+about the chord between its ends (pipeline.wind_clearance, with ``CLEARANCE``'s ``segments`` when that knob is on;
+insulator strings are not modelled) and ``output_towers/wind_clearance_info.csv`` gets one line per
+accepted wire piece: the rows nearer than ``radius`` metres (default 10) to the swung wire, those nearer than ``limit``,
+the smallest distance, the nearest point in world coordinates and the swing angle at which it is that near.  It logs
+one extra line; a failure is handled like one of ``SPANS``.  The returned tower dicts are the same with and without it.
 ``TERRAIN`` (env PCH_TERRAIN="cell,window,dh[,limit]", e.g. "1,12,0.5,7"; unset or empty = off; needs ``SPANS`` and the
 "reference" frame - importing the module with PCH_TERRAIN set and PCH_SPANS unset, or with PCH_FRAME=las, raises
 ValueError): right after the ground rule, a terrain grid of ``cell`` metres is built from the whole cloud, ground included
@@ -226,6 +234,33 @@ def clearance_from_env(value, spans=True):
 
 CLEARANCE = clearance_from_env(os.environ.get("PCH_CLEARANCE"), spans=SPANS is not None)
 CLEARANCE_COLUMNS = ("ID", "count", "violations", "min_distance", "min_row", "x", "y", "z", "chord_error")
+
+
+def wind_from_env(value, spans=True):
+    """WIND of an environment value: None (off) when unset or empty, else dict(angle, limit, radius) from
+    "angle_deg,limit[,radius]" - two or three numbers; the largest swing angle in degrees, finite with 0 <= angle < 90,
+    radius (default 10.0) and limit finite with 0 < limit <= radius.  ``spans``: whether SPANS is on - the distance is
+    measured to its pieces, so a value without it is refused (ValueError)"""
+    if value is None or not value.strip():
+        return None
+    parts = [t.strip() for t in value.split(",")]
+    if len(parts) not in (2, 3):
+        raise ValueError(f"PCH_WIND takes \"angle_deg,limit[,radius]\", got {value!r}")
+    angle, limit = float(parts[0]), float(parts[1])
+    radius = float(parts[2]) if len(parts) == 3 else 10.0
+    if not (np.isfinite(angle) and 0.0 <= angle < 90.0):
+        raise ValueError(f"PCH_WIND: angle_deg must be finite with 0 <= angle < 90, got {parts[0]!r}")
+    if not (np.isfinite(radius) and radius > 0.0):
+        raise ValueError(f"PCH_WIND: radius must be finite and > 0, got {radius!r}")
+    if not (np.isfinite(limit) and 0.0 < limit <= radius):
+        raise ValueError(f"PCH_WIND: limit must be finite with 0 < limit <= radius, got {parts[1]!r}")
+    if not spans:
+        raise ValueError("PCH_WIND needs PCH_SPANS: the distance is measured to the span table's pieces")
+    return dict(angle=angle, limit=limit, radius=radius)
+
+
+WIND = wind_from_env(os.environ.get("PCH_WIND"), spans=SPANS is not None)
+WIND_COLUMNS = ("ID", "count", "violations", "min_distance", "min_row", "x", "y", "z", "angle_deg", "chord_error")
 
 
 def terrain_from_env(value, spans=True, frame="reference"):
@@ -606,6 +641,18 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
             except (ValueError, RuntimeError) as e:
                 log(f"⚠️ 导线净空计算失败: {str(e)}")
                 return tower_obbs
+        # ---- opt-in: the same under the largest wind deviation
+        if WIND:
+            try:
+                wind = pipeline.wind_clearance(stage_b_points, spans, towers=local, cut_radius=SPANS["cut_radius"],
+                                               segments=CLEARANCE["segments"] if CLEARANCE else 32, **WIND)
+                rows = wind_rows(spans, wind, cen)
+                write_wind_csv(output_dir / "wind_clearance_info.csv", rows)
+                clock.mark("wind clearance")
+                log(wind_line(wind, rows, WIND))
+            except (ValueError, RuntimeError) as e:
+                log(f"⚠️ 风偏净空计算失败: {str(e)}")
+                return tower_obbs
         # ---- opt-in: how high those conductors hang above the ground
         if TERRAIN:
             try:
@@ -750,6 +797,42 @@ def clearance_line(clear, rows, knob):
     closest = min([r[3] for r in rows], default=float("inf"))
     return (f"📏 导线净空: 半径 {knob['radius']:g} m，限距 {knob['limit']:g} m，折线 {knob['segments']} 段；"
             f"半径内 {int(near)} 点，越限 {int(clear['violating'].sum())} 点，越限线段 {int(breached)}/{len(rows)}，"
+            f"最小净空 {closest:.3f} m")
+
+
+def wind_rows(spans, wind, centroid):
+    """the lines of wind_clearance_info.csv for a result of pipeline.wind_clearance: one list per accepted piece in
+    WIND_COLUMNS' order, the nearest point moved to world coordinates by ``centroid`` (3 float64; NaN without a row),
+    with the swing angle in degrees at which it is nearest"""
+    acc = spans["accepted"].cpu().numpy()
+    T = {key: v.cpu().numpy() for key, v in wind["table"].items()}
+    rows = []
+    for k in np.flatnonzero(acc):
+        p = T["min_point"][k].astype(np.float64) + centroid
+        rows.append([f"span_{int(k)}", int(T["count"][k]), int(T["violations"][k]), float(T["min_distance"][k]),
+                     int(T["min_row"][k]), float(p[0]), float(p[1]), float(p[2]), float(T["min_angle"][k]),
+                     float(T["chord_error"][k])])
+    return rows
+
+
+def write_wind_csv(path, rows):
+    """wind_clearance_info.csv: a header line (WIND_COLUMNS) and one line per accepted piece, floats with repr's
+    digits"""
+    import csv
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.writer(f)
+        w.writerow(WIND_COLUMNS)
+        for r in rows:
+            w.writerow([repr(float(v)) if isinstance(v, (float, np.floating)) else v for v in r])
+
+
+def wind_line(wind, rows, knob):
+    """the extra log line of WIND for a result of pipeline.wind_clearance and its csv lines"""
+    near = sum(r[1] for r in rows)
+    breached = sum(1 for r in rows if r[2] > 0)
+    closest = min([r[3] for r in rows], default=float("inf"))
+    return (f"🌬️ 风偏净空: 最大风偏角 {knob['angle']:g}°，半径 {knob['radius']:g} m，限距 {knob['limit']:g} m；"
+            f"半径内 {int(near)} 点，越限 {int(wind['violating'].sum())} 点，越限线段 {int(breached)}/{len(rows)}，"
             f"最小净空 {closest:.3f} m")
 
 
