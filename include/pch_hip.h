@@ -1029,6 +1029,63 @@ int pch_swing_clearance_f32(const float* xyz, const uint8_t* skip, int64_t n, co
                             int64_t* out_violations, double* out_min_dist2, int64_t* out_min_row,
                             int64_t* out_loops /* [2], may be NULL */, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ span sections, opt-in
+ * The longitudinal section of every span: station by station along the wire, how many rows lie in the corridor under
+ * it, how many of them within the vertical limit, how far below the wire the highest one is and which row that is; and
+ * for every row the span and station where a wire hangs lowest above it.
+ *
+ * The rule.  All arithmetic is float64 without FMA (the library is built with -ffp-contract=off); parentheses are as
+ * written.  The only other operations are one division, floor and the cast to float32.  tests/section_cases.py follows
+ * it literally in numpy.
+ *   Inputs.  xyz float32 [n,3]; an optional skip uint8 [n]; curves10 float64 [K,10] = (cx, cy, cz, ux, uy, a, b, c, m0,
+ *     m1), exactly ops.span_curves' records; B stations, 1 <= B <= 128; half (the corridor's half width), depth and
+ *     limit, all finite, with half > 0 and 0 < limit <= depth.
+ *   Span participation.  A span takes part if and only if all ten of its values are finite and m1 > m0.  Its step is
+ *     step = (m1 - m0) / (double)B.
+ *   Per row and span (pch_span_section_f32).  For row i with skip[i] == 0, spans are visited in ascending k:
+ *         dx = (double)px - cx;  dy = (double)py - cy;  w = (double)pz - cz
+ *         m = (dx*ux) + (dy*uy);  t = (dy*ux) - (dx*uy)
+ *         in the corridor iff  m >= m0 and m <= m1 and t >= -half and t <= half
+ *         zw = a + (m*(b + (c*m)));  v = zw - w                 # the wire above the row: v > 0
+ *         takes part iff in the corridor and v >= 0.0 and v <= depth
+ *         j = (int)floor((m - m0) / step);  if j > B - 1: j = B - 1
+ *         vf = fabsf((float)v)                                  # float32; the cast is monotone: min commutes with it
+ *     A NaN fails every comparison.  A row with a non-finite coordinate, or a skipped row, takes part nowhere.
+ *   The wire height is the parabola itself, not the polyline of pch_clearance_f32: the two differ, vertically, by at
+ *     most that rule's chord_error.  v is a vertical distance, t a horizontal one: neither is the spatial clearance.
+ *   Per cell (k, j), over EVERY row that takes part in span k - a row under three phases counts in all three; this is
+ *     not the nearest-only attribution of pch_clearance_f32: out_count[k][j] (int64): the rows; out_violations[k][j]
+ *     (int64): those with v <= limit, tested on the double; out_min_v[k][j] (float32): the smallest vf, +inf for an
+ *     empty cell; out_min_row[k][j] (int64): the lowest row index that attains the smallest vf, or -1.
+ *   Per row: out_v[i] (float32): the smallest vf over the spans the row takes part in, or +inf; out_span[i] (int32):
+ *     the lowest k that attains it, or -1; out_station[i] (int32): its j in that span, or -1.
+ *
+ * How: a small kernel over the spans writes the "takes part" flag and a cull record - a world box around the corridor
+ * rectangle and the heights a row under the wire can have, widened for the roundings of m, t and zw; a sweep over tiles
+ * of 1024 rows walks, in ascending order, the spans whose record meets the tile's own bounding box.  Culling skips only
+ * spans the rule cannot accept: the outputs are the rule's, whatever is culled.  A cell's smallest vf and its lowest row
+ * travel in one 64-bit key (bits(vf) << 32) | i - vf >= 0, so its bits order as integers - folded with an integer
+ * atomic minimum.  Every tile first combines its rows per station in LDS and adds each station that is not empty to the
+ * cell once per (tile, span): a cell that thousands of rows fall into receives two atomics per tile - the key and the
+ * packed tally -, not two per row.  A last kernel decodes the keys and the tallies.  Integer atomics only: the same
+ * input gives the same bits on every run; nothing waits on another workgroup.
+ *
+ * 0 <= n < 2^32, 0 <= nspans <= 4096, 1 <= nstations <= 128 (else PCH_ERR_ARG, as a half_width, depth or limit that is
+ * not finite, half_width <= 0, limit <= 0, limit > depth, a null buffer that is needed and a host pointer).  All
+ * buffers device; the cell tables are [K,B], row-major; skip may be NULL (no row is skipped); out_stats (int64 [3], may
+ * be NULL): the (row, span) pairs that took part, the (tile, span) pairs walked and the cell flushes (atomics on a
+ * cell's key) - figures for measurement, not part of the rule.  ws: the caller's, at least
+ * pch_span_section_ws_bytes(n, nspans, nstations) bytes - pure host code, 0 for sizes out of range (smaller:
+ * PCH_ERR_WORKSPACE).  n == 0 or nspans == 0: every row gets +inf / -1 / -1, every cell (0, 0, +inf, -1), and no launch
+ * reads a null pointer.  Enqueues on the caller's stream and returns; no host read. */
+size_t pch_span_section_ws_bytes(int64_t n, int32_t nspans, int32_t nstations);
+int pch_span_section_f32(const float* xyz, const uint8_t* skip, int64_t n, const double* curves10 /* [K,10] */,
+                         int32_t nspans, int32_t nstations, double half_width, double depth, double limit,
+                         float* out_v, int32_t* out_span, int32_t* out_station, int64_t* out_count /* [K,B] */,
+                         int64_t* out_violations /* [K,B] */, float* out_min_v /* [K,B] */,
+                         int64_t* out_min_row /* [K,B] */, int64_t* out_stats /* [3], may be NULL */, void* ws,
+                         size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ stage D1, fast mode
  * The reference boxes every cluster with trimesh (utils/tower_extraction.py:137-139:
  * trimesh.PointCloud(cluster_points).bounding_box_oriented): qhull's 3-D hull of the whole cluster, then a

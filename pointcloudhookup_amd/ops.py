@@ -20,7 +20,8 @@ Beyond the reference, on a retained fit (DbscanFit): assign, kdist, shape (+ sha
 DESIGN.md sections 5a, 5b, 5c; on a grouping: cluster_moments, span_frames, cluster_profile, span_fit - section 5d; on a cloud and the fitted
 curves: span_curves, span_segments, clearance - section 5e; on a cloud and a grid: terrain_grid, terrain_low,
 terrain_ground, terrain_height, terrain_sample, span_ground_profile - section 5f; on a cloud and the curves swung by
-wind: swing_heads, swing_segments, swing_clearance - section 5i.
+wind: swing_heads, swing_segments, swing_clearance - section 5i; on a cloud and the curves, station by station:
+span_section - section 5j.
 """
 from __future__ import annotations
 
@@ -1754,6 +1755,75 @@ def swing_clearance(xyz, heads, segs, radius, limit, skip=None, want_stats=False
                min_row=min_row)
     if want_stats:
         out["loops"] = loops
+    return out
+
+
+# ------------------------------------------------------------- span sections, opt-in
+SECTION_MAX_STATIONS = 128
+
+
+def check_stations(stations):
+    """the station count of a section as an int; ValueError unless 1 <= stations <= 128"""
+    if isinstance(stations, bool) or int(stations) != stations or not 1 <= int(stations) <= SECTION_MAX_STATIONS:
+        raise ValueError(f"stations must be an integer in 1..{SECTION_MAX_STATIONS}, got {stations!r}")
+    return int(stations)
+
+
+def span_section(xyz, curves, stations, half_width, depth, limit, skip=None, want_stats=False):
+    """The longitudinal section of every span (pch_span_section_f32; the rule is in include/pch_hip.h): the rows of
+    float32 [n,3] that lie within ``half_width`` (horizontal) of a span's track and at most ``depth`` below its sag
+    curve, binned into ``stations`` equal stations B along the span.  A dict of device tensors - over the [K,B] cells
+    ``count`` int64 (every row under the span counts, also one that lies under other spans as well), ``violations``
+    int64 (those at most ``limit`` below the wire), ``min_v`` float32 (the smallest vertical distance, +inf for an
+    empty cell) and ``min_row`` int64 (the lowest row that attains it, or -1); per row ``v`` float32 [n] (the smallest
+    vertical distance over the spans the row lies under, +inf if none), ``span`` int32 [n] (the lowest span that attains
+    it, -1 if none) and ``station`` int32 [n] (its station there, -1 if none).  ``curves`` float64 [K,10]
+    (``span_curves``): the wire height is the parabola itself.  ``skip`` an optional uint8 or bool [n]: rows with a
+    non-zero entry take part nowhere, as rows with a non-finite coordinate.  A span with a non-finite value or with
+    ``m1 <= m0`` takes no part.  ``want_stats`` adds ``stats`` int64 [3]: the (row, span) pairs that took part, the
+    (tile, span) pairs walked and the cell flushes.  ValueError: half_width, depth or limit not finite, half_width <= 0,
+    limit <= 0 or > depth, more than 4096 spans, stations outside 1..128.  The same input gives the same bits on every
+    run.  Asynchronous."""
+    import math
+    L = _lib.lib()
+    xyz = _need_cuda(xyz, torch.float32, "xyz").reshape(-1, 3)
+    curves = _need_cuda(curves, torch.float64, "curves")
+    if curves.dim() != 2 or curves.shape[1] != 10:
+        raise ValueError("curves must be [K,10]")
+    K = curves.shape[0]
+    B = check_stations(stations)
+    if K > CLEARANCE_MAX_SPANS:
+        raise ValueError(f"span_section takes at most {CLEARANCE_MAX_SPANS} spans per call, got {K}")
+    half_width, depth, limit = float(half_width), float(depth), float(limit)
+    if not (math.isfinite(half_width) and math.isfinite(depth) and math.isfinite(limit) and half_width > 0.0
+            and 0.0 < limit <= depth):
+        raise ValueError("half_width, depth and limit must be finite with half_width > 0 and 0 < limit <= depth, got "
+                         f"{half_width!r}, {depth!r}, {limit!r}")
+    n, dev = xyz.shape[0], xyz.device
+    if n >= 1 << 32:
+        raise ValueError("span_section takes fewer than 2^32 rows per call")
+    if skip is not None:
+        if isinstance(skip, torch.Tensor) and skip.dtype == torch.bool:
+            skip = skip.view(torch.uint8)
+        skip = _need_cuda(skip, torch.uint8, "skip").reshape(-1)
+        if skip.numel() != n:
+            raise ValueError("skip must hold one entry per row")
+    with torch.cuda.device(dev):
+        v = torch.empty((n,), dtype=torch.float32, device=dev)
+        span = torch.empty((n,), dtype=torch.int32, device=dev)
+        station = torch.empty((n,), dtype=torch.int32, device=dev)
+        count = torch.empty((K, B), dtype=torch.int64, device=dev)
+        violations = torch.empty((K, B), dtype=torch.int64, device=dev)
+        min_v = torch.empty((K, B), dtype=torch.float32, device=dev)
+        min_row = torch.empty((K, B), dtype=torch.int64, device=dev)
+        stats = torch.empty((3,), dtype=torch.int64, device=dev) if want_stats else None
+        ws = _workspace(L.pch_span_section_ws_bytes(n, K, B), dev)
+        _lib.check(L.pch_span_section_f32(_ptr(xyz), _ptr(skip), n, _ptr(curves), K, B, half_width, depth, limit,
+                                          _ptr(v), _ptr(span), _ptr(station), _ptr(count), _ptr(violations),
+                                          _ptr(min_v), _ptr(min_row), _ptr(stats), _ptr(ws), ws.numel(), _stream()))
+    out = dict(count=count, violations=violations, min_v=min_v, min_row=min_row, v=v, span=span, station=station)
+    if want_stats:
+        out["stats"] = stats
     return out
 
 

@@ -277,6 +277,90 @@ def wind_clearance(points, spans, angle, radius=10.0, limit=6.0, segments=32, to
                 violating=res["dist2"] <= float(limit) * float(limit), table=table)
 
 
+SECTION_KEYS = ("m", "xy", "wire_z", "count", "violations", "min_vertical", "min_row", "top", "ground")
+SECTION_TABLE_KEYS = ("count", "violations", "min_vertical", "min_station", "min_row", "min_point")
+
+
+def span_sections(points, spans, terrain=None, stations=64, half_width=15.0, depth=80.0, limit=7.0, towers=None,
+                  cut_radius=9.0):
+    """The longitudinal section of every accepted piece of ``spans``: station by station along the wire,
+    the rows of ``points`` (float32 [n,3] on the device) that lie within ``half_width`` metres (horizontal) of its track
+    and at most ``depth`` metres below its sag curve - how many, how many at most ``limit`` metres below it (the
+    vertical distance), the smallest vertical distance and its row.  ``spans`` is ``conductor_spans``' dict for the same
+    ``points``; the accepted pieces, their curves (``ops.span_curves``) and the skipped rows - the conductors and, with
+    ``towers``, the rows within ``cut_radius`` of a tower - are exactly ``conductor_clearance``'s; ``ops.span_section``
+    does the rest.  A row counts under every piece it lies under, not only the nearest.  The wire height is the
+    parabola's.
+
+    Returns dict: ``pieces`` (int64 [P]: the accepted pieces' ids, ascending); over the [P,B] cells, B = ``stations``:
+    ``m`` (float64: the station's centre, metres from the piece's centre along the track), ``xy`` ([P,B,2] float64:
+    that centre in the frame of ``points``), ``wire_z`` (float64: the wire's height there), ``count`` and ``violations``
+    (int64), ``min_vertical`` (float32, metres; +inf for an empty cell), ``min_row`` (int64; -1), ``top`` ([P,B,3]
+    float32: the coordinates of ``min_row``, NaN where there is none) and ``ground`` (float64: ``ops.terrain_sample`` of
+    ``terrain`` - ``terrain_model``'s dict in the same frame - under the station centres; NaN without ``terrain`` or
+    where the model has no value); per row ``v`` (float32 [n]: the smallest vertical distance over the pieces the row
+    lies under, +inf if none or skipped), ``span`` (int32 [n]: that piece's id in the span table, -1 if none) and
+    ``station`` (int32 [n]; -1); and ``table``, a dict over the K pieces of the span table: ``count`` and
+    ``violations`` (int64, summed over the stations), ``min_vertical`` (float32; +inf without a row), ``min_station``
+    (the lowest station that attains it, -1 without), ``min_row`` (that station's row, -1 without) and ``min_point``
+    ([K,3] float32, NaN without).  No accepted piece: P = 0 and a table without rows; nothing is raised.
+    Asynchronous."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32:
+        raise TypeError("points must be a float32 CUDA/HIP tensor (no CPU fallback in the product path)")
+    points = points.reshape(-1, 3).contiguous()
+    n, dev = int(points.shape[0]), points.device
+    wire = spans["wire"]
+    if wire.numel() != n:
+        raise ValueError("spans must be conductor_spans' result for the same points")
+    B = ops.check_stations(stations)
+    K = int(spans["nclusters"])
+    idx = torch.nonzero(spans["accepted"]).reshape(-1)                        # accepted pieces, ascending
+    P = int(idx.numel())
+    curves = ops.span_curves(spans["table"], spans["frames"], spans["ext"])[idx].contiguous()
+    near = _near_towers(points, towers, cut_radius)
+    skip = wire if near is None else (wire | near)
+    res = ops.span_section(points, curves, B, half_width, depth, limit, skip=skip)
+    span = res["span"]                                                        # (all -1 without an accepted piece)
+    if P:
+        span = torch.where(span >= 0, idx.to(torch.int32)[span.clamp(min=0).long()], torch.full_like(span, -1))
+    cx, cy, cz, ux, uy, a, b, c, m0, m1 = (curves[:, i:i + 1] for i in range(10))
+    step = (m1 - m0) / float(B)
+    m = m0 + ((torch.arange(B, dtype=torch.float64, device=dev)[None, :] + 0.5) * step)
+    xy = torch.stack([cx + (m * ux), cy + (m * uy)], dim=2)
+    wire_z = cz + (a + (m * (b + (c * m))))
+    nan = float("nan")
+    if terrain is not None and P:
+        ground = ops.terrain_sample(xy.reshape(-1, 2).contiguous(), terrain["grid"], terrain["ground"]).reshape(P, B)
+    else:
+        ground = torch.full((P, B), nan, dtype=torch.float64, device=dev)
+    min_row = res["min_row"]
+    top = torch.full((P, B, 3), nan, dtype=torch.float32, device=dev)
+    has = min_row >= 0
+    if n and P:
+        top[has] = points[min_row[has]]
+    count = torch.zeros((K,), dtype=torch.int64, device=dev)
+    violations = torch.zeros((K,), dtype=torch.int64, device=dev)
+    min_vertical = torch.full((K,), float("inf"), dtype=torch.float32, device=dev)
+    min_station = torch.full((K,), -1, dtype=torch.int64, device=dev)
+    tab_row = torch.full((K,), -1, dtype=torch.int64, device=dev)
+    min_point = torch.full((K, 3), nan, dtype=torch.float32, device=dev)
+    if P:
+        low = res["min_v"].min(dim=1).values
+        first = (res["min_v"] == low[:, None]).to(torch.int64).argmax(dim=1)
+        some = torch.isfinite(low)
+        count[idx], violations[idx], min_vertical[idx] = res["count"].sum(dim=1), res["violations"].sum(dim=1), low
+        min_station[idx] = torch.where(some, first, torch.full_like(first, -1))
+        tab_row[idx] = torch.where(some, min_row.gather(1, first[:, None]).reshape(-1), torch.full_like(first, -1))
+        got = tab_row >= 0
+        if n:
+            min_point[got] = points[tab_row[got]]
+    table = dict(count=count, violations=violations, min_vertical=min_vertical, min_station=min_station,
+                 min_row=tab_row, min_point=min_point)
+    return dict(pieces=idx, m=m, xy=xy, wire_z=wire_z, count=res["count"], violations=res["violations"],
+                min_vertical=res["min_v"], min_row=min_row, top=top, ground=ground, v=res["v"], span=span,
+                station=res["station"], table=table)
+
+
 def terrain_cells(cell, window, max_gap):
     """(R, G): the opening's window radius and the fill's gap in cells for ``window`` and ``max_gap`` in metres -
     ``R = ceil(window / (2·cell))``, ``G = ceil(max_gap / cell)``; ValueError beyond the library's limits"""

@@ -97,6 +97,16 @@ knob is on) - and ``output_towers/tree_fall_info.csv`` get
 row of every 2 m cell that strikes a conductor when it falls or comes within ``limit`` metres of one, in world
 coordinates, with its height, piece, distance and margin.  It logs one extra line; a failure is handled like one of
 ``SPANS``.  The returned tower dicts are the same with and without it.
+``SECTION`` (env PCH_SECTION="half_width,limit[,stations[,depth]]", e.g. "15,7" or "15,7,64,80"; unset or empty = off;
+needs ``SPANS`` - importing the module with PCH_SECTION set and PCH_SPANS unset raises ValueError): behind the other span
+steps, the longitudinal section of every accepted wire piece (pipeline.span_sections; the skipped rows are
+``CLEARANCE``'s): the piece is cut into ``stations`` stations (default 64), and
+``output_towers/section_info.csv`` gets one line per piece and station: the station's centre in world coordinates, the
+wire's height there, the ground's (``TERRAIN``'s model when that knob is on, else NaN), the rows within ``half_width``
+metres beside the track and at most ``depth`` metres (default 80) below the wire, those at most ``limit`` metres below
+it (the vertical distance), the smallest vertical distance and the highest return in world coordinates.  A row under
+several phases counts under each.  It logs one extra line; a failure is handled like one of ``SPANS``.  The returned
+tower dicts are the same with and without it.
 ``TOWER_PROFILE`` (env PCH_TOWER_PROFILE="dz[,height[,arm_window,arm_excess]]", e.g. "0.5"; unset or empty = off; needs
 no other knob): behind the tower table, the accepted towers' clusters are cut into height slices of ``dz`` metres over
 ``height`` metres (default 64; at most 256 slices) and their cross-arm levels are read off the slice widths
@@ -333,6 +343,37 @@ def treefall_from_env(value, spans=True, terrain=True, frame="reference"):
 TREEFALL = treefall_from_env(os.environ.get("PCH_TREEFALL"), spans=SPANS is not None, terrain=TERRAIN is not None,
                              frame=FRAME)
 TREEFALL_COLUMNS = ("ID", "row", "x", "y", "ground_z", "height", "span", "distance", "margin", "hazard")
+
+
+def section_from_env(value, spans=True):
+    """SECTION of an environment value: None (off) when unset or empty, else dict(half_width, limit, stations, depth)
+    from "half_width,limit[,stations[,depth]]" - two to four numbers; half_width finite and > 0, stations an integer in
+    1..128 (default 64), depth (default 80.0) and limit finite with 0 < limit <= depth.  ``spans``: whether SPANS is on -
+    the sections are those of its pieces, so a value without it is refused (ValueError)"""
+    if value is None or not value.strip():
+        return None
+    parts = [t.strip() for t in value.split(",")]
+    if len(parts) not in (2, 3, 4):
+        raise ValueError(f"PCH_SECTION takes \"half_width,limit[,stations[,depth]]\", got {value!r}")
+    half_width, limit = float(parts[0]), float(parts[1])
+    stations = int(parts[2]) if len(parts) >= 3 else 64
+    depth = float(parts[3]) if len(parts) == 4 else 80.0
+    if not (np.isfinite(half_width) and half_width > 0.0):
+        raise ValueError(f"PCH_SECTION: half_width must be finite and > 0, got {parts[0]!r}")
+    if not 1 <= stations <= 128:
+        raise ValueError(f"PCH_SECTION: stations must be in 1..128, got {parts[2]!r}")
+    if not (np.isfinite(depth) and depth > 0.0):
+        raise ValueError(f"PCH_SECTION: depth must be finite and > 0, got {depth!r}")
+    if not (np.isfinite(limit) and 0.0 < limit <= depth):
+        raise ValueError(f"PCH_SECTION: limit must be finite with 0 < limit <= depth, got {parts[1]!r}")
+    if not spans:
+        raise ValueError("PCH_SECTION needs PCH_SPANS: the sections are those of the span table's pieces")
+    return dict(half_width=half_width, limit=limit, stations=stations, depth=depth)
+
+
+SECTION = section_from_env(os.environ.get("PCH_SECTION"), spans=SPANS is not None)
+SECTION_COLUMNS = ("ID", "station", "m", "x", "y", "wire_z", "ground_z", "count", "violations", "min_vertical",
+                   "min_row", "top_x", "top_y", "top_z")
 
 
 def tower_profile_from_env(value):
@@ -678,6 +719,18 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
             except (ValueError, RuntimeError) as e:
                 log(f"⚠️ 倒树隐患计算失败: {str(e)}")
                 return tower_obbs
+        # ---- opt-in: the longitudinal section of every piece, station by station
+        if SECTION:
+            try:
+                section = pipeline.span_sections(stage_b_points, spans, terrain=terrain, towers=local,
+                                                 cut_radius=SPANS["cut_radius"], **SECTION)
+                rows = section_rows(section, cen)
+                write_section_csv(output_dir / "section_info.csv", rows)
+                clock.mark("span sections")
+                log(section_line(section, rows, SECTION))
+            except (ValueError, RuntimeError) as e:
+                log(f"⚠️ 导线断面计算失败: {str(e)}")
+                return tower_obbs
     # ---- opt-in: the accepted towers' slice tables, cross-arm levels and nominal height
     if TOWER_PROFILE and tower_rows:
         try:
@@ -834,6 +887,46 @@ def wind_line(wind, rows, knob):
     return (f"🌬️ 风偏净空: 最大风偏角 {knob['angle']:g}°，半径 {knob['radius']:g} m，限距 {knob['limit']:g} m；"
             f"半径内 {int(near)} 点，越限 {int(wind['violating'].sum())} 点，越限线段 {int(breached)}/{len(rows)}，"
             f"最小净空 {closest:.3f} m")
+
+
+def section_rows(section, centroid):
+    """the lines of section_info.csv for a result of pipeline.span_sections: one list per accepted piece and station in
+    SECTION_COLUMNS' order, the station's centre, the wire, the ground and the highest return moved to world coordinates
+    by ``centroid`` (3 float64; NaN without a row or without a ground value)"""
+    S = {key: section[key].cpu().numpy() for key in ("pieces", "m", "xy", "wire_z", "ground", "count", "violations",
+                                                      "min_vertical", "min_row", "top")}
+    rows = []
+    for p, k in enumerate(S["pieces"]):
+        for j in range(S["m"].shape[1]):
+            top = S["top"][p, j].astype(np.float64) + centroid
+            rows.append([f"span_{int(k)}", j, float(S["m"][p, j]), float(S["xy"][p, j, 0] + centroid[0]),
+                         float(S["xy"][p, j, 1] + centroid[1]), float(S["wire_z"][p, j] + centroid[2]),
+                         float(S["ground"][p, j] + centroid[2]), int(S["count"][p, j]), int(S["violations"][p, j]),
+                         float(S["min_vertical"][p, j]), int(S["min_row"][p, j]), float(top[0]), float(top[1]),
+                         float(top[2])])
+    return rows
+
+
+def write_section_csv(path, rows):
+    """section_info.csv: a header line (SECTION_COLUMNS) and one line per accepted piece and station, floats with
+    repr's digits"""
+    import csv
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.writer(f)
+        w.writerow(SECTION_COLUMNS)
+        for r in rows:
+            w.writerow([repr(float(v)) if isinstance(v, (float, np.floating)) else v for v in r])
+
+
+def section_line(section, rows, knob):
+    """the extra log line of SECTION for a result of pipeline.span_sections and its csv lines"""
+    under = sum(r[7] for r in rows)
+    over = sum(r[8] for r in rows)
+    breached = sum(1 for r in rows if r[8] > 0)
+    closest = min([r[9] for r in rows], default=float("inf"))
+    return (f"📐 导线断面: 走廊半宽 {knob['half_width']:g} m，深度 {knob['depth']:g} m，限距 {knob['limit']:g} m，"
+            f"每段 {knob['stations']} 站；走廊内 {int(under)} 点次，越限 {int(over)} 点次，"
+            f"越限区段 {int(breached)}/{len(rows)}，最小垂直距离 {closest:.3f} m")
 
 
 def ground_clearance_rows(spans, over, centroid):
