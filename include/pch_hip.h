@@ -1086,6 +1086,97 @@ int pch_span_section_f32(const float* xyz, const uint8_t* skip, int64_t n, const
                          int64_t* out_min_row /* [K,B] */, int64_t* out_stats /* [3], may be NULL */, void* ws,
                          size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ canopy grid and tree crowns, opt-in
+ * The vegetation as trees: the tallest return above the ground per cell of a fine xy grid (the canopy height model),
+ * the cells that are tree tops, the crown of cells that belongs to every top, one table record per tree, and for every
+ * row the tree it belongs to.
+ *
+ * The rule.  Arithmetic is float64 without FMA (the library is built with -ffp-contract=off), with parentheses as
+ * written; comparisons of sm are float32 comparisons.  tests/canopy_cases.py follows it literally in numpy.
+ *   Frames and participation.  The row frame, the cell rule and PchTerrainGrid are the terrain rule's.  Two grids take
+ *     part: the terrain grid with its ground array, as pch_terrain_height_f32 takes them, and a canopy grid, a second
+ *     PchTerrainGrid in the same frame, usually finer, with at most PCH_TERRAIN_MAX_CELLS cells.
+ *         g = g(X, Y) on the terrain grid;  Hd = Z - g;  H = (float)Hd
+ *     A row takes part iff skip[i] == 0, X, Y, Z are finite, it is inside the canopy grid, g is not NaN, and
+ *         h_min <= Hd and Hd <= h_max
+ *     tested on the double, as in the tree-fall rule.  0 <= h_min <= h_max, both finite.  One __device__ function
+ *     decides this for pch_canopy_top_f32 and pch_canopy_rows_f32: the two never disagree.
+ *   1. Canopy top (pch_canopy_top_f32).  Per canopy cell c: count[c] (int32) is the number of rows that take part;
+ *     top[c] (float32) is the H with the largest key(H) of the terrain rule, so -0.0 sorts below +0.0, NaN where
+ *     count[c] == 0; top_row[c] (int32) is the lowest row index that attains it, -1 without a row.  The optional
+ *     out_height (float32 [n]) is H for every row with finite coordinates, whether it takes part or not, NaN where g is
+ *     NaN and for a row that is not finite: pch_terrain_height_f32's out_height bit for bit.  The optional out_stats
+ *     (int64 [2]): the rows that took part and the (tile, cell) flushes - figures for measurement, not part of the rule.
+ *   2. Smoothing, with radius S in cells, 0 <= S <= PCH_CANOPY_MAX_SMOOTH.  sm[c] is NaN iff top[c] is NaN: empty cells
+ *     are not filled.  Otherwise, over the square window (2S+1)^2 clipped at the grid edge, fy ascending outside and fx
+ *     ascending inside: start with sum = 0.0; cnt = 0; for each non-NaN top[c'] in that order
+ *         sum = sum + (double)top[c'];  cnt = cnt + 1
+ *     and then sm[c] = (float)(sum / (double)cnt).  With S == 0, sm == top bit for bit.
+ *   3. The order "beats", on cells whose sm is not NaN.
+ *         c' beats c iff sm[c'] > sm[c], or sm[c'] == sm[c] and c' < c
+ *     in float32, so -0.0 and +0.0 tie and the index decides.  A strict total order; "the greatest" of a set is the one
+ *     that beats all others.
+ *   4. Window of a cell.
+ *         r = r0 + (r1 * (double)sm[c]);  W = (int)floor(r / cell), clamped to [1, PCH_CANOPY_MAX_WINDOW]
+ *     with r0 >= 0 and r1 >= 0, both finite (W = 1 should r / cell be NaN).  The window of c is the set of cells
+ *     c' != c inside the grid with integer dx*dx + dy*dy <= W*W whose sm is not NaN.
+ *   5. Tree tops.  c is a top iff sm[c] is not NaN, (double)sm[c] >= top_min, and no cell of its window beats it.
+ *     top_min is finite and >= 0.
+ *   6. Parent, for every cell with non-NaN sm.  Let b be the greatest of its up to eight neighbours (clipped at the
+ *     edge, non-NaN only).  If b exists and beats c, parent[c] = b.  Otherwise, if some cell of its window beats c,
+ *     parent[c] is the greatest cell of the window.  Otherwise parent[c] = c.  Every step goes to a cell that beats the
+ *     one before, so chains end in a fixed point root[c]: a top, or a cell below top_min.
+ *   7. Crowns.  Tops are numbered t = 0, 1, ... in ascending cell index.  With the crown radius Rc in cells,
+ *     1 <= Rc <= PCH_CANOPY_MAX_CROWN, and crown_frac in [0, 1]: tree[c] = t iff sm[c] is not NaN, root[c] is top t,
+ *         (double)sm[c] >= (crown_frac * (double)sm[root[c]])
+ *     and integer (64-bit) dx*dx + dy*dy <= Rc*Rc from the root cell.  Otherwise tree[c] = -1.
+ *   8. Tree table, per tree t: top_cell (int32): the cell of the top; cells (int32): the crown cells, the top among
+ *     them; rows (int64): the sum of count over the crown; max_height (float32): the largest top[c] over the crown by
+ *     key(.); max_row (int32): the lowest top_row[c] among the crown cells that attain max_height.  The tables have
+ *     tree_cap entries, 1 <= tree_cap <= PCH_TERRAIN_MAX_CELLS.  out_ntrees (int32 [1]) holds the true number of tops;
+ *     trees >= tree_cap are not written to the tables, tree[] keeps the true ids.  Entries from the number of tops on
+ *     read (-1, 0, 0, NaN, -1).
+ *   9. Rows (pch_canopy_rows_f32).  out_tree[i] (int32) is tree[] of the row's canopy cell for a row that takes part,
+ *     and -1 otherwise.
+ *
+ * How: step 1 sweeps tiles of 1024 rows (every row and skip load issued before anything is waited for), combining a
+ * tile's rows in an open-addressed table of 2048 slots in LDS - cell id, the 64-bit key (key(H) << 32) | ~row, whose
+ * largest value is the tallest return and among equals the lowest row, and a count; 0 is "empty" - and every occupied
+ * slot then issues one 64-bit atomicMax on a key grid and one atomicAdd on count; a small kernel decodes the keys.  Only
+ * rows that take part reach the table.  The grid-sized steps are one thread per cell: (2S+1)^2 reads for sm, the window
+ * and the neighbours for tops and parents, ceil(log2(cells)) rounds of pointer doubling between two buffers for the
+ * roots, a three-launch ordered count / scan / number of the top flags, then crown and table by integer atomics per
+ * tree (max_height and max_row in one 64-bit atomicMax of the same packing).  Integer atomics only, nothing waits on
+ * another workgroup: the same input gives the same bits on every run.
+ *
+ * 0 <= n < 2^31; the limits of both grids are terrain's (else PCH_ERR_ARG, as h_min, h_max, S, r0, r1, top_min,
+ * crown_frac, Rc or tree_cap outside the limits above, a null buffer that is needed and a host pointer where a device
+ * pointer is needed; an argument error writes nothing).  xyz float32 [n,3], skip uint8 [n] or NULL, ground float32 over
+ * the terrain grid; top / out_smooth float32, top_row / count / tree int32 over the canopy grid; the five tables
+ * [tree_cap] - all device; sub3_host 3 floats on the host or NULL; the grids on the host.  ws: the caller's, at least
+ * the matching *_ws_bytes bytes - pure host code, 0 for sizes out of range (smaller: PCH_ERR_WORKSPACE);
+ * pch_canopy_rows_f32 needs none.  With n == 0 every cell is (NaN, -1, 0) and no launch reads a null pointer.  Every call
+ * enqueues on the caller's stream and returns; no host read. */
+#define PCH_CANOPY_MAX_SMOOTH 8
+#define PCH_CANOPY_MAX_WINDOW 32
+#define PCH_CANOPY_MAX_CROWN  256
+size_t pch_canopy_top_ws_bytes(int64_t n, int32_t ncells);
+int pch_canopy_top_f32(const float* xyz, const uint8_t* skip, int64_t n, const float* sub3_host,
+                       const PchTerrainGrid* terrain_host, const float* ground, const PchTerrainGrid* canopy_host,
+                       double h_min, double h_max, float* out_top, int32_t* out_top_row, int32_t* out_count,
+                       float* out_height /* [n], may be NULL */, int64_t* out_stats /* [2], may be NULL */, void* ws,
+                       size_t ws_bytes, void* stream);
+size_t pch_canopy_trees_ws_bytes(int32_t ncells, int32_t tree_cap);
+int pch_canopy_trees_f32(const float* top, const int32_t* top_row, const int32_t* count,
+                         const PchTerrainGrid* canopy_host, int32_t smooth, double r0, double r1, double top_min,
+                         double crown_frac, int32_t crown_cells, int32_t tree_cap, float* out_smooth /* may be NULL */,
+                         int32_t* out_tree, int32_t* out_ntrees /* [1] */, int32_t* out_top_cell, int32_t* out_cells,
+                         int64_t* out_rows, float* out_max_height, int32_t* out_max_row, void* ws, size_t ws_bytes,
+                         void* stream);
+int pch_canopy_rows_f32(const float* xyz, const uint8_t* skip, int64_t n, const float* sub3_host,
+                        const PchTerrainGrid* terrain_host, const float* ground, const PchTerrainGrid* canopy_host,
+                        double h_min, double h_max, const int32_t* tree, int32_t* out_tree, void* stream);
+
 /* ------------------------------------------------------------------ stage D1, fast mode
  * The reference boxes every cluster with trimesh (utils/tower_extraction.py:137-139:
  * trimesh.PointCloud(cluster_points).bounding_box_oriented): qhull's 3-D hull of the whole cluster, then a

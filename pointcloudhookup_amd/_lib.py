@@ -117,6 +117,13 @@ _SIGS = {
     "pch_span_section_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "pch_span_section_f32": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _i32, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _sz, _vp]),
+    "pch_canopy_top_ws_bytes": (_sz, [_i64, _i32]),
+    "pch_canopy_top_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                     _vp]),
+    "pch_canopy_trees_ws_bytes": (_sz, [_i32, _i32]),
+    "pch_canopy_trees_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f64, _f64, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pch_canopy_rows_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp]),
     "pch_crop_aabb_ws_bytes": (_sz, [_i64]),
     "pch_crop_aabb_f64": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pch_crop_boxes_ws_bytes": (_sz, [_i64, _i32, _i64]),

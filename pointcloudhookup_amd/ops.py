@@ -21,7 +21,8 @@ DESIGN.md sections 5a, 5b, 5c; on a grouping: cluster_moments, span_frames, clus
 curves: span_curves, span_segments, clearance - section 5e; on a cloud and a grid: terrain_grid, terrain_low,
 terrain_ground, terrain_height, terrain_sample, span_ground_profile - section 5f; on a cloud and the curves swung by
 wind: swing_heads, swing_segments, swing_clearance - section 5i; on a cloud and the curves, station by station:
-span_section - section 5j.
+span_section - section 5j; on a cloud, a terrain grid and a canopy grid: canopy_grid, canopy_top, canopy_trees,
+canopy_rows - section 5k.
 """
 from __future__ import annotations
 
@@ -2143,6 +2144,164 @@ def treefall(points, curves, segs, grid, ground, h_min, h_max, grow, limit, sub=
                min_row=min_row, max_height=max_height, max_row=max_row)
     if want_stats:
         out["stats"] = stats
+    return out
+
+
+# ------------------------------------------------------------- canopy grid and tree crowns, opt-in
+CANOPY_TILE = 1024             # rows per workgroup of the canopy sweeps (cn_top_k, cn_rows_k): the sizes tests straddle
+CANOPY_MAX_SMOOTH = 8          # PCH_CANOPY_MAX_SMOOTH, cells
+CANOPY_MAX_WINDOW = 32         # PCH_CANOPY_MAX_WINDOW, cells
+CANOPY_MAX_CROWN = 256         # PCH_CANOPY_MAX_CROWN, cells
+CANOPY_TABLE_KEYS = ("top_cell", "cells", "rows", "max_height", "max_row")
+
+
+def check_canopy_rule(h_min=0.0, h_max=0.0, smooth=0, r0=0.0, r1=0.0, top_min=0.0, crown_frac=0.0, crown_cells=1):
+    """(h_min, h_max, smooth, r0, r1, top_min, crown_frac, crown_cells) as floats and ints; ValueError unless
+    0 <= h_min <= h_max, r0 >= 0, r1 >= 0 and top_min >= 0, all finite, smooth is an integer in 0..8, crown_frac lies in
+    [0, 1] and crown_cells is an integer in 1..256"""
+    import math
+    h_min, h_max, r0, r1, top_min, crown_frac = (float(v) for v in (h_min, h_max, r0, r1, top_min, crown_frac))
+    if not (all(math.isfinite(v) for v in (h_min, h_max, r0, r1, top_min)) and 0.0 <= h_min <= h_max and r0 >= 0.0
+            and r1 >= 0.0 and top_min >= 0.0):
+        raise ValueError("h_min, h_max, r0, r1 and top_min must be finite with 0 <= h_min <= h_max, r0 >= 0, r1 >= 0 and "
+                         f"top_min >= 0, got {h_min!r}, {h_max!r}, {r0!r}, {r1!r}, {top_min!r}")
+    if not 0.0 <= crown_frac <= 1.0:
+        raise ValueError(f"crown_frac must lie in [0, 1], got {crown_frac!r}")
+    for name, v, lo, top in (("smooth", smooth, 0, CANOPY_MAX_SMOOTH), ("crown_cells", crown_cells, 1, CANOPY_MAX_CROWN)):
+        if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= top:
+            raise ValueError(f"{name} must be an integer in {lo}..{top}, got {v!r}")
+    return h_min, h_max, int(smooth), r0, r1, top_min, crown_frac, int(crown_cells)
+
+
+def canopy_grid(grid, cell):
+    """The canopy grid of ``cell`` metres over the extent of a terrain grid (a dict as ``terrain_grid`` returns it), in
+    the same frame and from the same origin: per axis ``n = floor((b - a) / cell) + 1`` with ``a`` the origin and
+    ``b = a + n_terrain * cell_terrain`` the far edge - ``_terrain_grid_of``'s arithmetic on the extent.  ValueError
+    beyond 2^24 cells."""
+    import math
+    cell = float(cell)
+    if not (cell > 0.0 and math.isfinite(cell)):
+        raise ValueError(f"cell must be positive and finite, got {cell!r}")
+    out = dict(cell=cell)
+    for name in ("x", "y"):
+        a = float(grid[name + "0"])
+        b = a + int(grid["n" + name]) * float(grid["cell"])
+        out[name + "0"], out["n" + name] = a, int(math.floor((b - a) / cell)) + 1
+    if out["nx"] * out["ny"] > TERRAIN_MAX_CELLS:
+        raise ValueError(f"cell {cell:g} gives a canopy grid of {out['nx']} x {out['ny']} cells, more than 2^24 = "
+                         f"{TERRAIN_MAX_CELLS}")
+    return out
+
+
+def _canopy_rows_args(points, grid, ground, canopy_grid, skip, who):
+    points = _need_cuda(points, torch.float32, "points").reshape(-1, 3)
+    g, cg = _terrain_grid_c(grid), _terrain_grid_c(canopy_grid)
+    ground = _terrain_cells(ground, torch.float32, "ground", g)
+    n = points.shape[0]
+    if n >= 1 << 31:
+        raise ValueError(f"{who} takes fewer than 2^31 rows per call")
+    if skip is not None:
+        if isinstance(skip, torch.Tensor) and skip.dtype == torch.bool:
+            skip = skip.view(torch.uint8)
+        skip = _need_cuda(skip, torch.uint8, "skip").reshape(-1)
+        if skip.numel() != n:
+            raise ValueError("skip must hold one entry per row")
+    return points, g, cg, ground, skip, n
+
+
+def canopy_top(points, grid, ground, canopy_grid, h_min, h_max, sub=None, skip=None, want_height=False,
+               want_stats=False):
+    """The canopy height model (pch_canopy_top_f32; the rule is in include/pch_hip.h): dict of device tensors over the
+    cells of ``canopy_grid`` - ``top`` float32 [ny,nx], the largest height ``H = z - ground`` above the terrain model
+    (``grid``, ``ground`` as ``terrain_height`` takes them) over the rows of ``fl32(points - sub)`` that take part
+    (not skipped, finite, inside the canopy grid, over ground, ``h_min <= H <= h_max``), NaN for a cell without one;
+    ``top_row`` int32 [ny,nx], the lowest row that attains it (-1 without) and ``count`` int32 [ny,nx].  ``want_height``
+    adds ``height`` float32 [n], ``terrain_height``'s bit for bit; ``want_stats`` adds ``stats`` int64 [2]: the rows
+    that took part and the (tile, cell) flushes.  The same input gives the same bits on every run.  Asynchronous."""
+    L = _lib.lib()
+    points, g, cg, ground, skip, n = _canopy_rows_args(points, grid, ground, canopy_grid, skip, "canopy_top")
+    h_min, h_max = check_canopy_rule(h_min=h_min, h_max=h_max)[:2]
+    dev, ncells = points.device, cg.nx * cg.ny
+    s3 = _sub3(sub)
+    with torch.cuda.device(dev):
+        top = torch.empty((cg.ny, cg.nx), dtype=torch.float32, device=dev)
+        top_row = torch.empty((cg.ny, cg.nx), dtype=torch.int32, device=dev)
+        count = torch.empty((cg.ny, cg.nx), dtype=torch.int32, device=dev)
+        height = torch.empty((n,), dtype=torch.float32, device=dev) if want_height else None
+        stats = torch.empty((2,), dtype=torch.int64, device=dev) if want_stats else None
+        ws = _workspace(L.pch_canopy_top_ws_bytes(n, ncells), dev)
+        _lib.check(L.pch_canopy_top_f32(_ptr(points), _ptr(skip), n, _sub3_ptr(s3), _grid_ptr(g), _ptr(ground),
+                                        _grid_ptr(cg), h_min, h_max, _ptr(top), _ptr(top_row), _ptr(count),
+                                        _ptr(height), _ptr(stats), _ptr(ws), ws.numel(), _stream()))
+    out = dict(top=top, top_row=top_row, count=count)
+    if want_height:
+        out["height"] = height
+    if want_stats:
+        out["stats"] = stats
+    return out
+
+
+def canopy_trees(top, top_row, count, canopy_grid, smooth, r0, r1, top_min, crown_frac, crown_cells, tree_cap=None,
+                 want_smooth=False):
+    """Tree tops and crowns on a canopy height model (pch_canopy_trees_f32; the rule is in include/pch_hip.h): ``top``
+    smoothed over a square window of radius ``smooth`` cells; a cell is a top iff its smoothed height is at least
+    ``top_min`` and no cell within ``r0 + r1 * height`` (in cells, 1..32) beats it; every cell climbs to its greatest
+    neighbour until a top is reached and belongs to that top's crown if it stands at least ``crown_frac`` of the top's
+    height and lies within ``crown_cells`` cells of it.  Dict of device tensors - ``tree`` int32 [ny,nx] (-1: no tree),
+    ``ntrees`` (int) and over the T trees, numbered by ascending cell of the top, ``top_cell`` int32, ``cells`` int32,
+    ``rows`` int64, ``max_height`` float32 and ``max_row`` int32; ``want_smooth`` adds ``smooth`` float32 [ny,nx].
+    ``tree_cap`` (default ``min(cells, 2^20)``) bounds the tables; ValueError naming the cap if there are more trees.
+    Reads the number of trees once."""
+    L = _lib.lib()
+    cg = _terrain_grid_c(canopy_grid)
+    top = _terrain_cells(top, torch.float32, "top", cg)
+    top_row = _terrain_cells(top_row, torch.int32, "top_row", cg)
+    count = _terrain_cells(count, torch.int32, "count", cg)
+    _, _, smooth, r0, r1, top_min, crown_frac, crown_cells = check_canopy_rule(
+        smooth=smooth, r0=r0, r1=r1, top_min=top_min, crown_frac=crown_frac, crown_cells=crown_cells)
+    dev, ncells = top.device, cg.nx * cg.ny
+    cap = min(ncells, 1 << 20) if tree_cap is None else tree_cap
+    if isinstance(cap, bool) or int(cap) != cap or not 1 <= int(cap) <= TERRAIN_MAX_CELLS:
+        raise ValueError(f"tree_cap must be an integer in 1..2^24, got {tree_cap!r}")
+    cap = int(cap)
+    with torch.cuda.device(dev):
+        sm = torch.empty((cg.ny, cg.nx), dtype=torch.float32, device=dev) if want_smooth else None
+        tree = torch.empty((cg.ny, cg.nx), dtype=torch.int32, device=dev)
+        ntrees = torch.empty((1,), dtype=torch.int32, device=dev)
+        top_cell = torch.empty((cap,), dtype=torch.int32, device=dev)
+        cells = torch.empty((cap,), dtype=torch.int32, device=dev)
+        rows = torch.empty((cap,), dtype=torch.int64, device=dev)
+        max_height = torch.empty((cap,), dtype=torch.float32, device=dev)
+        max_row = torch.empty((cap,), dtype=torch.int32, device=dev)
+        ws = _workspace(L.pch_canopy_trees_ws_bytes(ncells, cap), dev)
+        _lib.check(L.pch_canopy_trees_f32(_ptr(top), _ptr(top_row), _ptr(count), _grid_ptr(cg), smooth, r0, r1, top_min,
+                                          crown_frac, crown_cells, cap, _ptr(sm), _ptr(tree), _ptr(ntrees),
+                                          _ptr(top_cell), _ptr(cells), _ptr(rows), _ptr(max_height), _ptr(max_row),
+                                          _ptr(ws), ws.numel(), _stream()))
+        T = int(ntrees.item())
+    if T > cap:
+        raise ValueError(f"{T} trees, more than tree_cap = {cap}: the tables are truncated; pass a larger tree_cap")
+    out = dict(tree=tree, ntrees=T, top_cell=top_cell[:T], cells=cells[:T], rows=rows[:T], max_height=max_height[:T],
+               max_row=max_row[:T])
+    if want_smooth:
+        out["smooth"] = sm
+    return out
+
+
+def canopy_rows(points, grid, ground, canopy_grid, h_min, h_max, tree, sub=None, skip=None):
+    """int32 [n], device: for every row of ``fl32(points - sub)`` that takes part by ``canopy_top``'s rule - the same
+    arguments - the entry of ``tree`` (int32 over ``canopy_grid``, ``canopy_trees``') for its cell, -1 for every other
+    row (pch_canopy_rows_f32).  Asynchronous."""
+    L = _lib.lib()
+    points, g, cg, ground, skip, n = _canopy_rows_args(points, grid, ground, canopy_grid, skip, "canopy_rows")
+    h_min, h_max = check_canopy_rule(h_min=h_min, h_max=h_max)[:2]
+    tree = _terrain_cells(tree, torch.int32, "tree", cg)
+    dev = points.device
+    s3 = _sub3(sub)
+    with torch.cuda.device(dev):
+        out = torch.empty((n,), dtype=torch.int32, device=dev)
+        _lib.check(L.pch_canopy_rows_f32(_ptr(points), _ptr(skip), n, _sub3_ptr(s3), _grid_ptr(g), _ptr(ground),
+                                         _grid_ptr(cg), h_min, h_max, _ptr(tree), _ptr(out), _stream()))
     return out
 
 

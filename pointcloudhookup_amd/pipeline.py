@@ -544,6 +544,125 @@ def _tree_records(rows, xyz, under, height, span, dist2, hazard, cell, grow):
             for j, p in enumerate(pick)]
 
 
+CANOPY_TREE_KEYS = ops.CANOPY_TABLE_KEYS + ("x", "y", "z", "ground", "crown_area")
+BY_TREE_KEYS = ("tree", "row", "x", "y", "ground", "height", "rows", "strikes", "hazard", "min_row", "distance", "margin",
+                "span")
+
+
+def canopy_cells(cell, crown_radius):
+    """the crown radius in cells for ``crown_radius`` metres, ``ceil(crown_radius / cell)`` as ``terrain_cells`` converts
+    its gap, at least 1; ValueError beyond the library's limit"""
+    import math
+    cell, crown_radius = float(cell), float(crown_radius)
+    if not (math.isfinite(cell) and cell > 0.0):
+        raise ValueError(f"cell must be finite and > 0, got {cell!r}")
+    if not (math.isfinite(crown_radius) and crown_radius >= 0.0):
+        raise ValueError(f"crown_radius must be finite and >= 0, got {crown_radius!r}")
+    Rc = max(1, math.ceil(crown_radius / cell))
+    if Rc > ops.CANOPY_MAX_CROWN:
+        raise ValueError(f"crown_radius {crown_radius:g} m at cell {cell:g} m is {Rc} cells; the limit is "
+                         f"{ops.CANOPY_MAX_CROWN} cells ({ops.CANOPY_MAX_CROWN * cell:g} m)")
+    return int(Rc)
+
+
+def tree_segments(points, terrain, sub=None, skip=None, cell=0.5, h_min=2.0, h_max=45.0, smooth=1, r0=1.0, r1=0.05,
+                  top_min=5.0, crown_frac=0.5, crown_radius=8.0):
+    """The vegetation of ``points`` (float32 [n,3] on the device) as trees: a canopy grid of ``cell``
+    metres over the extent of ``terrain`` (``terrain_model``'s dict, in the same frame; with ``sub`` the rows are
+    ``fl32(points - sub)``) holds the tallest return between ``h_min`` and ``h_max`` above the ground per cell
+    (``ops.canopy_top``); smoothed over ``smooth`` cells, a cell of at least ``top_min`` that no cell within
+    ``r0 + r1 * height`` metres beats is a tree top, every cell climbs to its top and belongs to its crown if it stands at
+    least ``crown_frac`` of the top's height within ``crown_radius`` metres of it (``ops.canopy_trees``), and every row
+    gets the tree of its cell (``ops.canopy_rows``).  ``skip`` (uint8 or bool [n]): rows that are no vegetation - the
+    conductors, the rows near towers.
+
+    Returns dict: ``grid`` and ``canopy_grid``, ``top``, ``count``, ``smooth`` and ``tree`` over the canopy cells,
+    ``row_tree`` (int32 [n], -1 for a row of no tree), ``height`` (float32 [n], ``height_above_ground``'s), ``ntrees``
+    and ``trees``, a dict of tensors over the T trees (CANOPY_TREE_KEYS): ``top_cell``, ``cells``, ``rows``,
+    ``max_height`` and ``max_row`` of the tree table, ``x``, ``y``, ``z`` of row ``max_row`` in the rows' frame
+    (float64), the ``ground`` under it (``ops.terrain_sample``) and ``crown_area = cells * cell^2``; ``points``, ``sub``,
+    ``ground`` and the rule are kept for ``danger_trees_by_tree``.  ValueError: a crown radius beyond 256 cells, a canopy grid beyond
+    2^24 cells, more than 2^20 trees.  Synchronises."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32:
+        raise TypeError("points must be a float32 CUDA/HIP tensor (no CPU fallback in the product path)")
+    points = points.reshape(-1, 3).contiguous()
+    dev = points.device
+    Rc = canopy_cells(cell, crown_radius)
+    grid, ground = terrain["grid"], terrain["ground"]
+    cg = ops.canopy_grid(grid, cell)
+    t = ops.canopy_top(points, grid, ground, cg, h_min, h_max, sub=sub, skip=skip, want_height=True)
+    seg = ops.canopy_trees(t["top"], t["top_row"], t["count"], cg, smooth, r0, r1, top_min, crown_frac, Rc,
+                           want_smooth=True)
+    row_tree = ops.canopy_rows(points, grid, ground, cg, h_min, h_max, seg["tree"], sub=sub, skip=skip)
+    s3 = ops._sub3(sub)
+    at = points[seg["max_row"].long()]
+    if s3 is not None:
+        at = at - torch.tensor(list(s3), dtype=torch.float32, device=dev)
+    at = at.to(torch.float64)
+    trees = {key: seg[key] for key in ops.CANOPY_TABLE_KEYS}
+    trees.update(x=at[:, 0], y=at[:, 1], z=at[:, 2], ground=ops.terrain_sample(at[:, :2].contiguous(), grid, ground),
+                 crown_area=seg["cells"].to(torch.float64) * (float(cell) * float(cell)))
+    return dict(grid=grid, ground=ground, canopy_grid=cg, top=t["top"], count=t["count"], smooth=seg["smooth"], tree=seg["tree"],
+                row_tree=row_tree, height=t["height"], ntrees=seg["ntrees"], trees=trees, points=points, sub=sub,
+                rule=dict(cell=float(cell), h_min=float(h_min), h_max=float(h_max), crown_cells=Rc))
+
+
+def danger_trees_by_tree(danger, segments, grow=0.0, cell=2.0):
+    """``danger_trees``' hazard rows per tree: ``danger`` is its result and ``segments`` ``tree_segments``' result for the
+    same points (and the same ``sub``).  One record (a dict, BY_TREE_KEYS) per tree that owns a hazard row: ``tree``,
+    the position of its tallest return (``row``, ``x``, ``y``, the ``ground`` under it and ``height``), the number of
+    its hazard ``rows`` and ``strikes``, the worst class ``hazard``, and of the hazard row with the smallest
+    ``margin = distance - (height + grow)`` - ties to the lowest row - ``min_row``, ``distance``, ``margin`` and ``span``.
+    Hazard rows of no tree are reported as records of their own with ``tree = -1``, binned into xy cells of ``cell``
+    metres exactly as ``danger_trees`` bins its ``trees`` (``rows`` and ``strikes`` counting the bin's rows): no hazard
+    row is lost.  Ordered by (span, tree, row).  The hazard rows are compacted on the device, the records made on the
+    host; ``danger`` itself is not changed.  Synchronises."""
+    row_tree, points = segments["row_tree"], segments["points"]
+    if danger["hazard"].numel() != row_tree.numel():
+        raise ValueError("danger and segments must be results for the same points")
+    rows = torch.nonzero(danger["hazard"] >= ops.TREEFALL_NEAR).reshape(-1)
+    at = points[rows]
+    s3 = ops._sub3(segments["sub"])
+    if s3 is not None:
+        at = at - torch.tensor(list(s3), dtype=torch.float32, device=points.device)
+    under = ops.terrain_sample(at[:, :2].to(torch.float64), segments["grid"], segments["ground"])
+    trees = {key: v.cpu().numpy() for key, v in segments["trees"].items()}
+    host = lambda v: v[rows].cpu().numpy()
+    return _by_tree_records(rows.cpu().numpy(), at.cpu().numpy(), under.cpu().numpy(), host(danger["height"]),
+                            host(danger["span"]), host(danger["dist2"]), host(danger["hazard"]), host(row_tree), trees,
+                            float(cell), float(grow))
+
+
+def _by_tree_records(rows, xyz, under, height, span, dist2, hazard, row_tree, trees, cell, grow):
+    """danger_trees_by_tree's records from the compacted hazard rows (numpy, ascending row index; ``under``: the ground
+    under each; ``trees``: tree_segments' table as numpy)"""
+    out = []
+    if not len(rows):
+        return out
+    distance = np.sqrt(dist2)
+    margin = distance - (height.astype(np.float64) + float(grow))
+    for t in np.unique(row_tree[row_tree >= 0]):
+        mine = np.flatnonzero(row_tree == t)
+        p = mine[np.lexsort((rows[mine], margin[mine]))[0]]                  # the smallest margin, ties to the lowest row
+        out.append(dict(tree=int(t), row=int(trees["max_row"][t]), x=float(trees["x"][t]), y=float(trees["y"][t]),
+                        ground=float(trees["ground"][t]), height=float(trees["max_height"][t]), rows=int(len(mine)),
+                        strikes=int((hazard[mine] == ops.TREEFALL_STRIKE).sum()), hazard=int(hazard[mine].max()),
+                        min_row=int(rows[p]), distance=float(distance[p]), margin=float(margin[p]), span=int(span[p])))
+    free = np.flatnonzero(row_tree < 0)
+    if len(free):
+        fx = np.floor(xyz[free, 0].astype(np.float64) / cell).astype(np.int64)
+        fy = np.floor(xyz[free, 1].astype(np.float64) / cell).astype(np.int64)
+        for rec in _tree_records(rows[free], xyz[free], under[free], height[free], span[free], dist2[free], hazard[free],
+                                 cell, grow):
+            j = int(np.flatnonzero(rows[free] == rec["row"])[0])
+            same = (fx == fx[j]) & (fy == fy[j])
+            out.append(dict(rec, tree=-1, rows=int(same.sum()),
+                            strikes=int((hazard[free][same] == ops.TREEFALL_STRIKE).sum()),
+                            hazard=int(hazard[free][same].max()), min_row=rec["row"]))
+    out.sort(key=lambda r: (r["span"], r["tree"], r["row"]))
+    return [{key: r[key] for key in BY_TREE_KEYS} for r in out]
+
+
 TOWER_PROFILE_TABLE_KEYS = ("ground", "ground_from", "top", "tower_height", "nominal_height", "n_levels", "z_low",
                             "z_high", "width", "rows", "lowest_wire")
 TOWER_PROFILE_MAX_LEVELS = 8

@@ -97,6 +97,14 @@ knob is on) - and ``output_towers/tree_fall_info.csv`` get
 row of every 2 m cell that strikes a conductor when it falls or comes within ``limit`` metres of one, in world
 coordinates, with its height, piece, distance and margin.  It logs one extra line; a failure is handled like one of
 ``SPANS``.  The returned tower dicts are the same with and without it.
+``TREES`` (env PCH_TREES="cell,top_min[,crown_radius[,smooth]]", e.g. "0.5,5" or "0.5,5,8,1"; unset or empty = off; needs
+``TERRAIN`` - importing the module with PCH_TREES set and PCH_TERRAIN unset, or with PCH_FRAME=las, raises ValueError):
+behind the tree-fall step, the rows the ground rule kept - without the conductors and the rows near the accepted towers -
+are segmented into trees on a canopy grid of ``cell`` metres (pipeline.tree_segments) and
+``output_towers/tree_info.csv`` gets one line per tree: its tallest return in world coordinates, the ground under it, its
+height, crown area, cells and rows.  With ``TREEFALL`` also on, ``output_towers/tree_fall_by_tree.csv`` holds that step's
+hazard rows per tree (pipeline.danger_trees_by_tree) beside the unchanged ``tree_fall_info.csv``.  It logs one extra
+line; a failure is handled like one of ``SPANS``.  The returned tower dicts are the same with and without it.
 ``SECTION`` (env PCH_SECTION="half_width,limit[,stations[,depth]]", e.g. "15,7" or "15,7,64,80"; unset or empty = off;
 needs ``SPANS`` - importing the module with PCH_SECTION set and PCH_SPANS unset raises ValueError): behind the other span
 steps, the longitudinal section of every accepted wire piece (pipeline.span_sections; the skipped rows are
@@ -343,6 +351,45 @@ def treefall_from_env(value, spans=True, terrain=True, frame="reference"):
 TREEFALL = treefall_from_env(os.environ.get("PCH_TREEFALL"), spans=SPANS is not None, terrain=TERRAIN is not None,
                              frame=FRAME)
 TREEFALL_COLUMNS = ("ID", "row", "x", "y", "ground_z", "height", "span", "distance", "margin", "hazard")
+
+
+def trees_from_env(value, terrain=True, frame="reference"):
+    """TREES of an environment value: None (off) when unset or empty, else dict(cell, top_min, crown_radius, smooth) from
+    "cell,top_min[,crown_radius[,smooth]]" - two to four numbers: cell > 0 and top_min >= 0, both finite; crown_radius
+    >= 0 and finite (default 8) and at most 256 cells; smooth an integer in 0..8 (default 1).  ``terrain``: whether
+    TERRAIN is on - a row's height comes from the terrain grid; ``frame``: FRAME - the terrain grid is not defined for the
+    LAS-integer frame.  Anything else is refused (ValueError)"""
+    if value is None or not value.strip():
+        return None
+    parts = [t.strip() for t in value.split(",")]
+    if len(parts) not in (2, 3, 4):
+        raise ValueError(f"PCH_TREES takes \"cell,top_min[,crown_radius[,smooth]]\", got {value!r}")
+    cell, top_min = float(parts[0]), float(parts[1])
+    crown_radius = float(parts[2]) if len(parts) >= 3 else 8.0
+    smooth = float(parts[3]) if len(parts) == 4 else 1.0
+    if not (np.isfinite(cell) and cell > 0.0):
+        raise ValueError(f"PCH_TREES: cell must be finite and > 0, got {parts[0]!r}")
+    if not (np.isfinite(top_min) and top_min >= 0.0):
+        raise ValueError(f"PCH_TREES: top_min must be finite and >= 0, got {parts[1]!r}")
+    if not (np.isfinite(crown_radius) and crown_radius >= 0.0):
+        raise ValueError(f"PCH_TREES: crown_radius must be finite and >= 0, got {parts[2]!r}")
+    if np.ceil(crown_radius / cell) > TREES_MAX_CROWN_CELLS:
+        raise ValueError(f"PCH_TREES: crown_radius {parts[2]!r} at cell {parts[0]!r} is more than "
+                         f"{TREES_MAX_CROWN_CELLS} cells")
+    if not (smooth == int(smooth) and 0 <= smooth <= TREES_MAX_SMOOTH_CELLS):
+        raise ValueError(f"PCH_TREES: smooth must be an integer in 0..{TREES_MAX_SMOOTH_CELLS}, got {parts[3]!r}")
+    if frame == "las":
+        raise ValueError("PCH_TREES is not defined for PCH_FRAME=las: the terrain grid is built from the float32 rows")
+    if not terrain:
+        raise ValueError("PCH_TREES needs PCH_TERRAIN: a row's height above the ground comes from the terrain grid")
+    return dict(cell=cell, top_min=top_min, crown_radius=crown_radius, smooth=int(smooth))
+
+
+TREES_MAX_CROWN_CELLS, TREES_MAX_SMOOTH_CELLS = 256, 8       # PCH_CANOPY_MAX_CROWN, PCH_CANOPY_MAX_SMOOTH
+TREES = trees_from_env(os.environ.get("PCH_TREES"), terrain=TERRAIN is not None, frame=FRAME)
+TREES_COLUMNS = ("ID", "row", "x", "y", "z", "ground_z", "height", "crown_area", "cells", "rows")
+TREES_FALL_COLUMNS = ("ID", "row", "x", "y", "ground_z", "height", "rows", "strikes", "hazard", "min_row", "distance",
+                      "margin", "span")
 
 
 def section_from_env(value, spans=True):
@@ -719,6 +766,22 @@ def _extract(input_las_path, resident_entry, progress_callback, log_callback, ep
             except (ValueError, RuntimeError) as e:
                 log(f"⚠️ 倒树隐患计算失败: {str(e)}")
                 return tower_obbs
+        # ---- opt-in: the vegetation as trees, and the tree-fall hazards per tree
+        if TREES:
+            try:
+                near = pipeline._near_towers(stage_b_points, local, SPANS["cut_radius"])
+                seg = pipeline.tree_segments(stage_b_points, terrain, skip=spans["wire"] | near, **TREES)
+                rows = tree_rows(seg, cen)
+                write_rows_csv(output_dir / "tree_info.csv", TREES_COLUMNS, rows)
+                if TREEFALL:
+                    by_tree = pipeline.danger_trees_by_tree(fall, seg, grow=TREEFALL["grow"])
+                    write_rows_csv(output_dir / "tree_fall_by_tree.csv", TREES_FALL_COLUMNS,
+                                   tree_fall_rows(by_tree, cen))
+                clock.mark("tree segments")
+                log(trees_line(seg, rows, TREES))
+            except (ValueError, RuntimeError) as e:
+                log(f"⚠️ 单木分割失败: {str(e)}")
+                return tower_obbs
         # ---- opt-in: the longitudinal section of every piece, station by station
         if SECTION:
             try:
@@ -994,6 +1057,42 @@ def treefall_line(fall, rows, knob):
     return (f"🌲 倒树隐患: 树高 {knob['h_min']:g}–{knob['h_max']:g} m，生长量 {knob['grow']:g} m，限距 {knob['limit']:g} m；"
             f"隐患点 {int((hazard >= 1).sum())}（可触线 {int((hazard == 2).sum())}），隐患树 {len(rows)} 处（可触线 {strikes}），"
             f"涉及线段 {pieces}，最小裕度 {tightest:.3f} m")
+
+
+def tree_rows(seg, centroid):
+    """the lines of tree_info.csv for a result of pipeline.tree_segments: one list per tree in TREES_COLUMNS' order, the
+    tallest return and the ground under it moved to world coordinates by ``centroid`` (3 float64)"""
+    t = {key: v.cpu().numpy() for key, v in seg["trees"].items()}
+    return [[f"tree_{j}", int(t["max_row"][j]), float(t["x"][j]) + float(centroid[0]), float(t["y"][j]) + float(centroid[1]),
+             float(t["z"][j]) + float(centroid[2]), float(t["ground"][j]) + float(centroid[2]), float(t["max_height"][j]),
+             float(t["crown_area"][j]), int(t["cells"][j]), int(t["rows"][j])] for j in range(len(t["cells"]))]
+
+
+def tree_fall_rows(records, centroid):
+    """the lines of tree_fall_by_tree.csv for the records of pipeline.danger_trees_by_tree, in TREES_FALL_COLUMNS' order
+    (a record of no tree has the ID "none"), positions moved to world coordinates by ``centroid``"""
+    return [["none" if r["tree"] < 0 else f"tree_{r['tree']}", int(r["row"]), r["x"] + float(centroid[0]),
+             r["y"] + float(centroid[1]), r["ground"] + float(centroid[2]), r["height"], int(r["rows"]), int(r["strikes"]),
+             int(r["hazard"]), int(r["min_row"]), r["distance"], r["margin"], f"span_{int(r['span'])}"] for r in records]
+
+
+def write_rows_csv(path, columns, rows):
+    """a header line and one line per record, floats with repr's digits"""
+    import csv
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.writer(f)
+        w.writerow(columns)
+        for r in rows:
+            w.writerow([repr(float(v)) if isinstance(v, (float, np.floating)) else v for v in r])
+
+
+def trees_line(seg, rows, knob):
+    """the extra log line of TREES for a result of pipeline.tree_segments and its csv lines"""
+    tallest = max([r[6] for r in rows], default=float("nan"))
+    area = sum(r[7] for r in rows)
+    owned = int((seg["row_tree"] >= 0).sum())
+    return (f"🌳 单木分割: 冠层网格 {knob['cell']:g} m，树顶下限 {knob['top_min']:g} m，冠幅半径 {knob['crown_radius']:g} m；"
+            f"树木 {len(rows)} 株，归属点 {owned}，最高 {tallest:.3f} m，冠幅面积合计 {area:.1f} m²")
 
 
 def tower_profile_rows(profile, ids, centroid):
