@@ -573,7 +573,8 @@ int pch_first_nonfinite_row_f32(const float* xyz, int64_t n, int64_t* out_row, v
  * labels [n] int32 in [-1, nclusters)
  * out_perm    [n] int32: point rows ordered by (label, row); noise rows last
  * out_offsets [nclusters+1] int64: cluster k owns out_perm[offsets[k]:offsets[k+1]]
- * out_stats   [nclusters,8] float32 (may be NULL): min xyz, max xyz, 0, 0 per cluster
+ * out_stats   [nclusters,8] float32 (may be NULL): min xyz, max xyz, 0, 0 per cluster; a cluster without rows
+ *             reads +inf, -inf (also with n = 0).  A label outside [-1, nclusters) counts as noise.
  */
 size_t pch_segment_by_label_ws_bytes(int64_t n, int32_t nclusters);
 int pch_segment_by_label(const int32_t* labels, const float* xyz, int64_t n,
@@ -1332,6 +1333,27 @@ int pch_crop_box_bounds_f64(const PchCropBox* boxes_host, int32_t nboxes, double
  * PCH_ERR_TIMEOUT when the six tiles behind it gave up within budget_ms (1..2000) as designed AND the count word they
  * marked (sign bit, as the data-path kernels mark theirs) reads negative; PCH_ERR_HIP when not.  dev_scratch: >= 256 bytes of device memory.  Synchronises.  Not part of the data path (tests only). */
 int pch_selftest_lookback_timeout(int budget_ms, void* dev_scratch, size_t scratch_bytes, void* stream);
+
+/* Self-test of the shared exclusive scans of uint32: out[i] = in[0] + ... + in[i-1] modulo 2^32, out_total [1] uint32
+ * (device, may be NULL) = the sum of all n.  form selects the routine the stages call: 0 the three-launch scan, 1 the
+ * same over the bit counts of the words of in (a row bitmap to ranks), 2 and 3 the one-launch look-back forms of 0 and
+ * 1 (their status words and out_total are zeroed here; out_total reads 0xFFFFFFFF if a bounded wait gave up), 4 the
+ * single-workgroup scan of n tile sums alone (in is copied to out and scanned there).  0 <= n < 2^31; in and out
+ * 16-byte aligned; out may be in for forms 0, 2 and 4, never for 1 and 3, and may not overlap it otherwise.  n = 0
+ * launches nothing and out_total reads 0.  A refused call (PCH_ERR_ARG, PCH_ERR_WORKSPACE) writes nothing.  Enqueues
+ * and returns.  Not part of the data path (tests only). */
+size_t pch_selftest_scan_u32_ws_bytes(int64_t n, int32_t form);
+int pch_selftest_scan_u32(const uint32_t* in, uint32_t* out, int64_t n, int32_t form, uint32_t* out_total,
+                          void* ws, size_t ws_bytes, void* stream);
+
+/* Self-test of the shared stable LSD radix sort: out_keys / out_vals [n] = the pairs (keys[i], vals[i]) ordered by
+ * the low nbits bits of the key (0 <= nbits <= 64), pairs that agree in those bits in input order; the bits above
+ * nbits travel with the key and are not looked at, nbits = 0 copies.  The pairs are sorted inside the workspace and
+ * the ping-pong buffer the sort names as its result is the one copied out.  0 <= n < 2^31.  A refused call writes
+ * nothing.  Enqueues and returns.  Not part of the data path (tests only). */
+size_t pch_selftest_radix_sort_ws_bytes(int64_t n);
+int pch_selftest_radix_sort_pairs(const uint64_t* keys, const uint32_t* vals, int64_t n, int32_t nbits,
+                                  uint64_t* out_keys, uint32_t* out_vals, void* ws, size_t ws_bytes, void* stream);
 
 /* Preview decimation: k distinct rows chosen by a seeded pseudo-random bijection of the row range.
  * Replaces: points[np.random.choice(len(points), k, replace=False)] (pyGUI_towers_test.py:174-177 with k =

@@ -131,6 +131,10 @@ _SIGS = {
     "pch_crop_box_bounds_f64": (C.c_int, [_vp, _i32, _vp]),
     "pch_decimate_f64": (C.c_int, [_vp, _i64, _i64, C.c_uint64, _vp, _vp, _vp]),
     "pch_selftest_lookback_timeout": (C.c_int, [C.c_int, _vp, _sz, _vp]),
+    "pch_selftest_scan_u32_ws_bytes": (_sz, [_i64, _i32]),
+    "pch_selftest_scan_u32": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "pch_selftest_radix_sort_ws_bytes": (_sz, [_i64]),
+    "pch_selftest_radix_sort_pairs": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
     "pch_obb_shell_ws_bytes": (_sz, [_i32]),
     "pch_obb_shell_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _sz, _vp]),
     "pch_upright_boxes_ws_bytes": (_sz, [_i32, _i64]),

@@ -349,3 +349,107 @@ int radix_sort_pairs(uint64_t* k0, uint32_t* v0, uint64_t* k1, uint32_t* v1, int
 }
 
 }  // namespace pch
+
+// =====================================================================================
+// self-tests (include/pch_hip.h): the scans and the sort above behind a C entry of their own, so that the suite
+// can put them next to numpy at the sizes and bit widths it chooses.  They only call the functions above.
+// Never part of the data path.
+// =====================================================================================
+using namespace pch;
+
+namespace {
+
+struct StScanWs { uint32_t* w; size_t words; };
+static void st_scan_plan(Arena& a, int64_t n, int32_t form, StScanWs& w) {
+    w.words = form == 0 || form == 1 ? scan_ws_u32(n) : form == 2 || form == 3 ? scan1_ws_u32(n) : 1;
+    w.w = a.take<uint32_t>(w.words);
+}
+
+struct StSortWs { uint64_t *k0, *k1; uint32_t *v0, *v1, *radix_ws; };
+static void st_sort_plan(Arena& a, int64_t n, StSortWs& w) {
+    const int64_t nn = n > 0 ? n : 1;
+    w.k0 = a.take<uint64_t>(nn);
+    w.k1 = a.take<uint64_t>(nn);
+    w.v0 = a.take<uint32_t>(nn);
+    w.v1 = a.take<uint32_t>(nn);
+    w.radix_ws = a.take<uint32_t>(radix_ws_u32(nn));
+}
+
+static inline bool st_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+}  // namespace
+
+extern "C" size_t pch_selftest_scan_u32_ws_bytes(int64_t n, int32_t form) {
+    if (n < 0 || form < 0 || form > 4) return 0;
+    Arena a;
+    StScanWs w;
+    st_scan_plan(a, n, form, w);
+    return a.off;
+}
+
+extern "C" int pch_selftest_scan_u32(const uint32_t* in, uint32_t* out, int64_t n, int32_t form, uint32_t* out_total,
+                                     void* ws, size_t ws_bytes, void* stream) {
+    PCH_DEVICE_GUARD(in ? (const void*)in : (const void*)out);
+    hipStream_t s = (hipStream_t)stream;
+    PCH_REQUIRE(form >= 0 && form <= 4, "form must be 0..4");
+    PCH_REQUIRE(n >= 0 && n < (int64_t(1) << 31), "bad size");
+    if (n == 0) {
+        if (out_total) PCH_HIP_TRY(hipMemsetAsync(out_total, 0, sizeof(uint32_t), s));
+        return PCH_OK;
+    }
+    PCH_REQUIRE(in && out && ws, "null buffer");
+    PCH_REQUIRE(st_aligned(in, 16) && st_aligned(out, 16), "in and out must be 16-byte aligned");
+    PCH_REQUIRE(!out_total || st_aligned(out_total, 4), "out_total must be 4-byte aligned");
+    const bool popc = form == 1 || form == 3;
+    PCH_REQUIRE(out == in || out + n <= in || in + n <= out, "in and out overlap without being the same buffer");
+    PCH_REQUIRE(!popc || out != in, "the popcount forms do not scan in place");
+    Arena a(ws, ws_bytes);
+    StScanWs w;
+    st_scan_plan(a, n, form, w);
+    if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
+    switch (form) {
+    case 0: return scan_exclusive_u32(in, out, n, w.w, out_total, s);
+    case 1: return scan_exclusive_popc_u32(in, out, n, w.w, out_total, s);
+    case 2:
+    case 3:
+        PCH_HIP_TRY(hipMemsetAsync(w.w, 0, w.words * sizeof(uint32_t), s));      // status words + ticket
+        if (out_total) PCH_HIP_TRY(hipMemsetAsync(out_total, 0, sizeof(uint32_t), s));
+        return form == 2 ? scan1_exclusive_u32(in, out, n, w.w, out_total, s)
+                         : scan1_exclusive_popc_u32(in, out, n, w.w, out_total, s);
+    default:
+        if (out != in) PCH_HIP_TRY(hipMemcpyAsync(out, in, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        return scan_tile_sums_u32(out, n, out_total, s);
+    }
+}
+
+extern "C" size_t pch_selftest_radix_sort_ws_bytes(int64_t n) {
+    if (n < 0) return 0;
+    Arena a;
+    StSortWs w;
+    st_sort_plan(a, n, w);
+    return a.off;
+}
+
+extern "C" int pch_selftest_radix_sort_pairs(const uint64_t* keys, const uint32_t* vals, int64_t n, int32_t nbits,
+                                             uint64_t* out_keys, uint32_t* out_vals, void* ws, size_t ws_bytes,
+                                             void* stream) {
+    PCH_DEVICE_GUARD(keys ? (const void*)keys : (const void*)out_keys);
+    hipStream_t s = (hipStream_t)stream;
+    PCH_REQUIRE(nbits >= 0 && nbits <= 64, "nbits must be 0..64");
+    PCH_REQUIRE(n >= 0 && n < (int64_t(1) << 31), "bad size");
+    if (n == 0) return PCH_OK;
+    PCH_REQUIRE(keys && vals && out_keys && out_vals && ws, "null buffer");
+    PCH_REQUIRE(st_aligned(keys, 8) && st_aligned(out_keys, 8) && st_aligned(vals, 4) && st_aligned(out_vals, 4),
+                "misaligned buffer");
+    Arena a(ws, ws_bytes);
+    StSortWs w;
+    st_sort_plan(a, n, w);
+    if (a.overflow) { set_error("workspace too small: need %zu bytes", a.off); return PCH_ERR_WORKSPACE; }
+    PCH_HIP_TRY(hipMemcpyAsync(w.k0, keys, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    PCH_HIP_TRY(hipMemcpyAsync(w.v0, vals, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    PCH_TRY(radix_sort_pairs(w.k0, w.v0, w.k1, w.v1, n, nbits, w.radix_ws, s));
+    const bool in1 = radix_sort_result_buffer(nbits) == 1;
+    PCH_HIP_TRY(hipMemcpyAsync(out_keys, in1 ? w.k1 : w.k0, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    PCH_HIP_TRY(hipMemcpyAsync(out_vals, in1 ? w.v1 : w.v0, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    return PCH_OK;
+}

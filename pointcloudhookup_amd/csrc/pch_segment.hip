@@ -239,6 +239,14 @@ __global__ __launch_bounds__(SG_THREADS) void sg_stats_out_k(const uint32_t* __r
     stats[i] = v;
 }
 
+// no rows at all: every cluster is empty (+inf, -inf, 0, 0 - what sg_stats_out_k and sg_decode_word write for one)
+__global__ __launch_bounds__(SG_THREADS) void sg_stats_empty_k(int32_t nclusters, float* __restrict__ stats) {
+    const int64_t i = (int64_t)blockIdx.x * SG_THREADS + threadIdx.x;
+    if (i >= 8 * (int64_t)nclusters) return;
+    const int a = (int)(i & 7);
+    stats[i] = a < 3 ? INFINITY : a < 6 ? -INFINITY : 0.0f;
+}
+
 struct SgWs {
     uint64_t *k0, *k1;
     uint32_t *v0, *v1, *radix_ws, *acc;
@@ -289,6 +297,9 @@ int pch::segment_run(const int32_t* labels, const float* xyz, int64_t n, int32_t
     PCH_REQUIRE(out_offsets != nullptr, "out_offsets is null");
     if (n == 0) {
         PCH_HIP_TRY(hipMemsetAsync(out_offsets, 0, sizeof(int64_t) * ((size_t)nclusters + 1), s));
+        if (out_stats && nclusters > 0)
+            PCH_LAUNCH("seg_stats_empty", sg_stats_empty_k, dim3((unsigned)ceil_div(8 * (int64_t)nclusters, SG_THREADS)),
+                       dim3(SG_THREADS), 0, s, nclusters, out_stats);
         return PCH_OK;
     }
     PCH_REQUIRE(labels && out_perm && ws, "null buffer");

@@ -1292,6 +1292,29 @@ def segment_by_label(labels, xyz, nclusters):
     return perm, offsets, stats[:K]
 
 
+# ------------------------------------------------------------- self-tests of the shared scan and sort (tests only)
+def selftest_scan_u32(inp, out, form, out_total=None):
+    """pch_selftest_scan_u32 on the buffers as given (no copy is made: the entry judges their addresses).  inp / out:
+    int32 [n] holding the uint32 bit patterns, out may be inp; out_total: int32 [1] or None."""
+    L = _lib.lib()
+    n = inp.shape[0]
+    with torch.cuda.device(inp.device):
+        ws = _workspace(L.pch_selftest_scan_u32_ws_bytes(n, int(form)), inp.device)
+        _lib.check(L.pch_selftest_scan_u32(_ptr(inp), _ptr(out), n, int(form), _ptr(out_total), _ptr(ws), ws.numel(),
+                                           _stream()))
+
+
+def selftest_radix_sort_pairs(keys, vals, nbits, out_keys, out_vals):
+    """pch_selftest_radix_sort_pairs on the buffers as given.  keys / out_keys: int64 [n] holding the uint64 bit
+    patterns; vals / out_vals: int32 [n] holding uint32."""
+    L = _lib.lib()
+    n = keys.shape[0]
+    with torch.cuda.device(keys.device):
+        ws = _workspace(L.pch_selftest_radix_sort_ws_bytes(n), keys.device)
+        _lib.check(L.pch_selftest_radix_sort_pairs(_ptr(keys), _ptr(vals), n, int(nbits), _ptr(out_keys),
+                                                   _ptr(out_vals), _ptr(ws), ws.numel(), _stream()))
+
+
 # ------------------------------------------------------------- between C and D0, opt-in: merge of cluster pieces
 def cluster_centers(xyz, perm, offsets, nclusters):
     """(centers float32 [K,3], sizes int64 [K]), both on the device: per cluster of the grouped rows (perm / offsets of
